@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of one SDXL-base training step (loss prep + UNet forward + loss + UNet backward,
 gradients zeroed each step; optimizer excluded) on synthetic data, batch 4 per GPU at 1024^2 (latent 128x128), bf16.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs outputs/bench]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -188,6 +188,36 @@ def cpu_baseline(threads_list=None, timed_steps: int = 3):
                       f"threads) scaled to 1024^2-equivalent images by the FLOP ratio 4.77/20.28; weight init {t_init:.1f} s untimed"}
 
 
+DUMP_GRAD_SAMPLES = 1 << 22          # 16 MB of fp32 gradient values
+
+
+def dump_outputs(net, out_dir, seed: int = 0):
+    """What the timed step hands its caller, as .npy files in `out_dir`:
+      loss.npy         float32 [8]  the step's loss vector (sdxl_read_loss: loss, sum w*(pred-target)^2, ... , gradient gate)
+      grad_sample.npy  float32 [DUMP_GRAD_SAMPLES]  the fp32 UNet gradients at fixed positions: a seeded uniform draw (with
+                       replacement, sorted) of flat indices into the concatenation of every parameter's gradient, in diffusers
+                       layout, parameters in sorted key order -- independent of the library's arena layout, so two builds compare
+                       element for element."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "loss.npy", np.asarray(net.read_loss(), dtype=np.float32))
+    names = sorted(net.param_table)
+    sizes = torch.tensor([math.prod(net.param_table[k]) for k in names], dtype=torch.int64)
+    ends = torch.cumsum(sizes, 0)
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, int(ends[-1]), (DUMP_GRAD_SAMPLES,), generator=g, dtype=torch.int64).sort().values
+    owner = torch.searchsorted(ends, idx, right=True)
+    local = idx - (ends - sizes)[owner]
+    cuts = torch.searchsorted(owner, torch.arange(len(names) + 1)).tolist()     # idx is sorted: parameter p owns [cuts[p], cuts[p+1])
+    sample = torch.empty(DUMP_GRAD_SAMPLES, dtype=torch.float32)
+    for p, name in enumerate(names):
+        a, b = cuts[p], cuts[p + 1]
+        if a < b:
+            sample[a:b] = net.export(name, grad=True).flatten()[local[a:b].to(net.device)].cpu()
+    np.save(out_dir / "grad_sample.npy", sample.numpy())
+
+
 def rccl_info(max_lines: int = 6):
     """what RCCL said about the algorithm / protocol / channels it picked (NCCL_DEBUG=INFO lines of this rank's log file), or None"""
     path = os.environ.get("SDXL_RCCL_LOG")
@@ -282,7 +312,12 @@ def main():
     ap.add_argument("--gemm-mode", type=int, default=None, help="A/B runs: sdxl_set_gemm_mode (0 = 128-row kernel only)")
     ap.add_argument("--knob", action="append", default=[], help="A/B runs: id=value for sdxl_set_knob (repeatable)")
     ap.add_argument("--lib", default=None, help="A/B runs: another build of libsdxlstep.so (e.g. last round's) on the same box")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (loss vector + a fixed seeded sample of the "
+                         "fp32 gradients; see dump_outputs); single process without --force-exchange only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import sdxl_amd  # noqa: F401
     from sdxl_amd import distributed as D
@@ -301,6 +336,9 @@ def main():
     if args.max_nchannels:
         os.environ["NCCL_MAX_NCHANNELS"] = str(args.max_nchannels)
     forced = bool(args.force_exchange) and world == 1
+    if args.dump_outputs and (world > 1 or forced):
+        # (with an exchange the step's result is the reduced bf16 buckets / shards, not this rank's fp32 arena)
+        sys.exit("--dump-outputs: single process without --force-exchange only")
     if (world > 1 or forced) and backend == "nccl" and rank == 0 and "NCCL_DEBUG" not in os.environ:
         # rank 0 logs RCCL's topology / algorithm choices to a file; the lines end up in config.exchange.rccl
         os.environ["SDXL_RCCL_LOG"] = f"/tmp/sdxl_rccl_{os.getpid()}.log"
@@ -426,6 +464,8 @@ def main():
         ev = shadow.pop("_ev")
         shadow["tail_ms_last_step"] = round(max(0.0, ev[0].elapsed_time(ev[1])), 3)
     loss = net.read_loss()[0]
+    if args.dump_outputs:             # before the clock probe / profiled steps below run further steps
+        dump_outputs(net, args.dump_outputs)
     net_param_elems = int(net.param_elems)       # bf16 gradient bytes sent (and, reduced, received) per rank and exchange = 2 x this
     images = world * wl["B"] * args.steps
     value = images / elapsed
