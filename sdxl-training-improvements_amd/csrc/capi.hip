@@ -419,6 +419,9 @@ static int run_backward_segment_body(Engine& e, int k, bool first, hipStream_t s
   // until the last segment (nothing on the main stream reads a weight gradient, and no gradient buffer is reused)
   CHK(e.flush_wgrads(p, st));
   CHK(e.flush_ln_params(p, st));
+  // the per-sample column sums are reduced only by the LinearOp that casts their fp32 buffer: one still queued after the last
+  // segment was never folded into its gradient (a silent zero), so that is an error.  (wg_pending / ln_pending: flushed just above)
+  ARG_CHECK(k != e.nseg - 1 || e.cs_pending.empty(), "backward: %zu per-sample column sums were never reduced", e.cs_pending.size());
   if (e.seg_on_side && !gemm_profiling()) {   // the side stream sees the segment's main-stream gradients (norm parameters, ...)
     HIP_CHECK_RET(hipEventRecord(e.ev_seg, st));
     HIP_CHECK_RET(hipStreamWaitEvent(e.side, e.ev_seg, 0));

@@ -4,7 +4,8 @@ cfg 1 of BASELINE.json (method=ddpm, batch 1, 512^2 -> latent 64x64) and one sam
 128x128 = 1024^2, both methods): HIP loss AND probe gradients vs the fp32 CPU oracle (autograd through oracle/unet_ref.py) on
 identical synthetic weights / latents / embeddings / timesteps -- loss tolerance 1e-3 relative (north_star), gradient probes spread
 over the network (11 at cfg 1, 14 at 1024^2, incl. the 1280-channel self-attention projections whose Delta comes from the
-out-projection dgrad's epilogue) at rel-L2 <= 6e-2 / cos >= 0.998.  B = 4 (configs[1], [2], the 1344x768 bucket of configs[4]) is tied
+out-projection dgrad's epilogue) at rel-L2 <= 6e-2 / cos >= 0.998, and every one of the 1 680 gradient tensors (tests/_gradparity.py;
+bars at FULL_GRAD_BAR below).  The B = 4 decompositions are also checked for every tensor of the arena.  B = 4 (configs[1], [2], the 1344x768 bucket of configs[4]) is tied
 to those B = 1 comparisons through size-independent properties: batch loss = mean of per-sample losses, batch gradient = 1/B-weighted
 sum of per-sample gradients, reproducibility, accumulation linearity across plans, independence from the previous step.
 """
@@ -20,6 +21,8 @@ from oracle import unet_ref as U
 from sdxl_amd import synth
 from sdxl_amd import unet as NU
 
+from _gradparity import GradParity, compare_autograd, group
+
 pytestmark = pytest.mark.gpu
 
 
@@ -34,7 +37,10 @@ def full():
 @pytest.fixture(scope="module")
 def oracle_w():
     """fp32 CPU copy of the same synthetic weights for the oracle (10.3 GB, ~1.5 min of host hashing): built once."""
-    torch.set_num_threads(min(32, os.cpu_count() or 8))
+    n = len(os.sched_getaffinity(0))                               # the CPUs this process may run on, not the machine's count
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        n = min(n, max(1, int(os.environ["OMP_NUM_THREADS"])))
+    torch.set_num_threads(n)
     return U.synth_weights(U.SDXL_BASE, seed=0)                    # same bytes as synth.load_synthetic (tested on CPU)
 
 
@@ -258,6 +264,65 @@ def test_bucket_1344x768_b1_loss_and_gradients_match_cpu_oracle(full, oracle_w):
     assert worst >= 0.998
 
 
+FULL_GRAD_BAR = (6e-2, 0.998)      # per tensor, every one of the 1 680: the bar of the probe comparisons above
+# Biases, convolution weights and the time-embedding path measure far below it: worst rel-L2 8.4e-3 / cos 0.99996 over the
+# three B = 1 shapes against the oracle (up_blocks.0.resnets.0.conv_shortcut.weight at 1024^2) and 7.3e-3 over the B = 4
+# decompositions, against 2.0e-2 / 1.7e-2 for the linears / norms -- so they answer to a bar of their own, ~2.5x above that.
+TIGHT_GRAD_BAR = (2e-2, 0.9995)
+TIGHT_GROUPS = ("biases", "convs", "time-embedding path")
+
+
+def _grad_bar(shapes):
+    return lambda k: TIGHT_GRAD_BAR if group(k, len(shapes[k])) in TIGHT_GROUPS else FULL_GRAD_BAR
+
+
+def _every_gradient_vs_oracle(net, w, label, method, x, ts):
+    """One B = 1 step on the GPU and autograd of the fp32 oracle loss into all 1 680 weights: each reference gradient is compared
+    with net.export(k, grad=True) as soon as autograd has it, then freed (the 10.3 GB of reference gradients never coexist)."""
+    _probe(w, list(w))
+    unet_fn = lambda s, t, e, p, ti: U.unet_forward(w, s, t, e, p, ti, U.SDXL_BASE)
+    batch = {"vae_latents": x["lat"], "prompt_embeds": x["ehs"], "pooled_prompt_embeds": x["pooled"], "time_ids": x["tid"]}
+    net.zero_grads()
+    if method == "ddpm":
+        sig = R.karras_sigmas()[ts]
+        net.forward_loss("ddpm", x["lat"], x["noise"], sig, ts.float(), x["ehs"], x["pooled"], x["tid"])
+        ref = R.compute_loss_ddpm(unet_fn, batch, x["noise"], ts)
+    else:
+        net.forward_loss("flow_matching", x["lat"], x["noise"], ts, ts, x["ehs"], x["pooled"], x["tid"])
+        ref = R.compute_loss_flow(unet_fn, batch, x["noise"], ts)
+    net.backward(1.0, True)
+    got = net.read_loss()[0]
+    rel = abs(got - float(ref["loss"])) / abs(float(ref["loss"]))
+    assert rel <= 1e-3, rel
+    par = GradParity(label)
+    try:
+        compare_autograd(par, ref["loss"], {k: w[k] for k in net.param_shapes()}, lambda k: net.export(k, grad=True))
+    finally:
+        del ref
+        _probe(w, [])
+    par.check(_grad_bar(net.param_shapes()), expect=net.param_shapes())
+
+
+def test_cfg1_every_gradient_matches_cpu_oracle(full, oracle_w):
+    """cfg 1 (ddpm, B = 1, 512^2), the inputs of test_cfg1_gradients_match_cpu_oracle: all 1 680 gradient tensors -- the up-sampler
+    bias column sums, the time-embedding path's per-sample column sums, norm parameters, split-K bias rows -- against the oracle."""
+    _every_gradient_vs_oracle(full, oracle_w, "FULL cfg1 ddpm 1x64x64", "ddpm", _inputs(1, 64, 64, seed=404), torch.tensor([377]))
+
+
+@pytest.mark.parametrize("method", ["ddpm", "flow_matching"])
+def test_headline_shape_b1_every_gradient_matches_cpu_oracle(full, oracle_w, method):
+    """1024^2 (latent 128 x 128), B = 1, the inputs of the headline probe test: all 1 680 gradient tensors against the oracle."""
+    x = _inputs(1, 128, 128, seed=515 if method == "ddpm" else 616)
+    ts = torch.tensor([613]) if method == "ddpm" else torch.tensor([0.3671875])
+    _every_gradient_vs_oracle(full, oracle_w, f"FULL 1024^2 {method} 1x128x128", method, x, ts)
+
+
+def test_bucket_1344x768_b1_every_gradient_matches_cpu_oracle(full, oracle_w):
+    """The 1344 x 768 bucket (latent 96 x 168, ragged attention and conv tiles), flow matching, B = 1: all 1 680 gradient tensors."""
+    _every_gradient_vs_oracle(full, oracle_w, "FULL 1344x768 flow_matching 1x96x168", "flow_matching", _inputs(1, 96, 168, seed=919),
+                              torch.tensor([0.62109375]))
+
+
 def test_configs1_shape_step_properties(full):
     """BASELINE configs[1] (B=4, 1024^2): reproducible loss, finite gradients, accumulation = sum of micro-steps."""
     net = full
@@ -438,6 +503,43 @@ def test_flow_matching_batch_decomposes(full, shape):
     # (the per-sample steps are small problems and take the split-K forward / dgrad launches: another fp32 summation order, the
     #  same bits to bf16 noise)
     assert abs(nb - ns) <= 5e-3 * nb and rel_g <= 1e-2
+
+
+@pytest.mark.parametrize("method,shape", [("ddpm", (4, 128, 128)), ("flow_matching", (4, 128, 128)), ("flow_matching", (4, 96, 168))],
+                         ids=["configs1_ddpm_1024sq", "configs2_flow_1024sq", "configs4_bucket_1344x768_b4"])
+def test_batch4_every_gradient_decomposes(full, method, shape):
+    """B = 4 is what bench.py times, and only B = 4 takes the 4096-row pl forward / dgrad, the cr256 weight gradients (grouped launches
+    of three 1280^2 outputs), wgrad256 over 16 384 rows and cfg 13 at M = 16 384.  Every tensor of the B = 4 gradient arena equals the
+    1/B-weighted sum of the four per-sample steps' arenas (which the B = 1 oracle tests tie to the fp32 CPU oracle), slice by slice
+    of the packed arena, on the device.  Bar: that of test_split_dgrad_shapes_keep_their_delta_pass, whose pairs differ the same way
+    (the per-sample steps take split-K forward / dgrad launches and the query-split attention backward)."""
+    net = full
+    B, H, W = shape
+    if method == "ddpm":
+        x = _inputs(B, H, W, seed=808)
+        ts = torch.tensor([450, 613, 700, 820])
+        sig = R.karras_sigmas()[ts]
+        a, b = sig, ts.float()
+    else:
+        x = _inputs(B, H, W, seed=303 + H)
+        a = b = torch.sigmoid(torch.randn(B, generator=torch.Generator().manual_seed(9)))
+
+    def run(idx, scale, first):
+        s = slice(idx, idx + 1) if idx is not None else slice(None)
+        net.forward_loss(method, x["lat"][s], x["noise"][s], a[s], b[s], x["ehs"][s], x["pooled"][s], x["tid"][s])
+        net.backward(scale, first)
+
+    net.zero_grads()
+    run(None, 1.0, True)
+    gb = net.grads.clone()                  # 10.3 GB on the device; nothing leaves it
+    net.zero_grads()
+    for i in range(B):
+        run(i, 1.0 / B, i == 0)
+    torch.cuda.synchronize()
+    par = GradParity(f"B=4 decomposition {method} {B}x{H}x{W}")
+    par.add_arena(net.grads, gb, net.param_ranges(), net.param_shapes())
+    del gb
+    par.check(_grad_bar(net.param_shapes()), expect=net.param_shapes())
 
 
 def test_configs4_mixed_buckets_accumulate_across_plans(full):

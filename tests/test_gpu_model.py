@@ -14,6 +14,8 @@ from oracle import loss_ref as R
 from oracle import unet_ref as U
 from sdxl_amd import unet as NU
 
+from _gradparity import GradParity, compare_autograd
+
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-3
@@ -141,6 +143,46 @@ def test_training_step_matches_oracle(tiny, method):
     assert worst <= 6e-2
     for t in w.values():
         t.requires_grad_(False)
+
+
+TINY_GRAD_BAR = (6e-2, 0.995)      # per tensor: rel-L2 <= 6e-2 (the probes' worst-case bar above), cosine >= 0.995
+
+
+@pytest.mark.parametrize("H,W", [(16, 16), (24, 40)])
+@pytest.mark.parametrize("method", ["ddpm", "flow_matching"])
+def test_training_step_every_gradient_matches_oracle(tiny, method, H, W):
+    """Every tiny-UNet gradient tensor (not only PROBE_GRADS) against autograd of the fp32 oracle loss: the bias / norm / time-
+    embedding gradients that come out of hand-written column sums and fixed-order reduces included; 24 x 40 is the non-square
+    shape of the forward test, with ragged tiles."""
+    cfg, w, net = tiny
+    B = 2
+    x = make_inputs(cfg, B, H, W, seed=13 if method == "ddpm" else 17)
+    for t in w.values():
+        t.grad = None
+        t.requires_grad_(True)
+    unet_fn = lambda s, t, e, p, ti: U.unet_forward(w, s, t, e, p, ti, cfg)
+    batch = {"vae_latents": x["lat"], "prompt_embeds": x["ehs"], "pooled_prompt_embeds": x["pooled"], "time_ids": x["tid"]}
+    if method == "ddpm":
+        ts = torch.tensor([610, 230])
+        sig = R.karras_sigmas()[ts]
+        ref = R.compute_loss_ddpm(unet_fn, batch, x["noise"], ts)
+        net.forward_loss("ddpm", x["lat"], x["noise"], sig, ts.float(), x["ehs"], x["pooled"], x["tid"])
+    else:
+        t = R.sample_logit_normal_from_z(x["z"])
+        ref = R.compute_loss_flow(unet_fn, batch, x["noise"], t)
+        net.forward_loss("flow_matching", x["lat"], x["noise"], t, t, x["ehs"], x["pooled"], x["tid"])
+    net.zero_grads()
+    net.backward(grad_scale=1.0, first_micro=True)
+    ref_loss = float(ref["loss"])
+    assert abs(net.read_loss()[0] - ref_loss) <= LOSS_RTOL * abs(ref_loss)
+    par = GradParity(f"tiny {method} {B}x{H}x{W}")
+    try:
+        compare_autograd(par, ref["loss"], w, lambda k: net.export(k, grad=True))
+    finally:
+        for t in w.values():
+            t.grad = None
+            t.requires_grad_(False)
+    par.check(TINY_GRAD_BAR, expect=net.param_shapes())
 
 
 def test_grad_accumulation_is_sum_of_micro_steps(tiny):
