@@ -2,15 +2,18 @@
 """Headline benchmark: images/sec of one SDXL-base training step (loss prep + UNet forward + loss + UNet backward,
 gradients zeroed each step; optimizer excluded) on synthetic data, batch 4 per GPU at 1024^2 (latent 128x128), bf16.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs outputs/bench]
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs outputs/bench] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One process per GPU; data parallel = each rank runs the same step on its own batch and the UNet gradients are
 all-reduced (bf16, pre-scaled by 1/N) over RCCL/xGMI in ~190 MB buckets overlapped with the rest of backward.
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel family (the bf16 MFMA GEMM behind every Linear and
-3x3 conv: forward, dgrad, wgrad), measured with HIP events around each of its launches in a separate profiled step;
-`cpu_baseline` is the fp32 CPU oracle (the restatement of the reference's arithmetic) timed on this box's host cores.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints: nothing else.
+--full adds, after the timed steps, what takes runs of its own: `clock` (rocm-smi beside a few more steps), `roofline` for the
+dominant kernel family (the bf16 MFMA GEMM behind every Linear and 3x3 conv: forward, dgrad, wgrad), measured with HIP events
+around each of its launches in a separate profiled step, `optimizer` (the fused AdamW update, timed apart) and `cpu_baseline`
+(the fp32 CPU oracle, the restatement of the reference's arithmetic, timed on the host's cores); without --full they are null
+or absent.
 """
 from __future__ import annotations
 
@@ -289,8 +292,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="ddpm_b4_1024", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-optimizer", action="store_true", help="skip the (untimed) fused-optimizer measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: clock probe, profiled GEMM-roofline steps, "
+                         "fused-optimizer update, CPU baseline (each can still be left out with the options below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-optimizer", action="store_true", help="--full: skip the (untimed) fused-optimizer measurement")
     ap.add_argument("--cpu-threads", type=int, nargs="*", default=None, help="thread counts of the CPU baseline (default: one socket's cores, 8)")
     ap.add_argument("--exchange", default="zero1", choices=["zero1", "allreduce"],
                     help="N > 1: zero1 (default = the trainer's default, training.shard_optimizer: DESIGN.md section 6) = reduce-scatter of the bf16 "
@@ -307,8 +313,8 @@ def main():
                          "a third stream for bucket_bytes x 2 x 7/8 / GBPS (default 300 GB/s: reduce-scatter + all-gather over 7 xGMI links)")
     ap.add_argument("--max-nchannels", type=int, default=None, help="N > 1: NCCL_MAX_NCHANNELS for RCCL (its kernels take one workgroup per channel)")
     ap.add_argument("--no-emit", action="store_true", help="N > 1 A/B: cast the fp32 gradient arena per bucket instead of bf16 wgrad epilogues")
-    ap.add_argument("--profile-steps", type=int, default=1, help="extra steps with per-launch GEMM event timing")
-    ap.add_argument("--no-clock-probe", action="store_true", help="skip the rocm-smi clock / power samples after the timed region")
+    ap.add_argument("--profile-steps", type=int, default=1, help="--full: extra steps with per-launch GEMM event timing")
+    ap.add_argument("--no-clock-probe", action="store_true", help="--full: skip the rocm-smi clock / power samples after the timed region")
     ap.add_argument("--gemm-mode", type=int, default=None, help="A/B runs: sdxl_set_gemm_mode (0 = 128-row kernel only)")
     ap.add_argument("--knob", action="append", default=[], help="A/B runs: id=value for sdxl_set_knob (repeatable)")
     ap.add_argument("--lib", default=None, help="A/B runs: another build of libsdxlstep.so (e.g. last round's) on the same box")
@@ -473,12 +479,12 @@ def main():
 
     # what the package lets the chip clock under this workload (untimed, after the timed region): rocm-smi sampled beside a few more steps
     clock = None
-    if world == 1 and not args.no_clock_probe:
+    if args.full and world == 1 and not args.no_clock_probe:
         clock = clock_probe(step)
 
     # dominant-kernel roofline: per-launch HIP events around every GEMM-family launch (same stream), profiled steps
     roof = None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         lib.check(L.sdxl_profile_gemm_begin())
         for _ in range(args.profile_steps):
             step()
@@ -519,7 +525,7 @@ def main():
     # row f1, measured OUTSIDE the timed region (the metric excludes the optimizer): the fused AdamW_BF16 update of all
     # parameters, HBM-bound: 20 algorithmic bytes per element (p, m, v, shift bf16 in + out, fp32 gradient in)
     opt_extra = None
-    if not args.no_optimizer:
+    if args.full and not args.no_optimizer:
         from sdxl_amd.optimizer import AdamWBF16
         opt = AdamWBF16(net, lr=4e-7, weight_decay=0.01)
         sharded = (world > 1 or forced) and sharded_exchange
@@ -587,7 +593,7 @@ def main():
             clock["peak_at_sclk_tflops"] = round(PEAK_BF16_TFLOPS * clock["sclk_mhz_under_load"] / clock["nominal_sclk_mhz"], 1)
             clock["step_mfma_frac_at_sclk"] = round(step_tflops / clock["peak_at_sclk_tflops"], 4)
             out["clock"] = clock
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del net, sync
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(args.cpu_threads or None)

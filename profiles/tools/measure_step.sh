@@ -18,7 +18,7 @@ SDXL_NO_SIDE_STREAM=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O
 cp $(find $O/l -name "*kernel_stats.csv" | head -1) $O/kernel_stats_serialized.csv
 rm -rf $O/k $O/l
 # 2. per-shape GEMM table from the per-launch HIP events of bench.py's profiled step
-(cd $R && SDXL_GEMM_PROF_DUMP=$O/gemm_dump.csv python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-optimizer --no-clock-probe --profile-steps 1 > /dev/null 2>&1)
+(cd $R && SDXL_GEMM_PROF_DUMP=$O/gemm_dump.csv python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-optimizer --no-clock-probe --profile-steps 1 > /dev/null 2>&1)
 python $R/profiles/tools/agg.py $O/gemm_dump.csv 0.4 > $O/gemm_shapes.txt; rm -f $O/gemm_dump.csv
 # 3. PMC over the whole step: three separate passes
 for c in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
@@ -59,5 +59,5 @@ print(json.dumps(out, indent=1)[:2500])
 PY
 rm -rf $O/pmc
 # 4. the bench line itself (with cpu_baseline + optimizer block)
-cd $R && python bench.py 2>/dev/null | tail -1 > $O/bench.json; cut -c1-400 $O/bench.json
+cd $R && python bench.py --full 2>/dev/null | tail -1 > $O/bench.json; cut -c1-400 $O/bench.json
 ls -la $O

@@ -4,7 +4,7 @@
 T=${1:-r06}
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="python bench.py --no-cpu-baseline --no-optimizer --profile-steps 0 --steps 20 --warmup 4"
+B="python bench.py --full --no-cpu-baseline --no-optimizer --profile-steps 0 --steps 20 --warmup 4"
 for w in ddpm_b4_1024 flow_b4_1024 flow_b4_1344x768 flow_mixed_accum4 ddpm_b1_512; do
   $B --workload $w 2>gpurun_out/${T}_bench_$w.err | grep "^{" | tail -1 > gpurun_out/${T}_bench_$w.json
   python -c "import json,sys; d=json.load(open('gpurun_out/${T}_bench_$w.json')); print('$w', d['ms_per_step'], d['value'], d['step_mfma_frac'], d.get('clock',{}).get('sclk_mhz_under_load'))"
