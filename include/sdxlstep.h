@@ -239,8 +239,20 @@ typedef struct {
   unsigned long long elem_offset; /* arena index of element 0 of this call (multiple of 8).  The stochastic-rounding counters are
                                    * (seed, step, arena index), so updating a sub-range [elem_offset, elem_offset + n) of the arena
                                    * (one rank's ZeRO-1 shard) gives exactly the bits of the full-arena update. */
+  /* ---- appended: algorithm selection (sdxl_adamw_default_config zeroes them: algorithm 0 as before) ---- */
+  int algorithm;               /* 0 = AdamW_BF16 (above); 1 = schedule-free Kahan AdamW (reference
+                                  src/training/optimizers/adamw_schedulefree/__init__.py): m, v and shift carry exp_avg,
+                                  exp_avg_sq and kahan_comp (shift may be NULL only when kahan_sum is 0); rand_inject must
+                                  be NULL; lr, step, decay_this_iteration, reference_ema, seed and elem_offset are not read */
+  int kahan_sum;               /* algorithm 1: 1 = keep the kahan_comp arena */
+  int sf_reference;            /* algorithm 1: 1 = the reference's bf16 arithmetic bit for bit (its compensation stays +0,
+                                  weight decay not scaled by lr); 0 = compensated: true parameter p + kahan_comp in fp32,
+                                  decoupled decay step_size * weight_decay */
+  double weight_decay;         /* algorithm 1 */
+  double sf_step_size;         /* algorithm 1: the reference's step_size = adjusted_lr / sqrt(1 - beta2^(k+1)), computed by
+                                  the caller in double precision */
 } sdxl_adamw_config;
-SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1 */
+SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1, algorithm 0 */
 SDXL_API int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,
                          void* stream);

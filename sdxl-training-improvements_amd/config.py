@@ -35,6 +35,13 @@ class OptimizerConfig:                   # data/config.py:42-49
     reference_ema: bool = True           # build-only key: True = the reference's actual first-moment update (its
                                          # add_stochastic_ operand order, SURVEY D17: almost no momentum), False = the
                                          # documented EMA; see optimizer.py::AdamWBF16
+    # schedule-free specific options (data/config.py:51-54), read by optimizer_type "adamw_schedule_free_kahan"
+    warmup_steps: int = 0
+    kahan_sum: bool = True
+    correct_bias: bool = True            # accepted and ignored (the reference class has no such option)
+    schedule_free_arithmetic: str = "compensated"   # build-only key: "compensated" = the Kahan-compensated fp32 update the
+                                         # reference's docstring describes, "reference" = its literal bf16 arithmetic bit for
+                                         # bit; see optimizer.py::AdamWScheduleFreeKahanBF16
 
 
 @dataclass

@@ -888,11 +888,39 @@ int sdxl_adamw_default_config(sdxl_adamw_config* c) {
   c->reference_ema = 1;
   return 0;
 }
+// algorithm 1 of sdxl_adamw_bf16_step: every argument error is reported before anything touches the device
+static int sf_kahan_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* kahan_comp, size_t n, const sdxl_adamw_config* c,
+                         const float* grad_scale_dev, const unsigned short* rand_inject, hipStream_t st) {
+  ARG_CHECK(rand_inject == nullptr, "schedule-free: rand_inject must be NULL (the update has no random rounding)");
+  ARG_CHECK(c->kahan_sum == 0 || kahan_comp != nullptr, "schedule-free: kahan_sum needs the kahan_comp arena (shift argument)");
+  ARG_CHECK(c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0 && c->weight_decay >= 0.0 &&
+            c->sf_step_size >= 0.0 && std::isfinite(c->sf_step_size), "schedule-free: invalid hyper-parameters");
+  SfkP q;
+  memset(&q, 0, sizeof(q));
+  q.p = (bf16*)p; q.m = (bf16*)m; q.v = (bf16*)v; q.c = c->kahan_sum ? (bf16*)kahan_comp : nullptr; q.n = n;
+  if (grad_dtype == 0) q.grad_f32 = (const float*)grad; else q.grad_bf16 = (const bf16*)grad;
+  // python doubles -> the float32 / bf16 scalars torch's ops on bf16 tensors use (tests/_schedulefree_ref.py)
+  const double b1 = c->beta1, b2 = c->beta2, ss = c->sf_step_size, wd = c->weight_decay;
+  q.beta1 = (float)b1; q.beta2 = (float)b2;
+  q.one_minus_beta1_bf16 = bf16_round_host((float)(1.0 - b1));
+  q.one_minus_beta2 = (float)(1.0 - b2);
+  q.eps_bf16 = bf16_round_host((float)c->eps);
+  q.has_wd = wd != 0.0;
+  q.wd_alpha_bf16 = bf16_round_host((float)-wd);
+  q.neg_step = (float)-ss;
+  q.step = (float)ss;
+  q.decay = (float)(ss * wd);
+  q.grad_round_bf16 = c->grad_round_bf16;
+  q.grad_scale = grad_scale_dev;
+  return launch_sfk(q, c->sf_reference, st);
+}
 int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,
                          void* st) {
   ARG_CHECK(c, "null config");
   ARG_CHECK(grad_dtype == 0 || grad_dtype == 1, "adamw: grad_dtype %d (0 = fp32, 1 = bf16)", grad_dtype);
+  ARG_CHECK(c->algorithm == 0 || c->algorithm == 1, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan)", c->algorithm);
+  if (c->algorithm == 1) return sf_kahan_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
   ARG_CHECK(c->step >= 1.0 && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0,
             "adamw: invalid hyper-parameters");
   AdamWP q;

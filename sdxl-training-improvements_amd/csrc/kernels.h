@@ -399,5 +399,25 @@ struct AdamWP {
                                // full-arena launch, so a sharded (ZeRO-1) update is bit-identical to the unsharded one
 };
 int launch_adamw_bf16(const AdamWP& q, hipStream_t st);
+// schedule-free Kahan AdamW (csrc/optimizer.hip, sfk_kernel): one launch over the arena slice
+struct SfkP {
+  bf16* p;
+  const float* grad_f32;       // native fp32 gradient arena, or
+  const bf16* grad_bf16;       //   bf16 gradients (exactly one of the two)
+  bf16 *m, *v, *c;             // exp_avg, exp_avg_sq, kahan_comp (c: nullptr without kahan_sum)
+  size_t n;                    // elements, multiple of 8
+  float beta1, beta2;          // float32, as torch's mul_ by a python scalar uses them
+  float one_minus_beta1_bf16;  // alpha of exp_avg.add_(grad, alpha=1-beta1): rounded to bf16 as torch does
+  float one_minus_beta2;       // value of addcmul_
+  float eps_bf16;              // denom.add_(eps): eps rounded to bf16
+  int has_wd;                  // weight_decay != 0
+  float wd_alpha_bf16;         // reference mode: alpha of p.add_(p, alpha=-weight_decay), rounded to bf16
+  float neg_step;              // reference mode: -step_size (float32)
+  float step;                  // compensated mode: step_size (float32)
+  float decay;                 // compensated mode: step_size * weight_decay (float32)
+  int grad_round_bf16;         // round the (scaled) gradient to bf16 first
+  const float* grad_scale;     // device scalar multiplied into the gradient (unscale / clip), or nullptr
+};
+int launch_sfk(const SfkP& q, int reference, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);
 

@@ -138,3 +138,96 @@ int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, h
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
+
+// ---- schedule-free Kahan AdamW (reference: src/training/optimizers/adamw_schedulefree/__init__.py, `step`) ----------------
+// One grid-stride pass, no random numbers.  Per element 16 B (p, m, v bf16 read and written + fp32 gradient read), 20 B with
+// the Kahan arena c: 41.1 / 51.3 GB over the 2.567 B-parameter arena.  Moments and denominator are the reference's bf16 ops
+// in both modes:  m = rn(rn(m*b1) + bf16(1-b1)*g)  v = rn(rn(v*b2) + ((1-b2)*g)*g)  d = rn(rn(sqrt(v)) + bf16(eps)).
+//   REF  (optimizer.schedule_free_arithmetic "reference"): the reference's sequence bit for bit --
+//        g = rn(g + c); p = rn(p + bf16(-wd)*p); u = rn(rn(m/d) * -step_size); p = rn(p + u);
+//        c = rn(rn(p - rn(p + u)) + rn(rn(p + u) - p))   (+0 for every finite value, as in the reference).
+//        The gradient is read only: the reference's in-place p.grad += kahan_comp is not reproduced.
+//   !REF ("compensated"): x = p + c in fp32; x -= (step_size*wd)*x; x -= step_size*(m/d); p = rn(x); c = rn(x - p).
+// KAHAN = kahan_sum (without it c is neither read nor written); F32G = fp32 (native arena) or bf16 gradients.
+template <bool REF, bool KAHAN, bool F32G>
+__global__ __launch_bounds__(256) void sfk_kernel(const SfkP q) {
+  const size_t nvec = q.n / 8;
+  const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e0 = i * 8;
+    bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), mv = __builtin_nontemporal_load((const bf16x8*)(q.m + e0)),
+           vv = __builtin_nontemporal_load((const bf16x8*)(q.v + e0));
+    bf16x8 cv;
+    if constexpr (KAHAN) cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0));
+    float g[8];
+    if constexpr (F32G) {
+      const f32x4 a = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0)), b = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0 + 4));
+      g[0] = a[0]; g[1] = a[1]; g[2] = a[2]; g[3] = a[3]; g[4] = b[0]; g[5] = b[1]; g[6] = b[2]; g[7] = b[3];
+    } else {
+      const bf16x8 gv = __builtin_nontemporal_load((const bf16x8*)(q.grad_bf16 + e0));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] = bf(gv[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float gr = g[e] * gscale;                                  // fused unscale / clip coefficient
+      if (q.grad_round_bf16) gr = bf(rn(gr));
+      if constexpr (REF && KAHAN) gr = bf(rn(gr + bf(cv[e])));  // grad.add_(kahan_comp)
+      const float m1 = bf(rn(bf(mv[e]) * q.beta1));
+      const bf16 m2b = rn(__builtin_fmaf(gr, q.one_minus_beta1_bf16, m1));
+      const float m2 = bf(m2b);
+      const float v1 = bf(rn(bf(vv[e]) * q.beta2));
+      const bf16 v2b = rn(__builtin_fmaf(q.one_minus_beta2 * gr, gr, v1));
+      float den = bf(rn(__builtin_sqrtf(bf(v2b))));
+      den = bf(rn(den + q.eps_bf16));
+      float pf = bf(pv[e]);
+      if constexpr (REF) {
+        if (q.has_wd) pf = bf(rn(__builtin_fmaf(pf, q.wd_alpha_bf16, pf)));   // p.data.add_(p.data, alpha=-weight_decay)
+        const float u = bf(rn(bf(rn(m2 / den)) * q.neg_step));                 // -step_size * (exp_avg / denom)
+        const float p1 = bf(rn(pf + u));
+        pv[e] = rn(p1);
+        if constexpr (KAHAN) {
+          const float b = bf(rn(p1 + u));
+          cv[e] = rn(bf(rn(p1 - b)) + bf(rn(b - p1)));
+        }
+      } else {
+        float x = pf;
+        if constexpr (KAHAN) x = pf + bf(cv[e]);
+        if (q.has_wd) x = x - q.decay * x;
+        x = x - q.step * (m2 / den);
+        const bf16 pb = rn(x);
+        pv[e] = pb;
+        if constexpr (KAHAN) cv[e] = rn(x - bf(pb));
+      }
+      mv[e] = m2b; vv[e] = v2b;
+    }
+    __builtin_nontemporal_store(pv, (bf16x8*)(q.p + e0));
+    __builtin_nontemporal_store(mv, (bf16x8*)(q.m + e0));
+    __builtin_nontemporal_store(vv, (bf16x8*)(q.v + e0));
+    if constexpr (KAHAN) __builtin_nontemporal_store(cv, (bf16x8*)(q.c + e0));
+  }
+}
+
+template <bool REF, bool KAHAN>
+static void launch_sfk_g(const SfkP& q, unsigned blocks, hipStream_t st) {
+  if (q.grad_f32) hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, true>), dim3(blocks), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, false>), dim3(blocks), dim3(256), 0, st, q);
+}
+
+int launch_sfk(const SfkP& q, int reference, hipStream_t st) {
+  ARG_CHECK(q.p && q.m && q.v && (q.grad_f32 || q.grad_bf16), "schedule-free: missing buffers");
+  ARG_CHECK(q.n % 8 == 0, "schedule-free: n=%zu must be a multiple of 8", q.n);
+  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.c | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16) & 15) == 0,
+            "schedule-free: buffers must be 16-byte aligned");
+  if (q.n == 0) return 0;
+  size_t blocks = (q.n / 8 + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;      // as adamw_bf16_kernel: 16 workgroups per CU, grid-stride the rest
+  const unsigned nb = (unsigned)blocks;
+  if (reference) {
+    if (q.c) launch_sfk_g<true, true>(q, nb, st); else launch_sfk_g<true, false>(q, nb, st);
+  } else {
+    if (q.c) launch_sfk_g<false, true>(q, nb, st); else launch_sfk_g<false, false>(q, nb, st);
+  }
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}

@@ -51,7 +51,10 @@ class Batch(C.Structure):
 class AdamWConfig(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("step", C.c_double), ("decay_this_iteration", C.c_double), ("reference_ema", C.c_int),
-                ("grad_round_bf16", C.c_int), ("seed", C.c_ulonglong), ("elem_offset", C.c_ulonglong)]
+                ("grad_round_bf16", C.c_int), ("seed", C.c_ulonglong), ("elem_offset", C.c_ulonglong),
+                # appended: algorithm 0 = AdamW_BF16, 1 = schedule-free Kahan (optimizer.AdamWScheduleFreeKahanBF16)
+                ("algorithm", C.c_int), ("kahan_sum", C.c_int), ("sf_reference", C.c_int),
+                ("weight_decay", C.c_double), ("sf_step_size", C.c_double)]
 
 
 _vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t

@@ -12,7 +12,9 @@ The objective comes from `training.native_objective` ("ddpm" | "flow_matching", 
 reference's config.  `model.unet` (the diffusers UNet loaded by models/sdxl.py:25-40) is imported into the native engine at
 construction and written back by `save_checkpoint` / `sync_to_model`.  The reference's AdamWBF16 instance (main.py:73-86)
 holds per-tensor PyTorch state and is replaced by the fused equivalent on the packed arena (same hyper-parameters, read from
-its `param_groups`)."""
+its `param_groups`).  The fused class follows `optimizer.optimizer_type` (trainer.build_optimizer); an optimizer handed in whose
+class is the reference's `AdamWScheduleFreeKahan` selects the fused schedule-free Kahan AdamW as well, with `warmup_steps` and
+`kahan_sum` also read from its `param_groups`."""
 from __future__ import annotations
 
 import copy
@@ -53,6 +55,10 @@ class NativeMI355XTrainer(NativeSDXLTrainer):
             cfg.optimizer.beta1, cfg.optimizer.beta2 = float(b[0]), float(b[1])
             cfg.optimizer.epsilon = float(g.get("eps", cfg.optimizer.epsilon))
             cfg.optimizer.weight_decay = float(g.get("weight_decay", cfg.optimizer.weight_decay))
+            if type(optimizer).__name__ == "AdamWScheduleFreeKahan":
+                cfg.optimizer.optimizer_type = "adamw_schedule_free_kahan"
+                cfg.optimizer.warmup_steps = int(g.get("warmup_steps", cfg.optimizer.warmup_steps))
+                cfg.optimizer.kahan_sum = bool(g.get("kahan_sum", cfg.optimizer.kahan_sum))
         self.parent_trainer = parent_trainer
         super().__init__(model, native_opt, train_dataloader, device, wandb_logger, cfg, **kwargs)
 

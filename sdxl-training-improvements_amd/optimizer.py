@@ -1,4 +1,11 @@
-"""AdamWBF16 on the packed arenas: host mirror of the reference optimizer class, arithmetic in csrc/optimizer.hip.
+"""The fused optimizers on the packed arenas: host mirrors of the reference optimizer classes, arithmetic in csrc/optimizer.hip.
+
+AdamWBF16 (optimizer_type "adamw_bf16", the default) and AdamWScheduleFreeKahanBF16 ("adamw_schedule_free_kahan", see its
+docstring).  Both take their gradients from the arena, one fused launch per update, and share the host surface the trainer
+uses: step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups, step_count,
+state_dict / load_state_dict, state_arenas.
+
+AdamWBF16:
 
 Reference: src/training/optimizers/adamw_bfloat16/__init__.py (class AdamWBF16, `_make_step`) and stochastic/__init__.py.
 Same constructor arguments, `step()`, `zero_grad()`, `state_dict()` / `load_state_dict()`, `param_groups` (a real list
@@ -71,12 +78,18 @@ class AdamWBF16:
                 "param_groups": self.param_groups}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        if sd.get("algorithm", "adamw_bf16") != "adamw_bf16":
+            raise ValueError(f"optimizer state of {sd.get('algorithm')!r} cannot be loaded into AdamWBF16")
         st = sd["state"]
         self.step_count = int(st["step"])
         for k in ("exp_avg", "exp_avg_sq", "shift"):
             getattr(self, k).copy_(st[k])
         self.accumulated_decay = dict(st["accumulated_decay"])
         self.param_groups = sd["param_groups"]
+
+    def state_arenas(self):
+        """the state arenas laid out like the weight arena (what ZeRO-1 gathers before a checkpoint)"""
+        return (self.exp_avg, self.exp_avg_sq, self.shift)
 
     @torch.no_grad()
     def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
@@ -131,3 +144,164 @@ class AdamWBF16:
             self.net.zero_grads()
         for fn in self._post_step_hooks:
             fn(self)
+
+
+class AdamWScheduleFreeKahanBF16:
+    """AdamWScheduleFreeKahan on the packed arenas (reference: src/training/optimizers/adamw_schedulefree/__init__.py).
+
+    Host scalars are the reference's python doubles (k = step_count before the increment):
+        sched = (k+1)/warmup_steps while k < warmup_steps, else 1;  bc2 = 1 - beta2**(k+1)
+        adjusted_lr = lr*sched*sqrt(bc2)   (-> lr_max, get_last_lr());   step_size = adjusted_lr / sqrt(bc2)
+    and the element arithmetic runs in one launch over the arena (csrc/optimizer.hip, sfk_kernel) in one of two modes, the
+    build-only key optimizer.schedule_free_arithmetic:
+
+    "reference": the reference's bf16 tensor ops bit for bit (pinned to fixtures the reference class produced,
+        tests/golden/schedulefree_kahan.npz).  Each op rounds to bf16, and that sequence has defects:
+          1. its Kahan term is identically +0 for finite values: rn(b - p) = -rn(p - b), so (p - b) + (b - p) = +0;
+          2. updates below half an ulp of the weight are rounded away (at lr 1e-6 almost every weight stays put);
+          3. weight decay is not multiplied by lr: p <- p - wd*p per step (1 % per step at the default wd 0.01);
+          4. main.py cannot construct the class (OptimizerConfig.kwargs passes correct_bias, which __init__ rejects).
+        The reference adds kahan_comp to p.grad in place; here the gradient arena is read, never written (the term is
+        +0, so only the sign of a -0 gradient could differ, and nothing reads the gradient afterwards).
+    "compensated" (default): what the reference's docstring promises, "Kahan summation for more accurate parameter
+        updates when training in low precision".  The true parameter is x = p + c, with c the bf16 compensation kept in
+        the kahan_comp arena.  Moments and denominator are computed exactly as in reference mode, then in fp32:
+            x = p + c;  x -= (step_size*wd)*x  (decoupled, lr-scaled);  x -= step_size*(m/d);  p = rn(x);  c = rn(x - p)
+        Without kahan_sum, c is 0 and is not stored.  This is the default, unlike optimizer.reference_ema, because the
+        literal arithmetic does not train a bf16 UNet (defects 2 and 3) and no reference run can produce it (defect 4).
+
+    `correct_bias` is accepted (the reference's config passes it) and ignored: the reference has no such option either.
+    The reference never creates its "z" state, so eval() / train() are no-ops there and here.
+    There is no PyTorch fallback: the step fails loudly without libsdxlstep.so."""
+
+    ARITHMETIC = ("compensated", "reference")
+    algorithm = "adamw_schedule_free_kahan"
+
+    def __init__(self, net, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, warmup_steps: int = 0,
+                 kahan_sum: bool = True, arithmetic: str = "compensated", grad_round_bf16: bool = False, correct_bias=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if int(warmup_steps) < 0:
+            raise ValueError(f"Invalid warmup_steps value: {warmup_steps}")
+        arithmetic = str(arithmetic).lower()
+        if arithmetic not in self.ARITHMETIC:
+            raise ValueError(f"optimizer.schedule_free_arithmetic must be one of {self.ARITHMETIC}, got {arithmetic!r}")
+        self.net = net
+        self.L = getattr(net, "L", None)
+        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, warmup_steps=int(warmup_steps),
+                                  kahan_sum=bool(kahan_sum))]
+        w = net.weights
+        assert w.dtype == torch.bfloat16, "only bfloat16 is supported."
+        self.kahan_sum = bool(kahan_sum)
+        self.arithmetic = arithmetic
+        self.grad_round_bf16 = bool(grad_round_bf16)
+        self.exp_avg = torch.zeros_like(w)
+        self.exp_avg_sq = torch.zeros_like(w)
+        self.kahan_comp = torch.zeros_like(w) if self.kahan_sum else None
+        self.step_count = 0                                   # the reference's self.k
+        self.lr_max = -1.0
+        self.last_lr = -1.0
+        self._post_step_hooks = []
+
+    def register_step_post_hook(self, fn) -> None:
+        """fn(optimizer) after every step()."""
+        self._post_step_hooks.append(fn)
+
+    # ------------------------------------------------------------------ reference surface
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        self.net.zero_grads()
+
+    def eval(self) -> None:
+        """no-op, as in the reference (its "z" state is never created)"""
+
+    def train(self) -> None:
+        """no-op, as in the reference"""
+
+    def get_last_lr(self) -> float:
+        return self.last_lr
+
+    def state_arenas(self):
+        """the state arenas laid out like the weight arena (what ZeRO-1 gathers before a checkpoint)"""
+        return (self.exp_avg, self.exp_avg_sq) + ((self.kahan_comp,) if self.kahan_sum else ())
+
+    def _tag(self) -> Dict[str, Any]:
+        return {"algorithm": self.algorithm, "arithmetic": self.arithmetic, "kahan_sum": self.kahan_sum}
+
+    def state_dict(self) -> Dict[str, Any]:
+        st = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+              "lr_max": self.lr_max, "last_lr": self.last_lr}
+        if self.kahan_sum:
+            st["kahan_comp"] = self.kahan_comp
+        return {**self._tag(), "state": st, "param_groups": self.param_groups}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        got = {k: sd.get(k) for k in self._tag()}
+        if got != self._tag():
+            raise ValueError(f"optimizer state tagged {got} cannot be loaded into an optimizer configured as {self._tag()}")
+        st = sd["state"]
+        self.step_count = int(st["step"])
+        for k in ("exp_avg", "exp_avg_sq") + (("kahan_comp",) if self.kahan_sum else ()):
+            getattr(self, k).copy_(st[k])
+        self.lr_max, self.last_lr = float(st["lr_max"]), float(st["last_lr"])
+        self.param_groups = sd["param_groups"]
+
+    def schedule(self):
+        """(adjusted_lr, step_size) of the next step, in python doubles exactly as the reference computes them"""
+        grp = self.param_groups[0]
+        k, lr, beta2, warm = self.step_count, float(grp["lr"]), float(grp["betas"][1]), int(grp.get("warmup_steps", 0))
+        sched = (k + 1) / warm if k < warm else 1.0
+        bias_correction2 = 1 - beta2 ** (k + 1)
+        adjusted_lr = lr * sched * (bias_correction2 ** 0.5)
+        return adjusted_lr, adjusted_lr / (bias_correction2 ** 0.5)
+
+    @torch.no_grad()
+    def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
+             zero_grad: bool = False, pieces=None) -> None:
+        """One update of every parameter; arguments as AdamWBF16.step (no random numbers are involved, so a ZeRO-1 update
+        of `pieces` is bit-identical to the unsharded one by construction)."""
+        if self.L is None:
+            raise lib.SdxlError("AdamWScheduleFreeKahanBF16.step needs libsdxlstep.so (there is no PyTorch fallback for the optimizer step)")
+        grp = self.param_groups[0]
+        g = self.net.grads if grads is None else grads
+        if g.dtype not in (torch.float32, torch.bfloat16) or (pieces is None and g.numel() != self.net.weights.numel()):
+            raise ValueError("grads must be an fp32 or bf16 tensor in arena layout")
+        adjusted_lr, step_size = self.schedule()
+        self.lr_max = max(adjusted_lr, self.lr_max)
+        cfg = lib.AdamWConfig()
+        lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
+        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
+        cfg.step = float(self.step_count + 1)
+        cfg.grad_round_bf16 = int(self.grad_round_bf16)
+        cfg.algorithm = 1
+        cfg.kahan_sum = int(self.kahan_sum)
+        cfg.sf_reference = int(self.arithmetic == "reference")
+        cfg.weight_decay = float(grp["weight_decay"])
+        cfg.sf_step_size = step_size
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if self.net.weights.is_cuda else None
+        gsz = g.element_size()
+        todo = [(0, self.net.weights.numel(), 0)] if pieces is None else list(pieces)
+        for off, cnt, goff in todo:
+            at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o) if t is not None else None
+            lib.check(self.L.sdxl_adamw_bf16_step(at(self.net.weights), C.c_void_p(g.data_ptr() + gsz * goff),
+                                                  0 if g.dtype == torch.float32 else 1, at(self.exp_avg), at(self.exp_avg_sq),
+                                                  at(self.kahan_comp), cnt, C.byref(cfg), _ptr(grad_scale), None, st),
+                      "sdxl_adamw_bf16_step (schedule-free Kahan)")
+        self.step_count += 1
+        self.last_lr = adjusted_lr
+        if zero_grad:
+            self.net.zero_grads()
+        for fn in self._post_step_hooks:
+            fn(self)
+
+
+FUSED = (AdamWBF16, AdamWScheduleFreeKahanBF16)          # the optimizers whose step() takes the arena, grad_scale and pieces
+# optimizer_type (lower-cased, as the reference's OptimizerConfig.class_name does) -> the fused class built for it
+BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16}

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import logging
 import math
 import os
 import time
@@ -41,9 +42,11 @@ import torch
 from . import distributed as D
 from . import lib
 from .config import Config
-from .optimizer import AdamWBF16
+from .optimizer import BY_TYPE, FUSED, AdamWBF16, AdamWScheduleFreeKahanBF16
 from .scheduler import NoiseScheduler
 from .unet import NativeUNet, config_from_unet
+
+logger = logging.getLogger(__name__)
 
 REQUIRED_KEYS = {"vae_latents", "prompt_embeds", "pooled_prompt_embeds", "time_ids", "metadata"}
 
@@ -97,13 +100,10 @@ class NativeSDXLTrainer:
             raise TypeError("model.unet must be a NativeUNet or a module with a diffusers-keyed state_dict(); got "
                             f"{type(unet).__name__}")
         self.noise_scheduler = NoiseScheduler(self.config, "cpu")
-        self.optimizer = optimizer if optimizer is not None else AdamWBF16(       # main.py:73-86 (optimizer_type adamw_bf16)
-            self.net, lr=self.config.optimizer.learning_rate, betas=(self.config.optimizer.beta1, self.config.optimizer.beta2),
-            eps=self.config.optimizer.epsilon, weight_decay=self.config.optimizer.weight_decay,
-            reference_ema=bool(getattr(self.config.optimizer, "reference_ema", True)))
+        self.optimizer = optimizer if optimizer is not None else build_optimizer(self.net, self.config.optimizer)
         self._clip_coef = None
         # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
-        want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, AdamWBF16)
+        want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, FUSED)
         seg_sizes = [n for _off, n in self.net.segment_ranges()] if hasattr(self.net, "segment_ranges") else None
         # force_exchange (build-only key / SDXL_FORCE_EXCHANGE=1): run the exchange through the backend even at world size 1
         force = bool(getattr(self.config.training, "force_exchange", False)) or os.environ.get("SDXL_FORCE_EXCHANGE", "0") == "1"
@@ -245,7 +245,7 @@ class NativeSDXLTrainer:
         the norm is taken over the exchanged gradients: the whole all-reduced arena, or (ZeRO-1) this rank's
         reduce-scattered slices + one float all-reduced -- the coefficient is then the same bits on every rank."""
         self.sync.finish()                                   # the asynchronous exchange must have landed
-        fused = isinstance(self.optimizer, AdamWBF16)        # the coefficient rides into the fused optimizer kernel
+        fused = isinstance(self.optimizer, FUSED)            # the coefficient rides into the fused optimizer kernel
         g = self.sync.reduced() if self.sync.active else self.net.grads
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if g.is_cuda else None
         if g.is_cuda:                                        # squared norm + coefficient on the device (HIP kernels)
@@ -279,7 +279,7 @@ class NativeSDXLTrainer:
         if self.config.training.clip_grad_norm and self.config.training.clip_grad_norm > 0:
             gn = self.clip_grad_norm_(float(self.config.training.clip_grad_norm))
         if self.optimizer is not None:
-            if isinstance(self.optimizer, AdamWBF16):
+            if isinstance(self.optimizer, FUSED):
                 if self.sync.active and self.sharded:        # ZeRO-1: update this rank's slices, then all-gather the parameters
                     self.optimizer.step(self.sync.reduced(), grad_scale=self._clip_coef, pieces=self.sync.pieces)
                     self.sync.gather_params(self.net.weights)
@@ -383,14 +383,15 @@ class NativeSDXLTrainer:
         return save_dir
 
     def _zero1_active(self) -> bool:
-        return bool(self.sharded and self.sync.active and isinstance(self.optimizer, AdamWBF16) and getattr(self.sync, "buckets", None))
+        return bool(self.sharded and self.sync.active and isinstance(self.optimizer, FUSED) and getattr(self.sync, "buckets", None))
 
     def prepare_checkpoint(self) -> None:
         """COLLECTIVE -- every rank calls it, at the same point of its loop, before rank 0 calls save_checkpoint().  Under ZeRO-1
-        each rank has updated exp_avg / exp_avg_sq / shift on its own slices only: all-gather them so that the optimizer.pt rank 0
-        writes holds the complete state.  No-op otherwise.  The gathered state stays valid until the next optimizer step."""
+        each rank has updated its state arenas (optimizer.state_arenas(): exp_avg / exp_avg_sq / shift or kahan_comp) on its own
+        slices only: all-gather them so that the optimizer.pt rank 0 writes holds the complete state.  No-op otherwise.  The
+        gathered state stays valid until the next optimizer step."""
         if self._zero1_active():
-            for arena in (self.optimizer.exp_avg, self.optimizer.exp_avg_sq, self.optimizer.shift):
+            for arena in self.optimizer.state_arenas():
                 self.sync.gather_arena(arena)
         self._opt_state_step = self._step_counter()
 
@@ -433,6 +434,24 @@ class NativeSDXLTrainer:
                 "exp_avg / exp_avg_sq / shift are current). Call prepare_checkpoint() on every rank before save_checkpoint(), or train "
                 "with training.shard_optimizer = false when the caller's loop saves on rank 0 only (INTEGRATION.md section 3)")
         self.optimizer.load_state_dict(sd)
+
+
+def build_optimizer(net, oc):
+    """The fused optimizer `optimizer_type` names (case-insensitive, as the reference's OptimizerConfig.class_name;
+    main.py:73-86 builds it from config.optimizer.kwargs).  A type this build has no fused kernel for ("soap", "adamw", ...)
+    trains with AdamWBF16, and the warning names it."""
+    kind = str(getattr(oc, "optimizer_type", "adamw_bf16")).lower()
+    cls = BY_TYPE.get(kind)
+    if cls is None:
+        logger.warning("optimizer_type %r has no fused implementation in this build: training with AdamWBF16 (adamw_bf16) instead",
+                       getattr(oc, "optimizer_type", None))
+        cls = AdamWBF16
+    common = dict(lr=oc.learning_rate, betas=(oc.beta1, oc.beta2), eps=oc.epsilon, weight_decay=oc.weight_decay)
+    if cls is AdamWScheduleFreeKahanBF16:
+        return cls(net, **common, warmup_steps=int(getattr(oc, "warmup_steps", 0)), kahan_sum=bool(getattr(oc, "kahan_sum", True)),
+                   arithmetic=str(getattr(oc, "schedule_free_arithmetic", "compensated")),
+                   correct_bias=getattr(oc, "correct_bias", None))
+    return AdamWBF16(net, **common, reference_ema=bool(getattr(oc, "reference_ema", True)))
 
 
 def checkpoint_dir(epoch_or_path, is_final: bool = False) -> Path:
