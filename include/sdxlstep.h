@@ -251,8 +251,14 @@ typedef struct {
   double weight_decay;         /* algorithm 1 */
   double sf_step_size;         /* algorithm 1: the reference's step_size = adjusted_lr / sqrt(1 - beta2^(k+1)), computed by
                                   the caller in double precision */
+  /* ---- appended: fp32 EMA of the weights, both algorithms (sdxl_adamw_default_config zeroes them: no EMA) ---- */
+  float* ema;                  /* NULL = no EMA; else an fp32 array aligned with p (its element 0 is p's element 0, 16-byte
+                                  aligned).  Once an element's new bf16 p is final: e <- e - omd * (e - float(p)), three
+                                  separately rounded fp32 ops (t1 = e - p, t2 = omd * t1, e = e - t2), i.e. diffusers'
+                                  EMAModel.step on the parameter the module holds (not p + shift / kahan_comp) */
+  float ema_one_minus_decay;   /* omd: 1 - decay of this update, in [0, 1] (the caller's python double rounded to float32) */
 } sdxl_adamw_config;
-SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1, algorithm 0 */
+SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1, algorithm 0, no EMA */
 SDXL_API int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,
                          void* stream);

@@ -60,6 +60,15 @@ class TrainingConfig:                    # data/config.py:152-168
                                          # all-gather) instead of all-reduce + a full update on every rank
     force_exchange: bool = False         # build-only key: drive the gradient exchange through the backend even at world size 1
                                          # (one-GPU RCCL test, tests/test_gpu_rccl.py); SDXL_FORCE_EXCHANGE=1 does the same
+    # build-only keys: an fp32 EMA of the UNet weights updated inside the fused optimizer kernel (diffusers' EMAModel, the SDXL
+    # script's --use_ema); see ema.py::WeightEMA for the rule.  Needs a fused optimizer.
+    use_ema: bool = False
+    ema_decay: float = 0.9999            # upper bound of the decay
+    ema_min_decay: float = 0.0           # lower bound of the decay
+    ema_update_after_step: int = 0       # optimizer steps during which the EMA just copies the weights
+    ema_use_warmup: bool = False         # the power warm-up schedule instead of (1+k)/(10+k)
+    ema_inv_gamma: float = 1.0           # warm-up parameter
+    ema_power: float = 2 / 3             # warm-up parameter
 
 
 @dataclass

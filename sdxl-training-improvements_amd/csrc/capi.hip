@@ -888,6 +888,10 @@ int sdxl_adamw_default_config(sdxl_adamw_config* c) {
   c->reference_ema = 1;
   return 0;
 }
+// the EMA fields, read by both algorithms
+static bool ema_omd_ok(const sdxl_adamw_config* c) {
+  return c->ema == nullptr || (c->ema_one_minus_decay >= 0.f && c->ema_one_minus_decay <= 1.f);
+}
 // algorithm 1 of sdxl_adamw_bf16_step: every argument error is reported before anything touches the device
 static int sf_kahan_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* kahan_comp, size_t n, const sdxl_adamw_config* c,
                          const float* grad_scale_dev, const unsigned short* rand_inject, hipStream_t st) {
@@ -912,6 +916,7 @@ static int sf_kahan_step(void* p, const void* grad, int grad_dtype, void* m, voi
   q.decay = (float)(ss * wd);
   q.grad_round_bf16 = c->grad_round_bf16;
   q.grad_scale = grad_scale_dev;
+  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
   return launch_sfk(q, c->sf_reference, st);
 }
 int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
@@ -920,6 +925,7 @@ int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, voi
   ARG_CHECK(c, "null config");
   ARG_CHECK(grad_dtype == 0 || grad_dtype == 1, "adamw: grad_dtype %d (0 = fp32, 1 = bf16)", grad_dtype);
   ARG_CHECK(c->algorithm == 0 || c->algorithm == 1, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan)", c->algorithm);
+  ARG_CHECK(ema_omd_ok(c), "adamw: ema_one_minus_decay %g must lie in [0, 1]", (double)c->ema_one_minus_decay);
   if (c->algorithm == 1) return sf_kahan_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
   ARG_CHECK(c->step >= 1.0 && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0,
             "adamw: invalid hyper-parameters");
@@ -942,6 +948,7 @@ int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, voi
   q.seed_lo = (unsigned)c->seed; q.seed_hi = (unsigned)(c->seed >> 32);
   q.step_counter = (unsigned)c->step;
   q.elem_offset = (size_t)c->elem_offset;
+  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
   return launch_adamw_bf16(q, (hipStream_t)st);
 }
 int sdxl_adamw_decay(void* shift, const void* p, size_t n, float decay, void* st) {

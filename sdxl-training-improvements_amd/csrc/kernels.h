@@ -397,6 +397,8 @@ struct AdamWP {
   unsigned seed_lo, seed_hi, step_counter;
   size_t elem_offset;          // arena index of element 0 of this launch (multiple of 8): the Philox counters are those of the
                                // full-arena launch, so a sharded (ZeRO-1) update is bit-identical to the unsharded one
+  float* ema;                  // fp32 EMA of the weights, element 0 = p's element 0, or nullptr (no EMA)
+  float ema_omd;               // 1 - decay of this update, float32: e <- e - omd * (e - p_new), three separately rounded ops
 };
 int launch_adamw_bf16(const AdamWP& q, hipStream_t st);
 // schedule-free Kahan AdamW (csrc/optimizer.hip, sfk_kernel): one launch over the arena slice
@@ -417,6 +419,8 @@ struct SfkP {
   float decay;                 // compensated mode: step_size * weight_decay (float32)
   int grad_round_bf16;         // round the (scaled) gradient to bf16 first
   const float* grad_scale;     // device scalar multiplied into the gradient (unscale / clip), or nullptr
+  float* ema;                  // as AdamWP::ema / ema_omd
+  float ema_omd;
 };
 int launch_sfk(const SfkP& q, int reference, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);

@@ -42,7 +42,22 @@ __device__ __forceinline__ bf16 sr(float x, unsigned r16) {                     
   return __builtin_bit_cast(bf16, (unsigned short)(u >> 16));
 }
 
-template <bool INJECT>
+// fp32 EMA of the weights, fused into both updates (diffusers EMAModel.step, `s_param.sub_(one_minus_decay * (s_param - param))`)
+// on 8 elements whose new bf16 p is final: t1 = e - p, t2 = omd * t1, e = e - t2, each rounded on its own -- the file-wide
+// fp contract(off) keeps the compiler from fusing t2 into the last subtraction.  +8 B per element (fp32 read + write).
+__device__ __forceinline__ void ema_update8(float* ema, const bf16x8& pv, float omd) {
+  f32x4 a = __builtin_nontemporal_load((const f32x4*)ema), b = __builtin_nontemporal_load((const f32x4*)(ema + 4));
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = a[e] - omd * (a[e] - bf(pv[e]));
+    b[e] = b[e] - omd * (b[e] - bf(pv[e + 4]));
+  }
+  __builtin_nontemporal_store(a, (f32x4*)ema);
+  __builtin_nontemporal_store(b, (f32x4*)(ema + 4));
+}
+
+// EMA: also update q.ema from the new p (ema_update8); EMA = false is the update alone
+template <bool INJECT, bool EMA>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
   const size_t nvec = q.n / 8;
   const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
@@ -106,6 +121,7 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
     __builtin_nontemporal_store(mv, (bf16x8*)(q.m + e0));
     __builtin_nontemporal_store(vv, (bf16x8*)(q.v + e0));
     __builtin_nontemporal_store(sv, (bf16x8*)(q.shift + e0));
+    if constexpr (EMA) ema_update8(q.ema + e0, pv, q.ema_omd);   // tracks p itself, not p + shift
   }
 }
 
@@ -118,14 +134,21 @@ __global__ void adamw_decay_kernel(bf16* shift, const bf16* p, size_t n, float a
 int launch_adamw_bf16(const AdamWP& q, hipStream_t st) {
   ARG_CHECK(q.p && q.m && q.v && q.shift && (q.grad_f32 || q.grad_bf16), "adamw: missing buffers");
   ARG_CHECK(q.n % 8 == 0 && q.elem_offset % 8 == 0, "adamw: n=%zu, elem_offset=%zu: each must be a multiple of 8", q.n, q.elem_offset);
-  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.shift | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16) & 15) == 0,
+  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.shift | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16 |
+              (uintptr_t)q.ema) & 15) == 0,
             "adamw: buffers must be 16-byte aligned");
   if (q.n == 0) return 0;
   size_t nvec = q.n / 8;
   size_t blocks = (nvec + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;      // 16 workgroups per CU, grid-stride the rest
-  if (q.rand) hipLaunchKernelGGL(adamw_bf16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL(adamw_bf16_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, q);
+  const dim3 grid((unsigned)blocks);
+  if (q.ema) {
+    if (q.rand) hipLaunchKernelGGL((adamw_bf16_kernel<true, true>), grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((adamw_bf16_kernel<false, true>), grid, dim3(256), 0, st, q);
+  } else {
+    if (q.rand) hipLaunchKernelGGL((adamw_bf16_kernel<true, false>), grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((adamw_bf16_kernel<false, false>), grid, dim3(256), 0, st, q);
+  }
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -148,8 +171,9 @@ int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, h
 //        c = rn(rn(p - rn(p + u)) + rn(rn(p + u) - p))   (+0 for every finite value, as in the reference).
 //        The gradient is read only: the reference's in-place p.grad += kahan_comp is not reproduced.
 //   !REF ("compensated"): x = p + c in fp32; x -= (step_size*wd)*x; x -= step_size*(m/d); p = rn(x); c = rn(x - p).
-// KAHAN = kahan_sum (without it c is neither read nor written); F32G = fp32 (native arena) or bf16 gradients.
-template <bool REF, bool KAHAN, bool F32G>
+// KAHAN = kahan_sum (without it c is neither read nor written); F32G = fp32 (native arena) or bf16 gradients; EMA = also update
+// q.ema from the new p (ema_update8: tracks p, not p + c).
+template <bool REF, bool KAHAN, bool F32G, bool EMA>
 __global__ __launch_bounds__(256) void sfk_kernel(const SfkP q) {
   const size_t nvec = q.n / 8;
   const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
@@ -205,28 +229,35 @@ __global__ __launch_bounds__(256) void sfk_kernel(const SfkP q) {
     __builtin_nontemporal_store(mv, (bf16x8*)(q.m + e0));
     __builtin_nontemporal_store(vv, (bf16x8*)(q.v + e0));
     if constexpr (KAHAN) __builtin_nontemporal_store(cv, (bf16x8*)(q.c + e0));
+    if constexpr (EMA) ema_update8(q.ema + e0, pv, q.ema_omd);
   }
 }
 
-template <bool REF, bool KAHAN>
+template <bool REF, bool KAHAN, bool EMA>
 static void launch_sfk_g(const SfkP& q, unsigned blocks, hipStream_t st) {
-  if (q.grad_f32) hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, true>), dim3(blocks), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, false>), dim3(blocks), dim3(256), 0, st, q);
+  if (q.grad_f32) hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, true, EMA>), dim3(blocks), dim3(256), 0, st, q);
+  else hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, false, EMA>), dim3(blocks), dim3(256), 0, st, q);
+}
+template <bool REF, bool KAHAN>
+static void launch_sfk_e(const SfkP& q, unsigned blocks, hipStream_t st) {
+  if (q.ema) launch_sfk_g<REF, KAHAN, true>(q, blocks, st);
+  else launch_sfk_g<REF, KAHAN, false>(q, blocks, st);
 }
 
 int launch_sfk(const SfkP& q, int reference, hipStream_t st) {
   ARG_CHECK(q.p && q.m && q.v && (q.grad_f32 || q.grad_bf16), "schedule-free: missing buffers");
   ARG_CHECK(q.n % 8 == 0, "schedule-free: n=%zu must be a multiple of 8", q.n);
-  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.c | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16) & 15) == 0,
+  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.c | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16 |
+              (uintptr_t)q.ema) & 15) == 0,
             "schedule-free: buffers must be 16-byte aligned");
   if (q.n == 0) return 0;
   size_t blocks = (q.n / 8 + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;      // as adamw_bf16_kernel: 16 workgroups per CU, grid-stride the rest
   const unsigned nb = (unsigned)blocks;
   if (reference) {
-    if (q.c) launch_sfk_g<true, true>(q, nb, st); else launch_sfk_g<true, false>(q, nb, st);
+    if (q.c) launch_sfk_e<true, true>(q, nb, st); else launch_sfk_e<true, false>(q, nb, st);
   } else {
-    if (q.c) launch_sfk_g<false, true>(q, nb, st); else launch_sfk_g<false, false>(q, nb, st);
+    if (q.c) launch_sfk_e<false, true>(q, nb, st); else launch_sfk_e<false, false>(q, nb, st);
   }
   HIP_CHECK_RET(hipGetLastError());
   return 0;

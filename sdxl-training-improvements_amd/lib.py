@@ -54,7 +54,9 @@ class AdamWConfig(C.Structure):
                 ("grad_round_bf16", C.c_int), ("seed", C.c_ulonglong), ("elem_offset", C.c_ulonglong),
                 # appended: algorithm 0 = AdamW_BF16, 1 = schedule-free Kahan (optimizer.AdamWScheduleFreeKahanBF16)
                 ("algorithm", C.c_int), ("kahan_sum", C.c_int), ("sf_reference", C.c_int),
-                ("weight_decay", C.c_double), ("sf_step_size", C.c_double)]
+                ("weight_decay", C.c_double), ("sf_step_size", C.c_double),
+                # appended: fp32 EMA of the weights (ema.WeightEMA), NULL = none
+                ("ema", C.c_void_p), ("ema_one_minus_decay", C.c_float)]
 
 
 _vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t

@@ -76,5 +76,6 @@ class NativeMI355XTrainer(NativeSDXLTrainer):
             save_dir = Path(out) if isinstance(out, (str, Path)) else checkpoint_dir(epoch_or_path, is_final)
             save_dir.mkdir(parents=True, exist_ok=True)
             self.save_optimizer_state(save_dir)
+            self.save_ema_state(save_dir)                  # training.use_ema: unet_ema/ + ema.json next to the parent's files
             return out
         return super().save_checkpoint(epoch_or_path, is_final)

@@ -3,7 +3,7 @@
 AdamWBF16 (optimizer_type "adamw_bf16", the default) and AdamWScheduleFreeKahanBF16 ("adamw_schedule_free_kahan", see its
 docstring).  Both take their gradients from the arena, one fused launch per update, and share the host surface the trainer
 uses: step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups, step_count,
-state_dict / load_state_dict, state_arenas.
+state_dict / load_state_dict, state_arenas, attach_ema (an ema.WeightEMA updated inside the same launch, on the same pieces).
 
 AdamWBF16:
 
@@ -27,6 +27,19 @@ from . import lib
 
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _checked_ema(ema, weights: torch.Tensor):
+    """the kernel writes the EMA arena wherever it updates `weights`: refuse an arena that does not cover them element for element"""
+    if ema is None:
+        return None
+    a = getattr(ema, "arena", None)
+    if not (torch.is_tensor(a) and a.dtype == torch.float32 and a.is_contiguous() and a.numel() == weights.numel()
+            and a.device == weights.device and getattr(ema, "param_elems", None) == weights.numel()):
+        raise ValueError(f"attach_ema: the EMA must hold a contiguous fp32 arena of {weights.numel()} elements on {weights.device}, "
+                         f"the weights' size and device; got {type(ema).__name__} with "
+                         + (f"{a.dtype} x {a.numel()} on {a.device}" if torch.is_tensor(a) else "no arena"))
+    return ema
 
 
 class AdamWBF16:
@@ -63,10 +76,16 @@ class AdamWBF16:
         g = torch.Generator().manual_seed(self.seed)
         self.accumulated_decay = {k: float(torch.rand([], generator=g) * self.decay_threshold) for k in self.ranges}
         self._post_step_hooks = []
+        self.ema = None
 
     def register_step_post_hook(self, fn) -> None:
         """fn(optimizer) after every step() (same idea as torch.optim.Optimizer.register_step_post_hook)."""
         self._post_step_hooks.append(fn)
+
+    def attach_ema(self, ema) -> None:
+        """ema (ema.WeightEMA): from now on every step() also updates its arena, fused into the update (None detaches).
+        ValueError when its arena is not an fp32 image of this optimizer's weight arena (size, device)."""
+        self.ema = _checked_ema(ema, self.net.weights)
 
     # ------------------------------------------------------------------ reference surface
     def zero_grad(self, set_to_none: bool = False) -> None:
@@ -123,11 +142,14 @@ class AdamWBF16:
         cfg.reference_ema = int(self.reference_ema)
         cfg.grad_round_bf16 = int(self.grad_round_bf16)
         cfg.seed = self.seed
+        if self.ema is not None:
+            cfg.ema_one_minus_decay = self.ema.advance()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if self.net.weights.is_cuda else None
         gsz = g.element_size()
         todo = [(0, self.net.weights.numel(), 0)] if pieces is None else list(pieces)
         for off, cnt, goff in todo:
             cfg.elem_offset = off
+            cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
             at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o)
             lib.check(self.L.sdxl_adamw_bf16_step(at(self.net.weights), C.c_void_p(g.data_ptr() + gsz * goff),
                                                   0 if g.dtype == torch.float32 else 1, at(self.exp_avg), at(self.exp_avg_sq),
@@ -210,10 +232,15 @@ class AdamWScheduleFreeKahanBF16:
         self.lr_max = -1.0
         self.last_lr = -1.0
         self._post_step_hooks = []
+        self.ema = None
 
     def register_step_post_hook(self, fn) -> None:
         """fn(optimizer) after every step()."""
         self._post_step_hooks.append(fn)
+
+    def attach_ema(self, ema) -> None:
+        """as AdamWBF16.attach_ema: the EMA tracks p, not p + kahan_comp"""
+        self.ema = _checked_ema(ema, self.net.weights)
 
     # ------------------------------------------------------------------ reference surface
     def zero_grad(self, set_to_none: bool = False) -> None:
@@ -285,10 +312,13 @@ class AdamWScheduleFreeKahanBF16:
         cfg.sf_reference = int(self.arithmetic == "reference")
         cfg.weight_decay = float(grp["weight_decay"])
         cfg.sf_step_size = step_size
+        if self.ema is not None:
+            cfg.ema_one_minus_decay = self.ema.advance()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if self.net.weights.is_cuda else None
         gsz = g.element_size()
         todo = [(0, self.net.weights.numel(), 0)] if pieces is None else list(pieces)
         for off, cnt, goff in todo:
+            cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
             at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o) if t is not None else None
             lib.check(self.L.sdxl_adamw_bf16_step(at(self.net.weights), C.c_void_p(g.data_ptr() + gsz * goff),
                                                   0 if g.dtype == torch.float32 else 1, at(self.exp_avg), at(self.exp_avg_sq),

@@ -42,6 +42,7 @@ import torch
 from . import distributed as D
 from . import lib
 from .config import Config
+from .ema import WeightEMA
 from .optimizer import BY_TYPE, FUSED, AdamWBF16, AdamWScheduleFreeKahanBF16
 from .scheduler import NoiseScheduler
 from .unet import NativeUNet, config_from_unet
@@ -101,6 +102,7 @@ class NativeSDXLTrainer:
                             f"{type(unet).__name__}")
         self.noise_scheduler = NoiseScheduler(self.config, "cpu")
         self.optimizer = optimizer if optimizer is not None else build_optimizer(self.net, self.config.optimizer)
+        self.ema = build_ema(self.net, self.optimizer, self.config.training)     # None unless training.use_ema
         self._clip_coef = None
         # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
         want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, FUSED)
@@ -345,13 +347,14 @@ class NativeSDXLTrainer:
             self.save_checkpoint(num_epochs, is_final=True)
 
     # -------------------------------------------------------------------------------- weights out (row f4)
-    def sync_to_model(self) -> None:
+    def sync_to_model(self, ema: bool = False) -> None:
         """Write the trained native weights back into the caller's PyTorch UNet (diffusers keys, the module's own dtypes), so
         everything the reference does with `model.unet` afterwards -- `save_pretrained` (models/sdxl.py:246-288), validation
-        sampling -- sees them."""
+        sampling -- sees them.  ema=True writes the EMA of the weights instead (training.use_ema): `save_pretrained` and
+        validation then see the averaged UNet."""
         if self._torch_unet is None:
             return
-        sd = self.net.state_dict()
+        sd = self.ema_state_dict() if ema else self.net.state_dict()
         ref = self._torch_unet.state_dict()
         self._torch_unet.load_state_dict({k: v.to(device=ref[k].device, dtype=ref[k].dtype) for k, v in sd.items()}, strict=True)
 
@@ -380,7 +383,49 @@ class NativeSDXLTrainer:
             json.dump(self.config.to_dict(), f, indent=2)
         if self.optimizer is not None and callable(getattr(self.optimizer, "state_dict", None)):
             torch.save(self._optimizer_state_for_save(), str(save_dir / "optimizer.pt"))      # (raises under ZeRO-1 on a stale state)
+        self.save_ema_state(save_dir)
         return save_dir
+
+    # -------------------------------------------------------------------------------- EMA of the weights (training.use_ema)
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """the EMA in diffusers keys and shapes, fp32, on the device (through the library's own layout inverse).  Under ZeRO-1 each
+        rank's arena is current only on its own slices until prepare_checkpoint() on every rank gathers it: before that (since the
+        last optimizer step) this raises instead of returning a partly stale EMA -- and so do sync_to_model(ema=True) and
+        save_ema_state, which read the EMA through it."""
+        if self.ema is None:
+            raise ValueError("ema_state_dict: this trainer keeps no EMA (training.use_ema is false)")
+        self._require_gathered("ema_state_dict (also behind sync_to_model(ema=True) and save_checkpoint)", "Nothing was read.")
+        return self.ema.state_tensors()
+
+    def save_ema_state(self, save_dir) -> None:
+        """`unet_ema/diffusion_pytorch_model.safetensors` (fp32, diffusers keys) and `ema.json` (step and settings) when the EMA
+        is on; no collective (see save_checkpoint), and under ZeRO-1 the same stale-state guard as optimizer.pt."""
+        if self.ema is None or not D.is_main_process():
+            return
+        self._require_gathered("save_checkpoint", "The model weights and config.json of this checkpoint were written; unet_ema/ "
+                                                  "and ema.json were not.")
+        from safetensors.torch import save_file
+        d = Path(save_dir)
+        (d / "unet_ema").mkdir(parents=True, exist_ok=True)
+        save_file({k: v.cpu().contiguous() for k, v in self.ema_state_dict().items()},
+                  str(d / "unet_ema" / "diffusion_pytorch_model.safetensors"))
+        with open(d / "ema.json", "w") as f:
+            json.dump(self.ema.state_dict(), f, indent=2)
+
+    def load_ema_state(self, checkpoint_dir) -> None:
+        """resume the EMA from what save_ema_state wrote: the packed arena comes back bit for bit, the step count with it.  The
+        settings and the arena size must match this trainer's (ValueError otherwise)."""
+        if self.ema is None:
+            raise ValueError("load_ema_state: this trainer keeps no EMA (training.use_ema is false)")
+        from safetensors.torch import load_file
+        d = Path(checkpoint_dir)
+        with open(d / "ema.json") as f:
+            st = json.load(f)
+        tensors = load_file(str(d / "unet_ema" / "diffusion_pytorch_model.safetensors"))
+        # every check before anything changes, the step count last: a refused or unreadable checkpoint leaves the EMA as it was
+        self.ema.check_state_dict(st)
+        self.ema.load_tensors(tensors)
+        self.ema.load_state_dict(st)
 
     def _zero1_active(self) -> bool:
         return bool(self.sharded and self.sync.active and isinstance(self.optimizer, FUSED) and getattr(self.sync, "buckets", None))
@@ -393,24 +438,34 @@ class NativeSDXLTrainer:
         if self._zero1_active():
             for arena in self.optimizer.state_arenas():
                 self.sync.gather_arena(arena)
+            if self.ema is not None:                 # the EMA is updated on the same slices, inside the same launches
+                self.sync.gather_arena(self.ema.arena)
         self._opt_state_step = self._step_counter()
 
     def _step_counter(self):
-        return getattr(self.optimizer, "step_count", None) if self.optimizer is not None else None
+        n = getattr(self.optimizer, "step_count", None) if self.optimizer is not None else None
+        return n if self.ema is None else (n, self.ema.optimization_step)
+
+    def _require_gathered(self, what: str, consequence: str) -> None:
+        """Under ZeRO-1 the state arenas (and the EMA) are current only on this rank's slices until prepare_checkpoint(): refuse
+        `what` (a save, or a read of the EMA) on a state that has stepped since the last gather."""
+        if self._zero1_active() and getattr(self, "_opt_state_step", object()) != self._step_counter():
+            # Surfaces at SAVE time, not at resume time: a file with this rank's slices only could never be loaded again
+            # (load_optimizer_state refuses it), and the run that could still have gathered the state would be long gone.
+            raise RuntimeError(
+                f"{what} under ZeRO-1 without prepare_checkpoint() on every rank since the last optimizer step: this rank "
+                f"(rank {int(self.sync.rank)} of {int(self.sync.world)}) holds only its own slices of exp_avg / exp_avg_sq / shift"
+                f"{' and of the EMA' if self.ema is not None else ''}. "
+                "Call prepare_checkpoint() on EVERY rank first (train() does, before a final save), or train with "
+                "training.shard_optimizer = false when the caller's loop saves on rank 0 only (INTEGRATION.md section 3). "
+                f"{consequence}")
 
     def _optimizer_state_for_save(self) -> dict:
         osd = self.optimizer.state_dict()
         if isinstance(osd.get("state"), dict):
             osd["state"] = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in osd["state"].items()}
-        if self._zero1_active() and getattr(self, "_opt_state_step", object()) != self._step_counter():
-            # Surfaces at SAVE time, not at resume time: a file with this rank's slices only could never be loaded again
-            # (load_optimizer_state refuses it), and the run that could still have gathered the state would be long gone.
-            raise RuntimeError(
-                "save_checkpoint under ZeRO-1 without prepare_checkpoint() on every rank since the last optimizer step: this rank "
-                f"(rank {int(self.sync.rank)} of {int(self.sync.world)}) holds only its own slices of exp_avg / exp_avg_sq / shift. "
-                "Call prepare_checkpoint() on EVERY rank first (train() does, before a final save), or train with "
-                "training.shard_optimizer = false when the caller's loop saves on rank 0 only (INTEGRATION.md section 3). "
-                "The model weights and config.json of this checkpoint were written; optimizer.pt was not.")
+        self._require_gathered("save_checkpoint", "The model weights and config.json of this checkpoint were written; optimizer.pt"
+                               + (", unet_ema/ and ema.json were not." if self.ema is not None else " was not."))
         return osd
 
     def save_optimizer_state(self, save_dir) -> None:
@@ -452,6 +507,22 @@ def build_optimizer(net, oc):
                    arithmetic=str(getattr(oc, "schedule_free_arithmetic", "compensated")),
                    correct_bias=getattr(oc, "correct_bias", None))
     return AdamWBF16(net, **common, reference_ema=bool(getattr(oc, "reference_ema", True)))
+
+
+def build_ema(net, optimizer, tc) -> Optional[WeightEMA]:
+    """The fp32 EMA of the weights when `training.use_ema` is set (after the weights are loaded: it starts as their fp32 image),
+    attached to the fused optimizer whose kernel updates it; None otherwise."""
+    if not bool(getattr(tc, "use_ema", False)):
+        return None
+    if not isinstance(optimizer, FUSED):
+        raise ValueError(f"training.use_ema needs one of the fused optimizers ({', '.join(c.__name__ for c in FUSED)}): the EMA "
+                         f"update runs inside their kernel, and {type(optimizer).__name__} has none")
+    ema = WeightEMA(net, decay=float(getattr(tc, "ema_decay", 0.9999)), min_decay=float(getattr(tc, "ema_min_decay", 0.0)),
+                    update_after_step=int(getattr(tc, "ema_update_after_step", 0)),
+                    use_ema_warmup=bool(getattr(tc, "ema_use_warmup", False)), inv_gamma=float(getattr(tc, "ema_inv_gamma", 1.0)),
+                    power=float(getattr(tc, "ema_power", 2 / 3)))
+    optimizer.attach_ema(ema)
+    return ema
 
 
 def checkpoint_dir(epoch_or_path, is_final: bool = False) -> Path:
