@@ -47,6 +47,13 @@ typedef struct {
   int use_min_snr;       /* model.min_snr_gamma is not None */
   float min_snr_gamma;
   int use_ztsnr;         /* clamp noisy latents to +-20000 */
+  /* ---- appended: element loss (zero = squared error, as before).  With d = pred - target:
+   *   0 l2        l(d) = d^2                          l'(d) = 2 d
+   *   1 huber     l(d) = 2 c (sqrt(d^2 + c^2) - c)    l'(d) = 2 c d / sqrt(d^2 + c^2)   (-> d^2 for |d| << c, 2 c |d| for |d| >> c)
+   *   2 smooth_l1 l(d) = 2 (sqrt(d^2 + c^2) - c)      l'(d) = 2 d / sqrt(d^2 + c^2)
+   * loss_type outside 0..2, or 1 / 2 with neither huber_c > 0 here nor sdxl_batch.huber_c, is a bad argument (1). ---- */
+  int   loss_type;
+  float huber_c;         /* c of every sample; used when sdxl_batch.huber_c is NULL */
 } sdxl_loss_config;
 
 /* One micro-batch, all device pointers.  RNG is the caller's: `noise` and `sigma_or_t` are inputs so that
@@ -62,6 +69,15 @@ typedef struct {
   const void* pooled;          /* [B,pooled_dim] bf16                 : batch["pooled_prompt_embeds"] */
   const float* time_ids;       /* [B,6] fp32                          : batch["time_ids"] */
   const float* tag_weights;    /* optional [B] fp32 (NULL = none)     : batch["tag_weights"] */
+  /* ---- appended: per-sample weights in, per-sample losses out (NULL = none, as before).  sdxl_forward_loss, sdxl_loss_fwd_bwd,
+   * sdxl_backward_* and sdxl_op_loss honour them; sdxl_unet_forward ignores them.
+   * sample_weights and huber_c are read AGAIN by the backward of the micro-step (like latents / noise): outside graph mode the
+   * caller keeps them alive and unchanged until that backward has been enqueued.  In graph mode they are staged inside the plan. ---- */
+  const float* sample_weights; /* optional [B] fp32: s_b, multiplied into each sample's loss and gradient (with the MinSNR
+                                  factor w_b: raw sum = sum_b sum_chw (s_b w_b) l(d)); s_b = 0 gives that sample an exact zero gradient */
+  const float* huber_c;        /* optional [B] fp32: per-sample c_b > 0 (a schedule computed by the caller), loss_type 1 / 2 */
+  float*       per_sample_loss;/* optional [B] fp32 OUT: L_b = s_b w_b mean_chw l(d), before the tag mean and the guard; written by
+                                  sdxl_forward_loss / sdxl_op_loss phase 1, stream-ordered; fixed-order sums, bitwise reproducible */
 } sdxl_batch;
 
 SDXL_API const char* sdxl_last_error(void);
@@ -121,11 +137,11 @@ SDXL_API int sdxl_loss_fwd_bwd(sdxl_handle* h, const sdxl_loss_config* lc, const
 /* every backward segment in one call (what a caller without a per-segment gradient exchange uses: one captured graph) */
 SDXL_API int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* stream);
 /* hipGraph replay of forward / backward (default OFF: measured slower than eager two-stream launches on ROCm 7.2, see
- * DESIGN.md): the second call with a given (plan, loss configuration, first_micro,
- * grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
+ * DESIGN.md): the second call with a given (plan, loss configuration including loss_type / huber_c and which per-sample arrays are
+ * present, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
  * kernel by kernel.  Inputs are staged at fixed addresses inside the plan, so the caller's tensors may move between steps. */
 SDXL_API int sdxl_set_graph_mode(sdxl_handle* h, int on);
-/* synchronises `stream`; out[0]=loss out[1]=sum w*(pred-target)^2 out[2]=sum|pred| out[3]=sum pred^2
+/* synchronises `stream`; out[0]=loss out[1]=sum s*w*l(pred-target) (s = 1, l = square unless set otherwise) out[2]=sum|pred| out[3]=sum pred^2
  * out[4]=sum|noise| out[5]=sum noise^2 (x0) out[6]=sum latents^2 (x1) out[7]=gradient gate */
 SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
 

@@ -69,6 +69,15 @@ class TrainingConfig:                    # data/config.py:152-168
     ema_use_warmup: bool = False         # the power warm-up schedule instead of (1+k)/(10+k)
     ema_inv_gamma: float = 1.0           # warm-up parameter
     ema_power: float = 2 / 3             # warm-up parameter
+    # build-only keys: per-sample weights, per-sample losses and the element loss of the device loss (csrc/loss.hip); the B floats
+    # each recipe needs are computed on the host (trainer.py::NativeSDXLTrainer._loss_ext).  Defaults = the reference's objective.
+    loss_type: str = "l2"                # "l2" | "huber" | "smooth_l1" (pseudo-Huber forms, include/sdxlstep.h)
+    huber_c: float = 0.1                 # the constant c, or the floor of the schedule
+    huber_schedule: str = "constant"     # "constant": c_b = huber_c ; "snr" (ddpm only): c_b = (1 - huber_c) / (1 + sigma_b)^2 + huber_c
+    snr_weighting: str = "reference"     # "reference": min(snr, gamma) ; "debiased" (ddpm, needs min_snr_gamma): additionally
+                                         # 1 / (snr + 1) for v_prediction, 1 / snr for epsilon (diffusers' --snr_gamma rule)
+    tag_weights_per_sample: bool = False # True: batch["tag_weights"] weights each image's own loss instead of the batch mean
+    log_per_sample_loss: bool = False    # True: compute_loss also returns "per_sample_loss" (CPU [B]) and "timesteps"
 
 
 @dataclass

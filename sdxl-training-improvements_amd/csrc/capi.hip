@@ -258,11 +258,25 @@ static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
   return 0;
 }
 
+// the appended fields of sdxl_loss_config / sdxl_batch (element loss, per-sample weights / c / losses), for both places that fill a LossP
+static void fill_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b, LossP& L) {
+  L.loss_type = lc->loss_type; L.huber_c = lc->huber_c;
+  L.sample_w = b->sample_weights; L.huber_cb = b->huber_c; L.ps_out = b->per_sample_loss;
+}
+// ... and their argument errors, reported before anything is copied or launched
+static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
+  ARG_CHECK(lc->loss_type >= 0 && lc->loss_type <= 2, "loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1)", lc->loss_type);
+  ARG_CHECK(lc->loss_type == 0 || b->huber_c || lc->huber_c > 0.f, "loss_type %d needs huber_c > 0 (got %g) or a per-sample huber_c array",
+            lc->loss_type, (double)lc->huber_c);
+  return 0;
+}
+
 static void fill_loss(Engine& e, const sdxl_loss_config* lc, const sdxl_batch* b, float grad_scale, LossP& L) {
   Plan& p = *e.cur;
   memset(&L, 0, sizeof(L));
   L.method = lc->method; L.prediction_type = lc->prediction_type; L.use_min_snr = lc->use_min_snr;
   L.min_snr_gamma = lc->min_snr_gamma; L.use_ztsnr = lc->use_ztsnr;
+  fill_loss_ext(lc, b, L);
   L.B = p.B; L.HW = p.H * p.W; L.C = 4;
   L.latents = b->latents; L.noise = b->noise; L.sigma = b->sigma_or_t; L.tag_w = b->tag_weights;
   L.unet_in = p.P(p.x_in); L.pred = p.P(p.pred); L.dpred = p.G(p.pred);
@@ -309,6 +323,17 @@ static unsigned loss_cfg_bits(const sdxl_loss_config& lc, bool tag) {
   return (unsigned)lc.method | ((unsigned)lc.prediction_type << 2) | ((unsigned)lc.use_min_snr << 4) | ((unsigned)lc.use_ztsnr << 5) |
          ((unsigned)tag << 6) | (g << 7);
 }
+// the second key word: element loss and which of the per-sample arrays are present (every one changes the captured kernels' arguments)
+static unsigned loss_cfg_bits2(const sdxl_loss_config& lc, const sdxl_batch& b) {
+  return (unsigned)lc.loss_type | ((unsigned)(b.sample_weights != nullptr) << 2) | ((unsigned)(b.huber_c != nullptr) << 3) |
+         ((unsigned)(b.per_sample_loss != nullptr) << 4);
+}
+// the third: the scalar huber_c, a kernel argument baked into a captured graph (not read for l2 or with a per-sample array)
+static unsigned loss_huber_bits(const sdxl_loss_config& lc, const sdxl_batch& b) {
+  unsigned h = 0;
+  if (lc.loss_type != 0 && !b.huber_c) memcpy(&h, &lc.huber_c, 4);
+  return h;
+}
 
 static int run_forward_ops(Engine& e, hipStream_t st) {
   Plan& p = *e.cur;
@@ -346,6 +371,7 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   ARG_CHECK(lc->method == 0 || lc->method == 1, "unknown method %d", lc->method);
   CHK(check_batch(e, b));
   ARG_CHECK(b->latents && b->noise && b->sigma_or_t, "batch is missing latents/noise/sigma");
+  CHK(check_loss_ext(lc, b));
   CHK(upload_cond(e, b, st));
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
   // kernels must not)
@@ -359,16 +385,28 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
     if (b->tag_weights) HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_tag_off), b->tag_weights, sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
     sb.latents = p.F(p.in_lat_off); sb.noise = p.F(p.in_noise_off); sb.sigma_or_t = p.F(p.in_sig_off);
     sb.tag_weights = b->tag_weights ? p.F(p.in_tag_off) : nullptr;
+    if (b->sample_weights) {
+      HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_sw_off), b->sample_weights, sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
+      sb.sample_weights = p.F(p.in_sw_off);
+    }
+    if (b->huber_c) {
+      HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_hc_off), b->huber_c, sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
+      sb.huber_c = p.F(p.in_hc_off);
+    }
   }
+  // the per-sample losses are produced inside the plan (a fixed address for a captured graph) and copied out below
+  if (b->per_sample_loss) sb.per_sample_loss = p.F(p.ps_loss_off);
   LossP L;
   fill_loss(e, lc, &sb, 1.f, L);
-  Engine::GraphKey key{&p, 0, 0, 0, 0, 0u, loss_cfg_bits(*lc, b->tag_weights != nullptr)};
+  Engine::GraphKey key{&p, 0, 0, 0, 0, 0u, loss_cfg_bits(*lc, b->tag_weights != nullptr), loss_cfg_bits2(*lc, *b), loss_huber_bits(*lc, *b)};
   CHK(run_graphed(e, key, st, [&](hipStream_t s) -> int {
     CHK(launch_loss_prepare(L, s));
     CHK(run_forward_ops(e, s));
     CHK(launch_loss_fwd(L, s));
     return 0;
   }));
+  if (b->per_sample_loss)
+    HIP_CHECK_RET(hipMemcpyAsync(b->per_sample_loss, p.F(p.ps_loss_off), sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
   h->step.lc = *lc; h->step.b = sb; h->step.valid = true;
   return 0;
 }
@@ -454,7 +492,8 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
   if (e.join_last_only) return body(st);
   unsigned sbits;
   memcpy(&sbits, &grad_scale, 4);
-  Engine::GraphKey key{e.cur, 1, k, first_micro != 0, 0, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr)};
+  Engine::GraphKey key{e.cur, 1, k, first_micro != 0, 0, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
+                      loss_cfg_bits2(h->step.lc, h->step.b), loss_huber_bits(h->step.lc, h->step.b)};
   return run_graphed(e, key, st, body);
 }
 
@@ -466,7 +505,8 @@ int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* s
   ARG_CHECK(h->step.valid, "sdxl_backward_all needs a preceding sdxl_forward_loss");
   unsigned sbits;
   memcpy(&sbits, &grad_scale, 4);
-  Engine::GraphKey key{e.cur, 2, 0, first_micro != 0, e.join_last_only, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr)};
+  Engine::GraphKey key{e.cur, 2, 0, first_micro != 0, e.join_last_only, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
+                      loss_cfg_bits2(h->step.lc, h->step.b), loss_huber_bits(h->step.lc, h->step.b)};
   return run_graphed(e, key, st, [&](hipStream_t s) -> int {
     LossP L;
     fill_loss(e, &h->step.lc, &h->step.b, grad_scale, L);
@@ -864,6 +904,8 @@ int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in,
   L.latents = b->latents; L.noise = b->noise; L.sigma = b->sigma_or_t; L.tag_w = b->tag_weights;
   L.unet_in = (bf16*)unet_in; L.pred = (const bf16*)pred; L.dpred = (bf16*)dpred;
   L.grad_scale = grad_scale; L.out = out8;
+  CHK(check_loss_ext(lc, b));
+  fill_loss_ext(lc, b, L);
   if (phase == 1) CHK(test_slab(loss_part_floats(L.B, L.HW), &L.part));
   if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st);
   if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);

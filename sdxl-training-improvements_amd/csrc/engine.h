@@ -78,6 +78,8 @@ struct Plan {
   size_t t_off = NONE, tid_off = NONE, loss_off = NONE, loss_part_off = NONE;
   size_t in_lat_off = NONE, in_noise_off = NONE, in_sig_off = NONE, in_tag_off = NONE;   // staged copies of the step's inputs (fixed
                                                                                           // addresses for the captured graphs)
+  size_t in_sw_off = NONE, in_hc_off = NONE;   // ... of the optional per-sample weights and per-sample Huber c ([B] each)
+  size_t ps_loss_off = NONE;                   // [B] per-sample losses, copied to the caller's pointer after the loss kernels
   size_t gn_ws_off = NONE, gn_ws_floats = 0;  // GroupNorm scratch shared by all (stream-ordered) norm ops
   size_t slab_off = NONE, slab_floats = 0;    // split-K partial slabs of the wgrad GEMMs (shared, stream-ordered)
   size_t slab_main_off = NONE, slab_main_floats = 0;   // the same for split forward / dgrad launches (caller's stream)
@@ -167,8 +169,10 @@ struct Engine {
   hipEvent_t ev_gin = nullptr, ev_gout = nullptr;
   struct GraphKey {
     const void* plan; int kind, k, first, join; unsigned scale_bits, cfg;
+    unsigned cfg2, huber_bits;      // element loss + which per-sample arrays are present; the scalar huber_c (capi.hip: loss_cfg_bits2)
     bool operator<(const GraphKey& o) const {
-      return std::tie(plan, kind, k, first, join, scale_bits, cfg) < std::tie(o.plan, o.kind, o.k, o.first, o.join, o.scale_bits, o.cfg);
+      return std::tie(plan, kind, k, first, join, scale_bits, cfg, cfg2, huber_bits) <
+             std::tie(o.plan, o.kind, o.k, o.first, o.join, o.scale_bits, o.cfg, o.cfg2, o.huber_bits);
     }
   };
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };

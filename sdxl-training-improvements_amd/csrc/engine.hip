@@ -1181,6 +1181,10 @@ void Engine::build(Plan* plan) {
     plan->apart_off = plan->alloc(sizeof(float) * (plan->apart_floats ? plan->apart_floats : 4));
     plan->apart_side_off = plan->alloc(sizeof(float) * (plan->apart_side_floats ? plan->apart_side_floats : 4));
     plan->ln_part_off = plan->alloc(sizeof(float) * (plan->ln_part_floats ? plan->ln_part_floats : 4));
+    // the loss's optional per-sample arrays, after everything else: no other offset of the plan depends on them
+    plan->in_sw_off = plan->alloc(sizeof(float) * plan->B);
+    plan->in_hc_off = plan->alloc(sizeof(float) * plan->B);
+    plan->ps_loss_off = plan->alloc(sizeof(float) * plan->B);
     plan->seg_first_op.assign(nseg, -1);
     plan->seg_last_op.assign(nseg, -2);
     for (int i = 0; i < (int)plan->ops.size(); ++i) {

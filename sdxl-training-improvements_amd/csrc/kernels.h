@@ -372,8 +372,18 @@ struct LossP {
   float* out;             // device: [0]=loss [1]=raw loss [2]=sum|pred| [3]=sum pred^2 [4]=sum|noise|
                           //         [5]=sum x0^2 [6]=sum x1^2 [7]=gate
   float* part;            // device scratch, loss_part_floats(B, HW): the blocks' partial sums (no atomics: the loss is bitwise reproducible)
+  // ---- per-sample weights / losses and the selectable element loss (all zero / NULL = the reference's two objectives as above) ----
+  int loss_type;          // 0 = l2: d^2 ; 1 = huber: 2c(sqrt(d^2+c^2)-c) ; 2 = smooth_l1: 2(sqrt(d^2+c^2)-c)
+  float huber_c;          // c when huber_cb is NULL
+  const float* sample_w;  // optional [B]: s_b, multiplied into each sample's loss and gradient
+  const float* huber_cb;  // optional [B]: per-sample c_b
+  float* ps_out;          // optional [B] OUT: L_b = s_b w_b mean_chw l(d), before the tag mean and the guard
 };
-static inline size_t loss_part_floats(int B, int HW) { return 6 * (((size_t)B * HW + 255) / 256); }
+// A 256-pixel block of the flat [B*HW] range touches at most loss_ps_slots samples (it straddles a sample boundary whenever
+// HW % 256 != 0, several when HW < 256).  The scratch holds the blocks' six batch sums first, then one partial of the weighted
+// element loss per (block, sample slot); slot j of block r belongs to sample (r * 256) / HW + j.
+static inline __host__ __device__ int loss_ps_slots(int B, int HW) { const int s = 255 / HW + 2; return s < B ? s : B; }
+static inline size_t loss_part_floats(int B, int HW) { return (6 + (size_t)loss_ps_slots(B, HW)) * (((size_t)B * HW + 255) / 256); }
 int launch_loss_prepare(const LossP& p, hipStream_t st);
 int launch_loss_fwd(const LossP& p, hipStream_t st);
 int launch_loss_bwd(const LossP& p, hipStream_t st);

@@ -9,6 +9,12 @@
 //   xt = (1-t_b)*x0 + t_b*x1 ; target = x1 - x0 ; loss = mean_b(mean_chw((pred-target)^2)) [* mean(tag_w)] -> guard
 // Guard: non-finite -> 1000 (no gradient) ; clamp(max=1000) (zero gradient above the cap).
 //
+// Beyond the reference, all off by default (LossP: loss_type, sample_w, huber_cb, ps_out), with d = pred - target:
+//   element loss l(d): l2 d^2 | huber 2c(sqrt(d^2+c^2)-c) | smooth_l1 2(sqrt(d^2+c^2)-c), c = c_b or the scalar;
+//   sqrt(d^2+c^2)-c is computed as d^2/(sqrt(d^2+c^2)+c) (the plain difference cancels for |d| << c)
+//   every sample's terms carry (s_b w_b): raw sum = sum_b sum_chw (s_b w_b) l(d), dpred = gate grad_scale (s_b w_b) l'(d) / numel
+//   L_b = s_b w_b mean_chw l(d) goes to ps_out, before the tag mean and the guard
+//
 // Inputs arrive as the reference hands them over: NCHW fp32 latents / noise.  The UNet consumes and
 // produces token-major [B*HW][8] bf16 (4 real channels + 4 zero pad so every row is one 16-byte vector).
 #include "kernels.h"
@@ -64,13 +70,24 @@ __global__ void loss_prepare_kernel(const LossP p) {
   *(bf16x8*)(p.unet_in + i * 8) = o;
 }
 
+// sqrt(d^2 + c^2) - c without the cancellation
+__device__ __forceinline__ float pseudo_huber(float d, float c) { return d * d / (sqrtf(d * d + c * c) + c); }
+
+// LT = LossP::loss_type.  The per-sample weight, the per-sample c and the per-sample output are wave-uniform branches on their
+// pointers: with all three NULL and LT = 0 the arithmetic is the reference's, operation for operation.
+template <int LT>
 __global__ void loss_fwd_kernel(const LossP p) {
   __shared__ float sred[4][8];
+  __shared__ float sps[4];
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int bs = -1;      // this thread's sample (-1: past the end)
   if (i < (long)p.B * p.HW) {
     int b = (int)(i / p.HW), hw = (int)(i - (long)b * p.HW);
+    bs = b;
     float sg = p.sigma[b];
+    const float sw = p.sample_w ? p.sample_w[b] : 1.f;
+    const float hc = LT != 0 ? (p.huber_cb ? p.huber_cb[b] : p.huber_c) : 0.f;
     bf16x8 pv = *(const bf16x8*)(p.pred + i * 8);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -79,7 +96,10 @@ __global__ void loss_fwd_kernel(const LossP p) {
       float tg, w;
       loss_target(p, b, x, n, sg, &tg, &w);
       float d = pr - tg;
-      acc[0] += w * d * d;
+      if (p.sample_w) w = sw * w;      // (s_b w_b) first: s_b = 1 leaves every bit as without weights
+      if (LT == 0) acc[0] += w * d * d;
+      else if (LT == 1) acc[0] += w * (2.f * hc * pseudo_huber(d, hc));
+      else acc[0] += w * (2.f * pseudo_huber(d, hc));
       acc[1] += fabsf(pr);
       acc[2] += pr * pr;
       acc[3] += fabsf(n);
@@ -96,11 +116,24 @@ __global__ void loss_fwd_kernel(const LossP p) {
   __syncthreads();
   if (threadIdx.x < 6)      // the block's six sums as a partial row: loss_finalize_kernel adds the rows in a fixed order (bitwise reproducible loss)
     p.part[(long)blockIdx.x * 6 + threadIdx.x] = sred[0][threadIdx.x] + sred[1][threadIdx.x] + sred[2][threadIdx.x] + sred[3][threadIdx.x];
+  if (p.ps_out) {      // the block's loss sum once more, split by sample: slot j = the j-th sample this block touches
+    const int S = loss_ps_slots(p.B, p.HW);
+    const long nb = ((long)p.B * p.HW + 255) / 256;
+    const int b0 = (int)(((long)blockIdx.x * 256) / p.HW);
+    for (int j = 0; j < S; ++j) {
+      float s = wave_sum(bs == b0 + j ? acc[0] : 0.f);      // selected, not multiplied: a non-finite sample stays in its own slot
+      __syncthreads();
+      if (lane == 0) sps[wv] = s;
+      __syncthreads();
+      if (threadIdx.x == 0) p.part[6 * nb + (long)blockIdx.x * S + j] = sps[0] + sps[1] + sps[2] + sps[3];
+    }
+  }
 }
 
 // one wave: lane l adds the partial rows l, l + 64, ... in order, lane 0 then adds the 64 lane sums in order
 __global__ void loss_finalize_kernel(const LossP p) {
   __shared__ float sl[6][64];
+  __shared__ float sp[64];
   const long nb = ((long)p.B * p.HW + 255) / 256;
   for (int k = 0; k < 6; ++k) {
     float s = 0.f;
@@ -108,6 +141,22 @@ __global__ void loss_finalize_kernel(const LossP p) {
     sl[k][threadIdx.x] = s;
   }
   __syncthreads();
+  if (p.ps_out) {      // per sample: the slots of the blocks [b*HW/256, ((b+1)*HW-1)/256] that belong to it, in the same fixed order
+    const int S = loss_ps_slots(p.B, p.HW);
+    for (int b = 0; b < p.B; ++b) {
+      const long lo = ((long)b * p.HW) / 256, hi = ((long)(b + 1) * p.HW - 1) / 256;
+      float s = 0.f;
+      for (long r = lo + threadIdx.x; r <= hi; r += 64) s += p.part[6 * nb + r * S + (b - (int)((r * 256) / p.HW))];
+      sp[threadIdx.x] = s;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int l = 0; l < 64; ++l) t += sp[l];
+        p.ps_out[b] = t / (4.f * (float)p.HW);
+      }
+      __syncthreads();
+    }
+  }
   if (threadIdx.x != 0) return;
   for (int k = 0; k < 6; ++k) {
     float s = 0.f;
@@ -128,11 +177,14 @@ __global__ void loss_finalize_kernel(const LossP p) {
   else { p.out[0] = l; p.out[7] = tm; }
 }
 
+template <int LT>
 __global__ void loss_bwd_kernel(const LossP p) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)p.B * p.HW) return;
   int b = (int)(i / p.HW), hw = (int)(i - (long)b * p.HW);
   float sg = p.sigma[b];
+  const float sw = p.sample_w ? p.sample_w[b] : 1.f;
+  const float hc = LT != 0 ? (p.huber_cb ? p.huber_cb[b] : p.huber_c) : 0.f;
   float k = p.out[7] * p.grad_scale * 2.f / ((float)p.B * 4.f * (float)p.HW);
   bf16x8 pv = *(const bf16x8*)(p.pred + i * 8), o;
 #pragma unroll
@@ -140,8 +192,15 @@ __global__ void loss_bwd_kernel(const LossP p) {
     long idx = ((long)b * 4 + c) * p.HW + hw;
     float tg, w;
     loss_target(p, b, p.latents[idx], p.noise[idx], sg, &tg, &w);
-    // guard taken (non-finite or clamped loss, out[7] == 0): an exact zero gradient, also where pred - target is inf / nan
-    o[c] = k == 0.f ? (bf16)0.f : (bf16)(k * w * ((float)pv[c] - tg));
+    if (p.sample_w) w = sw * w;
+    float d = (float)pv[c] - tg;
+    if (LT != 0) {      // l'(d) / 2: huber c d / sqrt(d^2 + c^2), smooth_l1 d / sqrt(d^2 + c^2)
+      const float q = sqrtf(d * d + hc * hc);
+      d = LT == 1 ? hc * d / q : d / q;
+    }
+    // guard taken (non-finite or clamped loss, out[7] == 0): an exact zero gradient, also where pred - target is inf / nan;
+    // s_b = 0: an exact zero slab for that sample, whatever d is
+    o[c] = (k == 0.f || (p.sample_w && sw == 0.f)) ? (bf16)0.f : (bf16)(k * w * d);
     o[c + 4] = (bf16)0.f;
   }
   *(bf16x8*)(p.dpred + i * 8) = o;
@@ -151,6 +210,9 @@ static int check_loss(const LossP& p) {
   ARG_CHECK(p.C == 4, "loss: latent channels must be 4 (got %d)", p.C);
   ARG_CHECK(p.B > 0 && p.HW > 0, "loss: empty batch");
   ARG_CHECK(p.latents && p.noise && p.sigma, "loss: missing inputs");
+  ARG_CHECK(p.loss_type >= 0 && p.loss_type <= 2, "loss: loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1)", p.loss_type);
+  ARG_CHECK(p.loss_type == 0 || p.huber_cb || p.huber_c > 0.f, "loss: loss_type %d needs huber_c > 0 (got %g)", p.loss_type,
+            (double)p.huber_c);
   return 0;
 }
 int launch_loss_prepare(const LossP& p, hipStream_t st) {
@@ -164,7 +226,9 @@ int launch_loss_fwd(const LossP& p, hipStream_t st) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
   ARG_CHECK(p.part != nullptr, "loss: missing partial-row scratch (loss_part_floats)");
-  hipLaunchKernelGGL(loss_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  if (p.loss_type == 0) hipLaunchKernelGGL(loss_fwd_kernel<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  else if (p.loss_type == 1) hipLaunchKernelGGL(loss_fwd_kernel<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(loss_fwd_kernel<2>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, p);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
@@ -172,7 +236,9 @@ int launch_loss_fwd(const LossP& p, hipStream_t st) {
 int launch_loss_bwd(const LossP& p, hipStream_t st) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  if (p.loss_type == 0) hipLaunchKernelGGL(loss_bwd_kernel<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  else if (p.loss_type == 1) hipLaunchKernelGGL(loss_bwd_kernel<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(loss_bwd_kernel<2>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

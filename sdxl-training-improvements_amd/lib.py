@@ -38,14 +38,21 @@ class UNetConfig(C.Structure):
 
 class LossConfig(C.Structure):
     _fields_ = [("method", C.c_int), ("prediction_type", C.c_int), ("use_min_snr", C.c_int),
-                ("min_snr_gamma", C.c_float), ("use_ztsnr", C.c_int)]
+                ("min_snr_gamma", C.c_float), ("use_ztsnr", C.c_int),
+                # appended: element loss 0 = l2, 1 = huber, 2 = smooth_l1 (LOSS_TYPES); the scalar c
+                ("loss_type", C.c_int), ("huber_c", C.c_float)]
 
 
 class Batch(C.Structure):
     _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ctx_len", C.c_int),
                 ("latents", C.c_void_p), ("noise", C.c_void_p), ("sigma_or_t", C.c_void_p),
                 ("timestep", C.c_void_p), ("prompt_embeds", C.c_void_p), ("pooled", C.c_void_p),
-                ("time_ids", C.c_void_p), ("tag_weights", C.c_void_p)]
+                ("time_ids", C.c_void_p), ("tag_weights", C.c_void_p),
+                # appended: optional [B] fp32 per-sample weights s_b / Huber c_b in, per-sample losses L_b out
+                ("sample_weights", C.c_void_p), ("huber_c", C.c_void_p), ("per_sample_loss", C.c_void_p)]
+
+
+LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
 
 
 class AdamWConfig(C.Structure):

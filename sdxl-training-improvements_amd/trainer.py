@@ -50,6 +50,9 @@ from .unet import NativeUNet, config_from_unet
 logger = logging.getLogger(__name__)
 
 REQUIRED_KEYS = {"vae_latents", "prompt_embeds", "pooled_prompt_embeds", "time_ids", "metadata"}
+LOSS_TYPES = ("l2", "huber", "smooth_l1")
+HUBER_SCHEDULES = ("constant", "snr")
+SNR_WEIGHTINGS = ("reference", "debiased")
 
 
 class _NativeLoss(torch.autograd.Function):
@@ -82,6 +85,7 @@ class NativeSDXLTrainer:
         if method not in ("ddpm", "flow_matching"):
             raise ValueError(f"Unsupported training method: {self.config.training.method}")   # sdxl_trainer.py:151
         self.method = method
+        self._check_loss_keys()
         self.gradient_accumulation_steps = int(self.config.training.gradient_accumulation_steps)
         unet = model.unet if hasattr(model, "unet") else model
         native_attrs = ("forward_loss", "backward", "read_loss", "zero_grads", "param_elems")
@@ -132,10 +136,88 @@ class NativeSDXLTrainer:
         lib.check(self.net.L.sdxl_grads_to_bf16(self.net.h, off, n, C.c_void_p(dst.data_ptr()), 1.0,
                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
+    def _check_loss_keys(self) -> None:
+        """the string keys of the loss extensions, checked when the trainer is built (ValueError names the key)"""
+        tc = self.config.training
+        self.loss_type = str(getattr(tc, "loss_type", "l2")).lower()
+        self.huber_schedule = str(getattr(tc, "huber_schedule", "constant")).lower()
+        self.snr_weighting = str(getattr(tc, "snr_weighting", "reference")).lower()
+        self.huber_c = float(getattr(tc, "huber_c", 0.1))
+        for key, val, known in (("loss_type", self.loss_type, LOSS_TYPES), ("huber_schedule", self.huber_schedule, HUBER_SCHEDULES),
+                                ("snr_weighting", self.snr_weighting, SNR_WEIGHTINGS)):
+            if val not in known:
+                raise ValueError(f"training.{key}: unknown value {getattr(tc, key)!r} (expected one of {', '.join(known)})")
+        if self.loss_type != "l2" and not self.huber_c > 0.0:
+            raise ValueError(f"training.huber_c must be > 0 for training.loss_type {self.loss_type!r} (got {self.huber_c})")
+        if self.method != "ddpm":
+            if self.huber_schedule == "snr":
+                raise ValueError("training.huber_schedule: 'snr' is defined on the ddpm sigma only (flow matching has none)")
+            if self.snr_weighting == "debiased":
+                raise ValueError("training.snr_weighting: 'debiased' is a ddpm weighting (flow matching has no snr)")
+        elif self.snr_weighting == "debiased" and self.config.model.min_snr_gamma is None:
+            raise ValueError("training.snr_weighting: 'debiased' divides min(snr, gamma) by the snr: it needs model.min_snr_gamma")
+
+    def _loss_ext(self, batch, sig) -> Dict[str, Any]:
+        """The device loss's optional arguments from the config keys: each recipe is B floats computed here.  Several sources of
+        the per-sample weight multiply.  Returns only what differs from the defaults (an empty dict = the reference's objective)."""
+        tc = self.config.training
+        ext: Dict[str, Any] = {}
+        s = None
+        if self.snr_weighting == "debiased":              # diffusers' --snr_gamma rule: min(snr, gamma) / (snr + 1 | snr)
+            snr = sig.double() ** -2
+            pred = str(tc.prediction_type)
+            s = 1.0 / (snr + 1.0) if pred == "v_prediction" else 1.0 / snr
+        tag = batch.get("tag_weights")
+        if bool(getattr(tc, "tag_weights_per_sample", False)) and tag is not None:
+            tw = torch.as_tensor(tag).double().reshape(-1)
+            s = tw if s is None else s * tw
+        if s is not None:
+            ext["sample_weights"] = s.float()
+        if self.loss_type != "l2":
+            ext["loss_type"] = self.loss_type
+            if self.huber_schedule == "snr":
+                c = self.huber_c
+                ext["huber_c"] = ((1.0 - c) / (1.0 + sig.double()) ** 2 + c).float()
+            else:
+                ext["huber_c"] = self.huber_c
+        if bool(getattr(tc, "log_per_sample_loss", False)):
+            ext["per_sample_loss"] = True
+        return ext
+
+    def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None):
+        """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used"""
+        B = lat.shape[0]
+        cm = self.config.model
+        tag = batch.get("tag_weights")
+        per_sample_tag = bool(getattr(self.config.training, "tag_weights_per_sample", False))
+        if self.method == "ddpm":
+            ts = timesteps if timesteps is not None else self.noise_scheduler.sample_timesteps(B, generator)
+            sig = self.noise_scheduler.timestep_to_sigma(ts)
+            ext = self._loss_ext(batch, sig)
+            ext.update(ext_over or {})
+            self.net.forward_loss("ddpm", lat, noise, sig, ts.float(), batch["prompt_embeds"],
+                                  batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag,
+                                  prediction_type=self.config.training.prediction_type,
+                                  min_snr_gamma=cm.min_snr_gamma, use_ztsnr=cm.use_ztsnr, **ext)
+            return ts
+        if timesteps is None:                                      # sample_logit_normal, :373-385
+            timesteps = torch.sigmoid(torch.randn(B, generator=generator))
+        t = timesteps.float()
+        if str(self.config.training.mixed_precision) == "bf16":     # D6: t is handed to the UNet in model dtype
+            t_unet = t.to(torch.bfloat16).float()
+        else:
+            t_unet = t
+        ext = self._loss_ext(batch, None)
+        ext.update(ext_over or {})
+        self.net.forward_loss("flow_matching", lat, noise, t, t_unet, batch["prompt_embeds"],
+                              batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag, **ext)
+        return t
+
     def compute_loss(self, *args, generator: Optional[torch.Generator] = None, timesteps=None, noise=None) -> Dict[str, Any]:
         """compute_loss(batch) or compute_loss(model, batch[, generator]).  `timesteps` (ddpm: int64 indices, flow
         matching: t in (0,1)) and `noise` (ddpm noise / flow-matching x0) may be injected for reproducible fixtures;
-        otherwise they are drawn as the reference draws them."""
+        otherwise they are drawn as the reference draws them.  With training.log_per_sample_loss the result also carries
+        "per_sample_loss" (CPU tensor [B], before the tag mean and the guard) and "timesteps"."""
         batch = args[-1] if not isinstance(args[-1], torch.Generator) else args[-2]
         if isinstance(args[-1], torch.Generator):
             generator = args[-1]
@@ -143,28 +225,9 @@ class NativeSDXLTrainer:
             raise ValueError(f"Batch missing required keys: {REQUIRED_KEYS - set(batch.keys())}")
         lat = batch["vae_latents"].float()
         B = lat.shape[0]
-        cm = self.config.model
         if noise is None:
             noise = torch.randn(lat.shape, generator=generator)
-        tag = batch.get("tag_weights")
-        if self.method == "ddpm":
-            ts = timesteps if timesteps is not None else self.noise_scheduler.sample_timesteps(B, generator)
-            sig = self.noise_scheduler.timestep_to_sigma(ts)
-            self.net.forward_loss("ddpm", lat, noise, sig, ts.float(), batch["prompt_embeds"],
-                                  batch["pooled_prompt_embeds"], batch["time_ids"], tag,
-                                  prediction_type=self.config.training.prediction_type,
-                                  min_snr_gamma=cm.min_snr_gamma, use_ztsnr=cm.use_ztsnr)
-        else:
-            if timesteps is None:                                      # sample_logit_normal, :373-385
-                timesteps = torch.sigmoid(torch.randn(B, generator=generator))
-            t = timesteps.float()
-            if str(self.config.training.mixed_precision) == "bf16":     # D6: t is handed to the UNet in model dtype
-                t_unet = t.to(torch.bfloat16).float()
-            else:
-                t_unet = t
-            self.net.forward_loss("flow_matching", lat, noise, t, t_unet, batch["prompt_embeds"],
-                                  batch["pooled_prompt_embeds"], batch["time_ids"], tag)
-            ts = t
+        ts = self._forward(batch, lat, noise, timesteps, generator)
         o = self.net.read_loss()                                        # the single host sync of the step
         numel = lat.numel()
         lr = self.optimizer.param_groups[0]["lr"] if self.optimizer is not None else 0.0
@@ -178,7 +241,38 @@ class NativeSDXLTrainer:
                        "time_mean": float(ts.mean()), "time_std": float(ts.std()) if B > 1 else float("nan"),
                        "velocity_norm": math.sqrt(o[3]), "batch_size": B, "lr": lr}
         loss = _NativeLoss.apply(self._anchor, self, o[0])
-        return {"loss": loss, "metrics": metrics}
+        out = {"loss": loss, "metrics": metrics}
+        if bool(getattr(self.config.training, "log_per_sample_loss", False)):
+            out["per_sample_loss"] = self.net.read_per_sample_loss()    # (after read_loss's sync: the copy only)
+            out["timesteps"] = ts
+        return out
+
+    def evaluate(self, batches, timesteps, generator: Optional[torch.Generator] = None):
+        """Held-out loss at fixed timesteps, forward only: every batch is evaluated at each of `timesteps` (ddpm: indices into
+        the sigma table; flow matching: t in (0, 1)) with noise drawn from `generator`.  No backward, no gradient zeroing, no
+        optimizer or EMA step; the accumulation state is not touched.  The loss is the one the config keys select (weights,
+        element loss), per sample, before the tag mean and the guard.  Returns ({timestep: mean per-sample loss}, overall mean).
+        Evaluates the trained weights (not the EMA)."""
+        batches = list(batches)
+        sums: Dict[Any, float] = {}
+        counts: Dict[Any, int] = {}
+        for batch in batches:
+            if not all(k in batch for k in REQUIRED_KEYS):
+                raise ValueError(f"Batch missing required keys: {REQUIRED_KEYS - set(batch.keys())}")
+            lat = batch["vae_latents"].float()
+            B = lat.shape[0]
+            for t in timesteps:
+                key = int(t) if self.method == "ddpm" else float(t)
+                noise = torch.randn(lat.shape, generator=generator)
+                ts = torch.full((B,), key, dtype=torch.long if self.method == "ddpm" else torch.float32)
+                self._forward(batch, lat, noise, ts, generator, {"per_sample_loss": True})
+                self.net.read_loss()                                    # the sync; its scalar (tag mean, guard) is not used
+                per = self.net.read_per_sample_loss().double()
+                sums[key] = sums.get(key, 0.0) + float(per.sum())
+                counts[key] = counts.get(key, 0) + B
+        per_t = {k: sums[k] / counts[k] for k in sums}
+        n = sum(counts.values())
+        return per_t, (sum(sums.values()) / n if n else float("nan"))
 
     training_step = compute_loss                                        # DDPM trainer's name for it
 

@@ -210,13 +210,38 @@ class NativeUNet:
         self._keep = ts
         return lib.Batch(B, H, W, ctx, *[None if t is None else t.data_ptr() for t in ts])
 
+    def _per_sample(self, t, B: int, what: str):
+        """an optional [B] fp32 device array of the batch (kept alive until the next forward_loss: the backward reads it again)"""
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.float32).to(self.device).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"{what}: expected {B} values (one per sample), got {t.numel()}")
+        return t
+
     def forward_loss(self, method: str, latents, noise, sigma_or_t, timestep, prompt_embeds, pooled, time_ids,
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
-                     use_ztsnr=True) -> None:
-        """loss preparation + UNet forward + loss; results stay on the device until read_loss()."""
+                     use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
+                     per_sample_loss: bool = False) -> None:
+        """loss preparation + UNet forward + loss; results stay on the device until read_loss().
+        sample_weights: optional [B] s_b multiplied into each sample's loss and gradient.  loss_type "l2" | "huber" |
+        "smooth_l1" (include/sdxlstep.h), with huber_c a float (every sample) or [B] values (per sample).
+        per_sample_loss: also produce the [B] per-sample losses, read with read_per_sample_loss() after read_loss()."""
+        if loss_type not in lib.LOSS_TYPES:
+            raise ValueError(f"loss_type {loss_type!r}: expected one of {sorted(lib.LOSS_TYPES)}")
+        B = latents.shape[0]
+        scalar_c = isinstance(huber_c, (int, float))
         lc = lib.LossConfig(METHODS[method], PRED_TYPES.get(prediction_type, 0), int(min_snr_gamma is not None),
-                            float(min_snr_gamma or 0.0), int(bool(use_ztsnr)))
+                            float(min_snr_gamma or 0.0), int(bool(use_ztsnr)), lib.LOSS_TYPES[loss_type],
+                            float(huber_c) if scalar_c else 0.0)
         b = self._batch(latents, noise, sigma_or_t, timestep, prompt_embeds, pooled, time_ids, tag_weights)
+        sw = self._per_sample(sample_weights, B, "sample_weights")
+        hc = None if scalar_c else self._per_sample(huber_c, B, "huber_c")
+        self._ps_loss = torch.empty(B, dtype=torch.float32, device=self.device) if per_sample_loss else None
+        self._keep = list(self._keep) + [sw, hc]
+        b.sample_weights = None if sw is None else sw.data_ptr()
+        b.huber_c = None if hc is None else hc.data_ptr()
+        b.per_sample_loss = None if self._ps_loss is None else self._ps_loss.data_ptr()
         lib.check(self.L.sdxl_forward_loss(self.h, C.byref(lc), C.byref(b), _stream()), "sdxl_forward_loss")
 
     def backward(self, grad_scale: float = 1.0, first_micro: bool = True, on_segment=None, segment_stream: bool = False) -> None:
@@ -269,6 +294,13 @@ class NativeUNet:
         out = (C.c_float * 8)()
         lib.check(self.L.sdxl_read_loss(self.h, out, _stream()))
         return [float(x) for x in out]
+
+    def read_per_sample_loss(self) -> torch.Tensor:
+        """the [B] per-sample losses of the last forward_loss(per_sample_loss=True), on the CPU.  Call it after read_loss(), which
+        has synchronised the stream: this adds the copy only."""
+        if getattr(self, "_ps_loss", None) is None:
+            raise lib.SdxlError("read_per_sample_loss: the last forward_loss was not called with per_sample_loss=True")
+        return self._ps_loss.cpu()
 
     # UNet only (sample NCHW fp32/bf16 in, NCHW fp32 out) -- for parity tests and validation sampling
     def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids) -> torch.Tensor:
