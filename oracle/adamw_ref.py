@@ -99,6 +99,33 @@ def make_step(grad, p, shift, m, v, rand, *, beta1, beta2, step, lr, eps, decay,
     return p1b, s2b, m2b, v2b
 
 
+def philox4x32_7(ctr, key):
+    """Philox-4x32-7 as csrc/optimizer.hip has it: ctr = four uint32 arrays (or scalars), key = two; returns the four output
+    words as uint32 arrays.  Multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, 7 rounds."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for c in ctr)
+    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
+    lo32 = np.uint64(0xFFFFFFFF)
+    for _ in range(7):
+        a = np.uint64(0xD2511F53) * c0                  # 32 x 32 -> 64 bits: high and low word of each product
+        b = np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (b >> np.uint64(32)) ^ c1 ^ np.uint64(k0), b & lo32, (a >> np.uint64(32)) ^ c3 ^ np.uint64(k1), a & lo32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return tuple(np.broadcast_to(c, np.broadcast(c0, c1, c2, c3).shape).astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def philox_rand(n: int, seed: int, step: int, elem_offset: int = 0) -> np.ndarray:
+    """The uint16 [4][n] table `make_step` takes, as adamw_bf16_kernel's built-in generator draws it (rand_inject == NULL):
+    arena element j = elem_offset + i belongs to pair j // 2, counter (pair low word, pair high word, step, 0x5D71A3B1),
+    key (seed low word, seed high word).  The even element of the pair takes output words 0 and 1, the odd one words 2 and 3;
+    with (a, b) those two words, r0 = a & 0xFFFF, r1 = a >> 16, r2 = b & 0xFFFF, r3 = b >> 16."""
+    j = np.arange(n, dtype=np.uint64) + np.uint64(elem_offset)
+    pair = j >> np.uint64(1)
+    w = philox4x32_7((pair, pair >> np.uint64(32), np.uint64(step), np.uint64(0x5D71A3B1)), (seed, seed >> 32))
+    odd = (j & np.uint64(1)).astype(bool)
+    a, b = np.where(odd, w[2], w[0]), np.where(odd, w[3], w[1])
+    return np.stack([a & 0xFFFF, a >> 16, b & 0xFFFF, b >> 16]).astype(np.uint16)
+
+
 class LazyDecay:
     """Host-side bookkeeping of AdamWBF16.step (:118-126): decay is owed per step and paid once it exceeds 5e-3."""
     threshold = 5e-3

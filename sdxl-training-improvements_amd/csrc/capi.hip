@@ -930,35 +930,40 @@ int sdxl_adamw_default_config(sdxl_adamw_config* c) {
   c->reference_ema = 1;
   return 0;
 }
-// the EMA fields, read by both algorithms
-static bool ema_omd_ok(const sdxl_adamw_config* c) {
-  return c->ema == nullptr || (c->ema_one_minus_decay >= 0.f && c->ema_one_minus_decay <= 1.f);
+// what both algorithms of sdxl_adamw_bf16_step check, then fill in the same way (`who` in front of the hyper-parameter message):
+// python doubles -> the float32 / bf16 scalars torch's ops on bf16 tensors use
+static int fill_optim(OptimP& q, void* p, const void* grad, int grad_dtype, void* m, void* v, size_t n, const sdxl_adamw_config* c,
+                      const float* grad_scale_dev, bool own_ok, const char* who) {
+  ARG_CHECK(own_ok && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0,
+            "%s: invalid hyper-parameters", who);
+  q.p = (bf16*)p; q.m = (bf16*)m; q.v = (bf16*)v; q.n = n;
+  if (grad_dtype == 0) q.grad_f32 = (const float*)grad; else q.grad_bf16 = (const bf16*)grad;
+  q.beta1 = (float)c->beta1; q.beta2 = (float)c->beta2;
+  q.one_minus_beta2 = (float)(1.0 - c->beta2);
+  q.eps_bf16 = bf16_round_host((float)c->eps);
+  q.grad_round_bf16 = c->grad_round_bf16;
+  q.grad_scale = grad_scale_dev;
+  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
+  return 0;
 }
 // algorithm 1 of sdxl_adamw_bf16_step: every argument error is reported before anything touches the device
 static int sf_kahan_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* kahan_comp, size_t n, const sdxl_adamw_config* c,
                          const float* grad_scale_dev, const unsigned short* rand_inject, hipStream_t st) {
   ARG_CHECK(rand_inject == nullptr, "schedule-free: rand_inject must be NULL (the update has no random rounding)");
   ARG_CHECK(c->kahan_sum == 0 || kahan_comp != nullptr, "schedule-free: kahan_sum needs the kahan_comp arena (shift argument)");
-  ARG_CHECK(c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0 && c->weight_decay >= 0.0 &&
-            c->sf_step_size >= 0.0 && std::isfinite(c->sf_step_size), "schedule-free: invalid hyper-parameters");
   SfkP q;
   memset(&q, 0, sizeof(q));
-  q.p = (bf16*)p; q.m = (bf16*)m; q.v = (bf16*)v; q.c = c->kahan_sum ? (bf16*)kahan_comp : nullptr; q.n = n;
-  if (grad_dtype == 0) q.grad_f32 = (const float*)grad; else q.grad_bf16 = (const bf16*)grad;
-  // python doubles -> the float32 / bf16 scalars torch's ops on bf16 tensors use (tests/_schedulefree_ref.py)
-  const double b1 = c->beta1, b2 = c->beta2, ss = c->sf_step_size, wd = c->weight_decay;
-  q.beta1 = (float)b1; q.beta2 = (float)b2;
-  q.one_minus_beta1_bf16 = bf16_round_host((float)(1.0 - b1));
-  q.one_minus_beta2 = (float)(1.0 - b2);
-  q.eps_bf16 = bf16_round_host((float)c->eps);
+  CHK(fill_optim(q, p, grad, grad_dtype, m, v, n, c, grad_scale_dev,
+                 c->weight_decay >= 0.0 && c->sf_step_size >= 0.0 && std::isfinite(c->sf_step_size), "schedule-free"));
+  q.c = c->kahan_sum ? (bf16*)kahan_comp : nullptr;
+  // the scalars of torch's ops as tests/_schedulefree_ref.py has them
+  const double ss = c->sf_step_size, wd = c->weight_decay;
+  q.one_minus_beta1_bf16 = bf16_round_host((float)(1.0 - c->beta1));
   q.has_wd = wd != 0.0;
   q.wd_alpha_bf16 = bf16_round_host((float)-wd);
   q.neg_step = (float)-ss;
   q.step = (float)ss;
   q.decay = (float)(ss * wd);
-  q.grad_round_bf16 = c->grad_round_bf16;
-  q.grad_scale = grad_scale_dev;
-  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
   return launch_sfk(q, c->sf_reference, st);
 }
 int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
@@ -967,30 +972,22 @@ int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, voi
   ARG_CHECK(c, "null config");
   ARG_CHECK(grad_dtype == 0 || grad_dtype == 1, "adamw: grad_dtype %d (0 = fp32, 1 = bf16)", grad_dtype);
   ARG_CHECK(c->algorithm == 0 || c->algorithm == 1, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan)", c->algorithm);
-  ARG_CHECK(ema_omd_ok(c), "adamw: ema_one_minus_decay %g must lie in [0, 1]", (double)c->ema_one_minus_decay);
+  ARG_CHECK(c->ema == nullptr || (c->ema_one_minus_decay >= 0.f && c->ema_one_minus_decay <= 1.f),
+            "adamw: ema_one_minus_decay %g must lie in [0, 1]", (double)c->ema_one_minus_decay);
   if (c->algorithm == 1) return sf_kahan_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
-  ARG_CHECK(c->step >= 1.0 && c->beta1 >= 0.0 && c->beta1 < 1.0 && c->beta2 >= 0.0 && c->beta2 < 1.0 && c->eps >= 0.0,
-            "adamw: invalid hyper-parameters");
   AdamWP q;
   memset(&q, 0, sizeof(q));
-  q.p = (bf16*)p; q.m = (bf16*)m; q.v = (bf16*)v; q.shift = (bf16*)shift; q.n = n;
-  if (grad_dtype == 0) q.grad_f32 = (const float*)grad; else q.grad_bf16 = (const bf16*)grad;
+  CHK(fill_optim(q, p, grad, grad_dtype, m, v, n, c, grad_scale_dev, c->step >= 1.0, "adamw"));
+  q.shift = (bf16*)shift;
   // scalars exactly as the reference's python floats reach the torch kernels: double arithmetic, then float32
-  const double b1 = c->beta1, b2 = c->beta2;
-  q.beta1 = (float)b1; q.beta2 = (float)b2;
-  q.one_minus_beta1 = (float)(1.0 - b1);
-  q.one_minus_beta2 = (float)(1.0 - b2);
-  q.eps_bf16 = bf16_round_host((float)c->eps);
-  q.value = (float)(-c->lr * sqrt(1.0 - pow(b2, c->step)));
+  q.one_minus_beta1 = (float)(1.0 - c->beta1);
+  q.value = (float)(-c->lr * sqrt(1.0 - pow(c->beta2, c->step)));
   q.decay_alpha_bf16 = c->decay_this_iteration > 0.0 ? bf16_round_host((float)-c->decay_this_iteration) : 0.f;
   q.reference_ema = c->reference_ema;
-  q.grad_round_bf16 = c->grad_round_bf16;
-  q.grad_scale = grad_scale_dev;
   q.rand = rand_inject;
   q.seed_lo = (unsigned)c->seed; q.seed_hi = (unsigned)(c->seed >> 32);
   q.step_counter = (unsigned)c->step;
   q.elem_offset = (size_t)c->elem_offset;
-  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
   return launch_adamw_bf16(q, (hipStream_t)st);
 }
 int sdxl_adamw_decay(void* shift, const void* p, size_t n, float decay, void* st) {

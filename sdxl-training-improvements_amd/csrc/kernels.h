@@ -388,49 +388,45 @@ int launch_loss_prepare(const LossP& p, hipStream_t st);
 int launch_loss_fwd(const LossP& p, hipStream_t st);
 int launch_loss_bwd(const LossP& p, hipStream_t st);
 
-// ---- fused AdamW_BF16 step (optimizer.hip; reference adamw_bfloat16/__init__.py:146-197) ----
-struct AdamWP {
+// ---- the fused optimizer updates (optimizer.hip): one launch over an arena slice ----
+// what both algorithms' kernels read
+struct OptimP {
   bf16* p;
   const float* grad_f32;       // native fp32 gradient arena, or
   const bf16* grad_bf16;       //   bf16 gradients (exactly one of the two)
-  bf16 *m, *v, *shift;
+  bf16 *m, *v;                 // exp_avg, exp_avg_sq
   size_t n;                    // elements, multiple of 8
-  float beta1, beta2, one_minus_beta1, one_minus_beta2;
+  float beta1, beta2;          // float32, as torch's mul_ by a python scalar uses them
+  float one_minus_beta2;       // value of addcmul_
   float eps_bf16;              // eps rounded to bf16 (torch casts the scalar it adds to a bf16 tensor)
+  int grad_round_bf16;         // round the (scaled) gradient to bf16 first, as the reference's bf16 autograd does
+  const float* grad_scale;     // device scalar multiplied into the gradient (unscale / clip), or nullptr
+  float* ema;                  // fp32 EMA of the weights, element 0 = p's element 0, or nullptr (no EMA)
+  float ema_omd;               // 1 - decay of this update, float32: e <- e - omd * (e - p_new), three separately rounded ops
+};
+// AdamW_BF16 (adamw_bf16_kernel; reference adamw_bfloat16/__init__.py:146-197)
+struct AdamWP : OptimP {
+  bf16* shift;
+  float one_minus_beta1;       // float32
   float value;                 // -lr * sqrt(1 - beta2^step)
   float decay_alpha_bf16;      // -decay_this_iteration rounded to bf16, 0 = no decay in this launch
   int reference_ema;           // 1: the reference's actual first-moment update  m <- SR(g + (1-b1) * b1*m)   (quirk D17)
                                // 0: the documented EMA                          m <- SR(b1*m + (1-b1) * g)
-  int grad_round_bf16;         // round the (scaled) gradient to bf16 first, as the reference's bf16 autograd does
-  const float* grad_scale;     // device scalar multiplied into the gradient (unscale / clip), or nullptr
   const unsigned short* rand;  // [4][n] injected random 16-bit integers (parity tests), or nullptr = Philox
   unsigned seed_lo, seed_hi, step_counter;
   size_t elem_offset;          // arena index of element 0 of this launch (multiple of 8): the Philox counters are those of the
                                // full-arena launch, so a sharded (ZeRO-1) update is bit-identical to the unsharded one
-  float* ema;                  // fp32 EMA of the weights, element 0 = p's element 0, or nullptr (no EMA)
-  float ema_omd;               // 1 - decay of this update, float32: e <- e - omd * (e - p_new), three separately rounded ops
 };
 int launch_adamw_bf16(const AdamWP& q, hipStream_t st);
-// schedule-free Kahan AdamW (csrc/optimizer.hip, sfk_kernel): one launch over the arena slice
-struct SfkP {
-  bf16* p;
-  const float* grad_f32;       // native fp32 gradient arena, or
-  const bf16* grad_bf16;       //   bf16 gradients (exactly one of the two)
-  bf16 *m, *v, *c;             // exp_avg, exp_avg_sq, kahan_comp (c: nullptr without kahan_sum)
-  size_t n;                    // elements, multiple of 8
-  float beta1, beta2;          // float32, as torch's mul_ by a python scalar uses them
+// schedule-free Kahan AdamW (sfk_kernel)
+struct SfkP : OptimP {
+  bf16* c;                     // kahan_comp (nullptr without kahan_sum)
   float one_minus_beta1_bf16;  // alpha of exp_avg.add_(grad, alpha=1-beta1): rounded to bf16 as torch does
-  float one_minus_beta2;       // value of addcmul_
-  float eps_bf16;              // denom.add_(eps): eps rounded to bf16
   int has_wd;                  // weight_decay != 0
   float wd_alpha_bf16;         // reference mode: alpha of p.add_(p, alpha=-weight_decay), rounded to bf16
   float neg_step;              // reference mode: -step_size (float32)
   float step;                  // compensated mode: step_size (float32)
   float decay;                 // compensated mode: step_size * weight_decay (float32)
-  int grad_round_bf16;         // round the (scaled) gradient to bf16 first
-  const float* grad_scale;     // device scalar multiplied into the gradient (unscale / clip), or nullptr
-  float* ema;                  // as AdamWP::ema / ema_omd
-  float ema_omd;
 };
 int launch_sfk(const SfkP& q, int reference, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);

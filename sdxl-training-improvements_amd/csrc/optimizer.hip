@@ -14,6 +14,7 @@
 // fp32 bit pattern and the low half dropped; r comes from a counter-based generator (Philox-4x32-7 keyed by the
 // seed, counter = (element-pair index, step)) or, for the parity tests, from a caller-supplied table.
 #include "kernels.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -56,6 +57,34 @@ __device__ __forceinline__ void ema_update8(float* ema, const bf16x8& pv, float 
   __builtin_nontemporal_store(b, (f32x4*)(ema + 4));
 }
 
+// ---- what both update kernels do the same way (OptimP: the fields they share) ----
+// 8 gradients from e0 on as floats.  f32: the native fp32 arena (else bf16 gradients); NT_BF16: stream the bf16 gradients past the
+// caches like the arenas (the fp32 ones always are)
+template <bool NT_BF16>
+__device__ __forceinline__ void load_grad8(const OptimP& q, bool f32, size_t e0, float g[8]) {
+  if (f32) {
+    const f32x4 a = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0)), b = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0 + 4));
+    g[0] = a[0]; g[1] = a[1]; g[2] = a[2]; g[3] = a[3]; g[4] = b[0]; g[5] = b[1]; g[6] = b[2]; g[7] = b[3];
+  } else {
+    const bf16x8 gv = NT_BF16 ? __builtin_nontemporal_load((const bf16x8*)(q.grad_bf16 + e0)) : *(const bf16x8*)(q.grad_bf16 + e0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = bf(gv[e]);
+  }
+}
+// the gradient the update sees: fused unscale / clip coefficient, then bf16 as the reference's gradients are bf16 tensors
+__device__ __forceinline__ float scaled_grad(const OptimP& q, float g, float gscale) {
+  const float gr = g * gscale;
+  return q.grad_round_bf16 ? bf(rn(gr)) : gr;
+}
+// exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2) -> v;  denom = exp_avg_sq.sqrt().add_(eps), returned
+// (adamw_bfloat16/__init__.py:164, :176-181; the schedule-free reference has the same ops)
+__device__ __forceinline__ float second_moment(const OptimP& q, bf16& v, float gr) {
+  const float v1 = bf(rn(bf(v) * q.beta2));
+  v = rn(__builtin_fmaf(q.one_minus_beta2 * gr, gr, v1));
+  const float den = bf(rn(__builtin_sqrtf(bf(v))));
+  return bf(rn(den + q.eps_bf16));
+}
+
 // EMA: also update q.ema from the new p (ema_update8); EMA = false is the update alone
 template <bool INJECT, bool EMA>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
@@ -66,14 +95,7 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
     bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), mv = __builtin_nontemporal_load((const bf16x8*)(q.m + e0)),
            vv = __builtin_nontemporal_load((const bf16x8*)(q.v + e0)), sv = __builtin_nontemporal_load((const bf16x8*)(q.shift + e0));
     float g[8];
-    if (q.grad_f32) {
-      const f32x4 a = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0)), b = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0 + 4));
-      g[0] = a[0]; g[1] = a[1]; g[2] = a[2]; g[3] = a[3]; g[4] = b[0]; g[5] = b[1]; g[6] = b[2]; g[7] = b[3];
-    } else {
-      const bf16x8 gv = *(const bf16x8*)(q.grad_bf16 + e0);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = bf(gv[e]);
-    }
+    load_grad8<false>(q, q.grad_f32 != nullptr, e0, g);
     unsigned rnd[4][4];     // [element pair][word]: counter = (pair index, step), key = seed
     if (!INJECT) {
 #pragma unroll
@@ -91,8 +113,7 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
         const unsigned a = rnd[e >> 1][(e & 1) * 2], b = rnd[e >> 1][(e & 1) * 2 + 1];
         r0 = a & 0xFFFFu; r1 = a >> 16; r2 = b & 0xFFFFu; r3 = b >> 16;
       }
-      float gr = g[e] * gscale;                                  // fused unscale / clip coefficient
-      if (q.grad_round_bf16) gr = bf(rn(gr));                    // the reference's gradients are bf16 tensors
+      const float gr = scaled_grad(q, g[e], gscale);
       const float pf = bf(pv[e]), sf = bf(sv[e]);
       // exp_avg.mul_(beta1); add_stochastic_(exp_avg, grad, alpha=1-beta1)       (__init__.py:162-163)
       const float m1 = bf(rn(bf(mv[e]) * q.beta1));
@@ -100,12 +121,8 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(const AdamWP q) {
                                        : __builtin_fmaf(gr, q.one_minus_beta1, m1);     // exp_avg + alpha * grad
       const bf16 m2b = sr(rm, r0);
       const float m2 = bf(m2b);
-      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)                 (:164)
-      const float v1 = bf(rn(bf(vv[e]) * q.beta2));
-      const bf16 v2b = rn(__builtin_fmaf(q.one_minus_beta2 * gr, gr, v1));
-      // denom = exp_avg_sq.sqrt().add_(eps)                                         (:176-181)
-      float den = bf(rn(__builtin_sqrtf(bf(v2b))));
-      den = bf(rn(den + q.eps_bf16));
+      bf16 v2b = vv[e];
+      const float den = second_moment(q, v2b, gr);
       // addcdiv_stochastic_(shift, exp_avg, denom, value=-lr*sqrt(1-beta2^t))       (stochastic:106-124)
       const bf16 s1b = sr(sf + (q.value * m2) / den, r1);
       const float s1 = bf(s1b);
@@ -131,24 +148,39 @@ __global__ void adamw_decay_kernel(bf16* shift, const bf16* p, size_t n, float a
     shift[i] = rn(__builtin_fmaf(bf(p[i]), alpha, bf(shift[i])));
 }
 
-int launch_adamw_bf16(const AdamWP& q, hipStream_t st) {
-  ARG_CHECK(q.p && q.m && q.v && q.shift && (q.grad_f32 || q.grad_bf16), "adamw: missing buffers");
-  ARG_CHECK(q.n % 8 == 0 && q.elem_offset % 8 == 0, "adamw: n=%zu, elem_offset=%zu: each must be a multiple of 8", q.n, q.elem_offset);
-  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.shift | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16 |
+// ---- what both launches do the same way ----
+// the argument checks, `who` in front of each message: the buffers are there (third: shift / kahan_comp, may be NULL unless
+// need_third), n and the launch's arena offset are multiples of 8 (mult8: that message, which names what the algorithm has), and
+// every buffer is 16-byte aligned
+static int check_arenas(const OptimP& q, const bf16* third, bool need_third, size_t elem_offset, const char* who, const char* mult8) {
+  ARG_CHECK(q.p && q.m && q.v && (third || !need_third) && (q.grad_f32 || q.grad_bf16), "%s: missing buffers", who);
+  ARG_CHECK(q.n % 8 == 0 && elem_offset % 8 == 0, mult8, who, q.n, elem_offset);
+  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)third | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16 |
               (uintptr_t)q.ema) & 15) == 0,
-            "adamw: buffers must be 16-byte aligned");
+            "%s: buffers must be 16-byte aligned", who);
+  return 0;
+}
+// 256 threads x 8 elements per workgroup, at most 16 workgroups per CU (256 CUs): the kernels grid-stride the rest
+static dim3 arena_grid(size_t n) {
+  size_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  return dim3((unsigned)blocks);
+}
+// runtime flags -> bool template arguments: with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+template <class F>
+static void with_flags(F f) { f(); }
+template <class F, class... Flags>
+static void with_flags(F f, bool flag, Flags... rest) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+int launch_adamw_bf16(const AdamWP& q, hipStream_t st) {
+  if (int rc = check_arenas(q, q.shift, true, q.elem_offset, "adamw", "%s: n=%zu, elem_offset=%zu: each must be a multiple of 8")) return rc;
   if (q.n == 0) return 0;
-  size_t nvec = q.n / 8;
-  size_t blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;      // 16 workgroups per CU, grid-stride the rest
-  const dim3 grid((unsigned)blocks);
-  if (q.ema) {
-    if (q.rand) hipLaunchKernelGGL((adamw_bf16_kernel<true, true>), grid, dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((adamw_bf16_kernel<false, true>), grid, dim3(256), 0, st, q);
-  } else {
-    if (q.rand) hipLaunchKernelGGL((adamw_bf16_kernel<true, false>), grid, dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((adamw_bf16_kernel<false, false>), grid, dim3(256), 0, st, q);
-  }
+  with_flags([&](auto inject, auto ema) {
+    hipLaunchKernelGGL((adamw_bf16_kernel<decltype(inject)::value, decltype(ema)::value>), arena_grid(q.n), dim3(256), 0, st, q);
+  }, q.rand != nullptr, q.ema != nullptr);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -184,26 +216,16 @@ __global__ __launch_bounds__(256) void sfk_kernel(const SfkP q) {
     bf16x8 cv;
     if constexpr (KAHAN) cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0));
     float g[8];
-    if constexpr (F32G) {
-      const f32x4 a = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0)), b = __builtin_nontemporal_load((const f32x4*)(q.grad_f32 + e0 + 4));
-      g[0] = a[0]; g[1] = a[1]; g[2] = a[2]; g[3] = a[3]; g[4] = b[0]; g[5] = b[1]; g[6] = b[2]; g[7] = b[3];
-    } else {
-      const bf16x8 gv = __builtin_nontemporal_load((const bf16x8*)(q.grad_bf16 + e0));
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = bf(gv[e]);
-    }
+    load_grad8<true>(q, F32G, e0, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float gr = g[e] * gscale;                                  // fused unscale / clip coefficient
-      if (q.grad_round_bf16) gr = bf(rn(gr));
+      float gr = scaled_grad(q, g[e], gscale);
       if constexpr (REF && KAHAN) gr = bf(rn(gr + bf(cv[e])));  // grad.add_(kahan_comp)
       const float m1 = bf(rn(bf(mv[e]) * q.beta1));
       const bf16 m2b = rn(__builtin_fmaf(gr, q.one_minus_beta1_bf16, m1));
       const float m2 = bf(m2b);
-      const float v1 = bf(rn(bf(vv[e]) * q.beta2));
-      const bf16 v2b = rn(__builtin_fmaf(q.one_minus_beta2 * gr, gr, v1));
-      float den = bf(rn(__builtin_sqrtf(bf(v2b))));
-      den = bf(rn(den + q.eps_bf16));
+      bf16 v2b = vv[e];
+      const float den = second_moment(q, v2b, gr);
       float pf = bf(pv[e]);
       if constexpr (REF) {
         if (q.has_wd) pf = bf(rn(__builtin_fmaf(pf, q.wd_alpha_bf16, pf)));   // p.data.add_(p.data, alpha=-weight_decay)
@@ -233,32 +255,13 @@ __global__ __launch_bounds__(256) void sfk_kernel(const SfkP q) {
   }
 }
 
-template <bool REF, bool KAHAN, bool EMA>
-static void launch_sfk_g(const SfkP& q, unsigned blocks, hipStream_t st) {
-  if (q.grad_f32) hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, true, EMA>), dim3(blocks), dim3(256), 0, st, q);
-  else hipLaunchKernelGGL((sfk_kernel<REF, KAHAN, false, EMA>), dim3(blocks), dim3(256), 0, st, q);
-}
-template <bool REF, bool KAHAN>
-static void launch_sfk_e(const SfkP& q, unsigned blocks, hipStream_t st) {
-  if (q.ema) launch_sfk_g<REF, KAHAN, true>(q, blocks, st);
-  else launch_sfk_g<REF, KAHAN, false>(q, blocks, st);
-}
-
 int launch_sfk(const SfkP& q, int reference, hipStream_t st) {
-  ARG_CHECK(q.p && q.m && q.v && (q.grad_f32 || q.grad_bf16), "schedule-free: missing buffers");
-  ARG_CHECK(q.n % 8 == 0, "schedule-free: n=%zu must be a multiple of 8", q.n);
-  ARG_CHECK((((uintptr_t)q.p | (uintptr_t)q.m | (uintptr_t)q.v | (uintptr_t)q.c | (uintptr_t)q.grad_f32 | (uintptr_t)q.grad_bf16 |
-              (uintptr_t)q.ema) & 15) == 0,
-            "schedule-free: buffers must be 16-byte aligned");
+  if (int rc = check_arenas(q, q.c, false, 0, "schedule-free", "%s: n=%zu must be a multiple of 8")) return rc;
   if (q.n == 0) return 0;
-  size_t blocks = (q.n / 8 + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;      // as adamw_bf16_kernel: 16 workgroups per CU, grid-stride the rest
-  const unsigned nb = (unsigned)blocks;
-  if (reference) {
-    if (q.c) launch_sfk_e<true, true>(q, nb, st); else launch_sfk_e<true, false>(q, nb, st);
-  } else {
-    if (q.c) launch_sfk_e<false, true>(q, nb, st); else launch_sfk_e<false, false>(q, nb, st);
-  }
+  with_flags([&](auto ref, auto kahan, auto f32g, auto ema) {
+    hipLaunchKernelGGL((sfk_kernel<decltype(ref)::value, decltype(kahan)::value, decltype(f32g)::value, decltype(ema)::value>),
+                       arena_grid(q.n), dim3(256), 0, st, q);
+  }, reference != 0, q.c != nullptr, q.grad_f32 != nullptr, q.ema != nullptr);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -1,9 +1,10 @@
 """The fused optimizers on the packed arenas: host mirrors of the reference optimizer classes, arithmetic in csrc/optimizer.hip.
 
-AdamWBF16 (optimizer_type "adamw_bf16", the default) and AdamWScheduleFreeKahanBF16 ("adamw_schedule_free_kahan", see its
-docstring).  Both take their gradients from the arena, one fused launch per update, and share the host surface the trainer
-uses: step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups, step_count,
-state_dict / load_state_dict, state_arenas, attach_ema (an ema.WeightEMA updated inside the same launch, on the same pieces).
+FusedArenaOptimizer is what the trainer knows: gradients taken from the arena, one fused launch per update (per piece under
+ZeRO-1), and the host surface step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups,
+step_count, state_dict / load_state_dict, state_arenas, attach_ema (an ema.WeightEMA updated inside the same launch, on the same
+pieces).  Its two algorithms, by optimizer_type (BY_TYPE): AdamWBF16 ("adamw_bf16", the default) and AdamWScheduleFreeKahanBF16
+("adamw_schedule_free_kahan", see its docstring).
 
 AdamWBF16:
 
@@ -42,15 +43,28 @@ def _checked_ema(ema, weights: torch.Tensor):
     return ema
 
 
-class AdamWBF16:
-    decay_threshold = 5e-3                                   # adamw_bfloat16/__init__.py:27
+class FusedArenaOptimizer:
+    """What the algorithms share: bf16 state arenas laid out like the weight arena (exp_avg, exp_avg_sq, an optional third one)
+    and the skeleton of step().  A subclass names its third arena (THIRD: attribute and state key), the context string of its
+    launches (LAUNCH) and its own constructor keywords (CONFIG_KEYS), and has begin_step, finish_step and its state format."""
 
-    def __init__(self, net, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, reference_ema: bool = True,
-                 grad_round_bf16: bool = False, seed: int = 0):
-        """reference_ema (config key optimizer.reference_ema, default True): True reproduces the reference's ACTUAL first
-        moment, m <- SR(g + (1-beta1) * beta1 * m) -- `add_stochastic_(_input, other, alpha)` computes other + alpha*_input
-        (stochastic/__init__.py:96, SURVEY D17), i.e. almost no momentum; False selects the documented EMA
-        m <- SR(beta1 * m + (1-beta1) * g)."""
+    def __init__(self, net, group: Dict[str, Any], *, third: bool, grad_round_bf16: bool):
+        """group: param_groups[0], already checked (check_hyper and the subclass's own); third: allocate the third arena"""
+        self.net = net
+        self.L = getattr(net, "L", None)                      # the loaded libsdxlstep; step() refuses to run without it
+        self.param_groups = [group]
+        w = net.weights
+        assert w.dtype == torch.bfloat16, "only bfloat16 is supported."          # adamw_bfloat16/__init__.py:98
+        self.exp_avg = torch.zeros_like(w)
+        self.exp_avg_sq = torch.zeros_like(w)
+        setattr(self, self.THIRD, torch.zeros_like(w) if third else None)
+        self.grad_round_bf16 = bool(grad_round_bf16)
+        self.step_count = 0
+        self._post_step_hooks = []
+        self.ema = None
+
+    @staticmethod
+    def check_hyper(betas, eps, weight_decay) -> None:
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
         if not 0.0 <= betas[0] < 1.0:
@@ -59,37 +73,98 @@ class AdamWBF16:
             raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        self.net = net
-        self.L = getattr(net, "L", None)                      # the loaded libsdxlstep; step() refuses to run without it
-        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)]
-        w = net.weights
-        assert w.dtype == torch.bfloat16, "only bfloat16 is supported."          # :98
-        self.exp_avg = torch.zeros_like(w)
-        self.exp_avg_sq = torch.zeros_like(w)
-        self.shift = torch.zeros_like(w)                      # true value is p + shift (:108-112)
-        self.step_count = 0
-        self.reference_ema = bool(reference_ema)
-        self.grad_round_bf16 = bool(grad_round_bf16)
-        self.seed = int(seed)
-        self.ranges = net.param_ranges() if hasattr(net, "param_ranges") else {}
-        # each tensor starts its decay account at a random phase so that they do not all pay at once (:116-119)
-        g = torch.Generator().manual_seed(self.seed)
-        self.accumulated_decay = {k: float(torch.rand([], generator=g) * self.decay_threshold) for k in self.ranges}
-        self._post_step_hooks = []
-        self.ema = None
+
+    @classmethod
+    def from_config(cls, net, oc):
+        """the optimizer for the `optimizer` section of the config (main.py:73-86 builds the reference's from config.optimizer.kwargs);
+        CONFIG_KEYS: the subclass's own keywords, {constructor keyword: (config key, default when the section lacks it)}"""
+        return cls(net, lr=oc.learning_rate, betas=(oc.beta1, oc.beta2), eps=oc.epsilon, weight_decay=oc.weight_decay,
+                   **{kw: getattr(oc, key, default) for kw, (key, default) in cls.CONFIG_KEYS.items()})
 
     def register_step_post_hook(self, fn) -> None:
         """fn(optimizer) after every step() (same idea as torch.optim.Optimizer.register_step_post_hook)."""
         self._post_step_hooks.append(fn)
 
     def attach_ema(self, ema) -> None:
-        """ema (ema.WeightEMA): from now on every step() also updates its arena, fused into the update (None detaches).
-        ValueError when its arena is not an fp32 image of this optimizer's weight arena (size, device)."""
+        """ema (ema.WeightEMA): from now on every step() also updates its arena, fused into the update (None detaches).  The EMA
+        tracks p itself, not p + the third arena.  ValueError when its arena is not an fp32 image of this optimizer's weight arena
+        (size, device)."""
         self.ema = _checked_ema(ema, self.net.weights)
 
-    # ------------------------------------------------------------------ reference surface
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.net.zero_grads()
+
+    def state_arenas(self):
+        """the state arenas laid out like the weight arena (what ZeRO-1 gathers before a checkpoint)"""
+        third = getattr(self, self.THIRD)
+        return (self.exp_avg, self.exp_avg_sq) + ((third,) if third is not None else ())
+
+    def _load_arenas(self, st: Dict[str, Any]) -> None:
+        self.step_count = int(st["step"])
+        for k, t in zip(("exp_avg", "exp_avg_sq", self.THIRD), self.state_arenas()):
+            t.copy_(st[k])
+
+    @torch.no_grad()
+    def _step(self, grads, grad_scale, zero_grad, pieces, rand=None) -> None:
+        """One update of every parameter.  grads: None = the net's fp32 gradient arena, or a bf16 / fp32 tensor in
+        arena layout (the all-reduced bf16 gradients under data parallelism).  grad_scale: optional 1-element device
+        tensor multiplied into the gradient inside the kernel (clip coefficient, 1/accumulation).
+        pieces (ZeRO-1, distributed.ShardedGradSync.pieces): [(arena offset, count, offset into `grads`)] -- only those
+        ranges of the arenas are updated, `grads` then holds just this rank's reduce-scattered shard; every launch is told its
+        arena offset (the stochastic-rounding counters are keyed by arena index), so the union over ranks is bit-identical to
+        the unsharded update."""
+        if self.L is None:
+            raise lib.SdxlError(f"{type(self).__name__}.step needs libsdxlstep.so (there is no PyTorch fallback for the optimizer step)")
+        grp = self.param_groups[0]
+        w = self.net.weights
+        g = self.net.grads if grads is None else grads
+        if g.dtype not in (torch.float32, torch.bfloat16) or (pieces is None and g.numel() != w.numel()):
+            raise ValueError("grads must be an fp32 or bf16 tensor in arena layout")
+        cfg = lib.AdamWConfig()
+        lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
+        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
+        cfg.grad_round_bf16 = int(self.grad_round_bf16)
+        begun = self.begin_step(cfg, grp)                          # the algorithm's fields and what it books before the launches
+        if self.ema is not None:
+            cfg.ema_one_minus_decay = self.ema.advance()          # once per step, whatever the number of pieces
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if w.is_cuda else None
+        gsz = g.element_size()
+        todo = [(0, w.numel(), 0)] if pieces is None else list(pieces)
+        for off, cnt, goff in todo:
+            cfg.elem_offset = off
+            cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
+            at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o) if t is not None else None
+            lib.check(self.L.sdxl_adamw_bf16_step(at(w), C.c_void_p(g.data_ptr() + gsz * goff), 0 if g.dtype == torch.float32 else 1,
+                                                  at(self.exp_avg), at(self.exp_avg_sq), at(getattr(self, self.THIRD)), cnt,
+                                                  C.byref(cfg), _ptr(grad_scale), _ptr(rand), st), self.LAUNCH)
+        self.finish_step(begun, todo, st)                         # its remaining launches and bookkeeping
+        if zero_grad:
+            self.net.zero_grads()
+        for fn in self._post_step_hooks:
+            fn(self)
+
+
+class AdamWBF16(FusedArenaOptimizer):
+    decay_threshold = 5e-3                                   # adamw_bfloat16/__init__.py:27
+    THIRD = "shift"                                          # true value is p + shift (:108-112)
+    LAUNCH = "sdxl_adamw_bf16_step"
+    CONFIG_KEYS = {"reference_ema": ("reference_ema", True)}
+
+    def __init__(self, net, *, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, reference_ema: bool = True,
+                 grad_round_bf16: bool = False, seed: int = 0):
+        """reference_ema (config key optimizer.reference_ema, default True): True reproduces the reference's ACTUAL first
+        moment, m <- SR(g + (1-beta1) * beta1 * m) -- `add_stochastic_(_input, other, alpha)` computes other + alpha*_input
+        (stochastic/__init__.py:96, SURVEY D17), i.e. almost no momentum; False selects the documented EMA
+        m <- SR(beta1 * m + (1-beta1) * g)."""
+        self.check_hyper(betas, eps, weight_decay)
+        super().__init__(net, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), third=True,
+                         grad_round_bf16=grad_round_bf16)
+        self.reference_ema = bool(reference_ema)
+        self.seed = int(seed)
+        self.ranges = net.param_ranges() if hasattr(net, "param_ranges") else {}
+        # each tensor starts its decay account at a random phase so that they do not all pay at once (:116-119)
+        g = torch.Generator().manual_seed(self.seed)
+        self.accumulated_decay = {k: float(torch.rand([], generator=g) * self.decay_threshold) for k in self.ranges}
 
     def state_dict(self) -> Dict[str, Any]:
         return {"state": {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
@@ -99,62 +174,34 @@ class AdamWBF16:
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if sd.get("algorithm", "adamw_bf16") != "adamw_bf16":
             raise ValueError(f"optimizer state of {sd.get('algorithm')!r} cannot be loaded into AdamWBF16")
-        st = sd["state"]
-        self.step_count = int(st["step"])
-        for k in ("exp_avg", "exp_avg_sq", "shift"):
-            getattr(self, k).copy_(st[k])
-        self.accumulated_decay = dict(st["accumulated_decay"])
+        self._load_arenas(sd["state"])
+        self.accumulated_decay = dict(sd["state"]["accumulated_decay"])
         self.param_groups = sd["param_groups"]
 
-    def state_arenas(self):
-        """the state arenas laid out like the weight arena (what ZeRO-1 gathers before a checkpoint)"""
-        return (self.exp_avg, self.exp_avg_sq, self.shift)
-
-    @torch.no_grad()
     def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
              zero_grad: bool = False, _rand: Optional[torch.Tensor] = None, pieces=None) -> None:
-        """One update of every parameter.  grads: None = the net's fp32 gradient arena, or a bf16 / fp32 tensor in
-        arena layout (the all-reduced bf16 gradients under data parallelism).  grad_scale: optional 1-element device
-        tensor multiplied into the gradient inside the kernel (clip coefficient, 1/accumulation).
-        pieces (ZeRO-1, distributed.ShardedGradSync.pieces): [(arena offset, count, offset into `grads`)] -- only those
-        ranges of the arenas are updated, `grads` then holds just this rank's reduce-scattered shard; the stochastic-rounding
-        counters are keyed by arena index, so the union over ranks is bit-identical to the unsharded update."""
-        if self.L is None:
-            raise lib.SdxlError("AdamWBF16.step needs libsdxlstep.so (there is no PyTorch fallback for the optimizer step)")
-        grp = self.param_groups[0]
-        g = self.net.grads if grads is None else grads
-        if g.dtype not in (torch.float32, torch.bfloat16) or (pieces is None and g.numel() != self.net.weights.numel()):
-            raise ValueError("grads must be an fp32 or bf16 tensor in arena layout")
+        """One update of every parameter: arguments as FusedArenaOptimizer._step.  _rand (the parity tests): uint16 [4][n] random
+        integers instead of the kernel's counter-based generator."""
+        self._step(grads, grad_scale, zero_grad, pieces, _rand)
+
+    def begin_step(self, cfg, grp):
+        """counts the step and books each tensor's decay before the launches; returns the tensors whose decay is due"""
         self.step_count += 1
-        lr, wd = float(grp["lr"]), float(grp["weight_decay"])
+        owed = float(grp["weight_decay"]) * float(grp["lr"])
         due = []
         for k in self.accumulated_decay:                      # :121-126, per tensor
-            acc = self.accumulated_decay[k] + wd * lr
+            acc = self.accumulated_decay[k] + owed
             d = acc if acc > self.decay_threshold else 0.0
             self.accumulated_decay[k] = acc - d
             if d > 0:
                 due.append((k, d))
-        cfg = lib.AdamWConfig()
-        lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
-        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = lr, grp["betas"], float(grp["eps"])
         cfg.step = float(self.step_count)
         cfg.decay_this_iteration = 0.0
         cfg.reference_ema = int(self.reference_ema)
-        cfg.grad_round_bf16 = int(self.grad_round_bf16)
         cfg.seed = self.seed
-        if self.ema is not None:
-            cfg.ema_one_minus_decay = self.ema.advance()
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if self.net.weights.is_cuda else None
-        gsz = g.element_size()
-        todo = [(0, self.net.weights.numel(), 0)] if pieces is None else list(pieces)
-        for off, cnt, goff in todo:
-            cfg.elem_offset = off
-            cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
-            at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o)
-            lib.check(self.L.sdxl_adamw_bf16_step(at(self.net.weights), C.c_void_p(g.data_ptr() + gsz * goff),
-                                                  0 if g.dtype == torch.float32 else 1, at(self.exp_avg), at(self.exp_avg_sq),
-                                                  at(self.shift), cnt, C.byref(cfg), _ptr(grad_scale), _ptr(_rand), st),
-                      "sdxl_adamw_bf16_step")
+        return due
+
+    def finish_step(self, due, todo, st) -> None:
         for k, d in due:                                       # :191-193 `shift.add_(p, alpha=-decay)`, on the owned part
             toff, tcnt = self.ranges[k]
             for off, cnt, _g in todo:
@@ -162,13 +209,9 @@ class AdamWBF16:
                 if lo < hi:
                     lib.check(self.L.sdxl_adamw_decay(C.c_void_p(self.shift.data_ptr() + 2 * lo),
                                                       C.c_void_p(self.net.weights.data_ptr() + 2 * lo), hi - lo, d, st), "sdxl_adamw_decay")
-        if zero_grad:
-            self.net.zero_grads()
-        for fn in self._post_step_hooks:
-            fn(self)
 
 
-class AdamWScheduleFreeKahanBF16:
+class AdamWScheduleFreeKahanBF16(FusedArenaOptimizer):
     """AdamWScheduleFreeKahan on the packed arenas (reference: src/training/optimizers/adamw_schedulefree/__init__.py).
 
     Host scalars are the reference's python doubles (k = step_count before the increment):
@@ -194,57 +237,32 @@ class AdamWScheduleFreeKahanBF16:
 
     `correct_bias` is accepted (the reference's config passes it) and ignored: the reference has no such option either.
     The reference never creates its "z" state, so eval() / train() are no-ops there and here.
+    No random numbers are involved, so a ZeRO-1 update of `pieces` is bit-identical to the unsharded one by construction.
     There is no PyTorch fallback: the step fails loudly without libsdxlstep.so."""
 
     ARITHMETIC = ("compensated", "reference")
     algorithm = "adamw_schedule_free_kahan"
+    THIRD = "kahan_comp"
+    LAUNCH = "sdxl_adamw_bf16_step (schedule-free Kahan)"
+    CONFIG_KEYS = {"warmup_steps": ("warmup_steps", 0), "kahan_sum": ("kahan_sum", True),
+                   "arithmetic": ("schedule_free_arithmetic", "compensated"), "correct_bias": ("correct_bias", None)}
 
     def __init__(self, net, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, warmup_steps: int = 0,
                  kahan_sum: bool = True, arithmetic: str = "compensated", grad_round_bf16: bool = False, correct_bias=None):
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self.check_hyper(betas, eps, weight_decay)
         if int(warmup_steps) < 0:
             raise ValueError(f"Invalid warmup_steps value: {warmup_steps}")
         arithmetic = str(arithmetic).lower()
         if arithmetic not in self.ARITHMETIC:
             raise ValueError(f"optimizer.schedule_free_arithmetic must be one of {self.ARITHMETIC}, got {arithmetic!r}")
-        self.net = net
-        self.L = getattr(net, "L", None)
-        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, warmup_steps=int(warmup_steps),
-                                  kahan_sum=bool(kahan_sum))]
-        w = net.weights
-        assert w.dtype == torch.bfloat16, "only bfloat16 is supported."
         self.kahan_sum = bool(kahan_sum)
         self.arithmetic = arithmetic
-        self.grad_round_bf16 = bool(grad_round_bf16)
-        self.exp_avg = torch.zeros_like(w)
-        self.exp_avg_sq = torch.zeros_like(w)
-        self.kahan_comp = torch.zeros_like(w) if self.kahan_sum else None
-        self.step_count = 0                                   # the reference's self.k
-        self.lr_max = -1.0
+        super().__init__(net, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, warmup_steps=int(warmup_steps),
+                                   kahan_sum=self.kahan_sum), third=self.kahan_sum, grad_round_bf16=grad_round_bf16)
+        self.lr_max = -1.0                                    # (step_count is the reference's self.k)
         self.last_lr = -1.0
-        self._post_step_hooks = []
-        self.ema = None
-
-    def register_step_post_hook(self, fn) -> None:
-        """fn(optimizer) after every step()."""
-        self._post_step_hooks.append(fn)
-
-    def attach_ema(self, ema) -> None:
-        """as AdamWBF16.attach_ema: the EMA tracks p, not p + kahan_comp"""
-        self.ema = _checked_ema(ema, self.net.weights)
-
-    # ------------------------------------------------------------------ reference surface
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        self.net.zero_grads()
 
     def eval(self) -> None:
         """no-op, as in the reference (its "z" state is never created)"""
@@ -254,10 +272,6 @@ class AdamWScheduleFreeKahanBF16:
 
     def get_last_lr(self) -> float:
         return self.last_lr
-
-    def state_arenas(self):
-        """the state arenas laid out like the weight arena (what ZeRO-1 gathers before a checkpoint)"""
-        return (self.exp_avg, self.exp_avg_sq) + ((self.kahan_comp,) if self.kahan_sum else ())
 
     def _tag(self) -> Dict[str, Any]:
         return {"algorithm": self.algorithm, "arithmetic": self.arithmetic, "kahan_sum": self.kahan_sum}
@@ -274,9 +288,7 @@ class AdamWScheduleFreeKahanBF16:
         if got != self._tag():
             raise ValueError(f"optimizer state tagged {got} cannot be loaded into an optimizer configured as {self._tag()}")
         st = sd["state"]
-        self.step_count = int(st["step"])
-        for k in ("exp_avg", "exp_avg_sq") + (("kahan_comp",) if self.kahan_sum else ()):
-            getattr(self, k).copy_(st[k])
+        self._load_arenas(st)
         self.lr_max, self.last_lr = float(st["lr_max"]), float(st["last_lr"])
         self.param_groups = sd["param_groups"]
 
@@ -289,49 +301,27 @@ class AdamWScheduleFreeKahanBF16:
         adjusted_lr = lr * sched * (bias_correction2 ** 0.5)
         return adjusted_lr, adjusted_lr / (bias_correction2 ** 0.5)
 
-    @torch.no_grad()
     def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
              zero_grad: bool = False, pieces=None) -> None:
-        """One update of every parameter; arguments as AdamWBF16.step (no random numbers are involved, so a ZeRO-1 update
-        of `pieces` is bit-identical to the unsharded one by construction)."""
-        if self.L is None:
-            raise lib.SdxlError("AdamWScheduleFreeKahanBF16.step needs libsdxlstep.so (there is no PyTorch fallback for the optimizer step)")
-        grp = self.param_groups[0]
-        g = self.net.grads if grads is None else grads
-        if g.dtype not in (torch.float32, torch.bfloat16) or (pieces is None and g.numel() != self.net.weights.numel()):
-            raise ValueError("grads must be an fp32 or bf16 tensor in arena layout")
+        """One update of every parameter: arguments as FusedArenaOptimizer._step."""
+        self._step(grads, grad_scale, zero_grad, pieces)
+
+    def begin_step(self, cfg, grp):
         adjusted_lr, step_size = self.schedule()
         self.lr_max = max(adjusted_lr, self.lr_max)
-        cfg = lib.AdamWConfig()
-        lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
-        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
         cfg.step = float(self.step_count + 1)
-        cfg.grad_round_bf16 = int(self.grad_round_bf16)
         cfg.algorithm = 1
         cfg.kahan_sum = int(self.kahan_sum)
         cfg.sf_reference = int(self.arithmetic == "reference")
         cfg.weight_decay = float(grp["weight_decay"])
         cfg.sf_step_size = step_size
-        if self.ema is not None:
-            cfg.ema_one_minus_decay = self.ema.advance()
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if self.net.weights.is_cuda else None
-        gsz = g.element_size()
-        todo = [(0, self.net.weights.numel(), 0)] if pieces is None else list(pieces)
-        for off, cnt, goff in todo:
-            cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
-            at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o) if t is not None else None
-            lib.check(self.L.sdxl_adamw_bf16_step(at(self.net.weights), C.c_void_p(g.data_ptr() + gsz * goff),
-                                                  0 if g.dtype == torch.float32 else 1, at(self.exp_avg), at(self.exp_avg_sq),
-                                                  at(self.kahan_comp), cnt, C.byref(cfg), _ptr(grad_scale), None, st),
-                      "sdxl_adamw_bf16_step (schedule-free Kahan)")
+        return adjusted_lr
+
+    def finish_step(self, adjusted_lr, todo, st) -> None:
+        """counts the step after the launches"""
         self.step_count += 1
         self.last_lr = adjusted_lr
-        if zero_grad:
-            self.net.zero_grads()
-        for fn in self._post_step_hooks:
-            fn(self)
 
 
-FUSED = (AdamWBF16, AdamWScheduleFreeKahanBF16)          # the optimizers whose step() takes the arena, grad_scale and pieces
 # optimizer_type (lower-cased, as the reference's OptimizerConfig.class_name does) -> the fused class built for it
 BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16}

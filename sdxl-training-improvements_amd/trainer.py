@@ -43,7 +43,7 @@ from . import distributed as D
 from . import lib
 from .config import Config
 from .ema import WeightEMA
-from .optimizer import BY_TYPE, FUSED, AdamWBF16, AdamWScheduleFreeKahanBF16
+from .optimizer import BY_TYPE, AdamWBF16, FusedArenaOptimizer
 from .scheduler import NoiseScheduler
 from .unet import NativeUNet, config_from_unet
 
@@ -109,7 +109,7 @@ class NativeSDXLTrainer:
         self.ema = build_ema(self.net, self.optimizer, self.config.training)     # None unless training.use_ema
         self._clip_coef = None
         # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
-        want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, FUSED)
+        want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, FusedArenaOptimizer)
         seg_sizes = [n for _off, n in self.net.segment_ranges()] if hasattr(self.net, "segment_ranges") else None
         # force_exchange (build-only key / SDXL_FORCE_EXCHANGE=1): run the exchange through the backend even at world size 1
         force = bool(getattr(self.config.training, "force_exchange", False)) or os.environ.get("SDXL_FORCE_EXCHANGE", "0") == "1"
@@ -341,7 +341,7 @@ class NativeSDXLTrainer:
         the norm is taken over the exchanged gradients: the whole all-reduced arena, or (ZeRO-1) this rank's
         reduce-scattered slices + one float all-reduced -- the coefficient is then the same bits on every rank."""
         self.sync.finish()                                   # the asynchronous exchange must have landed
-        fused = isinstance(self.optimizer, FUSED)            # the coefficient rides into the fused optimizer kernel
+        fused = isinstance(self.optimizer, FusedArenaOptimizer)   # the coefficient rides into the fused optimizer kernel
         g = self.sync.reduced() if self.sync.active else self.net.grads
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if g.is_cuda else None
         if g.is_cuda:                                        # squared norm + coefficient on the device (HIP kernels)
@@ -375,7 +375,7 @@ class NativeSDXLTrainer:
         if self.config.training.clip_grad_norm and self.config.training.clip_grad_norm > 0:
             gn = self.clip_grad_norm_(float(self.config.training.clip_grad_norm))
         if self.optimizer is not None:
-            if isinstance(self.optimizer, FUSED):
+            if isinstance(self.optimizer, FusedArenaOptimizer):
                 if self.sync.active and self.sharded:        # ZeRO-1: update this rank's slices, then all-gather the parameters
                     self.optimizer.step(self.sync.reduced(), grad_scale=self._clip_coef, pieces=self.sync.pieces)
                     self.sync.gather_params(self.net.weights)
@@ -522,7 +522,7 @@ class NativeSDXLTrainer:
         self.ema.load_state_dict(st)
 
     def _zero1_active(self) -> bool:
-        return bool(self.sharded and self.sync.active and isinstance(self.optimizer, FUSED) and getattr(self.sync, "buckets", None))
+        return bool(self.sharded and self.sync.active and isinstance(self.optimizer, FusedArenaOptimizer) and getattr(self.sync, "buckets", None))
 
     def prepare_checkpoint(self) -> None:
         """COLLECTIVE -- every rank calls it, at the same point of its loop, before rank 0 calls save_checkpoint().  Under ZeRO-1
@@ -595,12 +595,7 @@ def build_optimizer(net, oc):
         logger.warning("optimizer_type %r has no fused implementation in this build: training with AdamWBF16 (adamw_bf16) instead",
                        getattr(oc, "optimizer_type", None))
         cls = AdamWBF16
-    common = dict(lr=oc.learning_rate, betas=(oc.beta1, oc.beta2), eps=oc.epsilon, weight_decay=oc.weight_decay)
-    if cls is AdamWScheduleFreeKahanBF16:
-        return cls(net, **common, warmup_steps=int(getattr(oc, "warmup_steps", 0)), kahan_sum=bool(getattr(oc, "kahan_sum", True)),
-                   arithmetic=str(getattr(oc, "schedule_free_arithmetic", "compensated")),
-                   correct_bias=getattr(oc, "correct_bias", None))
-    return AdamWBF16(net, **common, reference_ema=bool(getattr(oc, "reference_ema", True)))
+    return cls.from_config(net, oc)
 
 
 def build_ema(net, optimizer, tc) -> Optional[WeightEMA]:
@@ -608,8 +603,8 @@ def build_ema(net, optimizer, tc) -> Optional[WeightEMA]:
     attached to the fused optimizer whose kernel updates it; None otherwise."""
     if not bool(getattr(tc, "use_ema", False)):
         return None
-    if not isinstance(optimizer, FUSED):
-        raise ValueError(f"training.use_ema needs one of the fused optimizers ({', '.join(c.__name__ for c in FUSED)}): the EMA "
+    if not isinstance(optimizer, FusedArenaOptimizer):
+        raise ValueError(f"training.use_ema needs one of the fused optimizers ({', '.join(c.__name__ for c in BY_TYPE.values())}): the EMA "
                          f"update runs inside their kernel, and {type(optimizer).__name__} has none")
     ema = WeightEMA(net, decay=float(getattr(tc, "ema_decay", 0.9999)), min_decay=float(getattr(tc, "ema_min_decay", 0.0)),
                     update_after_step=int(getattr(tc, "ema_update_after_step", 0)),

@@ -19,30 +19,15 @@ import torch.distributed as dist
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import sdxl_amd  # noqa: E402,F401
 from oracle import unet_ref as U  # noqa: E402
-from sdxl_amd import lib  # noqa: E402
 from sdxl_amd import unet as NU  # noqa: E402
+
+from _optim_common import Arena  # noqa: E402
 
 D = importlib.import_module("sdxl-training-improvements_amd.distributed")
 O = importlib.import_module("sdxl-training-improvements_amd.optimizer")
 E = importlib.import_module("sdxl-training-improvements_amd.ema")
 T = importlib.import_module("sdxl-training-improvements_amd.trainer")
 CFG = importlib.import_module("sdxl-training-improvements_amd.config")
-
-
-class Arena:
-    """path B: the weight arena, gradients and tensor ranges (the lazy per-tensor decay) of the same UNet, without its handle"""
-
-    def __init__(self, w, ranges):
-        self.L = lib.load()
-        self.weights = w.clone()
-        self.grads = torch.zeros(w.numel(), dtype=torch.float32, device=w.device)
-        self._ranges = ranges
-
-    def param_ranges(self):
-        return dict(self._ranges)
-
-    def zero_grads(self):
-        pass
 
 
 class TorchUNetStandIn:
@@ -85,6 +70,7 @@ def main():
                              native_config=net.cfg)
     total = net.param_elems
     segs = net.segment_ranges()                          # exchange order
+    # path B: the weight arena, gradients and tensor ranges (the lazy per-tensor decay) of the same UNet, without its handle
     net_f = Arena(net.weights, net.param_ranges())
     opt_f = O.AdamWBF16(net_f, lr=1e-2, weight_decay=c.optimizer.weight_decay)
     ema_f = E.WeightEMA(net_f, update_after_step=1)

@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 import sdxl_amd  # noqa: E402
 from sdxl_amd import lib  # noqa: E402
+from _optim_common import bits, dev, ptr, stream, to_dev_bits  # noqa: E402
 
 G = np.load(Path(__file__).parent / "golden" / "adamw_bf16.npz")
 
@@ -22,32 +23,12 @@ def L():
     return lib.load()
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
-def to_dev_bits(a):          # uint16 bit patterns -> bf16 device tensor
-    return torch.from_numpy(a.astype(np.int16)).to(dev()).view(torch.bfloat16)
-
-
-def bits(t):
-    return t.detach().cpu().view(torch.int16).numpy().astype(np.uint16)
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def run_step(L, p, grad, m, v, s, *, lr, b1, b2, eps, step, decay=0.0, rand=None, ref_ema=1, grad_dtype=1, round_bf16=0,
-             scale=None, seed=0):
+             scale=None, seed=0, elem_offset=0):
     cfg = lib.AdamWConfig()
     lib.check(L.sdxl_adamw_default_config(C.byref(cfg)))
     cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.step, cfg.decay_this_iteration = lr, b1, b2, eps, float(step), decay
-    cfg.reference_ema, cfg.grad_round_bf16, cfg.seed = ref_ema, round_bf16, seed
+    cfg.reference_ema, cfg.grad_round_bf16, cfg.seed, cfg.elem_offset = ref_ema, round_bf16, seed, elem_offset
     lib.check(L.sdxl_adamw_bf16_step(ptr(p), ptr(grad), grad_dtype, ptr(m), ptr(v), ptr(s), p.numel(), C.byref(cfg),
                                      ptr(scale), ptr(rand), stream()))
     torch.cuda.synchronize()
@@ -90,6 +71,35 @@ def test_vs_oracle_large_fp32_grads(L, ref_ema):
         for k, t, w in (("p", p, pb), ("m", m, mb), ("v", v, vb), ("s", s, sb)):
             bad = int((bits(t) != w).sum())
             assert bad == 0, f"step {st} {k}: {bad}/{n} elements differ from the oracle"
+
+
+def test_philox_mode_bit_exact(L):
+    """The built-in generator (no rand_inject, what every training step runs): 1 M elements, fp32 gradients, 3 steps, a
+    seed that uses both key words, the launch at arena offset 0 and at a non-zero one.  Which random bits element i receives
+    is pinned by oracle.adamw_ref.philox_rand fed to make_step: p, m, v and shift equal it bit for bit."""
+    for elem_offset in (0, 8 * 65537):
+        _philox_mode_bit_exact(L, elem_offset)
+
+
+def _philox_mode_bit_exact(L, elem_offset):
+    from oracle import adamw_ref as R
+    rng = np.random.default_rng(17 + elem_offset)
+    n, seed = 1 << 20, 0x0123456789ABCDEF
+    pb = R.f32_to_bf16_rn((rng.standard_normal(n) * 0.05).astype(np.float32))
+    mb = R.f32_to_bf16_rn((rng.standard_normal(n) * 3e-4).astype(np.float32))
+    vb = R.f32_to_bf16_rn((rng.random(n) * 1e-6).astype(np.float32))
+    sb = R.f32_to_bf16_rn((rng.standard_normal(n) * 1e-5).astype(np.float32))
+    p, m, v, s = (to_dev_bits(a) for a in (pb, mb, vb, sb))
+    for st in (1, 2, 3):
+        g32 = (rng.standard_normal(n) * 4e-3).astype(np.float32)
+        decay = 0.006 if st == 2 else 0.0
+        run_step(L, p, torch.from_numpy(g32).to(dev()), m, v, s, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, step=st, decay=decay,
+                 grad_dtype=0, seed=seed, elem_offset=elem_offset)
+        pb, sb, mb, vb = R.make_step(g32, pb, sb, mb, vb, R.philox_rand(n, seed, st, elem_offset), beta1=0.9, beta2=0.999,
+                                     step=float(st), lr=1e-4, eps=1e-8, decay=decay)
+        for k, t, w in (("p", p, pb), ("m", m, mb), ("v", v, vb), ("s", s, sb)):
+            bad = int((bits(t) != w).sum())
+            assert bad == 0, f"elem_offset {elem_offset} step {st} {k}: {bad}/{n} elements differ from the oracle"
 
 
 def test_philox_mode_properties(L):

@@ -15,6 +15,7 @@ import torch
 import _ema_ref as R
 import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
+from _optim_common import Arena, bits, dev, ptr, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -23,23 +24,6 @@ E = importlib.import_module("sdxl-training-improvements_amd.ema")
 ROOT = Path(__file__).resolve().parent.parent
 FULL_ELEMS = 2567486784                                   # the SDXL UNet's packed arena (tests/golden/sdxl_segments.json)
 GRID_STRIDE = 256 * 16 * 256 * 8                          # elements one pass of the optimizer kernels' largest grid covers
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy() if t.dtype == torch.bfloat16 else \
-        t.detach().cpu().contiguous().view(torch.int32).numpy()
-
-
-def ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _state(n, seed, grad_bf16, kahan=True):
@@ -120,18 +104,6 @@ def test_schedule_free_ema(L, reference, kahan, grad_bf16):
 def test_n_not_a_multiple_of_the_grid_stride(L, algorithm):
     """the grid-stride loop runs a second, partial pass"""
     _check_ema_variant(L, GRID_STRIDE + 4096 + 8, 41 + algorithm, algorithm, kahan=True, kahan_sum=1)
-
-
-class Arena:
-    """the arena surface the optimizers and the EMA read: weights (bf16) + fp32 gradients + the library"""
-
-    def __init__(self, w):
-        self.L = lib.load()
-        self.weights = w.clone()
-        self.grads = torch.zeros(w.numel(), dtype=torch.float32, device=w.device)
-
-    def zero_grads(self):
-        self.grads.zero_()
 
 
 @pytest.mark.parametrize("kind", ["adamw_bf16", "adamw_schedule_free_kahan"])

@@ -69,6 +69,6 @@ def test_zero1_update_bit_equal_to_unsharded():
     """Row f3 (ZeRO-1): reduce-scatter -> norm on the slices + 1 float -> sharded fused AdamW -> all-gather gives the SAME BITS as
     all-reduce + the full update, two ranks on one GPU over gloo (tests/_zero1_worker.py)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    r = run_dist([str(ROOT / "tests" / "_zero1_worker.py")], 29543, env)
+    r = run_dist([str(ROOT / "tests" / "_zero1_worker.py"), "adamw_bf16"], 29543, env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "ZERO1_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

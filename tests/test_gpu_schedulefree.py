@@ -14,6 +14,7 @@ import torch
 import _schedulefree_ref as S
 import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
+from _optim_common import Arena, bits, dev, to_dev_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -21,30 +22,6 @@ O = importlib.import_module("sdxl-training-improvements_amd.optimizer")
 G = np.load(Path(__file__).parent / "golden" / "schedulefree_kahan.npz")
 ROOT = Path(__file__).resolve().parent.parent
 FULL_ELEMS = 2567486784                                   # the SDXL UNet's packed arena (tests/golden/sdxl_segments.json)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def to_dev_bits(a):
-    return torch.from_numpy(a.astype(np.int16)).to(dev()).view(torch.bfloat16)
-
-
-def bits(t):
-    return t.detach().cpu().view(torch.int16).numpy().astype(np.uint16)
-
-
-class Arena:
-    """the arena surface the optimizer reads: weights (bf16) + fp32 gradients + the library"""
-
-    def __init__(self, w):
-        self.L = lib.load()
-        self.weights = w.clone()
-        self.grads = torch.zeros(w.numel(), dtype=torch.float32, device=w.device)
-
-    def zero_grads(self):
-        self.grads.zero_()
 
 
 def _state(o, net):
@@ -210,12 +187,12 @@ def test_trainer_steps_and_resume(tiny, tmp_path):
 
 
 def test_zero1_update_bit_equal_to_unsharded():
-    """two ranks on one GPU over gloo (tests/_sfk_zero1_worker.py): ZeRO-1 with the schedule-free Kahan update gives the same
+    """two ranks on one GPU over gloo (tests/_zero1_worker.py): ZeRO-1 with the schedule-free Kahan update gives the same
     bits as all-reduce + the full update"""
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from test_gpu_multiproc import run_dist
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    r = run_dist([str(ROOT / "tests" / "_sfk_zero1_worker.py")], 29611, env)
+    r = run_dist([str(ROOT / "tests" / "_zero1_worker.py"), "adamw_schedule_free_kahan"], 29611, env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "SFK_ZERO1_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 

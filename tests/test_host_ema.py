@@ -13,34 +13,13 @@ import torch
 import _ema_ref as R
 import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
+from _optim_common import StandInNet
 
 T = importlib.import_module("sdxl-training-improvements_amd.trainer")
 O = importlib.import_module("sdxl-training-improvements_amd.optimizer")
 E = importlib.import_module("sdxl-training-improvements_amd.ema")
 NM = importlib.import_module("sdxl-training-improvements_amd.native_mi355x")
 CFG = importlib.import_module("sdxl-training-improvements_amd.config")
-
-
-class StandInNet:
-    """the arena surface the optimizers, the EMA and the trainer read (no library unless one is handed in)"""
-
-    def __init__(self, n=64, L=None):
-        self.param_elems = n
-        self.weights = (torch.arange(n, dtype=torch.float32) * 0.01).to(torch.bfloat16)
-        self.grads = torch.zeros(n)
-        self.L = L
-
-    def zero_grads(self):
-        pass
-
-    def forward_loss(self, *a, **k):
-        pass
-
-    def backward(self, *a, **k):
-        pass
-
-    def read_loss(self):
-        return [0.0] * 8
 
 
 def _ema(**kw):

@@ -10,33 +10,12 @@ import torch
 
 import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
+from _optim_common import StandInNet
 
 T = importlib.import_module("sdxl-training-improvements_amd.trainer")
 O = importlib.import_module("sdxl-training-improvements_amd.optimizer")
 NM = importlib.import_module("sdxl-training-improvements_amd.native_mi355x")
 CFG = importlib.import_module("sdxl-training-improvements_amd.config")
-
-
-class StandInNet:
-    """the arena surface the optimizers and the trainer read (no library: L is None)"""
-
-    def __init__(self, n=64):
-        self.param_elems = n
-        self.weights = torch.zeros(n, dtype=torch.bfloat16)
-        self.grads = torch.zeros(n)
-        self.zeroed = 0
-
-    def zero_grads(self):
-        self.zeroed += 1
-
-    def forward_loss(self, *a, **k):
-        pass
-
-    def backward(self, *a, **k):
-        pass
-
-    def read_loss(self):
-        return [0.0] * 8
 
 
 def test_yaml_keys(tmp_path):
@@ -67,7 +46,7 @@ def test_optimizer_type_selects_the_schedule_free_class(caplog):
     g = o.param_groups[0]
     assert (g["lr"], g["weight_decay"], g["warmup_steps"], g["kahan_sum"], o.arithmetic) == (5e-6, 0.02, 3, False, "reference")
     assert o.kahan_comp is None and len(o.state_arenas()) == 2
-    assert tr.sync is not None and isinstance(tr.optimizer, O.FUSED)
+    assert tr.sync is not None and isinstance(tr.optimizer, O.FusedArenaOptimizer)
     assert type(_trainer().optimizer) is O.AdamWBF16     # default unchanged
 
 
