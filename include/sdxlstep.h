@@ -56,6 +56,25 @@ typedef struct {
   float huber_c;         /* c of every sample; used when sdxl_batch.huber_c is NULL */
 } sdxl_loss_config;
 
+/* One sampler step, run by sdxl_unet_forward behind its forward (sdxl_batch.sampler): classifier-free guidance, the denoiser, the solver
+ * step and the input of the next forward in one kernel that reads the plan's prediction buffer and writes the plan's input buffer, so a
+ * sampling loop is one call per step and the latent never leaves the device.  With F_c / F_u the conditional / unconditional prediction:
+ *   F       = F_c  (cfg 0)  |  F_u + guidance * (F_c - F_u)  (cfg 1)
+ *   F       = guidance_rescale * (F * std(F_c) / std(F)) + (1 - guidance_rescale) * F      per sample over C.H.W; skipped when 0
+ *   den     = a_skip * x + a_out * F
+ *   x       = p * x + q * den                                                              the state, in place
+ *   input   = bf16(clamp(a_in_next * x, +-clamp))                                          clamp <= 0: none; channels 4..7 zero
+ * fp32, every operation rounded on its own in this order (no FMA), the rescale sums in a fixed order: bitwise reproducible.  The scalars
+ * are the caller's (sampler.py derives them for the trained ddpm denoiser, the reference's Karras scalings and flow matching). */
+typedef struct {
+  float* x;                       /* [B,4,H,W] fp32 NCHW sampler state, in place */
+  int    cfg;                     /* 1: the plan's batch is 2B = [cond; uncond] */
+  int    init;                    /* 1: write the UNet input from x and return (no forward) */
+  float  a_skip, a_out, p, q;     /* this step */
+  float  a_in_next, clamp;        /* the input of the NEXT forward */
+  float  guidance, guidance_rescale;
+} sdxl_sampler_step;
+
 /* One micro-batch, all device pointers.  RNG is the caller's: `noise` and `sigma_or_t` are inputs so that
  * fixtures are exact (reference draws them at ddpm_trainer.py:303-304 / flow_matching_trainer.py:298-306). */
 typedef struct {
@@ -78,6 +97,9 @@ typedef struct {
   const float* huber_c;        /* optional [B] fp32: per-sample c_b > 0 (a schedule computed by the caller), loss_type 1 / 2 */
   float*       per_sample_loss;/* optional [B] fp32 OUT: L_b = s_b w_b mean_chw l(d), before the tag mean and the guard; written by
                                   sdxl_forward_loss / sdxl_op_loss phase 1, stream-ordered; fixed-order sums, bitwise reproducible */
+  /* ---- appended: a sampler step (NULL = none, as before).  A HOST pointer, read during the call.  Only sdxl_unet_forward honours it;
+   * every other entry point ignores it. ---- */
+  const sdxl_sampler_step* sampler;
 } sdxl_batch;
 
 SDXL_API const char* sdxl_last_error(void);
@@ -147,6 +169,11 @@ SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
 
 /* UNet only: sample_nhwc8 [B*H*W][8] bf16 in (channels 4..7 ignored) -> pred [B*H*W][8] bf16 out.
  * (replaces unet(sample, t, ehs, added_cond_kwargs).sample, ddpm_trainer.py:320-325) */
+/* With cond->sampler set, sample_nhwc8 and pred_nhwc8 must be NULL: the call uploads the conditioning, runs the forward on what the
+ * plan's input buffer holds (B, or 2B = [cond; uncond] with cfg: both halves hold the same latent), then the step kernel, which leaves
+ * the next input there -- no copy in or out.  init = 1 runs only the kernel's input-writing part (no upload, no forward): the first call
+ * of a loop.  cfg with an odd plan batch, x == NULL or a non-finite scalar is a bad argument (1), reported before any launch.  The sampler
+ * path always launches kernel by kernel, also in graph mode. */
 SDXL_API int sdxl_unet_forward(sdxl_handle* h, const void* sample_nhwc8, const sdxl_batch* cond, void* pred_nhwc8, void* stream);
 /* d(pred) in -> runs every backward segment; d(sample) is not produced (inputs carry no gradient) */
 SDXL_API int sdxl_unet_backward(sdxl_handle* h, const void* dpred_nhwc8, int first_micro, void* stream);

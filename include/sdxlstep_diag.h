@@ -42,6 +42,10 @@ SDXL_API int sdxl_op_gemm_ld(int form, const void* A, const void* B, void* C, in
 SDXL_API int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const void* o, const void* addend, void* d_o, float* delta, int B, int Nq,
                                int N, int K, void* stream);
 
+/* the sampler step kernel behind sdxl_batch.sampler on caller buffers, without a UNet: x [B][4][H][W] fp32 in place (s->x is
+ * not read), pred and x_in [(s->cfg ? 2B : B) * H * W][8] bf16 with the conditional rows first; B = samples.  Same argument checks. */
+SDXL_API int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* stream);
+
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the

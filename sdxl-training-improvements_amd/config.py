@@ -78,6 +78,15 @@ class TrainingConfig:                    # data/config.py:152-168
                                          # 1 / (snr + 1) for v_prediction, 1 / snr for epsilon (diffusers' --snr_gamma rule)
     tag_weights_per_sample: bool = False # True: batch["tag_weights"] weights each image's own loss instead of the batch mean
     log_per_sample_loss: bool = False    # True: compute_loss also returns "per_sample_loss" (CPU [B]) and "timesteps"
+    # build-only keys: validation sampling with the native sampler (sampler.py) from train(); decoding the latents is the caller's
+    validation_every_n_steps: int = 0    # sample the caller's validation_batches every N optimizer steps (0 = off)
+    validation_num_steps: int = 30       # UNet forwards per sample
+    validation_guidance_scale: float = 5.0   # classifier-free guidance (1 = none: the plan runs at B instead of 2B)
+    validation_guidance_rescale: float = 0.0 # guidance rescale phi in [0, 1]
+    validation_weights: Optional[str] = None # "trained" | "ema"; None = "ema" when use_ema, else "trained"
+    validation_seed: int = 0             # seed of the validation noise (the same noise at every validation)
+    sampler_parameterization: str = "trained"   # ddpm: "trained" = the denoiser this build's loss trains, "reference" = the
+                                         # reference's sample_with_ztsnr as written (inconsistent with its own training; sampler.py)
 
 
 @dataclass

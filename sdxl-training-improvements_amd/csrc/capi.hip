@@ -4,6 +4,7 @@
 #include "../../include/sdxlstep_diag.h"
 #include <functional>
 
+#include <stddef.h>
 #include <stdlib.h>
 
 const char* sdxl_get_error();
@@ -376,7 +377,9 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
   // kernels must not)
   Plan& p = *e.cur;
-  sdxl_batch sb = *b;
+  sdxl_batch sb;      // every field but the appended sampler pointer, which only sdxl_unet_forward reads (a caller of this entry point
+  memcpy(&sb, b, offsetof(sdxl_batch, sampler));      // may hold the struct as it was before that field was appended)
+  sb.sampler = nullptr;
   if (e.use_graphs) {
     const size_t nlat = sizeof(float) * (size_t)p.B * 4 * p.H * p.W;
     HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_lat_off), b->latents, nlat, hipMemcpyDeviceToDevice, st));
@@ -537,6 +540,21 @@ int sdxl_read_loss(sdxl_handle* h, float out[8], void* stp) {
   return 0;
 }
 
+// sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters
+static int fill_sampler(const sdxl_sampler_step* s, int image_batch, int HW, SamplerP& q) {
+  ARG_CHECK(s->x != nullptr, "sampler: x is NULL");
+  ARG_CHECK(!s->cfg || image_batch % 2 == 0, "sampler: cfg needs an even batch [cond; uncond] (got %d)", image_batch);
+  const float v[8] = {s->a_skip, s->a_out, s->p, s->q, s->a_in_next, s->clamp, s->guidance, s->guidance_rescale};
+  for (int i = 0; i < 8; ++i) ARG_CHECK(isfinite(v[i]), "sampler: scalar %d of (a_skip, a_out, p, q, a_in_next, clamp, guidance, guidance_rescale) is not finite", i);
+  memset(&q, 0, sizeof(q));
+  q.x = s->x;
+  q.B = s->cfg ? image_batch / 2 : image_batch; q.HW = HW;
+  q.cfg = s->cfg != 0; q.init = s->init != 0;
+  q.a_skip = s->a_skip; q.a_out = s->a_out; q.p = s->p; q.q = s->q; q.a_in_next = s->a_in_next; q.clamp = s->clamp;
+  q.guidance = s->guidance; q.rescale = s->guidance_rescale;
+  return 0;
+}
+
 int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond, void* pred, void* stp) {
   H_CHECK(h);
   Engine& e = h->e;
@@ -544,6 +562,17 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   CHK(ready(e));
   CHK(check_batch(e, cond));
   Plan& p = *e.cur;
+  if (cond->sampler) {      // a sampling step: the forward runs on what the plan's input buffer holds, the step kernel writes the next input there
+    SamplerP q;
+    CHK(fill_sampler(cond->sampler, p.B, p.H * p.W, q));
+    ARG_CHECK(sample == nullptr && pred == nullptr, "sampler: sample and pred must be NULL (the step reads and writes the plan's own buffers)");
+    q.pred = p.P(p.pred); q.x_in = p.P(p.x_in); q.part = p.F(p.samp_part_off);
+    if (!q.init) {
+      CHK(upload_cond(e, cond, st));
+      CHK(run_forward_ops(e, st));
+    }
+    return launch_sampler_step(q, st);
+  }
   CHK(upload_cond(e, cond, st));
   size_t bytes = (size_t)p.B * p.H * p.W * 8 * sizeof(bf16);
   HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, bytes, hipMemcpyDeviceToDevice, st));
@@ -911,6 +940,18 @@ int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in,
   if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);
   if (phase == 2) return launch_loss_bwd(L, (hipStream_t)st);
   ARG_CHECK(false, "phase %d", phase);
+}
+
+int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* st) {
+  ARG_CHECK(s, "null argument");
+  ARG_CHECK(B > 0 && H > 0 && W > 0, "sampler: empty batch");
+  sdxl_sampler_step t = *s;
+  t.x = x;
+  SamplerP q;
+  CHK(fill_sampler(&t, s->cfg ? 2 * B : B, H * W, q));      // B = samples here: the images hold 2B rows of HW with cfg
+  q.pred = (const bf16*)pred; q.x_in = (bf16*)x_in;
+  if (!q.init && q.rescale != 0.f) CHK(test_slab(sampler_part_floats(B, H * W), &q.part));
+  return launch_sampler_step(q, (hipStream_t)st);
 }
 
 // ---- row f1: fused AdamW_BF16 ----

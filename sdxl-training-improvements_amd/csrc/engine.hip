@@ -1185,6 +1185,7 @@ void Engine::build(Plan* plan) {
     plan->in_sw_off = plan->alloc(sizeof(float) * plan->B);
     plan->in_hc_off = plan->alloc(sizeof(float) * plan->B);
     plan->ps_loss_off = plan->alloc(sizeof(float) * plan->B);
+    plan->samp_part_off = plan->alloc(sizeof(float) * sampler_part_floats(plan->B, plan->H * plan->W));      // ... and the sampler step's
     plan->seg_first_op.assign(nseg, -1);
     plan->seg_last_op.assign(nseg, -2);
     for (int i = 0; i < (int)plan->ops.size(); ++i) {

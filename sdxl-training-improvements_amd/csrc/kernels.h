@@ -388,6 +388,19 @@ int launch_loss_prepare(const LossP& p, hipStream_t st);
 int launch_loss_fwd(const LossP& p, hipStream_t st);
 int launch_loss_bwd(const LossP& p, hipStream_t st);
 
+// ---- one sampler step (sampler.hip): guidance + denoiser + solver step + the next UNet input, the fields of sdxl_sampler_step ----
+struct SamplerP {
+  float* x;               // [B][4][HW] fp32 NCHW state, in place
+  const bf16* pred;       // [(cfg ? 2B : B) * HW][8]: conditional rows first, then the unconditional ones (not read with init)
+  bf16* x_in;             // same shape: the next UNet input, both halves (channels 4..7 zero)
+  int B, HW;              // B = samples (half the image's batch with cfg)
+  int cfg, init;
+  float a_skip, a_out, p, q, a_in_next, clamp, guidance, rescale;
+  float* part;            // device scratch, sampler_part_floats(B, HW), read only when rescale != 0
+};
+static inline size_t sampler_part_floats(int B, int HW) { return 4 * (size_t)B * (((size_t)HW + 255) / 256); }
+int launch_sampler_step(const SamplerP& p, hipStream_t st);
+
 // ---- the fused optimizer updates (optimizer.hip): one launch over an arena slice ----
 // what both algorithms' kernels read
 struct OptimP {

@@ -43,6 +43,13 @@ class LossConfig(C.Structure):
                 ("loss_type", C.c_int), ("huber_c", C.c_float)]
 
 
+class SamplerStep(C.Structure):
+    """sdxl_sampler_step: one sampler step behind sdxl_unet_forward's forward (Batch.sampler)"""
+    _fields_ = [("x", C.c_void_p), ("cfg", C.c_int), ("init", C.c_int),
+                ("a_skip", C.c_float), ("a_out", C.c_float), ("p", C.c_float), ("q", C.c_float),
+                ("a_in_next", C.c_float), ("clamp", C.c_float), ("guidance", C.c_float), ("guidance_rescale", C.c_float)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ctx_len", C.c_int),
                 ("latents", C.c_void_p), ("noise", C.c_void_p), ("sigma_or_t", C.c_void_p),
@@ -50,6 +57,12 @@ class Batch(C.Structure):
                 ("time_ids", C.c_void_p), ("tag_weights", C.c_void_p),
                 # appended: optional [B] fp32 per-sample weights s_b / Huber c_b in, per-sample losses L_b out
                 ("sample_weights", C.c_void_p), ("huber_c", C.c_void_p), ("per_sample_loss", C.c_void_p)]
+
+
+class SamplerBatch(Batch):
+    """sdxl_batch in full: Batch (what the training entry points read; they never look past it) + the appended host pointer to the
+    sampler step that sdxl_unet_forward -- the one entry point that takes this class -- runs behind its forward (NULL = none)"""
+    _fields_ = [("sampler", C.POINTER(SamplerStep))]
 
 
 LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
@@ -93,7 +106,7 @@ SIGNATURES = {
     "sdxl_backward_all": [_vp, _f, _i, _vp],
     "sdxl_set_graph_mode": [_vp, _i],
     "sdxl_read_loss": [_vp, _P(_f), _vp],
-    "sdxl_unet_forward": [_vp, _vp, _P(Batch), _vp, _vp],
+    "sdxl_unet_forward": [_vp, _vp, _P(SamplerBatch), _vp, _vp],
     "sdxl_unet_backward": [_vp, _vp, _i, _vp],
     "sdxl_grads_to_bf16": [_vp, _sz, _sz, _vp, _f, _vp],
     "sdxl_set_grad_emit": [_vp, _vp, _f],
@@ -137,6 +150,7 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_exchange_shadow": [_vp, _sz, _i, _i, _f, _vp],
     "sdxl_op_gemm_ld": [_i, _vp, _vp, _vp, _i, _i, _i, C.c_long, C.c_long, C.c_long, _vp, _vp, C.c_long, _i, _vp],
     "sdxl_op_linear_dgrad_delta": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sdxl_op_sampler_step": [_vp, _vp, _vp, _i, _i, _i, _P(SamplerStep), _vp],
 }
 # include/sdxlstep_diag.h part 2: experiment ABI, exported by libsdxlstep_diag.so only
 DIAG_SIGNATURES = {

@@ -34,6 +34,7 @@ import math
 import os
 import time
 from collections import defaultdict
+from contextlib import contextmanager
 from pathlib import Path
 from typing import Any, Dict, Optional
 
@@ -44,6 +45,7 @@ from . import lib
 from .config import Config
 from .ema import WeightEMA
 from .optimizer import BY_TYPE, AdamWBF16, FusedArenaOptimizer
+from .sampler import PARAMETERIZATIONS, NativeSampler
 from .scheduler import NoiseScheduler
 from .unet import NativeUNet, config_from_unet
 
@@ -53,6 +55,7 @@ REQUIRED_KEYS = {"vae_latents", "prompt_embeds", "pooled_prompt_embeds", "time_i
 LOSS_TYPES = ("l2", "huber", "smooth_l1")
 HUBER_SCHEDULES = ("constant", "snr")
 SNR_WEIGHTINGS = ("reference", "debiased")
+WEIGHT_SETS = ("trained", "ema")
 
 
 class _NativeLoss(torch.autograd.Function):
@@ -86,6 +89,7 @@ class NativeSDXLTrainer:
             raise ValueError(f"Unsupported training method: {self.config.training.method}")   # sdxl_trainer.py:151
         self.method = method
         self._check_loss_keys()
+        self._check_sampler_keys()
         self.gradient_accumulation_steps = int(self.config.training.gradient_accumulation_steps)
         unet = model.unet if hasattr(model, "unet") else model
         native_attrs = ("forward_loss", "backward", "read_loss", "zero_grads", "param_elems")
@@ -156,6 +160,105 @@ class NativeSDXLTrainer:
                 raise ValueError("training.snr_weighting: 'debiased' is a ddpm weighting (flow matching has no snr)")
         elif self.snr_weighting == "debiased" and self.config.model.min_snr_gamma is None:
             raise ValueError("training.snr_weighting: 'debiased' divides min(snr, gamma) by the snr: it needs model.min_snr_gamma")
+
+    def _check_sampler_keys(self) -> None:
+        """the validation / sampler keys, checked when the trainer is built (ValueError names the key)"""
+        tc = self.config.training
+        self.sampler_parameterization = str(getattr(tc, "sampler_parameterization", "trained")).lower()
+        if self.sampler_parameterization not in PARAMETERIZATIONS:
+            raise ValueError(f"training.sampler_parameterization: unknown value {getattr(tc, 'sampler_parameterization')!r} "
+                             f"(expected one of {', '.join(PARAMETERIZATIONS)})")
+        vw = getattr(tc, "validation_weights", None)
+        use_ema = bool(getattr(tc, "use_ema", False))
+        self.validation_weights = ("ema" if use_ema else "trained") if vw is None else str(vw).lower()
+        if self.validation_weights not in WEIGHT_SETS:
+            raise ValueError(f"training.validation_weights: unknown value {vw!r} (expected one of {', '.join(WEIGHT_SETS)})")
+        if self.validation_weights == "ema" and not use_ema:
+            raise ValueError("training.validation_weights: 'ema' needs training.use_ema")
+        every, steps = getattr(tc, "validation_every_n_steps", 0), getattr(tc, "validation_num_steps", 30)
+        if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+            raise ValueError(f"training.validation_every_n_steps must be an integer >= 0 (got {every!r})")
+        least = 2 if self.method == "ddpm" else 1
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < least:
+            raise ValueError(f"training.validation_num_steps must be an integer >= {least} for {self.method} (got {steps!r})")
+        for key in ("validation_guidance_scale", "validation_guidance_rescale"):
+            v = getattr(tc, key, 0.0)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+                raise ValueError(f"training.{key} must be a finite number (got {v!r})")
+        if not 0.0 <= float(getattr(tc, "validation_guidance_rescale", 0.0)) <= 1.0:
+            raise ValueError(f"training.validation_guidance_rescale must be in [0, 1] (got {tc.validation_guidance_rescale!r})")
+        seed = getattr(tc, "validation_seed", 0)
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"training.validation_seed must be an integer (got {seed!r})")
+
+    # -------------------------------------------------------------------------------- sampling / evaluation on either weight set
+    @contextmanager
+    def _weights(self, weights: str):
+        """run the body on the trained weights ("trained": nothing changes) or on the EMA ("ema"): the fp32 EMA arena -- laid out like
+        the weight arena -- is cast to bf16 into a temporary arena by the library's own cast (sdxl_grads_to_bf16 on the handle whose
+        gradient arena IS the EMA arena, the one ema_state_dict() exports through), the training handle is bound to it for the body
+        and bound back afterwards.  The trained weights, gradients, optimizer, EMA and accumulation state are not touched.  Under
+        ZeRO-1 the EMA is current only after prepare_checkpoint() on every rank: before that this raises, like ema_state_dict()."""
+        weights = str(weights).lower()
+        if weights not in WEIGHT_SETS:
+            raise ValueError(f"weights: unknown value {weights!r} (expected one of {', '.join(WEIGHT_SETS)})")
+        if weights == "trained":
+            yield
+            return
+        if self.ema is None:
+            raise ValueError("weights='ema': this trainer keeps no EMA (training.use_ema is false)")
+        self._require_gathered("sampling / evaluating the EMA", "Nothing was read.")
+        net, n = self.net, self.net.param_elems
+        buf = torch.empty(n + 128, dtype=torch.bfloat16, device=net.weights.device)
+        off = (-buf.data_ptr() % 256) // 2
+        tmp = buf[off:off + n]                                 # 256-byte aligned, as sdxl_bind_params requires of an arena
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lib.check(net.L.sdxl_grads_to_bf16(self.ema._handle(), 0, n, C.c_void_p(tmp.data_ptr()), 1.0, st), "cast EMA -> bf16")
+        lib.check(net.L.sdxl_bind_params(net.h, C.c_void_p(tmp.data_ptr()), C.c_void_p(net.grads.data_ptr())), "bind EMA weights")
+        try:
+            yield
+        finally:
+            torch.cuda.current_stream().synchronize()         # the body's kernels read tmp: finish them before it is freed
+            lib.check(net.L.sdxl_bind_params(net.h, C.c_void_p(net.weights.data_ptr()), C.c_void_p(net.grads.data_ptr())),
+                      "bind trained weights")
+
+    def sample(self, prompt_embeds, pooled, time_ids, neg_prompt_embeds=None, neg_pooled=None, neg_time_ids=None, *, height: int,
+               width: int, num_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
+               guidance_rescale: Optional[float] = None, generator: Optional[torch.Generator] = None, noise=None, sigmas=None,
+               timesteps=None, weights: Optional[str] = None) -> torch.Tensor:
+        """Latents [B,4,height,width] fp32 on the device, sampled natively (sampler.py::NativeSampler) from the trained weights or
+        the EMA; what is not given comes from the training.validation_* keys.  Decoding is the caller's.  Nothing of the training
+        state changes: the next step has the bits it would have had without the call."""
+        tc = self.config.training
+        sampler = NativeSampler(self.net, self.method, str(tc.prediction_type), bool(self.config.model.use_ztsnr),
+                                self.sampler_parameterization, config=self.config, t_bf16=str(tc.mixed_precision) == "bf16")
+        with self._weights(self.validation_weights if weights is None else weights):
+            return sampler.sample(prompt_embeds, pooled, time_ids, neg_prompt_embeds, neg_pooled, neg_time_ids, height=height,
+                                  width=width, num_steps=int(tc.validation_num_steps if num_steps is None else num_steps),
+                                  guidance_scale=float(tc.validation_guidance_scale if guidance_scale is None else guidance_scale),
+                                  guidance_rescale=float(tc.validation_guidance_rescale if guidance_rescale is None else guidance_rescale),
+                                  generator=generator, noise=noise, sigmas=sigmas, timesteps=timesteps)
+
+    def validate(self, step: int, validation_batches, on_validation=None):
+        """sample every conditioning batch of `validation_batches` (dicts with "prompt_embeds", "pooled_prompt_embeds", "time_ids",
+        optional "neg_prompt_embeds" / "neg_pooled_prompt_embeds" / "neg_time_ids", "height" / "width" of the latent or a
+        "vae_latents" whose shape gives them) with the training.validation_* keys and the noise of validation_seed; returns the list of
+        latents and hands each to on_validation(step, latents).  COLLECTIVE under ZeRO-1 with the EMA (prepare_checkpoint)."""
+        if self.validation_weights == "ema":
+            self.prepare_checkpoint()
+        gen = torch.Generator().manual_seed(int(self.config.training.validation_seed))
+        outs = []
+        for b in validation_batches:
+            if "height" in b and "width" in b:
+                h, w = int(b["height"]), int(b["width"])
+            else:
+                h, w = (int(v) for v in b["vae_latents"].shape[-2:])
+            lat = self.sample(b["prompt_embeds"], b["pooled_prompt_embeds"], b["time_ids"], b.get("neg_prompt_embeds"),
+                              b.get("neg_pooled_prompt_embeds"), b.get("neg_time_ids"), height=h, width=w, generator=gen)
+            outs.append(lat)
+            if on_validation is not None:
+                on_validation(step, lat)
+        return outs
 
     def _loss_ext(self, batch, sig) -> Dict[str, Any]:
         """The device loss's optional arguments from the config keys: each recipe is B floats computed here.  Several sources of
@@ -247,13 +350,16 @@ class NativeSDXLTrainer:
             out["timesteps"] = ts
         return out
 
-    def evaluate(self, batches, timesteps, generator: Optional[torch.Generator] = None):
+    def evaluate(self, batches, timesteps, generator: Optional[torch.Generator] = None, weights: str = "trained"):
         """Held-out loss at fixed timesteps, forward only: every batch is evaluated at each of `timesteps` (ddpm: indices into
         the sigma table; flow matching: t in (0, 1)) with noise drawn from `generator`.  No backward, no gradient zeroing, no
         optimizer or EMA step; the accumulation state is not touched.  The loss is the one the config keys select (weights,
         element loss), per sample, before the tag mean and the guard.  Returns ({timestep: mean per-sample loss}, overall mean).
-        Evaluates the trained weights (not the EMA)."""
-        batches = list(batches)
+        Evaluates the trained weights, or with weights="ema" the EMA (cast to bf16 into a temporary arena, see _weights)."""
+        with self._weights(weights):
+            return self._evaluate(list(batches), timesteps, generator)
+
+    def _evaluate(self, batches, timesteps, generator):
         sums: Dict[Any, float] = {}
         counts: Dict[Any, int] = {}
         for batch in batches:
@@ -387,13 +493,18 @@ class NativeSDXLTrainer:
         self._end_cycle()
         return gn
 
-    def train(self, num_epochs: int, save_checkpoints: bool = False) -> None:
-        """The template loop.  save_checkpoints: the reference's cadence (flow_matching_trainer.py:211-234): a checkpoint
+    def train(self, num_epochs: int, save_checkpoints: bool = False, validation_batches=None, on_validation=None) -> None:
+        """The template loop.  With training.validation_every_n_steps = N > 0 and `validation_batches` (conditioning only, see
+        validate()), every N-th optimizer step is followed by validate(): `on_validation(step, latents)` receives each sampled batch.
+          save_checkpoints: the reference's cadence (flow_matching_trainer.py:211-234): a checkpoint
         whenever the epoch's mean loss improves, and `final_checkpoint` at the end (off by default: writing the 5 GB UNet
         is the caller's decision, `SDXLTrainer.save_checkpoint` in the reference)."""
         N = self.gradient_accumulation_steps
         global_step = 0
         best = float("inf")
+        every = int(getattr(self.config.training, "validation_every_n_steps", 0)) if validation_batches is not None else 0
+        validation_batches = list(validation_batches) if every else None
+        opt_steps = 0
         for epoch in range(num_epochs):
             acc_loss, acc_metrics = 0.0, defaultdict(float)
             ep_loss, ep_n = 0.0, 0
@@ -417,6 +528,9 @@ class NativeSDXLTrainer:
                         else:
                             print({k: (round(v, 6) if isinstance(v, float) else v) for k, v in eff.items()}, flush=True)
                     acc_loss, acc_metrics = 0.0, defaultdict(float)
+                    opt_steps += 1
+                    if every and opt_steps % every == 0:
+                        self.validate(global_step, validation_batches, on_validation)
                 global_step += 1
             if save_checkpoints:
                 # the decision must be the same on every rank (each sees its own data): the epoch's loss sum and step count, both summed

@@ -307,12 +307,48 @@ class NativeUNet:
         B, Cc, H, W = sample.shape
         d = self.device
         dummy = torch.zeros(B, 4, H, W, device=d)
-        b = self._batch(dummy, dummy, torch.zeros(B), timestep, prompt_embeds, pooled, time_ids, None)
+        tb = self._batch(dummy, dummy, torch.zeros(B), timestep, prompt_embeds, pooled, time_ids, None)
+        b = lib.SamplerBatch(*[getattr(tb, f[0]) for f in lib.Batch._fields_])      # sdxl_batch in full, sampler = NULL
         x8 = torch.zeros(B * H * W, 8, dtype=torch.bfloat16, device=d)
         x8[:, :4] = sample.to(d).permute(0, 2, 3, 1).reshape(B * H * W, 4).to(torch.bfloat16)
         out8 = torch.empty_like(x8)
         lib.check(self.L.sdxl_unet_forward(self.h, _ptr(x8), C.byref(b), _ptr(out8), _stream()), "sdxl_unet_forward")
         return out8[:, :4].float().reshape(B, H, W, 4).permute(0, 3, 1, 2).contiguous()
+
+    # ------------------------------------------------------------------ sampling (sampler.py drives these)
+    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str) -> None:
+        """sdxl_unet_forward with sdxl_batch.sampler set.  Every tensor is already on the device in the library's dtype and
+        contiguous (checked, not converted: no torch arithmetic or copy runs here); the plan's batch is prompt_embeds' (B, or
+        2B = [cond; uncond] with cfg), x is [B,4,H,W] fp32."""
+        PB, ctx = int(prompt_embeds.shape[0]), int(prompt_embeds.shape[1])
+        B, _c, H, W = x.shape
+        for t, dt, n, name in ((x, torch.float32, B * 4 * H * W, "x"), (prompt_embeds, torch.bfloat16, None, "prompt_embeds"),
+                               (pooled, torch.bfloat16, None, "pooled"), (time_ids, torch.float32, PB * 6, "time_ids"),
+                               (timestep, torch.float32, PB, "timestep")):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or (n is not None and t.numel() != n):
+                raise ValueError(f"{what}: {name} must be a contiguous {dt} device tensor" + (f" of {n} elements" if n is not None else ""))
+        if _c != 4 or PB != (2 * B if step.cfg else B) or pooled.shape[0] != PB:
+            raise ValueError(f"{what}: x {tuple(x.shape)} does not fit a conditioning batch of {PB} with cfg = {step.cfg}")
+        self.plan(PB, H, W, ctx)
+        self._keep = [x, prompt_embeds, pooled, time_ids, timestep]
+        step.x = x.data_ptr()
+        b = lib.SamplerBatch(PB, H, W, ctx, None, None, None, timestep.data_ptr(), prompt_embeds.data_ptr(), pooled.data_ptr(),
+                             time_ids.data_ptr(), None)
+        b.sampler = C.pointer(step)
+        lib.check(self.L.sdxl_unet_forward(self.h, None, C.byref(b), None, _stream()), what)
+
+    def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0) -> None:
+        """write the first UNet input of a sampling loop, bf16(clamp(a_in * x, +-clamp)), into the plan's input buffer (no forward)"""
+        s = lib.SamplerStep(None, int(cfg), 1, 0.0, 0.0, 0.0, 0.0, float(a_in), float(clamp), 1.0, 0.0)
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init")
+
+    def sample_step(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg, a_skip, a_out, p, q, a_in_next=1.0, clamp=0.0,
+                    guidance=1.0, guidance_rescale=0.0, init=0) -> None:
+        """one forward on the plan's input buffer + the fused sampler step (include/sdxlstep.h sdxl_sampler_step): x is updated in
+        place and the next input is left in the plan; stream-ordered, no synchronisation"""
+        s = lib.SamplerStep(None, int(cfg), int(init), float(a_skip), float(a_out), float(p), float(q), float(a_in_next),
+                            float(clamp), float(guidance), float(guidance_rescale))
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_step")
 
     def unet_backward(self, dpred_nchw: torch.Tensor, first_micro: bool = True) -> None:
         B, Cc, H, W = dpred_nchw.shape
