@@ -14,6 +14,7 @@ from oracle import loss_ref as R
 from oracle import unet_ref as U
 from sdxl_amd import unet as NU
 
+import _bucket_cases as BK      # the default aspect buckets' latent shapes (tests/test_host_buckets.py pins them to the config)
 from _gradparity import GradParity, compare_autograd
 
 pytestmark = pytest.mark.gpu
@@ -56,19 +57,25 @@ def test_weight_roundtrip(tiny):
         assert torch.equal(got, w[k]), k
 
 
-@pytest.mark.parametrize("H,W", [(16, 16), (24, 40)])
-def test_unet_forward_matches_oracle(tiny, H, W):
+def _bhw_id(B, H, W):
+    return f"{B}-{H}-{W}"
+
+
+# the tiny config keeps a bucket's spatial geometry exactly (row widths, token counts with 64-wide heads, pad rows, the up-sampler
+# weight-gradient fallback, the three-tap policy at level 0): every default bucket's latent shape at B = 1, two of them at B = 2
+@pytest.mark.parametrize("B,H,W", [pytest.param(2, 16, 16, id="16-16"), pytest.param(2, 24, 40, id="24-40")]
+                         + [pytest.param(*s, id=_bhw_id(*s)) for s in BK.TINY_LATENTS + BK.TINY_LATENTS_B2])
+def test_unet_forward_matches_oracle(tiny, B, H, W):
     cfg, w, net = tiny
-    B = 2
     x = make_inputs(cfg, B, H, W, seed=3)
     sample = (x["lat"] * 2.0).to(torch.bfloat16).float()
-    t = torch.tensor([10.0, 500.0])
+    t = torch.tensor([10.0, 500.0][2 - B:])
     got = net.unet_forward(sample, t, x["ehs"], x["pooled"], x["tid"]).cpu()
     ref = U.unet_forward(w, sample, t, x["ehs"], x["pooled"], x["tid"], cfg)
     ref_bf = U.unet_forward(w, sample, t, x["ehs"], x["pooled"], x["tid"], cfg, emulate_bf16=True)
     e = float((got - ref).abs().max() / ref.abs().max())
     e_bf = float((ref_bf - ref).abs().max() / ref.abs().max())
-    print(f"[parity] tiny unet fwd {H}x{W}: hip vs fp32 oracle {e:.3e} ; bf16-emulating oracle vs fp32 oracle {e_bf:.3e}")
+    print(f"[parity] tiny unet fwd {B}x{H}x{W}: hip vs fp32 oracle {e:.3e} ; bf16-emulating oracle vs fp32 oracle {e_bf:.3e}")
     assert e <= max(3.0 * e_bf, 2e-2)
 
 
@@ -148,14 +155,17 @@ def test_training_step_matches_oracle(tiny, method):
 TINY_GRAD_BAR = (6e-2, 0.995)      # per tensor: rel-L2 <= 6e-2 (the probes' worst-case bar above), cosine >= 0.995
 
 
-@pytest.mark.parametrize("H,W", [(16, 16), (24, 40)])
-@pytest.mark.parametrize("method", ["ddpm", "flow_matching"])
-def test_training_step_every_gradient_matches_oracle(tiny, method, H, W):
+@pytest.mark.parametrize("method,B,H,W", [pytest.param(m, 2, H, W, id=f"{m}-{H}-{W}") for m in ("ddpm", "flow_matching") for H, W in ((16, 16), (24, 40))]
+                         + [pytest.param("flow_matching", *s, id="flow_matching-" + _bhw_id(*s)) for s in BK.TINY_LATENTS + BK.TINY_LATENTS_B2]
+                         + [pytest.param("ddpm", *s, id="ddpm-" + _bhw_id(*s)) for s in BK.TINY_DDPM])
+def test_training_step_every_gradient_matches_oracle(tiny, method, B, H, W):
     """Every tiny-UNet gradient tensor (not only PROBE_GRADS) against autograd of the fp32 oracle loss: the bias / norm / time-
     embedding gradients that come out of hand-written column sums and fixed-order reduces included; 24 x 40 is the non-square
-    shape of the forward test, with ragged tiles."""
+    shape of the forward test, with ragged tiles.  Then every default bucket's latent shape (flow matching for all nine at B = 1 and
+    two at B = 2 with per-sample t, ddpm for one orientation of each new family): the conv row widths, the ragged token counts 3952 /
+    988 and 3840 / 960, the linear weight gradients' zero-pad rows, the up-sampler weight gradient on the upsampled image, and at
+    W = 192 / 128 the three-tap weight gradient at level 0.  BK.TINY_REPEAT's step is also run twice: the same bits in the whole arena."""
     cfg, w, net = tiny
-    B = 2
     x = make_inputs(cfg, B, H, W, seed=13 if method == "ddpm" else 17)
     for t in w.values():
         t.grad = None
@@ -163,18 +173,22 @@ def test_training_step_every_gradient_matches_oracle(tiny, method, H, W):
     unet_fn = lambda s, t, e, p, ti: U.unet_forward(w, s, t, e, p, ti, cfg)
     batch = {"vae_latents": x["lat"], "prompt_embeds": x["ehs"], "pooled_prompt_embeds": x["pooled"], "time_ids": x["tid"]}
     if method == "ddpm":
-        ts = torch.tensor([610, 230])
+        ts = torch.tensor([610, 230][:B])
         sig = R.karras_sigmas()[ts]
         ref = R.compute_loss_ddpm(unet_fn, batch, x["noise"], ts)
-        net.forward_loss("ddpm", x["lat"], x["noise"], sig, ts.float(), x["ehs"], x["pooled"], x["tid"])
+        step = lambda: net.forward_loss("ddpm", x["lat"], x["noise"], sig, ts.float(), x["ehs"], x["pooled"], x["tid"])
     else:
-        t = R.sample_logit_normal_from_z(x["z"])
-        ref = R.compute_loss_flow(unet_fn, batch, x["noise"], t)
-        net.forward_loss("flow_matching", x["lat"], x["noise"], t, t, x["ehs"], x["pooled"], x["tid"])
+        tf = R.sample_logit_normal_from_z(x["z"])
+        assert B == 1 or float(tf[0]) != float(tf[1])
+        ref = R.compute_loss_flow(unet_fn, batch, x["noise"], tf)
+        step = lambda: net.forward_loss("flow_matching", x["lat"], x["noise"], tf, tf, x["ehs"], x["pooled"], x["tid"])
+    step()
     net.zero_grads()
     net.backward(grad_scale=1.0, first_micro=True)
     ref_loss = float(ref["loss"])
-    assert abs(net.read_loss()[0] - ref_loss) <= LOSS_RTOL * abs(ref_loss)
+    got_loss = net.read_loss()[0]
+    print(f"[parity] tiny {method} {B}x{H}x{W} loss: hip {got_loss:.6f} oracle {ref_loss:.6f} rel {abs(got_loss - ref_loss) / abs(ref_loss):.3e} (tol {LOSS_RTOL})")
+    assert abs(got_loss - ref_loss) <= LOSS_RTOL * abs(ref_loss)
     par = GradParity(f"tiny {method} {B}x{H}x{W}")
     try:
         compare_autograd(par, ref["loss"], w, lambda k: net.export(k, grad=True))
@@ -183,6 +197,15 @@ def test_training_step_every_gradient_matches_oracle(tiny, method, H, W):
             t.grad = None
             t.requires_grad_(False)
     par.check(TINY_GRAD_BAR, expect=net.param_shapes())
+    if (B, H, W) == BK.TINY_REPEAT:          # the form of test_forward_is_bitwise_reproducible, on the whole step: no sum in an order the hardware chooses
+        torch.cuda.synchronize()
+        first = net.grads.clone()
+        step()
+        net.zero_grads()
+        net.backward(grad_scale=1.0, first_micro=True)
+        torch.cuda.synchronize()
+        assert net.read_loss()[0] == got_loss
+        assert torch.equal(net.grads.view(torch.int32), first.view(torch.int32)), "the repeated step's gradient arena differs"
 
 
 def test_grad_accumulation_is_sum_of_micro_steps(tiny):

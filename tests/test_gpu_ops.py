@@ -12,6 +12,8 @@ import torch
 import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
 
+import _bucket_cases as BK      # the default aspect buckets' geometries (tests/test_host_buckets.py pins them to the config)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -85,7 +87,7 @@ def test_hw_layout_probe(L):
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 320), (308, 1280, 2048), (4, 1280, 320),
-                                   (1000, 640, 2560), (4096, 1280, 1280)])
+                                   (1000, 640, 2560), (4096, 1280, 1280)] + BK.GEMM_NT)
 def test_gemm_nt(L, M, N, K):
     a, w = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5)
     bias, res = rnd(N, seed=3), rnd(M, N, seed=4)
@@ -95,7 +97,7 @@ def test_gemm_nt(L, M, N, K):
     report(f"gemm_nt {M}x{N}x{K}", out, ref, 6e-3)
 
 
-@pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 320, 384), (308, 2048, 1280), (1000, 2560, 640)])
+@pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 320, 384), (308, 2048, 1280), (1000, 2560, 640)] + BK.GEMM_NN)
 def test_gemm_nn_and_accumulate(L, M, N, K):
     a, w = rnd(M, K, seed=5), rnd(K, N, seed=6, scale=K ** -0.5)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev())
@@ -129,7 +131,8 @@ def test_gemm_nt_nn_splitk_small_problems(L, M, N, K, splitk):
 
 
 @pytest.mark.parametrize("M,N,K,splitk", [(128, 128, 64, 1), (320, 384, 1000, 1), (1280, 640, 4096, 4),
-                                          (8, 320, 65536, 16), (640, 640, 308, 2), (896, 1120, 2048, 3)])      # 7 x 7 tiles x 3 splits (generic XCD order)
+                                          (8, 320, 65536, 16), (640, 640, 308, 2), (896, 1120, 2048, 3)]      # 7 x 7 tiles x 3 splits (generic XCD order)
+                                         + BK.GEMM_TN)             # bucket row counts as ragged reductions, splitk 0: the plan's choice
 def test_gemm_tn_wgrad(L, M, N, K, splitk):
     a, b = rnd(K, M, seed=8), rnd(K, N, seed=9)
     out = torch.zeros(M, N, dtype=torch.float32, device=dev())
@@ -207,7 +210,8 @@ def test_gemm_stream_k_fused_dgrad_wgrad_is_reproducible(L):
 
 @pytest.mark.parametrize("M,N,K", [(5120, 640, 16384), (640, 2560, 16384), (1920, 640, 16384), (640, 640, 16384), (200, 72, 16384),
                                    (256, 160, 32768),
-                                   (1792, 480, 16384)])      # 7 x 3 tiles: a grid no XCD rectangle divides, a short last band (xcd_seq_map)
+                                   (1792, 480, 16384)]       # 7 x 3 tiles: a grid no XCD rectangle divides, a short last band (xcd_seq_map)
+                                  + BK.GEMM_TN_LONG)         # the bucket row counts 15 808 / 3952: below the policy's 16 384, the same contract through its other route
 @pytest.mark.parametrize("splitk", [0, 1, 3])
 def test_gemm_tn_long_reduction_wgrad256(L, M, N, K, splitk):
     """wgrad256.hip (linear weight gradients over >= 16 384 rows: 256 x 160 tiles, two stacked dY tiles per staged X tile): fp32 result
@@ -469,7 +473,9 @@ def _conv_ref(x_nhwc, w_native, bias, stride):
                                                    # batch 1, 512^2 at the 1280-channel level: 256 pixels -> split (tap, channel) reduction
                                                    (1, 16, 16, 1280, 1280, 1), (1, 32, 32, 640, 1280, 1),
                                                    # B = 4, 1024^2 at the 1280-channel level: one round of 256 tiles -> two co-resident halves of the reduction
-                                                   (4, 32, 32, 1280, 1280, 1), (4, 32, 32, 1920, 1280, 1), (4, 32, 32, 640, 1280, 1)])
+                                                   (4, 32, 32, 1280, 1280, 1), (4, 32, 32, 1920, 1280, 1), (4, 32, 32, 640, 1280, 1)]
+                                                  # every other default bucket's row widths: one level-2, level-1 and level-0 image per family
+                                                  + BK.CONV_S1)
 def test_conv3x3_fwd_dgrad_wgrad(L, B, H, W, Cin, Cout, stride):
     x = rnd(B, H, W, Cin, seed=10)
     w = rnd(Cout, 9, Cin, seed=11, scale=(9 * Cin) ** -0.5)
@@ -492,7 +498,7 @@ def test_conv3x3_fwd_dgrad_wgrad(L, B, H, W, Cin, Cout, stride):
         report(f"conv wgrad splitk={splitk}", dw, wr.grad, 1e-4 * math.sqrt(B * Ho * Wo) / 8 + 1e-5)
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 16, 16, 64, 64), (4, 128, 128, 320, 320), (4, 64, 64, 640, 640), (2, 48, 84, 64, 128), (3, 12, 20, 72, 64)])
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 16, 16, 64, 64), (4, 128, 128, 320, 320), (4, 64, 64, 640, 640), (2, 48, 84, 64, 128), (3, 12, 20, 72, 64)] + BK.CONV_S2_DGRAD)
 def test_conv3x3_stride2_dgrad_by_output_phase(L, B, H, W, Cin, Cout):
     """The input gradient of the stride-2 convolution from 1 / 2 / 2 / 4 taps per output phase (GemmP::up2 == 2) against autograd in fp32,
     with and without an addend; the two downsampler shapes of the headline step and the 1344 x 768 bucket's level included."""
@@ -527,7 +533,7 @@ def test_conv3x3_stride2_dgrad_by_output_phase(L, B, H, W, Cin, Cout):
         report("conv s2 bias grad", db, dy.float().sum((0, 1, 2)), 1e-4 * math.sqrt(B * H * W / 4) / 8 + 1e-5)
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 16, 16, 128, 64), (4, 32, 32, 1280, 1280), (4, 64, 64, 640, 640), (2, 24, 42, 64, 192), (4, 24, 42, 128, 64), (1, 32, 32, 320, 640)])
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 16, 16, 128, 64), (4, 32, 32, 1280, 1280), (4, 64, 64, 640, 640), (2, 24, 42, 64, 192), (4, 24, 42, 128, 64), (1, 32, 32, 320, 640)] + BK.UPCONV)
 def test_upsample_conv3x3_without_the_upsampled_image(L, B, H, W, Cin, Cout):
     """conv3x3(nearest-2x(x)) as four 2 x 2 phase stencils on the low-resolution image (GemmP::up2) against conv2d(interpolate(x)) in fp32:
     forward (+ bias) and the input gradient (+ addend), borders included; the headline shapes of the two up-level transitions."""
@@ -568,7 +574,10 @@ def test_upsample_conv3x3_without_the_upsampled_image(L, B, H, W, Cin, Cout):
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 128, 128, 320, 320), (4, 64, 64, 640, 320), (2, 128, 128, 192, 200), (1, 128, 128, 8, 320),
                                             (5, 64, 64, 64, 64),
                                             # W = 32 (the 1280-channel level at 1024^2): a K-step is two image rows, each with its own halo
-                                            (4, 32, 32, 1280, 1280), (5, 32, 32, 200, 72), (8, 16, 32, 64, 128)])
+                                            (4, 32, 32, 1280, 1280), (5, 32, 32, 200, 72), (8, 16, 32, 64, 128)]
+                                           # W = 192 (the 640 x 1536 bucket): three K-steps per image row; the B = 1 case is below the policy's
+                                           # 16 384 pixels and goes through the one-tap route: the same problem, parity only
+                                           + BK.CONV_WGRAD3)
 @pytest.mark.parametrize("splitk", [0, 1, 5])
 def test_conv3x3_wgrad_three_taps_per_workgroup(L, B, H, W, Cin, Cout, splitk):
     """conv_wgrad3.hip (same-size stride-1 3x3, W % 64 == 0, >= 16 384 pixels: the 128^2 / 64^2 levels): a workgroup computes the three
@@ -630,7 +639,9 @@ def _attn_ref(q, k, v, heads):
                                                      # tile), level-2 self attention (N = 1024, 20 heads), level-1 cross attention
                                                      (1, 10, 4096, 4096, True), (1, 10, 4032, 4032, True),
                                                      (1, 20, 1008, 1008, True), (1, 20, 1024, 1024, True),
-                                                     (1, 10, 4096, 77, False), (1, 10, 4032, 77, False)])
+                                                     (1, 10, 4096, 77, False), (1, 10, 4032, 77, False)]
+                                                    # the other buckets: 3952 = 61 key tiles + 48 on the pipelined backward's route, 988 % 64 = 28
+                                                    + BK.ATTENTION)
 def test_attention_fwd_bwd(L, B, heads, Nq, Nk, self_attn):
     Cc = heads * 64
     if self_attn:
@@ -701,7 +712,7 @@ def test_attention_fwd_pipelined(L, form, B, heads, Nq, Nk):
 
 @pytest.mark.diag
 @pytest.mark.parametrize("B,heads,Nq,Nk", [(2, 2, 256, 256), (1, 4, 1008, 1008), (1, 20, 1024, 1024), (1, 3, 336, 320), (2, 1, 264, 257), (1, 2, 300, 4032),
-                                            (1, 1, 4096, 264)])
+                                            (1, 1, 4096, 264)] + BK.ATTENTION_BWD_PL)
 def test_attention_bwd_pipelined(L, B, heads, Nq, Nk):
     """csrc/attention_bwd_pl.hip on the shapes the policy does NOT send it (knob 35 = 2, diagnostics build; the product routes Nq, Nk >= 2048 there,
     which test_attention_fwd_bwd covers at 4096 and 4032): block ranges that cross (batch, head) boundaries with 0 .. 4 blocks per wave (1008, 336:
@@ -738,7 +749,7 @@ def test_attention_bwd_pipelined(L, B, heads, Nq, Nk):
 
 
 @pytest.mark.parametrize("B,Nq,N,K,addend", [(1, 1024, 1280, 1280, True), (4, 1024, 1280, 1280, False), (1, 1000, 1280, 1280, True),
-                                             (2, 200, 256, 128, False), (3, 70, 128, 64, True)])
+                                             (2, 200, 256, 128, False), (3, 70, 128, 64, True)] + BK.LINEAR_DGRAD_DELTA)
 def test_linear_dgrad_delta_epilogue(L, B, Nq, N, K, addend):
     """GemmP::delta_out (csrc/gemm.hip epilogue of the 128 x 128 4-wave NN kernel; the plan uses it for the out-projection dgrad of the
     1280-channel self-attention layers, engine.hip LinearOp::plan_bwd): dO = dY W (+ addend) AND Delta = rowsum_head(bf16(dO) * O).
@@ -808,7 +819,7 @@ def test_attention_fixed_reference_overflow_fallback(L, F, Nk):
 
 @pytest.mark.parametrize("B,HW,Cc,silu", [(2, 64, 64, 1), (2, 256, 320, 1), (1, 1024, 960, 1), (2, 144, 1280, 0),
                                           (2, 64, 192, 1), (1, 64, 2560, 1), (2, 4096, 640, 1), (1, 100, 320, 1),
-                                          (2, 1000, 1920, 0)])
+                                          (2, 1000, 1920, 0)] + BK.GROUPNORM)
 def test_groupnorm_fwd_bwd(L, B, HW, Cc, silu):
     G = 32
     x = (rnd(B, HW, Cc, seed=40) * 3.0 + 1.5).to(torch.bfloat16)
@@ -848,7 +859,7 @@ def test_groupnorm_large_offset_inputs(L):
     report("groupnorm offset 2e4", y, ref.float(), 1e-2)
 
 
-@pytest.mark.parametrize("M,Cc", [(64, 128), (308, 640), (1000, 1280), (16, 256), (4096, 1280), (4100, 640)])
+@pytest.mark.parametrize("M,Cc", [(64, 128), (308, 640), (1000, 1280), (16, 256), (4096, 1280), (4100, 640)] + BK.LAYERNORM)
 def test_layernorm_fwd_bwd(L, M, Cc):
     x = (rnd(M, Cc, seed=50) * 2.0 + 0.5).to(torch.bfloat16)
     gamma, beta = (rnd(Cc, seed=51) * 0.1 + 1.0).to(torch.bfloat16), rnd(Cc, seed=52)
@@ -950,7 +961,7 @@ def geglu_unpack_cols(u, C4, G=64):
 
 
 @pytest.mark.parametrize("M,K,C4,G", [(64, 128, 256, 64), (308, 320, 1280, 64), (308, 320, 1280, 80), (100, 128, 160, 80),
-                                      (4096, 1280, 5120, 80), (4096, 1280, 5120, 64), (256, 256, 256, 64), (512, 256, 1280, 64)])
+                                      (4096, 1280, 5120, 80), (4096, 1280, 5120, 64), (256, 256, 256, 64), (512, 256, 1280, 64)] + BK.FF_GEGLU)
 def test_ff_geglu_fused_fwd_bwd(L, M, K, C4, G):
     lib.check(L.sdxl_set_gemm_mode(2 if G == 64 else 1))      # group 64: through the 256 x 256 kernel's in-register GEGLU epilogues
     try:
