@@ -51,10 +51,30 @@ typedef struct {
    *   0 l2        l(d) = d^2                          l'(d) = 2 d
    *   1 huber     l(d) = 2 c (sqrt(d^2 + c^2) - c)    l'(d) = 2 c d / sqrt(d^2 + c^2)   (-> d^2 for |d| << c, 2 c |d| for |d| >> c)
    *   2 smooth_l1 l(d) = 2 (sqrt(d^2 + c^2) - c)      l'(d) = 2 d / sqrt(d^2 + c^2)
-   * loss_type outside 0..2, or 1 / 2 with neither huber_c > 0 here nor sdxl_batch.huber_c, is a bad argument (1). ---- */
+   * The element loss is the low byte of loss_type; SDXL_LOSS_EXT may be or-ed in (below).  loss_type < 0, a low byte outside 0..2,
+   * any other bit above the low byte, or 1 / 2 with neither huber_c > 0 here nor sdxl_batch.huber_c, is a bad argument (1). ---- */
   int   loss_type;
   float huber_c;         /* c of every sample; used when sdxl_batch.huber_c is NULL */
+  /* ---- appended; read ONLY when loss_type & SDXL_LOSS_EXT (a caller without the flag may hold the 28-byte struct that ends above).
+   * sdxl_forward_loss, sdxl_loss_fwd_bwd, sdxl_backward_* and sdxl_op_loss honour them.  With m the mask value of a latent pixel
+   * (all 4 channels), M_b = sum_hw m, and s_b, w_b, l, the tag mean tm and the guard as without a mask, m joins the weight first,
+   * (s_b w_b) m, so m = 1 leaves every bit as it is without a mask:
+   *   mean        out[1] = sum_b sum_chw (s_b w_b m) l(d)     L_b = s_b w_b sum_chw m l(d) / (4 HW)
+   *               loss = guard(out[1] / numel * tm)           dpred = gate grad_scale (s_b w_b m) l'(d) / numel
+   *   masked_mean L_b = s_b w_b sum_chw m l(d) / (4 M_b), 0 when M_b = 0                out[1] = 4 HW sum_b L_b
+   *               loss = guard(tm mean_b L_b)                 dpred = gate grad_scale (s_b w_b m) l'(d) / (B 4 M_b), 0 when M_b = 0
+   * m = 0 gives an exact zero in dpred whatever d is; out[2..6] ignore the mask.  Fixed-order sums, no atomics: bitwise reproducible.
+   * mask_norm outside 0..1 while a mask is set is a bad argument (1).
+   * loss_mask is read AGAIN by the backward of the micro-step (like latents): outside graph mode the caller keeps it alive and
+   * unchanged until that backward has been enqueued.  noise_in is read by the loss preparation only.  In graph mode both are staged
+   * inside the plan. ---- */
+  int          mask_norm;   /* 0 "mean", 1 "masked_mean" (above); read only with loss_mask */
+  const float* loss_mask;   /* device, optional [B,H,W] fp32, m >= 0 per latent pixel, applied to all 4 channels; NULL = none */
+  const float* noise_in;    /* device, optional [B,4,H,W] fp32: the noise (ddpm) / x0 (flow matching) the UNet INPUT is built from
+                               (input perturbation), with the same separately rounded operations; the target, the MinSNR weight
+                               and out[4], out[5] keep using sdxl_batch.noise; NULL = noise */
 } sdxl_loss_config;
+#define SDXL_LOSS_EXT 0x100   /* or-ed into loss_type: this sdxl_loss_config is the full current struct, the fields behind huber_c are read */
 
 /* One sampler step, run by sdxl_unet_forward behind its forward (sdxl_batch.sampler): classifier-free guidance, the denoiser, the solver
  * step and the input of the next forward in one kernel that reads the plan's prediction buffer and writes the plan's input buffer, so a
@@ -160,7 +180,7 @@ SDXL_API int sdxl_loss_fwd_bwd(sdxl_handle* h, const sdxl_loss_config* lc, const
 SDXL_API int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* stream);
 /* hipGraph replay of forward / backward (default OFF: measured slower than eager two-stream launches on ROCm 7.2, see
  * DESIGN.md): the second call with a given (plan, loss configuration including loss_type / huber_c and which per-sample arrays are
- * present, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
+ * present, the loss mask / noise_in and mask_norm, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
  * kernel by kernel.  Inputs are staged at fixed addresses inside the plan, so the caller's tensors may move between steps. */
 SDXL_API int sdxl_set_graph_mode(sdxl_handle* h, int on);
 /* synchronises `stream`; out[0]=loss out[1]=sum s*w*l(pred-target) (s = 1, l = square unless set otherwise) out[2]=sum|pred| out[3]=sum pred^2
@@ -259,6 +279,9 @@ SDXL_API int sdxl_op_ff_geglu_fwd(const void* x, const void* w1, const void* b1,
                          int group, void* stream);
 SDXL_API int sdxl_op_ff_geglu_bwd(const void* dy, const void* w2, const void* u, void* du, int M, int C, int C4, int group,
                          void* stream);
+/* phase 2 follows phase 1 of the same batch on the same stream: it reads the gate phase 1 left in out8_dev[7] and, with
+ * mask_norm 1 (masked_mean), the per-sample normalisers M_b phase 1 left in the library's scratch.  Phase 0 reads
+ * noise_in only: the mask, mask_norm and that scratch are nothing to it. */
 SDXL_API int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in, const void* pred, void* dpred,
                  float grad_scale, float* out8_dev, int phase /*0 prepare,1 loss,2 dpred*/, void* stream);
 /* ---- row f1: fused AdamW_BF16 step (replaces AdamWBF16.step / _make_step,

@@ -78,6 +78,13 @@ class TrainingConfig:                    # data/config.py:152-168
                                          # 1 / (snr + 1) for v_prediction, 1 / snr for epsilon (diffusers' --snr_gamma rule)
     tag_weights_per_sample: bool = False # True: batch["tag_weights"] weights each image's own loss instead of the batch mean
     log_per_sample_loss: bool = False    # True: compute_loss also returns "per_sample_loss" (CPU [B]) and "timesteps"
+    # build-only keys: masked loss and the training-only augmentations (trainer.py::NativeSDXLTrainer._loss_ext / _augment); the extra
+    # draws come from the step's generator after the base noise and the timesteps, in this order, each only when its key is on
+    masked_loss: str = "off"             # "off" | "mean" | "masked_mean": batch["loss_mask"] ([B,H,W] / [B,1,H,W], latent resolution)
+                                         # goes to the device loss; "masked_mean" divides each sample by its own mask sum
+    noise_offset: float = 0.0            # >= 0: noise += noise_offset * randn(B,4,1,1); the target uses the offset noise (diffusers)
+    input_perturbation: float = 0.0      # >= 0: the UNet input is built from noise + gamma * randn(B,4,H,W), the target from noise
+    cond_dropout_prob: float = 0.0       # in [0,1]: per sample, prompt_embeds / pooled_prompt_embeds zeroed on a copy (time_ids kept)
     # build-only keys: validation sampling with the native sampler (sampler.py) from train(); decoding the latents is the caller's
     validation_every_n_steps: int = 0    # sample the caller's validation_batches every N optimizer steps (0 = off)
     validation_num_steps: int = 30       # UNet forwards per sample

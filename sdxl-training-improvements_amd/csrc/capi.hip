@@ -10,7 +10,7 @@
 const char* sdxl_get_error();
 
 struct StepState {  // what backward needs from the preceding forward
-  sdxl_loss_config lc;
+  sdxl_loss_config lc;      // in full (read_loss_config), the flag cleared
   sdxl_batch b;
   bool valid = false;
 };
@@ -259,14 +259,30 @@ static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
   return 0;
 }
 
-// the appended fields of sdxl_loss_config / sdxl_batch (element loss, per-sample weights / c / losses), for both places that fill a LossP
+// The caller's sdxl_loss_config is the short struct (everything before mask_norm) unless loss_type carries SDXL_LOSS_EXT: this is the
+// one place that reads it.  `out` is the struct in full with the flag cleared (loss_type = the element loss) and the fields the caller
+// did not pass zero / NULL; every other function here takes that copy.  loss_type's own errors come before any appended field is read.
+static int read_loss_config(const sdxl_loss_config* lc, sdxl_loss_config* out) {
+  const int lt = lc->loss_type;
+  ARG_CHECK(lt >= 0 && (lt & 0xff) <= 2 && (lt & ~(0xff | SDXL_LOSS_EXT)) == 0,
+            "loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1, optionally | SDXL_LOSS_EXT)", lt);
+  memset(out, 0, sizeof(*out));
+  memcpy(out, lc, (lt & SDXL_LOSS_EXT) ? sizeof(*out) : offsetof(sdxl_loss_config, mask_norm));
+  out->loss_type = lt & 0xff;
+  ARG_CHECK(!out->loss_mask || (out->mask_norm >= 0 && out->mask_norm <= 1), "mask_norm %d (0 = mean, 1 = masked_mean)", out->mask_norm);
+  if (!out->loss_mask) out->mask_norm = 0;      // read only with a mask
+  return 0;
+}
+// the appended fields of sdxl_loss_config / sdxl_batch (element loss, per-sample weights / c / losses, mask, the input's noise), for
+// both places that fill a LossP; lc is read_loss_config's copy
 static void fill_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b, LossP& L) {
   L.loss_type = lc->loss_type; L.huber_c = lc->huber_c;
   L.sample_w = b->sample_weights; L.huber_cb = b->huber_c; L.ps_out = b->per_sample_loss;
+  L.mask = lc->loss_mask; L.mask_norm = lc->mask_norm;
+  L.noise_in = lc->noise_in ? lc->noise_in : b->noise;
 }
 // ... and their argument errors, reported before anything is copied or launched
 static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
-  ARG_CHECK(lc->loss_type >= 0 && lc->loss_type <= 2, "loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1)", lc->loss_type);
   ARG_CHECK(lc->loss_type == 0 || b->huber_c || lc->huber_c > 0.f, "loss_type %d needs huber_c > 0 (got %g) or a per-sample huber_c array",
             lc->loss_type, (double)lc->huber_c);
   return 0;
@@ -284,6 +300,7 @@ static void fill_loss(Engine& e, const sdxl_loss_config* lc, const sdxl_batch* b
   L.grad_scale = grad_scale;
   L.out = p.F(p.loss_off);
   L.part = p.F(p.loss_part_off);
+  L.mnorm = p.F(p.mask_norm_off);
 }
 
 
@@ -324,10 +341,12 @@ static unsigned loss_cfg_bits(const sdxl_loss_config& lc, bool tag) {
   return (unsigned)lc.method | ((unsigned)lc.prediction_type << 2) | ((unsigned)lc.use_min_snr << 4) | ((unsigned)lc.use_ztsnr << 5) |
          ((unsigned)tag << 6) | (g << 7);
 }
-// the second key word: element loss and which of the per-sample arrays are present (every one changes the captured kernels' arguments)
+// the second key word: element loss, which of the per-sample arrays, the mask and noise_in are present and the mask's normalisation
+// (every one changes the captured kernels' arguments); lc is read_loss_config's copy, so loss_type is without the flag
 static unsigned loss_cfg_bits2(const sdxl_loss_config& lc, const sdxl_batch& b) {
-  return (unsigned)lc.loss_type | ((unsigned)(b.sample_weights != nullptr) << 2) | ((unsigned)(b.huber_c != nullptr) << 3) |
-         ((unsigned)(b.per_sample_loss != nullptr) << 4);
+  return (unsigned)(lc.loss_type & 3) | ((unsigned)(b.sample_weights != nullptr) << 2) | ((unsigned)(b.huber_c != nullptr) << 3) |
+         ((unsigned)(b.per_sample_loss != nullptr) << 4) | ((unsigned)(lc.loss_mask != nullptr) << 5) |
+         ((unsigned)(lc.noise_in != nullptr) << 6) | ((unsigned)(lc.mask_norm & 1) << 7);
 }
 // the third: the scalar huber_c, a kernel argument baked into a captured graph (not read for l2 or with a per-sample array)
 static unsigned loss_huber_bits(const sdxl_loss_config& lc, const sdxl_batch& b) {
@@ -372,6 +391,9 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   ARG_CHECK(lc->method == 0 || lc->method == 1, "unknown method %d", lc->method);
   CHK(check_batch(e, b));
   ARG_CHECK(b->latents && b->noise && b->sigma_or_t, "batch is missing latents/noise/sigma");
+  sdxl_loss_config full;
+  CHK(read_loss_config(lc, &full));
+  lc = &full;
   CHK(check_loss_ext(lc, b));
   CHK(upload_cond(e, b, st));
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
@@ -396,6 +418,14 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
       HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_hc_off), b->huber_c, sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
       sb.huber_c = p.F(p.in_hc_off);
     }
+    if (full.loss_mask) {
+      HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_mask_off), full.loss_mask, sizeof(float) * (size_t)p.B * p.H * p.W, hipMemcpyDeviceToDevice, st));
+      full.loss_mask = p.F(p.in_mask_off);
+    }
+    if (full.noise_in) {
+      HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_nin_off), full.noise_in, nlat, hipMemcpyDeviceToDevice, st));
+      full.noise_in = p.F(p.in_nin_off);
+    }
   }
   // the per-sample losses are produced inside the plan (a fixed address for a captured graph) and copied out below
   if (b->per_sample_loss) sb.per_sample_loss = p.F(p.ps_loss_off);
@@ -410,7 +440,7 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   }));
   if (b->per_sample_loss)
     HIP_CHECK_RET(hipMemcpyAsync(b->per_sample_loss, p.F(p.ps_loss_off), sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
-  h->step.lc = *lc; h->step.b = sb; h->step.valid = true;
+  h->step.lc = full; h->step.b = sb; h->step.valid = true;
   return 0;
 }
 
@@ -925,6 +955,9 @@ int sdxl_op_ff_geglu_bwd(const void* dy, const void* w2, const void* u, void* du
 int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in, const void* pred, void* dpred,
                  float grad_scale, float* out8, int phase, void* st) {
   ARG_CHECK(lc && b, "null argument");
+  sdxl_loss_config full;
+  CHK(read_loss_config(lc, &full));
+  lc = &full;
   LossP L;
   memset(&L, 0, sizeof(L));
   L.method = lc->method; L.prediction_type = lc->prediction_type; L.use_min_snr = lc->use_min_snr;
@@ -935,7 +968,12 @@ int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in,
   L.grad_scale = grad_scale; L.out = out8;
   CHK(check_loss_ext(lc, b));
   fill_loss_ext(lc, b, L);
-  if (phase == 1) CHK(test_slab(loss_part_floats(L.B, L.HW), &L.part));
+  // the partial rows of phase 1, and behind them the [B] normaliser that masked_mean's phase 1 leaves for its phase 2
+  if (phase == 1 || (phase == 2 && L.mask && L.mask_norm == 1)) {
+    ARG_CHECK(L.B > 0 && L.HW > 0, "loss: empty batch");
+    CHK(test_slab(loss_part_floats(L.B, L.HW) + (size_t)L.B, &L.part));
+    L.mnorm = L.part + loss_part_floats(L.B, L.HW);
+  }
   if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st);
   if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);
   if (phase == 2) return launch_loss_bwd(L, (hipStream_t)st);

@@ -1186,6 +1186,10 @@ void Engine::build(Plan* plan) {
     plan->in_hc_off = plan->alloc(sizeof(float) * plan->B);
     plan->ps_loss_off = plan->alloc(sizeof(float) * plan->B);
     plan->samp_part_off = plan->alloc(sizeof(float) * sampler_part_floats(plan->B, plan->H * plan->W));      // ... and the sampler step's
+    // ... and the masked loss's: the staged mask and input noise, the per-sample normaliser
+    plan->in_mask_off = plan->alloc(sizeof(float) * (size_t)plan->B * plan->H * plan->W);
+    plan->in_nin_off = plan->alloc(sizeof(float) * (size_t)plan->B * 4 * plan->H * plan->W);
+    plan->mask_norm_off = plan->alloc(sizeof(float) * plan->B);
     plan->seg_first_op.assign(nseg, -1);
     plan->seg_last_op.assign(nseg, -2);
     for (int i = 0; i < (int)plan->ops.size(); ++i) {

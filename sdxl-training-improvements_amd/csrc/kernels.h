@@ -378,12 +378,19 @@ struct LossP {
   const float* sample_w;  // optional [B]: s_b, multiplied into each sample's loss and gradient
   const float* huber_cb;  // optional [B]: per-sample c_b
   float* ps_out;          // optional [B] OUT: L_b = s_b w_b mean_chw l(d), before the tag mean and the guard
+  // ---- masked loss / input perturbation (NULL / 0 = every pixel counts, the input is built from `noise`) ----
+  const float* noise_in;  // [B][4][HW]: what loss_prepare_kernel builds the UNet input from (the callers set it to `noise` when the
+                          // batch has none); the target, the weights and out[4], out[5] always use `noise`
+  const float* mask;      // optional [B][HW]: m >= 0 per latent pixel, multiplied into (s_b w_b) for all four channels
+  int mask_norm;          // with mask: 0 = mean (divide by numel), 1 = masked_mean (per sample by 4 M_b, M_b = sum_hw m)
+  float* mnorm;           // masked_mean: [B] scratch, M_b left by loss_finalize_kernel for loss_bwd_kernel
 };
 // A 256-pixel block of the flat [B*HW] range touches at most loss_ps_slots samples (it straddles a sample boundary whenever
 // HW % 256 != 0, several when HW < 256).  The scratch holds the blocks' six batch sums first, then one partial of the weighted
-// element loss per (block, sample slot); slot j of block r belongs to sample (r * 256) / HW + j.
+// element loss per (block, sample slot); slot j of block r belongs to sample (r * 256) / HW + j.  masked_mean adds a second such
+// column behind it: the block's partial of the mask sum M_b per slot.
 static inline __host__ __device__ int loss_ps_slots(int B, int HW) { const int s = 255 / HW + 2; return s < B ? s : B; }
-static inline size_t loss_part_floats(int B, int HW) { return (6 + (size_t)loss_ps_slots(B, HW)) * (((size_t)B * HW + 255) / 256); }
+static inline size_t loss_part_floats(int B, int HW) { return (6 + 2 * (size_t)loss_ps_slots(B, HW)) * (((size_t)B * HW + 255) / 256); }
 int launch_loss_prepare(const LossP& p, hipStream_t st);
 int launch_loss_fwd(const LossP& p, hipStream_t st);
 int launch_loss_bwd(const LossP& p, hipStream_t st);

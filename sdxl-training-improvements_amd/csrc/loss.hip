@@ -14,6 +14,13 @@
 //   sqrt(d^2+c^2)-c is computed as d^2/(sqrt(d^2+c^2)+c) (the plain difference cancels for |d| << c)
 //   every sample's terms carry (s_b w_b): raw sum = sum_b sum_chw (s_b w_b) l(d), dpred = gate grad_scale (s_b w_b) l'(d) / numel
 //   L_b = s_b w_b mean_chw l(d) goes to ps_out, before the tag mean and the guard
+// Masked loss (LossP: mask, mask_norm, mnorm), m >= 0 per latent pixel, M_b = sum_hw m; m joins the weight first, (s_b w_b) m:
+//   mean        raw = sum (s_b w_b m) l(d), L_b = s_b w_b sum_chw m l(d) / (4 HW), dpred = gate grad_scale (s_b w_b m) l'(d) / numel
+//   masked_mean L_b = s_b w_b sum_chw m l(d) / (4 M_b) (0 when M_b = 0), raw = 4 HW sum_b L_b, loss = guard(tm mean_b L_b),
+//               dpred = gate grad_scale (s_b w_b m) l'(d) / (B 4 M_b) (0 when M_b = 0); M_b goes from the finalize kernel to the
+//               backward through mnorm
+//   m = 0 is an exact zero in dpred whatever d is.  The six other sums ignore the mask.
+// Input perturbation (LossP: noise_in): only loss_prepare_kernel reads it, in place of noise.
 //
 // Inputs arrive as the reference hands them over: NCHW fp32 latents / noise.  The UNet consumes and
 // produces token-major [B*HW][8] bf16 (4 real channels + 4 zero pad so every row is one 16-byte vector).
@@ -54,7 +61,7 @@ __global__ void loss_prepare_kernel(const LossP p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     long idx = ((long)b * 4 + c) * p.HW + hw;
-    float x = p.latents[idx], n = p.noise[idx];
+    float x = p.latents[idx], n = p.noise_in[idx];
     float v;
     // every product and sum rounded on its own (no FMA contraction), exactly as the reference's separate torch ops do:
     // the bf16 UNet input is then the round-to-nearest-even image of the reference's fp32 tensor, bit for bit
@@ -73,14 +80,16 @@ __global__ void loss_prepare_kernel(const LossP p) {
 // sqrt(d^2 + c^2) - c without the cancellation
 __device__ __forceinline__ float pseudo_huber(float d, float c) { return d * d / (sqrtf(d * d + c * c) + c); }
 
-// LT = LossP::loss_type.  The per-sample weight, the per-sample c and the per-sample output are wave-uniform branches on their
-// pointers: with all three NULL and LT = 0 the arithmetic is the reference's, operation for operation.
+// LT = LossP::loss_type.  The per-sample weight, the per-sample c, the mask and the per-sample output are wave-uniform branches on
+// their pointers: with all of them NULL and LT = 0 the arithmetic is the reference's, operation for operation.
 template <int LT>
 __global__ void loss_fwd_kernel(const LossP p) {
   __shared__ float sred[4][8];
-  __shared__ float sps[4];
+  __shared__ float sps[4], spm[4];
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float mk = 0.f;   // this thread's mask value (0 past the end)
+  const bool mm = p.mask && p.mask_norm == 1;
   int bs = -1;      // this thread's sample (-1: past the end)
   if (i < (long)p.B * p.HW) {
     int b = (int)(i / p.HW), hw = (int)(i - (long)b * p.HW);
@@ -88,6 +97,7 @@ __global__ void loss_fwd_kernel(const LossP p) {
     float sg = p.sigma[b];
     const float sw = p.sample_w ? p.sample_w[b] : 1.f;
     const float hc = LT != 0 ? (p.huber_cb ? p.huber_cb[b] : p.huber_c) : 0.f;
+    if (p.mask) mk = p.mask[i];
     bf16x8 pv = *(const bf16x8*)(p.pred + i * 8);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -97,6 +107,7 @@ __global__ void loss_fwd_kernel(const LossP p) {
       loss_target(p, b, x, n, sg, &tg, &w);
       float d = pr - tg;
       if (p.sample_w) w = sw * w;      // (s_b w_b) first: s_b = 1 leaves every bit as without weights
+      if (p.mask) w = w * mk;          // ... then m: m = 1 leaves every bit as without a mask
       if (LT == 0) acc[0] += w * d * d;
       else if (LT == 1) acc[0] += w * (2.f * hc * pseudo_huber(d, hc));
       else acc[0] += w * (2.f * pseudo_huber(d, hc));
@@ -116,16 +127,20 @@ __global__ void loss_fwd_kernel(const LossP p) {
   __syncthreads();
   if (threadIdx.x < 6)      // the block's six sums as a partial row: loss_finalize_kernel adds the rows in a fixed order (bitwise reproducible loss)
     p.part[(long)blockIdx.x * 6 + threadIdx.x] = sred[0][threadIdx.x] + sred[1][threadIdx.x] + sred[2][threadIdx.x] + sred[3][threadIdx.x];
-  if (p.ps_out) {      // the block's loss sum once more, split by sample: slot j = the j-th sample this block touches
+  if (p.ps_out || mm) {      // the block's loss sum once more, split by sample: slot j = the j-th sample this block touches
     const int S = loss_ps_slots(p.B, p.HW);
     const long nb = ((long)p.B * p.HW + 255) / 256;
     const int b0 = (int)(((long)blockIdx.x * 256) / p.HW);
     for (int j = 0; j < S; ++j) {
       float s = wave_sum(bs == b0 + j ? acc[0] : 0.f);      // selected, not multiplied: a non-finite sample stays in its own slot
+      float t = mm ? wave_sum(bs == b0 + j ? mk : 0.f) : 0.f;      // masked_mean: the slot's share of M_b, the column behind
       __syncthreads();
-      if (lane == 0) sps[wv] = s;
+      if (lane == 0) { sps[wv] = s; spm[wv] = t; }
       __syncthreads();
-      if (threadIdx.x == 0) p.part[6 * nb + (long)blockIdx.x * S + j] = sps[0] + sps[1] + sps[2] + sps[3];
+      if (threadIdx.x == 0) {
+        p.part[6 * nb + (long)blockIdx.x * S + j] = sps[0] + sps[1] + sps[2] + sps[3];
+        if (mm) p.part[(6 + S) * nb + (long)blockIdx.x * S + j] = spm[0] + spm[1] + spm[2] + spm[3];
+      }
     }
   }
 }
@@ -133,26 +148,42 @@ __global__ void loss_fwd_kernel(const LossP p) {
 // one wave: lane l adds the partial rows l, l + 64, ... in order, lane 0 then adds the 64 lane sums in order
 __global__ void loss_finalize_kernel(const LossP p) {
   __shared__ float sl[6][64];
-  __shared__ float sp[64];
+  __shared__ float sp[64], sq[64];
   const long nb = ((long)p.B * p.HW + 255) / 256;
+  const bool mm = p.mask && p.mask_norm == 1;
+  float sum_lb = 0.f;      // masked_mean, thread 0: sum_b L_b in sample order
   for (int k = 0; k < 6; ++k) {
     float s = 0.f;
     for (long r = threadIdx.x; r < nb; r += 64) s += p.part[r * 6 + k];
     sl[k][threadIdx.x] = s;
   }
   __syncthreads();
-  if (p.ps_out) {      // per sample: the slots of the blocks [b*HW/256, ((b+1)*HW-1)/256] that belong to it, in the same fixed order
+  if (p.ps_out || mm) {      // per sample: the slots of the blocks [b*HW/256, ((b+1)*HW-1)/256] that belong to it, in the same fixed order
     const int S = loss_ps_slots(p.B, p.HW);
     for (int b = 0; b < p.B; ++b) {
       const long lo = ((long)b * p.HW) / 256, hi = ((long)(b + 1) * p.HW - 1) / 256;
-      float s = 0.f;
-      for (long r = lo + threadIdx.x; r <= hi; r += 64) s += p.part[6 * nb + r * S + (b - (int)((r * 256) / p.HW))];
+      float s = 0.f, q = 0.f;
+      for (long r = lo + threadIdx.x; r <= hi; r += 64) {
+        const long slot = r * S + (b - (int)((r * 256) / p.HW));
+        s += p.part[6 * nb + slot];
+        if (mm) q += p.part[(6 + S) * nb + slot];
+      }
       sp[threadIdx.x] = s;
+      sq[threadIdx.x] = q;
       __syncthreads();
       if (threadIdx.x == 0) {
         float t = 0.f;
         for (int l = 0; l < 64; ++l) t += sp[l];
-        p.ps_out[b] = t / (4.f * (float)p.HW);
+        if (mm) {      // L_b over the sample's own mask sum; an empty mask is a zero loss (and, in the backward, a zero gradient)
+          float M = 0.f;
+          for (int l = 0; l < 64; ++l) M += sq[l];
+          const float lb = M == 0.f ? 0.f : t / (4.f * M);
+          p.mnorm[b] = M;
+          sum_lb += lb;
+          if (p.ps_out) p.ps_out[b] = lb;
+        } else {
+          p.ps_out[b] = t / (4.f * (float)p.HW);
+        }
       }
       __syncthreads();
     }
@@ -164,7 +195,8 @@ __global__ void loss_finalize_kernel(const LossP p) {
     p.out[1 + k] = s;
   }
   float numel = (float)p.B * 4.f * (float)p.HW;
-  float l = p.out[1] / numel;
+  if (mm) p.out[1] = 4.f * (float)p.HW * sum_lb;      // so that out[0] = out[1] / numel * tm still holds
+  float l = mm ? sum_lb / (float)p.B : p.out[1] / numel;
   float tm = 1.f;
   if (p.tag_w) {
     float s = 0.f;
@@ -185,7 +217,12 @@ __global__ void loss_bwd_kernel(const LossP p) {
   float sg = p.sigma[b];
   const float sw = p.sample_w ? p.sample_w[b] : 1.f;
   const float hc = LT != 0 ? (p.huber_cb ? p.huber_cb[b] : p.huber_c) : 0.f;
+  const float mk = p.mask ? p.mask[i] : 1.f;
   float k = p.out[7] * p.grad_scale * 2.f / ((float)p.B * 4.f * (float)p.HW);
+  if (p.mask && p.mask_norm == 1) {      // masked_mean: the sample's own normaliser, left by loss_finalize_kernel
+    const float M = p.mnorm[b];
+    k = M == 0.f ? 0.f : p.out[7] * p.grad_scale * 2.f / ((float)p.B * 4.f * M);
+  }
   bf16x8 pv = *(const bf16x8*)(p.pred + i * 8), o;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -193,14 +230,15 @@ __global__ void loss_bwd_kernel(const LossP p) {
     float tg, w;
     loss_target(p, b, p.latents[idx], p.noise[idx], sg, &tg, &w);
     if (p.sample_w) w = sw * w;
+    if (p.mask) w = w * mk;
     float d = (float)pv[c] - tg;
     if (LT != 0) {      // l'(d) / 2: huber c d / sqrt(d^2 + c^2), smooth_l1 d / sqrt(d^2 + c^2)
       const float q = sqrtf(d * d + hc * hc);
       d = LT == 1 ? hc * d / q : d / q;
     }
     // guard taken (non-finite or clamped loss, out[7] == 0): an exact zero gradient, also where pred - target is inf / nan;
-    // s_b = 0: an exact zero slab for that sample, whatever d is
-    o[c] = (k == 0.f || (p.sample_w && sw == 0.f)) ? (bf16)0.f : (bf16)(k * w * d);
+    // s_b = 0: an exact zero slab for that sample, m = 0: an exact zero pixel, whatever d is
+    o[c] = (k == 0.f || (p.sample_w && sw == 0.f) || (p.mask && mk == 0.f)) ? (bf16)0.f : (bf16)(k * w * d);
     o[c + 4] = (bf16)0.f;
   }
   *(bf16x8*)(p.dpred + i * 8) = o;
@@ -213,11 +251,13 @@ static int check_loss(const LossP& p) {
   ARG_CHECK(p.loss_type >= 0 && p.loss_type <= 2, "loss: loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1)", p.loss_type);
   ARG_CHECK(p.loss_type == 0 || p.huber_cb || p.huber_c > 0.f, "loss: loss_type %d needs huber_c > 0 (got %g)", p.loss_type,
             (double)p.huber_c);
+  ARG_CHECK(!p.mask || (p.mask_norm >= 0 && p.mask_norm <= 1), "loss: mask_norm %d (0 = mean, 1 = masked_mean)", p.mask_norm);
   return 0;
 }
 int launch_loss_prepare(const LossP& p, hipStream_t st) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
+  ARG_CHECK(p.noise_in != nullptr, "loss: missing noise_in (the callers set it to noise)");
   hipLaunchKernelGGL(loss_prepare_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
@@ -226,6 +266,7 @@ int launch_loss_fwd(const LossP& p, hipStream_t st) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
   ARG_CHECK(p.part != nullptr, "loss: missing partial-row scratch (loss_part_floats)");
+  ARG_CHECK(!(p.mask && p.mask_norm == 1) || p.mnorm, "loss: masked_mean needs the [B] normaliser scratch");
   if (p.loss_type == 0) hipLaunchKernelGGL(loss_fwd_kernel<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   else if (p.loss_type == 1) hipLaunchKernelGGL(loss_fwd_kernel<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(loss_fwd_kernel<2>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
@@ -236,6 +277,7 @@ int launch_loss_fwd(const LossP& p, hipStream_t st) {
 int launch_loss_bwd(const LossP& p, hipStream_t st) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
+  ARG_CHECK(!(p.mask && p.mask_norm == 1) || p.mnorm, "loss: masked_mean needs the [B] normaliser scratch");
   if (p.loss_type == 0) hipLaunchKernelGGL(loss_bwd_kernel<0>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   else if (p.loss_type == 1) hipLaunchKernelGGL(loss_bwd_kernel<1>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(loss_bwd_kernel<2>, dim3(cdiv(n, 256)), dim3(256), 0, st, p);

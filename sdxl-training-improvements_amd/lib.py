@@ -43,6 +43,15 @@ class LossConfig(C.Structure):
                 ("loss_type", C.c_int), ("huber_c", C.c_float)]
 
 
+LOSS_EXT = 0x100      # SDXL_LOSS_EXT, or-ed into loss_type: the struct passed is a LossConfigExt
+
+
+class LossConfigExt(LossConfig):
+    """sdxl_loss_config in full: LossConfig (what every caller without a mask or a separate input noise passes) + the fields the
+    library reads only when loss_type carries LOSS_EXT.  mask_norm: MASK_NORMS."""
+    _fields_ = [("mask_norm", C.c_int), ("loss_mask", C.c_void_p), ("noise_in", C.c_void_p)]
+
+
 class SamplerStep(C.Structure):
     """sdxl_sampler_step: one sampler step behind sdxl_unet_forward's forward (Batch.sampler)"""
     _fields_ = [("x", C.c_void_p), ("cfg", C.c_int), ("init", C.c_int),
@@ -66,6 +75,7 @@ class SamplerBatch(Batch):
 
 
 LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
+MASK_NORMS = {"mean": 0, "masked_mean": 1}
 
 
 class AdamWConfig(C.Structure):

@@ -47,7 +47,7 @@ from .ema import WeightEMA
 from .optimizer import BY_TYPE, AdamWBF16, FusedArenaOptimizer
 from .sampler import PARAMETERIZATIONS, NativeSampler
 from .scheduler import NoiseScheduler
-from .unet import NativeUNet, config_from_unet
+from .unet import NativeUNet, config_from_unet, loss_mask_bhw
 
 logger = logging.getLogger(__name__)
 
@@ -56,6 +56,7 @@ LOSS_TYPES = ("l2", "huber", "smooth_l1")
 HUBER_SCHEDULES = ("constant", "snr")
 SNR_WEIGHTINGS = ("reference", "debiased")
 WEIGHT_SETS = ("trained", "ema")
+MASKED_LOSSES = ("off", "mean", "masked_mean")
 
 
 class _NativeLoss(torch.autograd.Function):
@@ -151,6 +152,15 @@ class NativeSDXLTrainer:
                                 ("snr_weighting", self.snr_weighting, SNR_WEIGHTINGS)):
             if val not in known:
                 raise ValueError(f"training.{key}: unknown value {getattr(tc, key)!r} (expected one of {', '.join(known)})")
+        self.masked_loss = str(getattr(tc, "masked_loss", "off")).lower()
+        if self.masked_loss not in MASKED_LOSSES:
+            raise ValueError(f"training.masked_loss: unknown value {getattr(tc, 'masked_loss')!r} (expected one of {', '.join(MASKED_LOSSES)})")
+        for key, top in (("noise_offset", None), ("input_perturbation", None), ("cond_dropout_prob", 1.0)):
+            v = getattr(tc, key, 0.0)
+            ok = not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(float(v)) and float(v) >= 0.0
+            if not ok or (top is not None and float(v) > top):
+                raise ValueError(f"training.{key} must be a number {'>= 0' if top is None else 'in [0, 1]'} (got {v!r})")
+            setattr(self, key, float(v))
         if self.loss_type != "l2" and not self.huber_c > 0.0:
             raise ValueError(f"training.huber_c must be > 0 for training.loss_type {self.loss_type!r} (got {self.huber_c})")
         if self.method != "ddpm":
@@ -285,10 +295,38 @@ class NativeSDXLTrainer:
                 ext["huber_c"] = self.huber_c
         if bool(getattr(tc, "log_per_sample_loss", False)):
             ext["per_sample_loss"] = True
+        mask = batch.get("loss_mask") if self.masked_loss != "off" else None      # a batch without one is unmasked
+        if mask is not None:
+            ext["loss_mask"] = loss_mask_bhw(mask, batch["vae_latents"].shape)
+            if self.masked_loss != "mean":
+                ext["mask_norm"] = self.masked_loss
         return ext
 
-    def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None):
-        """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used"""
+    def _augment(self, batch, noise, generator):
+        """The training-only recipes on top of the base noise (drawn or injected), each drawn from the step's generator only when its
+        key is on, in the order noise offset, input perturbation, conditioning dropout -- after the base noise and the timesteps.
+        Returns (batch, noise, ext): the batch a shallow copy with zeroed conditioning rows where dropout drew them (the caller's
+        tensors are not modified), the noise after the offset (what the target uses), and noise_in for forward_loss."""
+        ext: Dict[str, Any] = {}
+        B = noise.shape[0]
+        if self.noise_offset > 0.0:                        # diffusers' --noise_offset: one draw per sample and channel
+            r = torch.randn(B, noise.shape[1], 1, 1, generator=generator)
+            noise = noise.float() + self.noise_offset * r.to(noise.device)
+        if self.input_perturbation > 0.0:                  # diffusers' --input_perturbation: the input's noise only
+            r = torch.randn(noise.shape, generator=generator)
+            ext["noise_in"] = noise.float() + self.input_perturbation * r.to(noise.device)
+        if self.cond_dropout_prob > 0.0:                   # zero conditioning, what the sampler's guidance runs against; time_ids stay
+            drop = torch.rand(B, generator=generator) < self.cond_dropout_prob
+            batch = dict(batch)
+            for key in ("prompt_embeds", "pooled_prompt_embeds"):
+                t = batch[key].clone()
+                t[drop.to(t.device)] = 0
+                batch[key] = t
+        return batch, noise, ext
+
+    def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None, augment: bool = False):
+        """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used.
+        augment: apply the training-only recipes (noise offset, input perturbation, conditioning dropout; _augment)"""
         B = lat.shape[0]
         cm = self.config.model
         tag = batch.get("tag_weights")
@@ -298,6 +336,9 @@ class NativeSDXLTrainer:
             sig = self.noise_scheduler.timestep_to_sigma(ts)
             ext = self._loss_ext(batch, sig)
             ext.update(ext_over or {})
+            if augment:
+                batch, noise, aug = self._augment(batch, noise, generator)
+                ext.update(aug)
             self.net.forward_loss("ddpm", lat, noise, sig, ts.float(), batch["prompt_embeds"],
                                   batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag,
                                   prediction_type=self.config.training.prediction_type,
@@ -312,6 +353,9 @@ class NativeSDXLTrainer:
             t_unet = t
         ext = self._loss_ext(batch, None)
         ext.update(ext_over or {})
+        if augment:
+            batch, noise, aug = self._augment(batch, noise, generator)
+            ext.update(aug)
         self.net.forward_loss("flow_matching", lat, noise, t, t_unet, batch["prompt_embeds"],
                               batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag, **ext)
         return t
@@ -330,7 +374,7 @@ class NativeSDXLTrainer:
         B = lat.shape[0]
         if noise is None:
             noise = torch.randn(lat.shape, generator=generator)
-        ts = self._forward(batch, lat, noise, timesteps, generator)
+        ts = self._forward(batch, lat, noise, timesteps, generator, augment=True)
         o = self.net.read_loss()                                        # the single host sync of the step
         numel = lat.numel()
         lr = self.optimizer.param_groups[0]["lr"] if self.optimizer is not None else 0.0
@@ -354,7 +398,8 @@ class NativeSDXLTrainer:
         """Held-out loss at fixed timesteps, forward only: every batch is evaluated at each of `timesteps` (ddpm: indices into
         the sigma table; flow matching: t in (0, 1)) with noise drawn from `generator`.  No backward, no gradient zeroing, no
         optimizer or EMA step; the accumulation state is not touched.  The loss is the one the config keys select (weights,
-        element loss), per sample, before the tag mean and the guard.  Returns ({timestep: mean per-sample loss}, overall mean).
+        element loss, the batch's loss mask; none of noise offset, input perturbation, conditioning dropout), per sample, before
+        the tag mean and the guard.  Returns ({timestep: mean per-sample loss}, overall mean).
         Evaluates the trained weights, or with weights="ema" the EMA (cast to bf16 into a temporary arena, see _weights)."""
         with self._weights(weights):
             return self._evaluate(list(batches), timesteps, generator)

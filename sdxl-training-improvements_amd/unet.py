@@ -79,6 +79,19 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def loss_mask_bhw(m, latent_shape) -> torch.Tensor:
+    """a loss mask given as [B,H,W] or [B,1,H,W] at latent resolution as [B,H,W] fp32; ValueError for any other shape and for a
+    value that is negative or not finite (downsampling a pixel mask is the caller's job)"""
+    B, _, H, W = latent_shape
+    m = torch.as_tensor(m)
+    if tuple(m.shape) not in ((B, H, W), (B, 1, H, W)):
+        raise ValueError(f"loss_mask: expected shape {(B, H, W)} or {(B, 1, H, W)} (latent resolution), got {tuple(m.shape)}")
+    m = m.to(torch.float32).reshape(B, H, W)
+    if not bool(torch.isfinite(m).all()) or bool((m < 0).any()):
+        raise ValueError("loss_mask: every value must be finite and >= 0")
+    return m
+
+
 class NativeUNet:
     """SDXL UNet + loss, forward and backward, on one MI355X.
 
@@ -219,26 +232,49 @@ class NativeUNet:
             raise ValueError(f"{what}: expected {B} values (one per sample), got {t.numel()}")
         return t
 
+    def _loss_mask(self, m, latents):
+        """an optional loss mask as a contiguous [B,H,W] fp32 device array (kept alive like the per-sample arrays: the backward reads
+        it again); ValueError for a shape that is not the latents' [B,H,W] / [B,1,H,W] or a value that is negative or not finite"""
+        return None if m is None else loss_mask_bhw(m, latents.shape).to(self.device).contiguous()
+
     def forward_loss(self, method: str, latents, noise, sigma_or_t, timestep, prompt_embeds, pooled, time_ids,
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
                      use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
-                     per_sample_loss: bool = False) -> None:
+                     per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean") -> None:
         """loss preparation + UNet forward + loss; results stay on the device until read_loss().
         sample_weights: optional [B] s_b multiplied into each sample's loss and gradient.  loss_type "l2" | "huber" |
         "smooth_l1" (include/sdxlstep.h), with huber_c a float (every sample) or [B] values (per sample).
-        per_sample_loss: also produce the [B] per-sample losses, read with read_per_sample_loss() after read_loss()."""
+        per_sample_loss: also produce the [B] per-sample losses, read with read_per_sample_loss() after read_loss().
+        loss_mask: optional [B,H,W] or [B,1,H,W] at latent resolution, finite and >= 0, multiplied into every channel's loss and
+        gradient; mask_norm "mean" divides by the element count as without a mask, "masked_mean" each sample by its own mask sum.
+        noise_in: optional [B,4,H,W], the noise (ddpm) / x0 (flow matching) the UNet input is built from while the target keeps
+        `noise` (input perturbation)."""
         if loss_type not in lib.LOSS_TYPES:
             raise ValueError(f"loss_type {loss_type!r}: expected one of {sorted(lib.LOSS_TYPES)}")
+        if mask_norm not in lib.MASK_NORMS:
+            raise ValueError(f"mask_norm {mask_norm!r}: expected one of {sorted(lib.MASK_NORMS)}")
         B = latents.shape[0]
+        mask = self._loss_mask(loss_mask, latents)
+        if noise_in is not None and tuple(noise_in.shape) != tuple(latents.shape):
+            raise ValueError(f"noise_in: expected the latents' shape {tuple(latents.shape)}, got {tuple(noise_in.shape)}")
         scalar_c = isinstance(huber_c, (int, float))
         lc = lib.LossConfig(METHODS[method], PRED_TYPES.get(prediction_type, 0), int(min_snr_gamma is not None),
                             float(min_snr_gamma or 0.0), int(bool(use_ztsnr)), lib.LOSS_TYPES[loss_type],
                             float(huber_c) if scalar_c else 0.0)
+        ext = []
+        if mask is not None or noise_in is not None:      # the full struct, flagged; without either the call is the short struct's
+            nin = None if noise_in is None else noise_in.to(self.device, torch.float32).contiguous()
+            ext = [mask, nin]
+            lc = lib.LossConfigExt(*[getattr(lc, f[0]) for f in lib.LossConfig._fields_])
+            lc.loss_type |= lib.LOSS_EXT
+            lc.mask_norm = lib.MASK_NORMS[mask_norm]
+            lc.loss_mask = None if mask is None else mask.data_ptr()
+            lc.noise_in = None if nin is None else nin.data_ptr()
         b = self._batch(latents, noise, sigma_or_t, timestep, prompt_embeds, pooled, time_ids, tag_weights)
         sw = self._per_sample(sample_weights, B, "sample_weights")
         hc = None if scalar_c else self._per_sample(huber_c, B, "huber_c")
         self._ps_loss = torch.empty(B, dtype=torch.float32, device=self.device) if per_sample_loss else None
-        self._keep = list(self._keep) + [sw, hc]
+        self._keep = list(self._keep) + [sw, hc] + ext
         b.sample_weights = None if sw is None else sw.data_ptr()
         b.huber_c = None if hc is None else hc.data_ptr()
         b.per_sample_loss = None if self._ps_loss is None else self._ps_loss.data_ptr()
