@@ -85,7 +85,8 @@ typedef struct {
  *   x       = p * x + q * den                                                              the state, in place
  *   input   = bf16(clamp(a_in_next * x, +-clamp))                                          clamp <= 0: none; channels 4..7 zero
  * fp32, every operation rounded on its own in this order (no FMA), the rescale sums in a fixed order: bitwise reproducible.  The scalars
- * are the caller's (sampler.py derives them for the trained ddpm denoiser, the reference's Karras scalings and flow matching). */
+ * are the caller's (sampler.py derives them for the trained ddpm denoiser, the reference's Karras scalings and flow matching).
+ * The struct sdxl_sampler_step_ext below appends the terms of the second-order and stochastic solvers and of inpainting. */
 typedef struct {
   float* x;                       /* [B,4,H,W] fp32 NCHW sampler state, in place */
   int    cfg;                     /* 1: the plan's batch is 2B = [cond; uncond] */
@@ -94,6 +95,37 @@ typedef struct {
   float  a_in_next, clamp;        /* the input of the NEXT forward */
   float  guidance, guidance_rescale;
 } sdxl_sampler_step;
+
+/* The extended step: sdxl_sampler_step with the fields below appended behind guidance_rescale (`base` IS that struct, so the layout is
+ * the appended one).  They are read ONLY when SDXL_SAMPLER_EXT is or-ed into base.init; the caller then passes a pointer to this struct
+ * wherever a sdxl_sampler_step* is taken (sdxl_batch.sampler).  A caller without the flag may keep passing the struct that ends at
+ * guidance_rescale: nothing behind it is read.  The solver line of the step widens to
+ *   acc    = p * x + q * den
+ *   acc    = acc + r * hist      (r != 0)        acc = acc + u * xsave   (u != 0)        acc = acc + s * noise   (s != 0)
+ *   hist  <- den                 (save & 1, after hist was read)         xsave <- x before this step             (save & 2)
+ *   y      = k_a * known  [+ k_b * knoise, k_b != 0] ;  acc = m * acc + (1 - m) * y                              (mask != NULL)
+ *   x      = acc ;  input as above
+ * fp32, every product and sum rounded on its own, left to right; guidance and guidance rescale combine with every term.  Every access
+ * is elementwise per pixel, so one buffer may be read and overwritten by the same step (hist with r != 0 and save & 1).  A term whose
+ * coefficient is 0 is not read at all.  With these one kernel is every solver of sampler.py: DPM++ 2M (hist = the previous denoised
+ * estimate), Heun (hist / xsave = the first stage's estimate and state), ancestral Euler (noise), and the inpainting blend (the kept
+ * region is carried as k_a * known + k_b * knoise on the noise level the new state lives at).  base.init with the flag writes the input
+ * image only, as without it.  Bad arguments (1, before any launch): r, u or s != 0 or a save bit whose pointer is NULL, mask without
+ * known, k_b != 0 without knoise, a non-finite r, u, s, k_a or k_b, save outside 0..3; and, with or without the flag, any bit of init
+ * other than bit 0 and SDXL_SAMPLER_EXT. */
+typedef struct {
+  sdxl_sampler_step base;
+  float*       hist;    /* [B,4,H,W] fp32: a denoised estimate of an earlier step */
+  float*       xsave;   /* [B,4,H,W] fp32: a state of an earlier step */
+  const float* noise;   /* [B,4,H,W] fp32: this step's standard normal draw */
+  float        r, u, s; /* coefficients of hist, xsave, noise; a term is read iff its coefficient != 0 */
+  int          save;    /* bit 0: hist <- den of this step; bit 1: xsave <- x before this step */
+  const float* mask;    /* [B,H,W] fp32 in [0,1], 1 = generated, 0 = kept; NULL = no blend */
+  const float* known;   /* [B,4,H,W] fp32: the latent to keep */
+  const float* knoise;  /* [B,4,H,W] fp32: the noise the kept region is carried on */
+  float        k_a, k_b;
+} sdxl_sampler_step_ext;
+#define SDXL_SAMPLER_EXT 0x100   /* or-ed into sdxl_sampler_step.init: the struct passed is a sdxl_sampler_step_ext */
 
 /* One micro-batch, all device pointers.  RNG is the caller's: `noise` and `sigma_or_t` are inputs so that
  * fixtures are exact (reference draws them at ddpm_trainer.py:303-304 / flow_matching_trainer.py:298-306). */

@@ -92,6 +92,9 @@ class TrainingConfig:                    # data/config.py:152-168
     validation_guidance_rescale: float = 0.0 # guidance rescale phi in [0, 1]
     validation_weights: Optional[str] = None # "trained" | "ema"; None = "ema" when use_ema, else "trained"
     validation_seed: int = 0             # seed of the validation noise (the same noise at every validation)
+    validation_sampler: str = "euler"    # "euler" | "euler_a" | "dpmpp_2m" | "heun" (sampler.py: euler_a / dpmpp_2m need ddpm, all but euler
+                                         # the "trained" parameterization; checked when the trainer is built)
+    validation_eta: float = 1.0          # euler_a only: the share of each step's noise that is drawn afresh (0 = euler), >= 0
     sampler_parameterization: str = "trained"   # ddpm: "trained" = the denoiser this build's loss trains, "reference" = the
                                          # reference's sample_with_ztsnr as written (inconsistent with its own training; sampler.py)
 

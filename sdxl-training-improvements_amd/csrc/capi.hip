@@ -570,18 +570,33 @@ int sdxl_read_loss(sdxl_handle* h, float out[8], void* stp) {
   return 0;
 }
 
-// sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters
+// sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters.  The caller's struct
+// ends at guidance_rescale unless init carries SDXL_SAMPLER_EXT: nothing behind it is read without the flag.
 static int fill_sampler(const sdxl_sampler_step* s, int image_batch, int HW, SamplerP& q) {
   ARG_CHECK(s->x != nullptr, "sampler: x is NULL");
   ARG_CHECK(!s->cfg || image_batch % 2 == 0, "sampler: cfg needs an even batch [cond; uncond] (got %d)", image_batch);
   const float v[8] = {s->a_skip, s->a_out, s->p, s->q, s->a_in_next, s->clamp, s->guidance, s->guidance_rescale};
   for (int i = 0; i < 8; ++i) ARG_CHECK(isfinite(v[i]), "sampler: scalar %d of (a_skip, a_out, p, q, a_in_next, clamp, guidance, guidance_rescale) is not finite", i);
+  ARG_CHECK((s->init & ~(1 | SDXL_SAMPLER_EXT)) == 0, "sampler: init %d (0 | 1, optionally | SDXL_SAMPLER_EXT)", s->init);
   memset(&q, 0, sizeof(q));
   q.x = s->x;
   q.B = s->cfg ? image_batch / 2 : image_batch; q.HW = HW;
-  q.cfg = s->cfg != 0; q.init = s->init != 0;
+  q.cfg = s->cfg != 0; q.init = (s->init & 1) != 0;
   q.a_skip = s->a_skip; q.a_out = s->a_out; q.p = s->p; q.q = s->q; q.a_in_next = s->a_in_next; q.clamp = s->clamp;
   q.guidance = s->guidance; q.rescale = s->guidance_rescale;
+  if (!(s->init & SDXL_SAMPLER_EXT)) return 0;
+  const sdxl_sampler_step_ext* e = (const sdxl_sampler_step_ext*)s;
+  const float w[5] = {e->r, e->u, e->s, e->k_a, e->k_b};
+  for (int i = 0; i < 5; ++i) ARG_CHECK(isfinite(w[i]), "sampler: scalar %d of (r, u, s, k_a, k_b) is not finite", i);
+  ARG_CHECK(e->save >= 0 && e->save <= 3, "sampler: save %d (bit 0: hist, bit 1: xsave)", e->save);
+  ARG_CHECK(e->hist || (e->r == 0.f && !(e->save & 1)), "sampler: hist is NULL but r != 0 or save bit 0 is set");
+  ARG_CHECK(e->xsave || (e->u == 0.f && !(e->save & 2)), "sampler: xsave is NULL but u != 0 or save bit 1 is set");
+  ARG_CHECK(e->noise || e->s == 0.f, "sampler: noise is NULL but s != 0");
+  ARG_CHECK(!e->mask || e->known, "sampler: mask needs known");
+  ARG_CHECK(e->knoise || e->k_b == 0.f, "sampler: knoise is NULL but k_b != 0");
+  q.ext = 1;
+  q.hist = e->hist; q.xsave = e->xsave; q.noise = e->noise; q.r = e->r; q.u = e->u; q.s = e->s; q.save = e->save;
+  q.mask = e->mask; q.known = e->known; q.knoise = e->knoise; q.k_a = e->k_a; q.k_b = e->k_b;
   return 0;
 }
 
@@ -983,10 +998,12 @@ int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in,
 int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* st) {
   ARG_CHECK(s, "null argument");
   ARG_CHECK(B > 0 && H > 0 && W > 0, "sampler: empty batch");
-  sdxl_sampler_step t = *s;
-  t.x = x;
+  sdxl_sampler_step_ext t;      // the caller's struct as far as its flag says it goes, with x set
+  memset(&t, 0, sizeof(t));
+  memcpy(&t, s, (s->init & SDXL_SAMPLER_EXT) ? sizeof(sdxl_sampler_step_ext) : sizeof(sdxl_sampler_step));
+  t.base.x = x;
   SamplerP q;
-  CHK(fill_sampler(&t, s->cfg ? 2 * B : B, H * W, q));      // B = samples here: the images hold 2B rows of HW with cfg
+  CHK(fill_sampler(&t.base, s->cfg ? 2 * B : B, H * W, q));      // B = samples here: the images hold 2B rows of HW with cfg
   q.pred = (const bf16*)pred; q.x_in = (bf16*)x_in;
   if (!q.init && q.rescale != 0.f) CHK(test_slab(sampler_part_floats(B, H * W), &q.part));
   return launch_sampler_step(q, (hipStream_t)st);

@@ -404,6 +404,17 @@ struct SamplerP {
   int cfg, init;
   float a_skip, a_out, p, q, a_in_next, clamp, guidance, rescale;
   float* part;            // device scratch, sampler_part_floats(B, HW), read only when rescale != 0
+  // ---- the extended step (sdxl_sampler_step_ext); ext = 0: none of these is read and the plain kernel runs ----
+  int ext;
+  float* hist;            // [B][4][HW] fp32: read with r != 0, written (den) with save & 1
+  float* xsave;           // [B][4][HW] fp32: read with u != 0, written (x before the step) with save & 2
+  const float* noise;     // [B][4][HW] fp32: read with s != 0
+  float r, u, s;
+  int save;
+  const float* mask;      // [B][HW] fp32, 1 = generated, 0 = kept; NULL = no blend
+  const float* known;     // [B][4][HW] fp32
+  const float* knoise;    // [B][4][HW] fp32: read with k_b != 0
+  float k_a, k_b;
 };
 static inline size_t sampler_part_floats(int B, int HW) { return 4 * (size_t)B * (((size_t)HW + 255) / 256); }
 int launch_sampler_step(const SamplerP& p, hipStream_t st);

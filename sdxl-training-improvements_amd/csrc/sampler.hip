@@ -7,6 +7,13 @@
 //   x_next  = p * x + q * den
 //   in_next = bf16(clamp(a_in_next * x_next, +-clamp))                              (clamp <= 0: none)
 //
+// The extended step (SamplerP::ext, sdxl_sampler_step_ext) is its own instantiation of the step kernel and widens the solver line to
+//   acc     = p * x + q * den  [+ r * hist] [+ u * xsave] [+ s * noise]                (a term is read iff its coefficient != 0)
+//   hist   <- den (save & 1) ; xsave <- x before the step (save & 2)                   (after hist / xsave were read)
+//   y       = k_a * known [+ k_b * knoise] ; x_next = m * acc + (1 - m) * y            (mask != NULL only; m one value per pixel)
+// with the same rule: every product and sum rounded on its own, left to right.  All of it is elementwise per pixel, so a buffer may be
+// read and overwritten by the same step; the new planes are NCHW fp32 like x (one 256-byte run per wave and channel, one for the mask).
+//
 // fp32 throughout, every product, sum and difference rounded on its own (no FMA contraction) and in exactly the order written above:
 // tests/_sampler_ref.py restates it in separate fp32 torch ops and the kernel is held to it bit for bit.  x is the caller's fp32 NCHW
 // state, updated in place; F_c / F_u are read from, and in_next is written to, token-major [rows][8] bf16 images (the plan's prediction and
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(256) void sampler_stats_kernel(const SamplerP p) {
   if (threadIdx.x < 4) p.part[((long)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = v[threadIdx.x];
 }
 
-template <int RESCALE>
+template <int RESCALE, int EXT>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerP p) {
   __shared__ float sm[4][4];
   const int b = blockIdx.y;
@@ -89,6 +96,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerP p) {
   if (hw >= p.HW) return;
   const long ic = ((long)b * p.HW + hw) * 8, iu = ((long)(p.B + b) * p.HW + hw) * 8;
   bf16x8 fc = {}, fu = {}, o;
+  float m = 1.f;
+  if (EXT && p.mask && !p.init) m = p.mask[(long)b * p.HW + hw];
   if (!p.init) {
     fc = *(const bf16x8*)(p.pred + ic);
     fu = fc;
@@ -109,7 +118,23 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerP p) {
       const float d1 = p.a_skip * x, d2 = p.a_out * f;
       const float den = d1 + d2;
       const float u1 = p.p * x, u2 = p.q * den;
-      x = u1 + u2;
+      if (EXT) {
+        float acc = u1 + u2;
+        if (p.r != 0.f) { const float t = p.r * p.hist[idx]; acc = acc + t; }
+        if (p.u != 0.f) { const float t = p.u * p.xsave[idx]; acc = acc + t; }
+        if (p.s != 0.f) { const float t = p.s * p.noise[idx]; acc = acc + t; }
+        if (p.save & 1) p.hist[idx] = den;
+        if (p.save & 2) p.xsave[idx] = x;
+        if (p.mask) {
+          float y = p.k_a * p.known[idx];
+          if (p.k_b != 0.f) { const float t = p.k_b * p.knoise[idx]; y = y + t; }
+          const float t1 = m * acc, t2 = (1.f - m) * y;
+          acc = t1 + t2;
+        }
+        x = acc;
+      } else {
+        x = u1 + u2;
+      }
       p.x[idx] = x;
     }
     float v = p.a_in_next * x;
@@ -127,11 +152,13 @@ int launch_sampler_step(const SamplerP& p, hipStream_t st) {
   const bool rescale = !p.init && p.rescale != 0.f;
   ARG_CHECK(!rescale || p.part, "sampler: guidance rescale needs the partial-row scratch (sampler_part_floats)");
   const dim3 grid(cdiv(p.HW, 256), p.B), block(256);
-  if (rescale) {
-    hipLaunchKernelGGL(sampler_stats_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(sampler_step_kernel<1>, grid, block, 0, st, p);
+  if (rescale) hipLaunchKernelGGL(sampler_stats_kernel, grid, block, 0, st, p);
+  if (p.ext && !p.init) {      // (init writes the input image only: the plain kernel)
+    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 1>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((sampler_step_kernel<0, 1>), grid, block, 0, st, p);
   } else {
-    hipLaunchKernelGGL(sampler_step_kernel<0>, grid, block, 0, st, p);
+    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 0>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((sampler_step_kernel<0, 0>), grid, block, 0, st, p);
   }
   HIP_CHECK_RET(hipGetLastError());
   return 0;

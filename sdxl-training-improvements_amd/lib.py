@@ -59,6 +59,17 @@ class SamplerStep(C.Structure):
                 ("a_in_next", C.c_float), ("clamp", C.c_float), ("guidance", C.c_float), ("guidance_rescale", C.c_float)]
 
 
+SAMPLER_EXT = 0x100   # SDXL_SAMPLER_EXT, or-ed into SamplerStep.init: the struct passed is a SamplerStepExt
+
+
+class SamplerStepExt(SamplerStep):
+    """sdxl_sampler_step_ext: SamplerStep (what every caller of the plain step passes) + the fields the library reads only when init
+    carries SAMPLER_EXT: the terms of the second-order and ancestral solvers and the inpainting blend (include/sdxlstep.h)"""
+    _fields_ = [("hist", C.c_void_p), ("xsave", C.c_void_p), ("noise", C.c_void_p),
+                ("r", C.c_float), ("u", C.c_float), ("s", C.c_float), ("save", C.c_int),
+                ("mask", C.c_void_p), ("known", C.c_void_p), ("knoise", C.c_void_p), ("k_a", C.c_float), ("k_b", C.c_float)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("ctx_len", C.c_int),
                 ("latents", C.c_void_p), ("noise", C.c_void_p), ("sigma_or_t", C.c_void_p),

@@ -39,6 +39,31 @@ flow_matching -- the model predicts the velocity x1 - x0 at x_t = (1 - t) x0 + t
 q = t_{j+1} - t_j on t_j = j / N, a_in = 1, the state starts as the noise x0 and t is the time input (rounded to bf16 where training
 rounds it).
 
+Solvers.  The extended step (sdxl_sampler_step_ext) adds three optional terms and two optional saves to the solver line,
+
+    x_next = p * x + q * den [+ r * hist] [+ u * xsave] [+ s * noise] ;  hist <- den (save & 1) ;  xsave <- x (save & 2)
+
+and `solver_steps` expands a schedule into one such step per forward.  With sigma this forward's level, sigma' the next one's and
+p = sigma' / sigma (doubles on the host):
+
+    euler     as above: one forward per grid point, nothing new is read
+    euler_a   ancestral Euler (k-diffusion's sample_euler_ancestral): sigma_up = min(sigma', eta sqrt(sigma'^2 (sigma^2 - sigma'^2) / sigma^2)),
+              sigma_down = sqrt(sigma'^2 - sigma_up^2); p = sigma_down / sigma, q = 1 - p, s = sigma_up on a fresh normal draw per step;
+              the last step (to 0) is Euler, eta = 0 is Euler
+    dpmpp_2m  k-diffusion's sample_dpmpp_2m: h = ln sigma - ln sigma', rho = h_prev / h, q = (1 - p) (1 + 1 / (2 rho)),
+              r = -(1 - p) / (2 rho) on hist = the previous step's den; every step saves its den; the first and the last are Euler
+    heun      two forwards per interval.  A: the Euler step, saving den_A and x.  B: a forward on the predicted state at the NEXT grid
+              point (its time input and scalings), then with c = (sigma' - sigma) / 2: p = c / sigma', q = -c / sigma', r = -c / sigma,
+              u = 1 + c / sigma, i.e. x + c ((x - den_A) / sigma + (x~ - den_B) / sigma').  Flow matching, dt = t' - t: A is Euler,
+              B has p = 0, q = dt / 2, r = dt / 2, u = 1.  The last interval is one Euler step.
+
+euler_a and dpmpp_2m are defined on the ddpm sigma, heun on it and on flow matching; all need the "trained" parameterization (the
+reference's set puts each forward one grid point behind its step).  Anything else raises ValueError.
+
+img2img starts from `init_latents` noised to the grid point the run begins at and runs the last round(strength N) of the N grid points;
+inpainting (`inpaint_mask`, 1 = generate, 0 = keep) blends every step's result with the known latent carried to the level the new state
+lives at, x = m x + (1 - m) (k_a known + k_b n): ddpm k_a = 1, k_b = that sigma; flow k_a = t', k_b = 1 - t'; n is the initial noise.
+
 VAE decode and text encoding are the caller's, as all preconditioning is."""
 from __future__ import annotations
 
@@ -52,6 +77,7 @@ from .scheduler import NoiseScheduler
 METHODS = ("ddpm", "flow_matching")
 PREDICTION_TYPES = ("epsilon", "v_prediction")
 PARAMETERIZATIONS = ("trained", "reference")
+SOLVERS = ("euler", "euler_a", "dpmpp_2m", "heun")
 
 Step = Tuple[float, float, float, float, float, float, float]      # (a_in, a_skip, a_out, p, q, clamp, timestep)
 
@@ -138,6 +164,96 @@ def kernel_steps(steps: Sequence[Step], guidance_scale: float, guidance_rescale:
     return out
 
 
+def check_solver(solver: str, method: str, parameterization: str = "trained") -> str:
+    """the solver's name, or ValueError naming the solver and the method it cannot run on"""
+    solver = str(solver).lower()
+    if solver not in SOLVERS:
+        raise ValueError(f"solver: unknown value {solver!r} (expected one of {', '.join(SOLVERS)})")
+    if solver != "euler" and method == "ddpm" and parameterization != "trained":
+        raise ValueError(f"solver {solver!r} needs method ddpm's 'trained' parameterization (got {parameterization!r}: only euler runs it)")
+    if solver in ("euler_a", "dpmpp_2m") and method != "ddpm":
+        raise ValueError(f"solver {solver!r} is defined on the ddpm sigma: method {method!r} cannot run it (euler or heun can)")
+    return solver
+
+
+def ancestral_sigmas(sigma: float, sigma_next: float, eta: float = 1.0) -> Tuple[float, float]:
+    """(sigma_down, sigma_up) of an ancestral step: sigma_down^2 + sigma_up^2 = sigma_next^2 (k-diffusion's get_ancestral_step)"""
+    up = min(sigma_next, eta * math.sqrt(sigma_next * sigma_next * (sigma * sigma - sigma_next * sigma_next) / (sigma * sigma)))
+    return math.sqrt(sigma_next * sigma_next - up * up), up
+
+
+def solver_steps(steps: Sequence[Step], grid: Sequence[float], method: str = "ddpm", solver: str = "euler", eta: float = 1.0,
+                 guidance_scale: float = 1.0, guidance_rescale: float = 0.0, cfg: bool = False, inpaint: bool = False,
+                 parameterization: str = "trained"):
+    """(kernel dictionaries, time inputs, levels), one entry per FORWARD: `steps` (a parameter set, one entry per grid point) expanded
+    by `solver`.  `grid` holds the levels the parameter set was built on: the sigmas of `steps` for ddpm, the len(steps) + 1 times
+    for flow matching.  A dictionary holds kernel_steps' keys and, only where a solver needs them, the non-zero scalars of
+    sdxl_sampler_step_ext (r, u, s, save) -- euler's are kernel_steps' own -- plus k_a, k_b with `inpaint`.  levels[f] is the sigma
+    (ddpm) or t (flow) the state forward f runs on lives at."""
+    solver = check_solver(solver, method, parameterization)
+    if not float(eta) >= 0.0 or not math.isfinite(float(eta)):
+        raise ValueError(f"eta must be a finite number >= 0 (got {eta})")
+    flow = method == "flow_matching"
+    lv = [float(g) for g in grid]
+    n = len(steps)
+    if len(lv) != (n + 1 if flow else n):
+        raise ValueError(f"solver_steps: {n} steps need {n + 1 if flow else n} grid values for {method} (got {len(lv)})")
+    if inpaint and not flow and parameterization != "trained":
+        raise ValueError("inpainting needs the 'trained' parameterization (the reference's set runs each forward one grid point behind)")
+    nxt = (lambda j: lv[j + 1]) if flow else (lambda j: lv[j + 1] if j + 1 < n else 0.0)
+    fw = []      # per forward: (index into steps of the input scaling / time input / denoiser, p, q, extras, level, level after)
+    h_prev = None
+    for j in range(n):
+        a, b = lv[j], nxt(j)
+        p, q = steps[j][3], steps[j][4]
+        last = j + 1 == n
+        if solver == "euler_a" and not last:
+            down, up = ancestral_sigmas(a, b, float(eta))
+            p = down / a
+            fw.append((j, p, 1.0 - p, dict(s=up), a, b))
+        elif solver == "dpmpp_2m":
+            ex = dict(save=1)
+            if not last:
+                h = math.log(a) - math.log(b)
+                if h_prev is not None:
+                    rho = h_prev / h
+                    q, ex = (1.0 - p) * (1.0 + 1.0 / (2.0 * rho)), dict(r=-(1.0 - p) / (2.0 * rho), save=1)
+                h_prev = h
+            fw.append((j, p, q, ex, a, b))
+        elif solver == "heun" and not last:
+            fw.append((j, p, q, dict(save=3), a, b))
+            if flow:
+                dt = b - a
+                fw.append((j + 1, 0.0, dt / 2.0, dict(r=dt / 2.0, u=1.0), b, b))
+            else:
+                c = (b - a) / 2.0
+                fw.append((j + 1, c / b, -c / b, dict(r=-c / a, u=1.0 + c / a), b, b))
+        else:
+            fw.append((j, p, q, {}, a, b))
+    ks = []
+    for f, (j, p, q, ex, _lv, after) in enumerate(fw):
+        a_in_next, clamp_next = (steps[fw[f + 1][0]][0], steps[fw[f + 1][0]][5]) if f + 1 < len(fw) else (1.0, 0.0)
+        k = dict(cfg=int(cfg), init=0, a_skip=steps[j][1], a_out=steps[j][2], p=p, q=q, a_in_next=a_in_next, clamp=clamp_next,
+                 guidance=float(guidance_scale) if cfg else 1.0, guidance_rescale=float(guidance_rescale))
+        k.update({key: v for key, v in ex.items() if v != 0})
+        if inpaint:
+            k.update(dict(k_a=after, k_b=1.0 - after) if flow else dict(k_a=1.0, k_b=after))
+        ks.append(k)
+    return ks, [steps[j][6] for j, *_ in fw], [f[4] for f in fw]
+
+
+def blend_known(x: torch.Tensor, mask: torch.Tensor, known: torch.Tensor, knoise: torch.Tensor, k_a: float, k_b: float) -> torch.Tensor:
+    """the inpainting blend of the step kernel in separate fp32 torch ops (the start state's): m x + (1 - m) (k_a known + k_b knoise),
+    mask [B,1,H,W]"""
+    c = lambda v: torch.tensor(float(v), dtype=torch.float32)
+    y = c(k_a) * known
+    if float(k_b) != 0.0:
+        y = y + c(k_b) * knoise
+    t1 = mask * x
+    t2 = (c(1.0) - mask) * y
+    return t1 + t2
+
+
 class NativeSampler:
     """sample(...) -> latents [B,4,H,W] fp32 on the device.  `unet` is a NativeUNet (its bound weight arena is what is sampled)."""
 
@@ -158,12 +274,17 @@ class NativeSampler:
         self.table = NoiseScheduler(config, "cpu").sigmas                 # the training table (fp32)
 
     # ------------------------------------------------------------------ the schedule
-    def schedule(self, num_steps: int, sigmas=None, timesteps=None) -> Tuple[float, List[Step]]:
-        """(scale of the initial noise, steps) of this sampler; explicit `sigmas` / `timesteps` override the default grid"""
+    def grid(self, num_steps: int, sigmas=None, timesteps=None) -> Tuple[List[float], Optional[List[float]]]:
+        """(levels, time inputs) the schedule is built on: ddpm the sigmas of the forwards and their time inputs; flow matching the
+        num_steps + 1 times (their time inputs are the times themselves: None)"""
         if self.method == "flow_matching":
             if sigmas is not None:
                 raise ValueError("flow matching has no sigmas: pass the grid as timesteps")
-            return flow_steps(num_steps, None if timesteps is None else [float(t) for t in timesteps], self.t_bf16)
+            if timesteps is not None:
+                return [float(t) for t in timesteps], None
+            if int(num_steps) < 1:
+                raise ValueError(f"num_steps must be >= 1 for flow matching (got {num_steps})")
+            return [j / int(num_steps) for j in range(int(num_steps) + 1)], None
         if sigmas is None:
             idx = ddpm_indices(num_steps, self.table.numel()) if timesteps is None else [int(t) for t in timesteps]
             sig = [float(self.table[i]) for i in idx]
@@ -171,9 +292,16 @@ class NativeSampler:
         else:
             sig = [float(s) for s in sigmas]
             ts = [float(t) for t in timesteps] if timesteps is not None else [float(i) for i in nearest_indices(self.table, sig)]
+        return sig, ts
+
+    def schedule(self, num_steps: int, sigmas=None, timesteps=None) -> Tuple[float, List[Step]]:
+        """(scale of the initial noise, steps) of this sampler; explicit `sigmas` / `timesteps` override the default grid"""
+        lv, ts = self.grid(num_steps, sigmas, timesteps)
+        if self.method == "flow_matching":
+            return flow_steps(num_steps, None if timesteps is None else lv, self.t_bf16)
         if self.parameterization == "reference":
-            return ddpm_reference_steps(sig, ts)
-        return ddpm_trained_steps(sig, ts, self.prediction_type, self.use_ztsnr)
+            return ddpm_reference_steps(lv, ts)
+        return ddpm_trained_steps(lv, ts, self.prediction_type, self.use_ztsnr)
 
     @staticmethod
     def plan_batch(B: int, guidance_scale: float) -> int:
@@ -184,25 +312,50 @@ class NativeSampler:
     def sample(self, prompt_embeds, pooled, time_ids, neg_prompt_embeds=None, neg_pooled=None, neg_time_ids=None, *,
                height: int, width: int, num_steps: int, guidance_scale: float = 1.0, guidance_rescale: float = 0.0,
                generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None, sigmas=None,
-               timesteps=None) -> torch.Tensor:
+               timesteps=None, solver: str = "euler", eta: float = 1.0, step_noise: Optional[torch.Tensor] = None,
+               init_latents: Optional[torch.Tensor] = None, strength: float = 1.0,
+               inpaint_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """height / width are the latent's.  Negative conditioning that is missing with guidance_scale != 1 is zeros of the same
         shape (neg_time_ids: the positive ones).  `noise` [B,4,H,W] overrides the draw from `generator` (CPU, as in training).  The
-        loop enqueues every forward and step without a host synchronisation; the result is stream-ordered."""
+        loop enqueues every forward and step without a host synchronisation; the result is stream-ordered.
+
+        `solver`: SOLVERS (the module docstring).  euler_a draws one [B,4,H,W] normal tensor per stochastic step, all of them as one
+        torch.randn((n,B,4,H,W)) from `generator` behind the initial noise; `step_noise` [n,B,4,H,W] overrides that draw.
+        `init_latents` [B,4,H,W] with 0 < strength <= 1 (img2img) runs the last max(1, round(strength N)) of the N grid points from
+        init + sigma_start n (ddpm) or (1 - t_start) n + t_start init (flow); strength = 1 is pure noise, the call without
+        init_latents.  `inpaint_mask` [B,H,W] or [B,1,H,W] in [0,1] (1 = generate, 0 = keep) needs init_latents, the latent kept."""
         net = self.unet
         dev = net.device
         B = int(prompt_embeds.shape[0])
         H, W = int(height), int(width)
         if not 0.0 <= float(guidance_rescale) <= 1.0:
             raise ValueError(f"guidance_rescale must be in [0, 1] (got {guidance_rescale})")
+        solver = check_solver(solver, self.method, self.parameterization)
         cfg = float(guidance_scale) != 1.0
         x0_scale, steps = self.schedule(num_steps, sigmas, timesteps)
+        first, mask, known = self._start(len(steps), B, H, W, init_latents, strength, inpaint_mask)
+        plain = solver == "euler" and known is None              # today's sampler: today's calls
+        if not plain:
+            lv, _ts = self.grid(num_steps, sigmas, timesteps)
+            steps, lv = steps[first:], lv[first:]
+            ks, tin, _levels = solver_steps(steps, lv, self.method, solver, eta, guidance_scale, guidance_rescale, cfg,
+                                            mask is not None, self.parameterization)
         if noise is None:
             noise = torch.randn((B, 4, H, W), generator=generator)
         if tuple(noise.shape) != (B, 4, H, W):
             raise ValueError(f"noise: expected shape {(B, 4, H, W)}, got {tuple(noise.shape)}")
         x = noise.to(torch.float32)
-        if x0_scale != 1.0:
-            x = torch.tensor(x0_scale, dtype=torch.float32, device=x.device) * x     # sigma_0 * n: one fp32 product where the noise lives, before the loop
+        if plain or known is None or first == 0:
+            if x0_scale != 1.0:
+                x = torch.tensor(x0_scale, dtype=torch.float32, device=x.device) * x     # sigma_0 * n: one fp32 product where the noise lives, before the loop
+        elif self.method == "flow_matching":                                             # img2img: the known latent noised to the first grid point run
+            c = lambda v: torch.tensor(v, dtype=torch.float32, device=x.device)
+            x = c(1.0 - lv[0]) * x + c(lv[0]) * known.to(x.device)
+        else:
+            x = known.to(x.device) + torch.tensor(lv[0], dtype=torch.float32, device=x.device) * x
+        if not plain and mask is not None:
+            k_a, k_b = (lv[0], 1.0 - lv[0]) if self.method == "flow_matching" else (1.0, lv[0])
+            x = blend_known(x, mask.to(x.device), known.to(x.device), noise.to(torch.float32), k_a, k_b)
         x = x.to(dev).contiguous()
         if x.data_ptr() == noise.data_ptr():
             x = x.clone()                                                             # the state is updated in place: never the caller's tensor
@@ -215,10 +368,65 @@ class NativeSampler:
             nti = ti if neg_time_ids is None else neg_time_ids.to(dev, torch.float32).reshape(B, 6)
             pe, po, ti = torch.cat([pe, npe]), torch.cat([po, npo]), torch.cat([ti, nti])
         PB = self.plan_batch(B, guidance_scale)
-        # the time inputs of all forwards, uploaded once: row j is forward j's [PB] values
-        tall = torch.tensor([[s[6]] * PB for s in steps], dtype=torch.float32).to(dev)
-        ks = kernel_steps(steps, guidance_scale, guidance_rescale, cfg)
+        if plain:
+            # the time inputs of all forwards, uploaded once: row j is forward j's [PB] values
+            tall = torch.tensor([[s[6]] * PB for s in steps], dtype=torch.float32).to(dev)
+            ks = kernel_steps(steps, guidance_scale, guidance_rescale, cfg)
+            net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5])
+            for j, k in enumerate(ks):
+                net.sample_step(x, pe, po, ti, tall[j], **k)
+            return x
+        # every buffer of the extended steps is made and uploaded here, before the loop: no torch op runs between forwards
+        tall = torch.tensor([[t] * PB for t in tin], dtype=torch.float32).to(dev)
+        need = lambda key, bit: any(k.get(key, 0) != 0 or k.get("save", 0) & bit for k in ks)
+        hist = torch.zeros_like(x) if need("r", 1) else None
+        xsave = torch.zeros_like(x) if need("u", 2) else None
+        nstoch = sum(1 for k in ks if k.get("s", 0) != 0)
+        draws = None
+        if nstoch:
+            if step_noise is None:
+                step_noise = torch.randn((nstoch, B, 4, H, W), generator=generator)
+            if tuple(step_noise.shape) != (nstoch, B, 4, H, W):
+                raise ValueError(f"step_noise: expected shape {(nstoch, B, 4, H, W)}, got {tuple(step_noise.shape)}")
+            draws = step_noise.to(dev, torch.float32).contiguous()
+        blend = {}
+        if mask is not None:
+            blend = dict(mask=mask.to(dev).contiguous(), known=known.to(dev).contiguous(),
+                         knoise=noise.to(torch.float32).to(dev).contiguous())
         net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5])
-        for j, k in enumerate(ks):
-            net.sample_step(x, pe, po, ti, tall[j], **k)
+        d = 0
+        for f, k in enumerate(ks):
+            ex = dict(blend)
+            if k.get("r", 0) != 0 or k.get("save", 0) & 1:
+                ex["hist"] = hist
+            if k.get("u", 0) != 0 or k.get("save", 0) & 2:
+                ex["xsave"] = xsave
+            if k.get("s", 0) != 0:
+                ex["noise"], d = draws[d], d + 1
+            net.sample_step(x, pe, po, ti, tall[f], **k, **ex)
         return x
+
+    def _start(self, n: int, B: int, H: int, W: int, init_latents, strength, inpaint_mask):
+        """(index of the first grid point run, mask [B,1,H,W] fp32 or None, known latent fp32 or None) of an img2img / inpainting call"""
+        if inpaint_mask is not None and init_latents is None:
+            raise ValueError("inpaint_mask needs init_latents (the latent that is kept where the mask is 0)")
+        if init_latents is None:
+            if float(strength) != 1.0:
+                raise ValueError(f"strength = {strength} needs init_latents")
+            return 0, None, None
+        if self.method == "ddpm" and self.parameterization != "trained":
+            raise ValueError("init_latents needs the 'trained' parameterization (the reference's set starts from the noise alone)")
+        if tuple(init_latents.shape) != (B, 4, H, W):
+            raise ValueError(f"init_latents: expected shape {(B, 4, H, W)}, got {tuple(init_latents.shape)}")
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"strength must be in (0, 1] (got {strength})")
+        run = max(1, int(math.floor(float(strength) * n + 0.5)))
+        known = init_latents.detach().to("cpu", torch.float32).contiguous()
+        mask = None
+        if inpaint_mask is not None:
+            if tuple(inpaint_mask.shape) not in ((B, H, W), (B, 1, H, W)):
+                raise ValueError(f"inpaint_mask: expected shape {(B, H, W)} or {(B, 1, H, W)}, got {tuple(inpaint_mask.shape)}")
+            mask = inpaint_mask.detach().to("cpu", torch.float32).reshape(B, 1, H, W).contiguous()
+            if not bool(torch.isfinite(mask).all()) or float(mask.min()) < 0.0 or float(mask.max()) > 1.0:
+                raise ValueError("inpaint_mask: values must be finite and in [0, 1]")
+        return n - run, mask, known

@@ -45,7 +45,7 @@ from . import lib
 from .config import Config
 from .ema import WeightEMA
 from .optimizer import BY_TYPE, AdamWBF16, FusedArenaOptimizer
-from .sampler import PARAMETERIZATIONS, NativeSampler
+from .sampler import PARAMETERIZATIONS, SOLVERS, NativeSampler, check_solver
 from .scheduler import NoiseScheduler
 from .unet import NativeUNet, config_from_unet, loss_mask_bhw
 
@@ -200,6 +200,17 @@ class NativeSDXLTrainer:
         seed = getattr(tc, "validation_seed", 0)
         if isinstance(seed, bool) or not isinstance(seed, int):
             raise ValueError(f"training.validation_seed must be an integer (got {seed!r})")
+        self.validation_sampler = str(getattr(tc, "validation_sampler", "euler")).lower()
+        if self.validation_sampler not in SOLVERS:
+            raise ValueError(f"training.validation_sampler: unknown value {getattr(tc, 'validation_sampler')!r} "
+                             f"(expected one of {', '.join(SOLVERS)})")
+        try:
+            check_solver(self.validation_sampler, self.method, self.sampler_parameterization)
+        except ValueError as e:
+            raise ValueError(f"training.validation_sampler: {e}") from None
+        eta = getattr(tc, "validation_eta", 1.0)
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not math.isfinite(float(eta)) or float(eta) < 0.0:
+            raise ValueError(f"training.validation_eta must be a finite number >= 0 (got {eta!r})")
 
     # -------------------------------------------------------------------------------- sampling / evaluation on either weight set
     @contextmanager
@@ -235,9 +246,11 @@ class NativeSDXLTrainer:
     def sample(self, prompt_embeds, pooled, time_ids, neg_prompt_embeds=None, neg_pooled=None, neg_time_ids=None, *, height: int,
                width: int, num_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
                guidance_rescale: Optional[float] = None, generator: Optional[torch.Generator] = None, noise=None, sigmas=None,
-               timesteps=None, weights: Optional[str] = None) -> torch.Tensor:
+               timesteps=None, weights: Optional[str] = None, solver: Optional[str] = None, eta: Optional[float] = None,
+               step_noise=None, init_latents=None, strength: float = 1.0, inpaint_mask=None) -> torch.Tensor:
         """Latents [B,4,height,width] fp32 on the device, sampled natively (sampler.py::NativeSampler) from the trained weights or
-        the EMA; what is not given comes from the training.validation_* keys.  Decoding is the caller's.  Nothing of the training
+        the EMA; what is not given comes from the training.validation_* keys (solver / eta: validation_sampler / validation_eta;
+        step_noise, init_latents, strength and inpaint_mask are NativeSampler.sample's).  Decoding is the caller's.  Nothing of the training
         state changes: the next step has the bits it would have had without the call."""
         tc = self.config.training
         sampler = NativeSampler(self.net, self.method, str(tc.prediction_type), bool(self.config.model.use_ztsnr),
@@ -247,11 +260,15 @@ class NativeSDXLTrainer:
                                   width=width, num_steps=int(tc.validation_num_steps if num_steps is None else num_steps),
                                   guidance_scale=float(tc.validation_guidance_scale if guidance_scale is None else guidance_scale),
                                   guidance_rescale=float(tc.validation_guidance_rescale if guidance_rescale is None else guidance_rescale),
-                                  generator=generator, noise=noise, sigmas=sigmas, timesteps=timesteps)
+                                  generator=generator, noise=noise, sigmas=sigmas, timesteps=timesteps,
+                                  solver=self.validation_sampler if solver is None else solver,
+                                  eta=float(getattr(tc, "validation_eta", 1.0) if eta is None else eta), step_noise=step_noise,
+                                  init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask)
 
     def validate(self, step: int, validation_batches, on_validation=None):
         """sample every conditioning batch of `validation_batches` (dicts with "prompt_embeds", "pooled_prompt_embeds", "time_ids",
-        optional "neg_prompt_embeds" / "neg_pooled_prompt_embeds" / "neg_time_ids", "height" / "width" of the latent or a
+        optional "neg_prompt_embeds" / "neg_pooled_prompt_embeds" / "neg_time_ids", "init_latents" / "strength" / "inpaint_mask" (img2img /
+        inpainting, NativeSampler.sample), "height" / "width" of the latent or a
         "vae_latents" whose shape gives them) with the training.validation_* keys and the noise of validation_seed; returns the list of
         latents and hands each to on_validation(step, latents).  COLLECTIVE under ZeRO-1 with the EMA (prepare_checkpoint)."""
         if self.validation_weights == "ema":
@@ -264,7 +281,9 @@ class NativeSDXLTrainer:
             else:
                 h, w = (int(v) for v in b["vae_latents"].shape[-2:])
             lat = self.sample(b["prompt_embeds"], b["pooled_prompt_embeds"], b["time_ids"], b.get("neg_prompt_embeds"),
-                              b.get("neg_pooled_prompt_embeds"), b.get("neg_time_ids"), height=h, width=w, generator=gen)
+                              b.get("neg_pooled_prompt_embeds"), b.get("neg_time_ids"), height=h, width=w, generator=gen,
+                              init_latents=b.get("init_latents"), strength=float(b.get("strength", 1.0)),
+                              inpaint_mask=b.get("inpaint_mask"))
             outs.append(lat)
             if on_validation is not None:
                 on_validation(step, lat)

@@ -352,25 +352,27 @@ class NativeUNet:
         return out8[:, :4].float().reshape(B, H, W, 4).permute(0, 3, 1, 2).contiguous()
 
     # ------------------------------------------------------------------ sampling (sampler.py drives these)
-    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str) -> None:
+    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str, planes=()) -> None:
         """sdxl_unet_forward with sdxl_batch.sampler set.  Every tensor is already on the device in the library's dtype and
         contiguous (checked, not converted: no torch arithmetic or copy runs here); the plan's batch is prompt_embeds' (B, or
-        2B = [cond; uncond] with cfg), x is [B,4,H,W] fp32."""
+        2B = [cond; uncond] with cfg), x is [B,4,H,W] fp32.  `planes`: (name, tensor, elements) of an extended step's buffers."""
         PB, ctx = int(prompt_embeds.shape[0]), int(prompt_embeds.shape[1])
         B, _c, H, W = x.shape
         for t, dt, n, name in ((x, torch.float32, B * 4 * H * W, "x"), (prompt_embeds, torch.bfloat16, None, "prompt_embeds"),
                                (pooled, torch.bfloat16, None, "pooled"), (time_ids, torch.float32, PB * 6, "time_ids"),
-                               (timestep, torch.float32, PB, "timestep")):
+                               (timestep, torch.float32, PB, "timestep")) + tuple((t, torch.float32, n, name) for name, t, n in planes):
             if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or (n is not None and t.numel() != n):
                 raise ValueError(f"{what}: {name} must be a contiguous {dt} device tensor" + (f" of {n} elements" if n is not None else ""))
         if _c != 4 or PB != (2 * B if step.cfg else B) or pooled.shape[0] != PB:
             raise ValueError(f"{what}: x {tuple(x.shape)} does not fit a conditioning batch of {PB} with cfg = {step.cfg}")
         self.plan(PB, H, W, ctx)
-        self._keep = [x, prompt_embeds, pooled, time_ids, timestep]
+        self._keep = [x, prompt_embeds, pooled, time_ids, timestep] + [t for _n, t, _e in planes]
         step.x = x.data_ptr()
+        for name, t, _e in planes:
+            setattr(step, name, t.data_ptr())
         b = lib.SamplerBatch(PB, H, W, ctx, None, None, None, timestep.data_ptr(), prompt_embeds.data_ptr(), pooled.data_ptr(),
                              time_ids.data_ptr(), None)
-        b.sampler = C.pointer(step)
+        b.sampler = C.cast(C.pointer(step), C.POINTER(lib.SamplerStep))      # (a SamplerStepExt goes through the same pointer)
         lib.check(self.L.sdxl_unet_forward(self.h, None, C.byref(b), None, _stream()), what)
 
     def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0) -> None:
@@ -379,12 +381,24 @@ class NativeUNet:
         self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init")
 
     def sample_step(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg, a_skip, a_out, p, q, a_in_next=1.0, clamp=0.0,
-                    guidance=1.0, guidance_rescale=0.0, init=0) -> None:
+                    guidance=1.0, guidance_rescale=0.0, init=0, hist=None, xsave=None, noise=None, r=0.0, u=0.0, s=0.0, save=0,
+                    mask=None, known=None, knoise=None, k_a=0.0, k_b=0.0) -> None:
         """one forward on the plan's input buffer + the fused sampler step (include/sdxlstep.h sdxl_sampler_step): x is updated in
-        place and the next input is left in the plan; stream-ordered, no synchronisation"""
-        s = lib.SamplerStep(None, int(cfg), int(init), float(a_skip), float(a_out), float(p), float(q), float(a_in_next),
-                            float(clamp), float(guidance), float(guidance_rescale))
-        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_step")
+        place and the next input is left in the plan; stream-ordered, no synchronisation.  hist ... k_b are the fields of
+        sdxl_sampler_step_ext ([B,4,H,W] fp32 device tensors, mask [B,H,W]); the extended struct and its flag are passed only when
+        one of them is given, otherwise the call is the plain step's."""
+        base = (None, int(cfg), int(init), float(a_skip), float(a_out), float(p), float(q), float(a_in_next), float(clamp),
+                float(guidance), float(guidance_rescale))
+        tensors = (("hist", hist), ("xsave", xsave), ("noise", noise), ("mask", mask), ("known", known), ("knoise", knoise))
+        if all(t is None for _n, t in tensors) and not any((r, u, s, save, k_a, k_b)):
+            self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, lib.SamplerStep(*base), "sample_step")
+            return
+        st = lib.SamplerStepExt(*base)
+        st.init |= lib.SAMPLER_EXT
+        st.r, st.u, st.s, st.save, st.k_a, st.k_b = float(r), float(u), float(s), int(save), float(k_a), float(k_b)
+        n = x.numel()
+        planes = tuple((name, t, n // 4 if name == "mask" else n) for name, t in tensors if t is not None)
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, st, "sample_step", planes)
 
     def unet_backward(self, dpred_nchw: torch.Tensor, first_micro: bool = True) -> None:
         B, Cc, H, W = dpred_nchw.shape
