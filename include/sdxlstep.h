@@ -154,6 +154,27 @@ typedef struct {
   const sdxl_sampler_step* sampler;
 } sdxl_batch;
 
+/* The batch with conditioning gradients: sdxl_batch with two output pointers appended behind `sampler` (`base` IS that struct, so the
+ * layout is the one of a struct with the fields appended).  Passed as a sdxl_batch* with SDXL_BATCH_EXT or-ed into base.ctx_len; nothing
+ * behind `sampler` is read without the flag, so a caller without it may keep passing the struct that ends at `sampler`
+ * (sdxl_unet_forward) or at `per_sample_loss` (every other entry point).
+ * sdxl_forward_loss, sdxl_loss_fwd_bwd and sdxl_unet_forward (without `sampler`) read the two pointers and remember the request for
+ * that micro-step; the backward of that micro-step writes them, stream-ordered, by the time its last-executed segment returns
+ * (sdxl_backward_segment(num_segments - 1), the segment that holds the K | V projection executed last; sdxl_backward_all;
+ * sdxl_loss_fwd_bwd; sdxl_unet_backward).  The value is the gradient of grad_scale x loss with respect to prompt_embeds / pooled as the
+ * UNet read them (bf16), in fp32: the same scale and gradient gate as that micro-step's parameter gradients (a closed gate gives exact
+ * zeros; sdxl_unet_backward: of <dpred, pred>, no scale, no gate), summed in fp32 in a fixed order, bitwise reproducible.  Always
+ * OVERWRITTEN, never accumulated: first_micro does not matter.  Either pointer alone is valid; either together with `sampler` is a bad
+ * argument (1, before any launch).  The caller keeps the buffers alive until that backward has been enqueued.  In graph mode which of
+ * the two is present is part of the capture key and the values leave through the plan's buffers by a copy behind the replay, so the
+ * buffers may move between steps.  Exchanging the gradients of a text encoder across ranks is the caller's (DDP on its own modules). */
+typedef struct {
+  sdxl_batch base;
+  float* d_prompt_embeds;      /* optional OUT [B,ctx_len,cross_attention_dim] fp32; NULL = none */
+  float* d_pooled;             /* optional OUT [B,pooled_dim] fp32; NULL = none */
+} sdxl_batch_ext;
+#define SDXL_BATCH_EXT 0x10000   /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_ext */
+
 SDXL_API const char* sdxl_last_error(void);
 SDXL_API int sdxl_version(void);
 
@@ -227,7 +248,8 @@ SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
  * of a loop.  cfg with an odd plan batch, x == NULL or a non-finite scalar is a bad argument (1), reported before any launch.  The sampler
  * path always launches kernel by kernel, also in graph mode. */
 SDXL_API int sdxl_unet_forward(sdxl_handle* h, const void* sample_nhwc8, const sdxl_batch* cond, void* pred_nhwc8, void* stream);
-/* d(pred) in -> runs every backward segment; d(sample) is not produced (inputs carry no gradient) */
+/* d(pred) in -> runs every backward segment; d(sample) is not produced.  The conditioning gradients are, when the preceding
+ * sdxl_unet_forward asked for them (sdxl_batch_ext): of <dpred, pred>, no scale, no gate */
 SDXL_API int sdxl_unet_backward(sdxl_handle* h, const void* dpred_nhwc8, int first_micro, void* stream);
 
 /* fp32 grads -> bf16 (scaled) for the gradient exchange; global L2 norm of the fp32 grads */

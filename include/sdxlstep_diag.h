@@ -46,6 +46,18 @@ SDXL_API int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const voi
  * not read), pred and x_in [(s->cfg ? 2B : B) * H * W][8] bf16 with the conditional rows first; B = samples.  Same argument checks. */
 SDXL_API int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* stream);
 
+/* the conditioning-gradient kernel the plan launches (csrc/cond_dgrad.hip) on caller buffers: C [M][N] fp32 (row stride ldc, overwritten) =
+ * sum over n <= 2 groups of A[g] [M][K[g]] bf16 (row stride lda[g]; rows >= M are never read) . W[g] [K[g]][N] bf16 (row stride ldb[g] >= N),
+ * fp32 sums in a fixed order (no atomics).  K[g] % 64 == 0, N % 8 == 0, M >= 1.  The split-K slab is library-owned. */
+SDXL_API int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, const void* const* W, const long* ldb, const int* K, float* C,
+                       long ldc, int M, int N, void* stream);
+
+/* where the current plan's conditioning-gradient launches find their operands, so that a test can hand the same buffers to
+ * sdxl_op_cond_dgrad: which = 0 (d prompt_embeds; g = 0 .. *n_groups - 1, the K | V projections in forward order) or 1 (d pooled; g = 0).
+ * A = workspace + *a_ws_byte_off (bf16 [M][*lda]), W = weight arena + *w_elem_off (bf16 [*K][*ldb]).  g out of range is a bad argument. */
+SDXL_API int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off,
+                             long* ldb, int* K);
+
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the

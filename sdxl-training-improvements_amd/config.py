@@ -85,6 +85,9 @@ class TrainingConfig:                    # data/config.py:152-168
     noise_offset: float = 0.0            # >= 0: noise += noise_offset * randn(B,4,1,1); the target uses the offset noise (diffusers)
     input_perturbation: float = 0.0      # >= 0: the UNet input is built from noise + gamma * randn(B,4,H,W), the target from noise
     cond_dropout_prob: float = 0.0       # in [0,1]: per sample, prompt_embeds / pooled_prompt_embeds zeroed on a copy (time_ids kept)
+    # build-only key: conditioning gradients (csrc/cond_dgrad.hip).  "auto": a batch["prompt_embeds"] / batch["pooled_prompt_embeds"] that
+    # requires grad gets d loss / d itself back through compute_loss(...)["loss"].backward() (text encoders, textual inversion); "off": never
+    conditioning_grads: str = "auto"
     # build-only keys: validation sampling with the native sampler (sampler.py) from train(); decoding the latents is the caller's
     validation_every_n_steps: int = 0    # sample the caller's validation_batches every N optimizer steps (0 = off)
     validation_num_steps: int = 30       # UNet forwards per sample

@@ -13,6 +13,8 @@ struct StepState {  // what backward needs from the preceding forward
   sdxl_loss_config lc;      // in full (read_loss_config), the flag cleared
   sdxl_batch b;
   bool valid = false;
+  float* d_ehs = nullptr;   // the conditioning gradients this micro-step asked for (sdxl_batch_ext): the caller's
+  float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
 };
 struct sdxl_handle {
   Engine e;
@@ -240,11 +242,48 @@ int sdxl_zero_grads(sdxl_handle* h, void* st) {
 static int check_batch(Engine& e, const sdxl_batch* b) {
   Plan& p = *e.cur;
   ARG_CHECK(b, "null batch");
-  ARG_CHECK(b->B == p.B && b->H == p.H && b->W == p.W && b->ctx_len == p.ctx,
+  const int ctx = b->ctx_len & ~SDXL_BATCH_EXT;
+  ARG_CHECK(b->B == p.B && b->H == p.H && b->W == p.W && ctx == p.ctx,
             "batch shape (B=%d,H=%d,W=%d,ctx=%d) does not match the current plan (B=%d,H=%d,W=%d,ctx=%d)", b->B, b->H,
-            b->W, b->ctx_len, p.B, p.H, p.W, p.ctx);
+            b->W, ctx, p.B, p.H, p.W, p.ctx);
   ARG_CHECK(b->timestep && b->prompt_embeds && b->pooled && b->time_ids, "batch is missing conditioning pointers");
   return 0;
+}
+
+// The conditioning-gradient request of a micro-step: sdxl_batch_ext's two fields, read only behind SDXL_BATCH_EXT (a caller without the
+// flag passes a shorter struct).  The one error that needs no plan comes first, before the handle is looked at or anything is launched.
+static int check_cond_request(const sdxl_batch* b) {
+  if (!b || !(b->ctx_len & SDXL_BATCH_EXT)) return 0;
+  const sdxl_batch_ext* x = (const sdxl_batch_ext*)b;
+  ARG_CHECK(!(b->sampler && (x->d_prompt_embeds || x->d_pooled)), "d_prompt_embeds / d_pooled cannot be combined with a sampler step");
+  return 0;
+}
+static int read_cond_request(Engine& e, const sdxl_batch* b, float** d_ehs, float** d_pool) {
+  *d_ehs = *d_pool = nullptr;
+  if (!(b->ctx_len & SDXL_BATCH_EXT)) return 0;
+  const sdxl_batch_ext* x = (const sdxl_batch_ext*)b;
+  if (x->d_prompt_embeds) {
+    for (int g = 0; g < e.cur->cond_nkv; ++g)
+      ARG_CHECK(e.cur->cond_kv[g].K % 64 == 0, "d_prompt_embeds: K | V width %d is not a multiple of 64", e.cur->cond_kv[g].K);
+  }
+  if (x->d_pooled) ARG_CHECK(e.cur->cond_add.K >= 64 && e.cur->cond_add.K % 64 == 0, "d_pooled: time-embedding width %d is not a multiple of 64", e.cur->cond_add.K);
+  *d_ehs = x->d_prompt_embeds; *d_pool = x->d_pooled;
+  return 0;
+}
+// which of them the backward of this micro-step produces: part of the capture key of its graphs (the launch sequence differs)
+static unsigned cond_bits(const StepState& s) { return ((unsigned)(s.d_ehs != nullptr) << 8) | ((unsigned)(s.d_pool != nullptr) << 9); }
+// ... and the copies from the plan's buffers to the caller's, behind the last segment (outside any captured graph: the caller's buffers may move)
+static int copy_cond_grads(sdxl_handle* h, hipStream_t st) {
+  Plan& p = *h->e.cur;
+  const sdxl_unet_config& c = h->e.cfg;
+  if (h->step.d_ehs)
+    HIP_CHECK_RET(hipMemcpyAsync(h->step.d_ehs, p.F(p.dehs_off), sizeof(float) * (size_t)p.B * p.ctx * c.cross_attention_dim, hipMemcpyDeviceToDevice, st));
+  if (h->step.d_pool)
+    HIP_CHECK_RET(hipMemcpyAsync(h->step.d_pool, p.F(p.dpool_off), sizeof(float) * (size_t)p.B * c.pooled_dim, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+static void set_cond_request(sdxl_handle* h, bool gated) {
+  h->e.cond_ehs = h->step.d_ehs != nullptr; h->e.cond_pool = h->step.d_pool != nullptr; h->e.cond_gated = gated;
 }
 
 static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
@@ -383,6 +422,7 @@ static int run_forward_ops(Engine& e, hipStream_t st) {
 }
 
 int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_batch* b, void* stp) {
+  CHK(check_cond_request(b));
   H_CHECK(h);
   Engine& e = h->e;
   hipStream_t st = (hipStream_t)stp;
@@ -395,13 +435,15 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   CHK(read_loss_config(lc, &full));
   lc = &full;
   CHK(check_loss_ext(lc, b));
+  float *d_ehs, *d_pool;
+  CHK(read_cond_request(e, b, &d_ehs, &d_pool));
   CHK(upload_cond(e, b, st));
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
   // kernels must not)
   Plan& p = *e.cur;
   sdxl_batch sb;      // every field but the appended sampler pointer, which only sdxl_unet_forward reads (a caller of this entry point
   memcpy(&sb, b, offsetof(sdxl_batch, sampler));      // may hold the struct as it was before that field was appended)
-  sb.sampler = nullptr;
+  sb.sampler = nullptr; sb.ctx_len = p.ctx;
   if (e.use_graphs) {
     const size_t nlat = sizeof(float) * (size_t)p.B * 4 * p.H * p.W;
     HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_lat_off), b->latents, nlat, hipMemcpyDeviceToDevice, st));
@@ -441,6 +483,7 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   if (b->per_sample_loss)
     HIP_CHECK_RET(hipMemcpyAsync(b->per_sample_loss, p.F(p.ps_loss_off), sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
   h->step.lc = full; h->step.b = sb; h->step.valid = true;
+  h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
   return 0;
 }
 
@@ -503,6 +546,8 @@ static int run_backward_segment_body(Engine& e, int k, bool first, hipStream_t s
     HIP_CHECK_RET(hipStreamWaitEvent(st, e.ev_join, 0));
     e.side_dirty = false;
   }
+  // the conditioning gradients, when this micro-step asked: behind the last join (dK | dV come from the side stream), on the caller's stream
+  if (k == e.nseg - 1 && (e.cond_ehs || e.cond_pool)) CHK(e.launch_cond_grads(p, st));
   return 0;
 }
 
@@ -513,6 +558,7 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
   CHK(ready(e));
   ARG_CHECK(k >= 0 && k < e.nseg, "segment %d out of range", k);
   if (k == 0) ARG_CHECK(h->step.valid, "sdxl_backward_segment(0) needs a preceding sdxl_forward_loss");
+  set_cond_request(h, true);
   auto body = [&](hipStream_t s) -> int {
     if (k == 0) {
       LossP L;
@@ -522,12 +568,16 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
     return run_backward_segment(e, k, first_micro != 0, s);
   };
   // a segment can only be captured on its own when it ends with the side stream joined (per-segment join mode, or the last one)
-  if (e.join_last_only) return body(st);
-  unsigned sbits;
-  memcpy(&sbits, &grad_scale, 4);
-  Engine::GraphKey key{e.cur, 1, k, first_micro != 0, 0, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
-                      loss_cfg_bits2(h->step.lc, h->step.b), loss_huber_bits(h->step.lc, h->step.b)};
-  return run_graphed(e, key, st, body);
+  if (e.join_last_only) {
+    CHK(body(st));
+  } else {
+    unsigned sbits;
+    memcpy(&sbits, &grad_scale, 4);
+    Engine::GraphKey key{e.cur, 1, k, first_micro != 0, 0, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
+                        loss_cfg_bits2(h->step.lc, h->step.b) | cond_bits(h->step), loss_huber_bits(h->step.lc, h->step.b)};
+    CHK(run_graphed(e, key, st, body));
+  }
+  return k == e.nseg - 1 ? copy_cond_grads(h, st) : 0;
 }
 
 int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* stp) {
@@ -538,15 +588,17 @@ int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* s
   ARG_CHECK(h->step.valid, "sdxl_backward_all needs a preceding sdxl_forward_loss");
   unsigned sbits;
   memcpy(&sbits, &grad_scale, 4);
+  set_cond_request(h, true);
   Engine::GraphKey key{e.cur, 2, 0, first_micro != 0, e.join_last_only, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
-                      loss_cfg_bits2(h->step.lc, h->step.b), loss_huber_bits(h->step.lc, h->step.b)};
-  return run_graphed(e, key, st, [&](hipStream_t s) -> int {
+                      loss_cfg_bits2(h->step.lc, h->step.b) | cond_bits(h->step), loss_huber_bits(h->step.lc, h->step.b)};
+  CHK(run_graphed(e, key, st, [&](hipStream_t s) -> int {
     LossP L;
     fill_loss(e, &h->step.lc, &h->step.b, grad_scale, L);
     CHK(launch_loss_bwd(L, s));
     for (int k = 0; k < e.nseg; ++k) CHK(run_backward_segment(e, k, first_micro != 0, s));
     return 0;
-  });
+  }));
+  return copy_cond_grads(h, st);
 }
 int sdxl_set_graph_mode(sdxl_handle* h, int on) {
   H_CHECK(h);
@@ -601,12 +653,15 @@ static int fill_sampler(const sdxl_sampler_step* s, int image_batch, int HW, Sam
 }
 
 int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond, void* pred, void* stp) {
+  CHK(check_cond_request(cond));
   H_CHECK(h);
   Engine& e = h->e;
   hipStream_t st = (hipStream_t)stp;
   CHK(ready(e));
   CHK(check_batch(e, cond));
   Plan& p = *e.cur;
+  float *d_ehs, *d_pool;
+  CHK(read_cond_request(e, cond, &d_ehs, &d_pool));
   if (cond->sampler) {      // a sampling step: the forward runs on what the plan's input buffer holds, the step kernel writes the next input there
     SamplerP q;
     CHK(fill_sampler(cond->sampler, p.B, p.H * p.W, q));
@@ -619,6 +674,7 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
     return launch_sampler_step(q, st);
   }
   CHK(upload_cond(e, cond, st));
+  h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
   size_t bytes = (size_t)p.B * p.H * p.W * 8 * sizeof(bf16);
   HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, bytes, hipMemcpyDeviceToDevice, st));
   CHK(run_forward_ops(e, st));
@@ -634,8 +690,9 @@ int sdxl_unet_backward(sdxl_handle* h, const void* dpred, int first_micro, void*
   Plan& p = *e.cur;
   size_t bytes = (size_t)p.B * p.H * p.W * 8 * sizeof(bf16);
   HIP_CHECK_RET(hipMemcpyAsync(p.G(p.pred), dpred, bytes, hipMemcpyDeviceToDevice, st));
+  set_cond_request(h, false);
   for (int k = 0; k < e.nseg; ++k) CHK(run_backward_segment(e, k, first_micro != 0, st));
-  return 0;
+  return copy_cond_grads(h, st);
 }
 
 int sdxl_grads_to_bf16(sdxl_handle* h, size_t off, size_t n, void* dst, float scale, void* st) {
@@ -739,6 +796,34 @@ int sdxl_op_gemm(int form, const void* A, const void* B, void* C, int M, int N, 
   if (resid) { g.resid = (const bf16*)resid; g.ldr = N; }
   g.accumulate = accumulate;
   return launch_gemm(g, (hipStream_t)st);
+}
+
+int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, const void* const* W, const long* ldb, const int* K, float* C, long ldc,
+                       int M, int N, void* st) {
+  ARG_CHECK(n >= 1 && n <= 2 && A && lda && W && ldb && K, "cond_dgrad: 1 or 2 groups, no null array");
+  CondDgradP q;
+  memset(&q, 0, sizeof(q));
+  q.n = n;
+  for (int g = 0; g < n; ++g) { q.A[g] = (const bf16*)A[g]; q.lda[g] = lda[g]; q.W[g] = (const bf16*)W[g]; q.ldb[g] = ldb[g]; q.K[g] = K[g]; }
+  q.C = C; q.ldc = ldc; q.M = M; q.N = N;
+  ARG_CHECK(M >= 1 && N >= 8, "cond_dgrad: M = %d, N = %d", M, N);
+  for (int g = 0; g < n; ++g) ARG_CHECK(K[g] >= 64 && K[g] % 64 == 0, "cond_dgrad: K[%d] = %d must be a positive multiple of 64", g, K[g]);
+  const size_t need = cond_dgrad_slab_floats(n, K, M, N);
+  if (need) CHK(test_slab(need, &q.slab));
+  return launch_cond_dgrad(q, (hipStream_t)st);
+}
+
+int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off, long* ldb,
+                             int* K) {
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(n_groups && a_ws_byte_off && lda && w_elem_off && ldb && K, "null output");
+  const Plan& p = *h->e.cur;
+  const int n = which == 0 ? p.cond_nkv : 1;
+  ARG_CHECK((which == 0 || which == 1) && g >= 0 && g < n, "cond operands: which = %d, group %d of %d", which, g, n);
+  const Plan::CondSrc& cs = which == 0 ? p.cond_kv[g] : p.cond_add;
+  *n_groups = n; *a_ws_byte_off = cs.dy_off; *lda = cs.lda; *w_elem_off = cs.w.off; *ldb = cs.ldb; *K = cs.K;
+  return 0;
 }
 
 int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, float* const* dw, float* const* dbias, int Mo, int No,

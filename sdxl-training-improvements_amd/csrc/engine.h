@@ -92,6 +92,13 @@ struct Plan {
   // column tiles of a row block exchange; shared, stream-ordered; zeroed at the start of a backward, whose fused launches count the epoch up
   size_t ln_part_off = NONE, ln_part_floats = 0;
   int ln_epoch = 0;
+  // conditioning gradients (cond_dgrad.hip): d ehs = sum over the K | V projections of dKV . Wkv, d pooled = dA1 . W_add1[:, :pooled_dim], fp32.
+  // Buffers and slab are always reserved (behind every other allocation); the kernels run only in a backward whose micro-step asked
+  // (Engine::cond_ehs / cond_pool), at the end of the last segment, on the caller's stream, behind the join with the side stream.
+  struct CondSrc { size_t dy_off = NONE; long lda = 0; PRef w; long ldb = 0; int K = 0; };
+  CondSrc cond_kv[2], cond_add;        // the hoisted K | V projections in forward order (at most one per attention width); add_embedding.linear_1
+  int cond_nkv = 0;
+  size_t dehs_off = NONE, dpool_off = NONE, cond_slab_off = NONE;
 
   Act* new_act(long rows, int cols, bool need_grad = true, int pad_rows = 0);
   Act* view(Act* parent, int col0, int cols);   // columns [col0, col0 + cols) of parent
@@ -160,6 +167,9 @@ struct Engine {
   // step's or plan's buffers).
   void drop_pending() { side_leaves.clear(); wg_pending.clear(); ln_pending.clear(); cs_pending.clear(); }
   bool side_dirty = false;       // the side stream has work the caller's stream has not joined yet
+  bool cond_ehs = false, cond_pool = false;   // this micro-step's backward also produces d prompt_embeds / d pooled (set by the C ABI)
+  bool cond_gated = false;                    // ... behind a loss (its gate scalar is read), not behind sdxl_unet_backward
+  int launch_cond_grads(Plan& p, hipStream_t st);
   // hipGraph replay of the step (sdxl_set_graph_mode, OFF by default): forward (+ loss) and backward are captured once per
   // (plan, configuration) -- both streams, every event edge -- and replayed with one hipGraphLaunch, on an engine-owned
   // stream (the caller's may be the legacy default stream, which cannot be captured) fenced by two events.  Measured on

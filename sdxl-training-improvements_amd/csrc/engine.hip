@@ -153,6 +153,39 @@ int Engine::flush_ln_params(Plan& p, hipStream_t main) {
   ln_pending.clear();
   return 0;
 }
+// d prompt_embeds / d pooled of this backward, into the plan's fp32 buffers: everything they read (dK | dV of every cross-attention
+// block, produced on the side stream; d(add_embedding.linear_1's output)) is complete and visible to `st` when this is called
+int Engine::launch_cond_grads(Plan& p, hipStream_t st) {
+  const float* gate = cond_gated ? p.F(p.loss_off) + 7 : nullptr;      // out[7] of the loss: 0 = gate closed
+  if (cond_ehs) {
+    const int M = p.B * p.ctx, N = cfg.cross_attention_dim;
+    if (p.cond_nkv == 0) {      // a UNet without cross-attention: the prompt reaches nothing
+      HIP_CHECK_RET(hipMemsetAsync(p.F(p.dehs_off), 0, sizeof(float) * (size_t)M * N, st));
+    } else {
+      CondDgradP q;
+      memset(&q, 0, sizeof(q));
+      q.n = p.cond_nkv;
+      for (int g = 0; g < q.n; ++g) {
+        const Plan::CondSrc& cs = p.cond_kv[g];
+        ARG_CHECK(cs.dy_off != NONE, "conditioning gradients: the K | V projection has no output gradient");
+        q.A[g] = p.GP(cs.dy_off); q.lda[g] = cs.lda; q.W[g] = Wp(cs.w); q.ldb[g] = cs.ldb; q.K[g] = cs.K;
+      }
+      q.C = p.F(p.dehs_off); q.ldc = N; q.M = M; q.N = N; q.slab = p.F(p.cond_slab_off); q.gate = gate;
+      CHK(launch_cond_dgrad(q, st));
+    }
+  }
+  if (cond_pool) {
+    const Plan::CondSrc& cs = p.cond_add;
+    ARG_CHECK(cs.dy_off != NONE, "conditioning gradients: add_embedding.linear_1 has no output gradient");
+    CondDgradP q;
+    memset(&q, 0, sizeof(q));
+    q.n = 1;
+    q.A[0] = p.GP(cs.dy_off); q.lda[0] = cs.lda; q.W[0] = Wp(cs.w); q.ldb[0] = cs.ldb; q.K[0] = cs.K;      // the first pooled_dim columns of [temb][add_in]
+    q.C = p.F(p.dpool_off); q.ldc = cfg.pooled_dim; q.M = p.B; q.N = cfg.pooled_dim; q.slab = p.F(p.cond_slab_off); q.gate = gate;
+    CHK(launch_cond_dgrad(q, st));
+  }
+  return 0;
+}
 bool Plan::grad_alias(Act* x, Act* y) {
   if (x->goff == NONE) {
     x->goff = y->goff;
@@ -821,6 +854,8 @@ struct Builder {
   std::map<int, Act*> kv_all;                // per channel width C: [B*ctx][sum 2C] cross-attention K | V of every transformer block of that width
   std::map<std::string, int> kv_col;        // transformer block prefix -> first column in its group's tensor
   std::map<int, bool> kv_done;
+  std::vector<LinearOp*> kv_ops;             // the grouped K | V projections, forward order
+  LinearOp* add1_op = nullptr;               // add_embedding.linear_1
   explicit Builder(Engine& e_, Plan* p_) : e(e_), pl(p_) {
     if (pl) { B = pl->B; H = pl->H; W = pl->W; ctx = pl->ctx; } else { B = H = W = ctx = 0; }
   }
@@ -1038,6 +1073,7 @@ struct Builder {
         kv_all[Cgrp] = all;
         LinearOp* op = tagseg(pl->add<LinearOp>(ehs, all, wkv, PRef(), cross, (int)ntot, nullptr), wkv);
         op->hoist_fwd = true;
+        kv_ops.push_back(op);
       }
     };
     {
@@ -1066,7 +1102,7 @@ struct Builder {
     Act* t1 = linear("time_embedding.linear_1", te_sin, ch[0], temb, true, nullptr);
     Act* t1s = silu(t1);
     Act* t2 = linear("time_embedding.linear_2", t1s, temb, temb, true, nullptr);
-    Act* a1 = linear("add_embedding.linear_1", aug_in, add_in, temb, true, nullptr);
+    Act* a1 = linear("add_embedding.linear_1", aug_in, add_in, temb, true, nullptr, false, 0, &add1_op);
     Act* a1s = silu(a1);
     Act* emb = linear("add_embedding.linear_2", a1s, temb, temb, true, t2);
     emb_act = silu(emb);
@@ -1190,6 +1226,30 @@ void Engine::build(Plan* plan) {
     plan->in_mask_off = plan->alloc(sizeof(float) * (size_t)plan->B * plan->H * plan->W);
     plan->in_nin_off = plan->alloc(sizeof(float) * (size_t)plan->B * 4 * plan->H * plan->W);
     plan->mask_norm_off = plan->alloc(sizeof(float) * plan->B);
+    // ... and the conditioning gradients': the two fp32 results and the split-K slab of their kernel (cond_dgrad.hip)
+    {
+      const sdxl_unet_config& c = cfg;
+      const int Mk = plan->B * plan->ctx;
+      plan->cond_nkv = 0;
+      int Ks[2] = {0, 0};
+      for (LinearOp* op : b.kv_ops) {
+        if (plan->cond_nkv == 2) break;
+        Plan::CondSrc& cs = plan->cond_kv[plan->cond_nkv];
+        cs.dy_off = op->dy_off; cs.lda = op->y->ld(); cs.w = op->w; cs.ldb = op->K; cs.K = op->N;
+        Ks[plan->cond_nkv++] = op->N;
+      }
+      if (b.add1_op) {
+        Plan::CondSrc& cs = plan->cond_add;
+        cs.dy_off = b.add1_op->dy_off; cs.lda = b.add1_op->y->ld(); cs.w = b.add1_op->w; cs.ldb = b.add1_op->K; cs.K = b.add1_op->N;
+      }
+      plan->dehs_off = plan->alloc(sizeof(float) * (size_t)Mk * c.cross_attention_dim);
+      plan->dpool_off = plan->alloc(sizeof(float) * (size_t)plan->B * c.pooled_dim);
+      size_t slab = plan->cond_nkv ? cond_dgrad_slab_floats(plan->cond_nkv, Ks, Mk, c.cross_attention_dim) : 0;
+      const int Ka[2] = {plan->cond_add.K, 0};
+      const size_t slab2 = cond_dgrad_slab_floats(1, Ka, plan->B, c.pooled_dim);
+      if (slab2 > slab) slab = slab2;
+      plan->cond_slab_off = plan->alloc(sizeof(float) * (slab ? slab : 4));
+    }
     plan->seg_first_op.assign(nseg, -1);
     plan->seg_last_op.assign(nseg, -2);
     for (int i = 0; i < (int)plan->ops.size(); ++i) {

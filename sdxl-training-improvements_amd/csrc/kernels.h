@@ -462,3 +462,19 @@ struct SfkP : OptimP {
 int launch_sfk(const SfkP& q, int reference, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);
 
+
+// ---- conditioning gradients (cond_dgrad.hip): C32 [M][N] = sum_g A_g [M][K_g] . W_g [K_g][N], bf16 operands, fp32 sums and output ----
+struct CondDgradP {
+  int n;                  // groups, 1 or 2
+  const bf16* A[2];       // [M][K_g], row stride lda (rows >= M are never read)
+  const bf16* W[2];       // [K_g][N], row stride ldb >= N (a column slice of a wider weight)
+  long lda[2], ldb[2];
+  int K[2];               // multiples of 64
+  float* C;               // [M][N] fp32, row stride ldc: overwritten
+  long ldc;
+  int M, N;               // N % 8 == 0
+  float* slab;            // cond_dgrad_slab_floats(n, K, M, N) floats (may be null when that is 0)
+  const float* gate;      // device scalar or null: when it reads 0 (closed gradient gate) the result is exact zeros
+};
+size_t cond_dgrad_slab_floats(int n, const int* K, int M, int N);
+int launch_cond_dgrad(const CondDgradP& p, hipStream_t st);

@@ -85,6 +85,15 @@ class SamplerBatch(Batch):
     _fields_ = [("sampler", C.POINTER(SamplerStep))]
 
 
+BATCH_EXT = 0x10000    # SDXL_BATCH_EXT, or-ed into Batch.ctx_len: the struct passed is a CondGradBatch
+
+
+class CondGradBatch(SamplerBatch):
+    """sdxl_batch_ext: SamplerBatch + the two optional fp32 outputs of the conditioning gradients, which the library reads only when
+    ctx_len carries BATCH_EXT (include/sdxlstep.h)"""
+    _fields_ = [("d_prompt_embeds", C.c_void_p), ("d_pooled", C.c_void_p)]
+
+
 LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
 MASK_NORMS = {"mean": 0, "masked_mean": 1}
 
@@ -172,6 +181,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_gemm_ld": [_i, _vp, _vp, _vp, _i, _i, _i, C.c_long, C.c_long, C.c_long, _vp, _vp, C.c_long, _i, _vp],
     "sdxl_op_linear_dgrad_delta": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sdxl_op_sampler_step": [_vp, _vp, _vp, _i, _i, _i, _P(SamplerStep), _vp],
+    "sdxl_debug_cond_operands": [_vp, _i, _i, _P(_i), _P(_sz), _P(_l), _P(_sz), _P(_l), _P(_i)],
+    "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
 }
 # include/sdxlstep_diag.h part 2: experiment ABI, exported by libsdxlstep_diag.so only
 DIAG_SIGNATURES = {

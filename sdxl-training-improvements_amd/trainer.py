@@ -57,20 +57,36 @@ HUBER_SCHEDULES = ("constant", "snr")
 SNR_WEIGHTINGS = ("reference", "debiased")
 WEIGHT_SETS = ("trained", "ema")
 MASKED_LOSSES = ("off", "mean", "masked_mean")
+CONDITIONING_GRADS = ("auto", "off")
 
 
 class _NativeLoss(torch.autograd.Function):
-    """0-d loss whose backward runs the HIP backward with the incoming scale (so `(loss / N).backward()` works)."""
+    """0-d loss whose backward runs the HIP backward with the incoming scale (so `(loss / N).backward()` works).
+    prompt_embeds / pooled: the conditioning tensors the UNet read (after conditioning dropout) when one of them requires grad, else
+    None.  Their gradients come back from the device (NativeUNet.read_cond_grads) in each input's device and dtype, so the caller's
+    autograd graph -- text encoders, an embedding table -- continues from here."""
 
     @staticmethod
-    def forward(ctx, anchor, trainer, value):
+    def forward(ctx, anchor, trainer, value, prompt_embeds=None, pooled=None):
         ctx.trainer = trainer
+        ctx.cond = [None if t is None else (t.shape, t.dtype, t.device) for t in (prompt_embeds, pooled)]
         return anchor.new_tensor(value)
 
     @staticmethod
     def backward(ctx, grad_out):
         ctx.trainer._native_backward(float(grad_out))
-        return None, None, None
+        grads = [None, None]
+        if any(ctx.needs_input_grad[3:5]):
+            # the backward ran with grad_scale / world (the parameter gradients are summed over the ranks afterwards); the caller's own
+            # modules average theirs across ranks themselves (DDP), so they get this rank's gradient of grad_scale x loss
+            world = float(ctx.trainer.sync.world)
+            dev = ctx.trainer.net.read_cond_grads()
+            for i in range(2):
+                if ctx.needs_input_grad[3 + i] and ctx.cond[i] is not None:
+                    shape, dtype, device = ctx.cond[i]
+                    g = dev[i] if world == 1.0 else dev[i] * world
+                    grads[i] = g.reshape(shape).to(device=device, dtype=dtype)
+        return None, None, None, grads[0], grads[1]
 
 
 class NativeSDXLTrainer:
@@ -155,6 +171,10 @@ class NativeSDXLTrainer:
         self.masked_loss = str(getattr(tc, "masked_loss", "off")).lower()
         if self.masked_loss not in MASKED_LOSSES:
             raise ValueError(f"training.masked_loss: unknown value {getattr(tc, 'masked_loss')!r} (expected one of {', '.join(MASKED_LOSSES)})")
+        cg = getattr(tc, "conditioning_grads", "auto")
+        self.conditioning_grads = cg.lower() if isinstance(cg, str) else cg
+        if self.conditioning_grads not in CONDITIONING_GRADS:
+            raise ValueError(f"training.conditioning_grads: unknown value {cg!r} (expected one of {', '.join(CONDITIONING_GRADS)})")
         for key, top in (("noise_offset", None), ("input_perturbation", None), ("cond_dropout_prob", 1.0)):
             v = getattr(tc, key, 0.0)
             ok = not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(float(v)) and float(v) >= 0.0
@@ -321,11 +341,13 @@ class NativeSDXLTrainer:
                 ext["mask_norm"] = self.masked_loss
         return ext
 
-    def _augment(self, batch, noise, generator):
+    def _augment(self, batch, noise, generator, cond_grads: bool = False):
         """The training-only recipes on top of the base noise (drawn or injected), each drawn from the step's generator only when its
         key is on, in the order noise offset, input perturbation, conditioning dropout -- after the base noise and the timesteps.
         Returns (batch, noise, ext): the batch a shallow copy with zeroed conditioning rows where dropout drew them (the caller's
-        tensors are not modified), the noise after the offset (what the target uses), and noise_in for forward_loss."""
+        tensors are not modified), the noise after the offset (what the target uses), and noise_in for forward_loss.
+        cond_grads: the conditioning carries a gradient back to the caller: the dropped rows are zeroed by a differentiable select, so
+        autograd hands those samples zero rows."""
         ext: Dict[str, Any] = {}
         B = noise.shape[0]
         if self.noise_offset > 0.0:                        # diffusers' --noise_offset: one draw per sample and channel
@@ -338,14 +360,32 @@ class NativeSDXLTrainer:
             drop = torch.rand(B, generator=generator) < self.cond_dropout_prob
             batch = dict(batch)
             for key in ("prompt_embeds", "pooled_prompt_embeds"):
+                if cond_grads:
+                    t = batch[key]
+                    d = drop.to(t.device).reshape((B,) + (1,) * (t.dim() - 1))
+                    batch[key] = torch.where(d, torch.zeros((), dtype=t.dtype, device=t.device), t)
+                    continue
                 t = batch[key].clone()
                 t[drop.to(t.device)] = 0
                 batch[key] = t
         return batch, noise, ext
 
-    def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None, augment: bool = False):
+    def _cond_request(self, batch, ext) -> None:
+        """compute_loss only: when the conditioning (after dropout) requires grad, ask the net for its gradients and keep the tensors
+        for _NativeLoss; the net itself gets detached tensors"""
+        self._cond_inputs = tuple(batch[k] if torch.is_tensor(batch[k]) and batch[k].requires_grad else None
+                                  for k in ("prompt_embeds", "pooled_prompt_embeds"))
+        want = tuple(n for n, t in zip(("prompt", "pooled"), self._cond_inputs) if t is not None)
+        if want:
+            ext["cond_grads"] = want
+            for k in ("prompt_embeds", "pooled_prompt_embeds"):
+                batch[k] = batch[k].detach() if torch.is_tensor(batch[k]) else batch[k]
+
+    def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None, augment: bool = False,
+                 cond_grads: bool = False):
         """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used.
-        augment: apply the training-only recipes (noise offset, input perturbation, conditioning dropout; _augment)"""
+        augment: apply the training-only recipes (noise offset, input perturbation, conditioning dropout; _augment).
+        cond_grads: compute_loss found a conditioning tensor that requires grad (_cond_request)"""
         B = lat.shape[0]
         cm = self.config.model
         tag = batch.get("tag_weights")
@@ -356,8 +396,11 @@ class NativeSDXLTrainer:
             ext = self._loss_ext(batch, sig)
             ext.update(ext_over or {})
             if augment:
-                batch, noise, aug = self._augment(batch, noise, generator)
+                batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
                 ext.update(aug)
+            if cond_grads:
+                batch = dict(batch)
+                self._cond_request(batch, ext)
             self.net.forward_loss("ddpm", lat, noise, sig, ts.float(), batch["prompt_embeds"],
                                   batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag,
                                   prediction_type=self.config.training.prediction_type,
@@ -373,8 +416,11 @@ class NativeSDXLTrainer:
         ext = self._loss_ext(batch, None)
         ext.update(ext_over or {})
         if augment:
-            batch, noise, aug = self._augment(batch, noise, generator)
+            batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
             ext.update(aug)
+        if cond_grads:
+            batch = dict(batch)
+            self._cond_request(batch, ext)
         self.net.forward_loss("flow_matching", lat, noise, t, t_unet, batch["prompt_embeds"],
                               batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag, **ext)
         return t
@@ -393,7 +439,12 @@ class NativeSDXLTrainer:
         B = lat.shape[0]
         if noise is None:
             noise = torch.randn(lat.shape, generator=generator)
-        ts = self._forward(batch, lat, noise, timesteps, generator, augment=True)
+        # conditioning gradients (training.conditioning_grads "auto"): a prompt_embeds / pooled_prompt_embeds that requires grad gets its
+        # gradient back through the loss, so the caller's text encoders or embedding table train with the UNet
+        cond = (self.conditioning_grads != "off" and torch.is_grad_enabled() and
+                any(torch.is_tensor(batch[k]) and batch[k].requires_grad for k in ("prompt_embeds", "pooled_prompt_embeds")))
+        self._cond_inputs = (None, None)
+        ts = self._forward(batch, lat, noise, timesteps, generator, augment=True, cond_grads=cond)
         o = self.net.read_loss()                                        # the single host sync of the step
         numel = lat.numel()
         lr = self.optimizer.param_groups[0]["lr"] if self.optimizer is not None else 0.0
@@ -406,7 +457,7 @@ class NativeSDXLTrainer:
             metrics = {"loss": o[0], "x0_norm": math.sqrt(o[5]), "x1_norm": math.sqrt(o[6]),
                        "time_mean": float(ts.mean()), "time_std": float(ts.std()) if B > 1 else float("nan"),
                        "velocity_norm": math.sqrt(o[3]), "batch_size": B, "lr": lr}
-        loss = _NativeLoss.apply(self._anchor, self, o[0])
+        loss = _NativeLoss.apply(self._anchor, self, o[0], *self._cond_inputs)
         out = {"loss": loss, "metrics": metrics}
         if bool(getattr(self.config.training, "log_per_sample_loss", False)):
             out["per_sample_loss"] = self.net.read_per_sample_loss()    # (after read_loss's sync: the copy only)

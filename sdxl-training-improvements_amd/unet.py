@@ -237,10 +237,38 @@ class NativeUNet:
         it again); ValueError for a shape that is not the latents' [B,H,W] / [B,1,H,W] or a value that is negative or not finite"""
         return None if m is None else loss_mask_bhw(m, latents.shape).to(self.device).contiguous()
 
+    def _cond_request(self, cond_grads, B: int, ctx: int):
+        """the buffers a micro-step's conditioning gradients are written to: cond_grads is None / False (none), True (both) or a
+        collection of "prompt" / "pooled".  Owned here and kept until the next request; read_cond_grads() hands them out."""
+        want = {"prompt", "pooled"} if cond_grads is True else set(cond_grads or ())
+        if want - {"prompt", "pooled"}:
+            raise ValueError(f"cond_grads {cond_grads!r}: expected True, None or a collection of 'prompt' / 'pooled'")
+        z = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        self._d_prompt = z(B, ctx, int(self.cfg.cross_attention_dim)) if "prompt" in want else None
+        self._d_pooled = z(B, int(self.cfg.pooled_dim)) if "pooled" in want else None
+        return bool(want)
+
+    def _cond_batch(self, b):
+        """b as a lib.CondGradBatch carrying the current request (flagged), or b itself when nothing is requested"""
+        if getattr(self, "_d_prompt", None) is None and getattr(self, "_d_pooled", None) is None:
+            return b
+        x = lib.CondGradBatch(*[getattr(b, f[0]) for f in lib.Batch._fields_])
+        x.ctx_len |= lib.BATCH_EXT
+        x.d_prompt_embeds = None if self._d_prompt is None else self._d_prompt.data_ptr()
+        x.d_pooled = None if self._d_pooled is None else self._d_pooled.data_ptr()
+        return x
+
+    def read_cond_grads(self):
+        """(d_prompt_embeds [B,ctx,cross_attention_dim] | None, d_pooled [B,pooled_dim] | None) of the last micro-step that asked for
+        them (forward_loss / unet_forward with cond_grads) and whose backward has been enqueued: fp32, on the device, stream-ordered
+        (no synchronisation).  The gradient of grad_scale x loss, as the parameter gradients of that micro-step."""
+        return getattr(self, "_d_prompt", None), getattr(self, "_d_pooled", None)
+
     def forward_loss(self, method: str, latents, noise, sigma_or_t, timestep, prompt_embeds, pooled, time_ids,
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
                      use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
-                     per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean") -> None:
+                     per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean",
+                     cond_grads=None) -> None:
         """loss preparation + UNet forward + loss; results stay on the device until read_loss().
         sample_weights: optional [B] s_b multiplied into each sample's loss and gradient.  loss_type "l2" | "huber" |
         "smooth_l1" (include/sdxlstep.h), with huber_c a float (every sample) or [B] values (per sample).
@@ -248,7 +276,9 @@ class NativeUNet:
         loss_mask: optional [B,H,W] or [B,1,H,W] at latent resolution, finite and >= 0, multiplied into every channel's loss and
         gradient; mask_norm "mean" divides by the element count as without a mask, "masked_mean" each sample by its own mask sum.
         noise_in: optional [B,4,H,W], the noise (ddpm) / x0 (flow matching) the UNet input is built from while the target keeps
-        `noise` (input perturbation)."""
+        `noise` (input perturbation).
+        cond_grads: ("prompt", "pooled"), a subset, True (both) or None: the backward of this micro-step also produces the gradient
+        with respect to prompt_embeds / pooled, read with read_cond_grads()."""
         if loss_type not in lib.LOSS_TYPES:
             raise ValueError(f"loss_type {loss_type!r}: expected one of {sorted(lib.LOSS_TYPES)}")
         if mask_norm not in lib.MASK_NORMS:
@@ -278,6 +308,8 @@ class NativeUNet:
         b.sample_weights = None if sw is None else sw.data_ptr()
         b.huber_c = None if hc is None else hc.data_ptr()
         b.per_sample_loss = None if self._ps_loss is None else self._ps_loss.data_ptr()
+        self._cond_request(cond_grads, B, b.ctx_len)
+        b = self._cond_batch(b)
         lib.check(self.L.sdxl_forward_loss(self.h, C.byref(lc), C.byref(b), _stream()), "sdxl_forward_loss")
 
     def backward(self, grad_scale: float = 1.0, first_micro: bool = True, on_segment=None, segment_stream: bool = False) -> None:
@@ -339,12 +371,15 @@ class NativeUNet:
         return self._ps_loss.cpu()
 
     # UNet only (sample NCHW fp32/bf16 in, NCHW fp32 out) -- for parity tests and validation sampling
-    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids) -> torch.Tensor:
+    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids, cond_grads=None) -> torch.Tensor:
+        """cond_grads as in forward_loss: the following unet_backward also produces d prompt_embeds / d pooled of <dpred, pred>"""
         B, Cc, H, W = sample.shape
         d = self.device
         dummy = torch.zeros(B, 4, H, W, device=d)
         tb = self._batch(dummy, dummy, torch.zeros(B), timestep, prompt_embeds, pooled, time_ids, None)
         b = lib.SamplerBatch(*[getattr(tb, f[0]) for f in lib.Batch._fields_])      # sdxl_batch in full, sampler = NULL
+        self._cond_request(cond_grads, B, tb.ctx_len)
+        b = self._cond_batch(b)
         x8 = torch.zeros(B * H * W, 8, dtype=torch.bfloat16, device=d)
         x8[:, :4] = sample.to(d).permute(0, 2, 3, 1).reshape(B * H * W, 4).to(torch.bfloat16)
         out8 = torch.empty_like(x8)
