@@ -298,7 +298,9 @@ SDXL_API int sdxl_op_upconv3x3_dgrad(const void* dy, const void* weff, void* pla
 SDXL_API int sdxl_op_conv3x3_s2_dgrad(const void* dy, const void* w, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
                              int Cout, void* stream);
 /* ... and its weight / bias gradient: `planar` as _dgrad left it (dy de-interleaved into its four phases), x the low-resolution input;
-   dweff [Cout][16][Cin] fp32 scratch; dw [Cout][9][Cin] fp32 (accumulate 0: =, 1: +=), dbias[Cout] += (may be NULL); splitk >= 1. */
+   dweff [Cout][16][Cin] fp32 scratch; dw [Cout][9][Cin] fp32 (accumulate 0: =, 1: +=), dbias[Cout] += (may be NULL); splitk >= 1.
+   The reduction over the B*H*W low-resolution pixels runs in whole 64-pixel steps: B*H*W % 64 != 0 is rejected as an argument
+   error, where _fwd and _dgrad take any B*H*W (the plan then takes the weight gradient from the up-sampled image instead). */
 SDXL_API int sdxl_op_upconv3x3_wgrad(const void* planar, const void* x, float* dweff, float* dw, float* dbias, int accumulate, int B, int H,
                             int W, int Cin, int Cout, int splitk, void* stream);
 SDXL_API int sdxl_op_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B, int H, int W, int Cin, int Cout,

@@ -27,6 +27,7 @@ from sdxl_amd import unet as NU
 
 import _bucket_cases as BK
 from _gradparity import GradParity, compare_autograd
+from _isolation import assert_step_isolated
 from test_gpu_fullsize import _grad_bar, _inputs      # the full-size tests' bars (TIGHT_GRAD_BAR / FULL_GRAD_BAR by role group) and inputs
 
 pytestmark = pytest.mark.gpu
@@ -145,3 +146,15 @@ def test_shallow_mixed_buckets_accumulate_across_plans(shallow):
         par = GradParity(f"shallow mixed buckets order {order}")
         par.add_arena(net.grads, want, ranges, pshapes)
         par.check((1e-5, 1.0 - 1e-9), expect=pshapes)
+
+
+def test_shallow_step_does_not_depend_on_workspace_or_stale_gradients(shallow):
+    """The form of tests/test_gpu_model.py::test_step_does_not_depend_on_workspace_or_stale_gradients at real widths, clean against 0xFF:
+    the routes no tiny width reaches (co-resident 256-row tiles, the long-reduction and grouped weight gradients, the Delta epilogue, the
+    split-K of small-M problems) on a workspace and a gradient arena of NaN.  No oracle: two steps."""
+    _, net = shallow
+    B, H, W = 1, 104, 152
+    x = _inputs(B, H, W, seed=4100)
+    t = torch.tensor([0.3671875])
+    step = lambda: net.forward_loss("flow_matching", x["lat"], x["noise"], t, t, x["ehs"], x["pooled"], x["tid"])
+    assert_step_isolated(net, (B, H, W), [step], fills=(0x00, 0xFF), what=f"shallow flow_matching {B}x{H}x{W}")

@@ -16,6 +16,7 @@ from sdxl_amd import unet as NU
 
 import _bucket_cases as BK      # the default aspect buckets' latent shapes (tests/test_host_buckets.py pins them to the config)
 from _gradparity import GradParity, compare_autograd
+from _isolation import FILLS, assert_step_isolated, fill_bytes, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -329,3 +330,47 @@ def test_grad_emit_equals_cast_of_the_fp32_arena(tiny):
     print(f"[parity] grad emit: {int((d > 0).sum())} of {n} elements differ, max |d| / max |ref| = {float(d.max()) / scale:.2e}")
     assert float(d.max()) <= 2e-2 * scale
     assert int((d > 0).sum()) <= 0.02 * n                       # only the atomically accumulated small parameters may differ
+
+
+@pytest.mark.parametrize("micro_steps", [1, 2], ids=["one-step", "two-micro-steps"])
+@pytest.mark.parametrize("method,B,H,W", [pytest.param("ddpm", 2, 16, 16, id="ddpm-2-16-16"), pytest.param("flow_matching", 2, 16, 16, id="flow_matching-2-16-16"),
+                                          pytest.param("flow_matching", 1, 104, 152, id="flow_matching-1-104-152"),      # 988 / 3952 tokens: pad rows everywhere
+                                          pytest.param("flow_matching", *BK.TINY_REPEAT, id="flow_matching-" + _bhw_id(*BK.TINY_REPEAT))])
+def test_step_does_not_depend_on_workspace_or_stale_gradients(tiny, method, B, H, W, micro_steps):
+    """The workspace is caller memory and first_micro OVERWRITES the weight-matrix gradients (include/sdxlstep.h): with every byte of the
+    workspace and of the gradient arena set to 0xFF (NaN) or 0x7F (3.39e38) before the step, the loss and every parameter gradient have the
+    bits of the step on zero-filled memory -- no tolerance, the step is bit-reproducible end to end.  Alone, and as a two-micro-step
+    accumulation cycle whose workspace is filled again between the micro-steps."""
+    cfg, w, net = tiny
+    xs = [make_inputs(cfg, B, H, W, seed=81 + i) for i in range(micro_steps)]
+    if method == "ddpm":
+        ts = torch.tensor([610, 230][:B])
+        sig = R.karras_sigmas()[ts]
+        fwd = lambda x: (lambda: net.forward_loss("ddpm", x["lat"], x["noise"], sig, ts.float(), x["ehs"], x["pooled"], x["tid"]))
+    else:
+        fwd = lambda x: (lambda t=R.sample_logit_normal_from_z(x["z"]): net.forward_loss("flow_matching", x["lat"], x["noise"], t, t, x["ehs"], x["pooled"], x["tid"]))
+    assert_step_isolated(net, (B, H, W), [fwd(x) for x in xs], what=f"tiny {method} {B}x{H}x{W} x{micro_steps}")
+
+
+def test_inference_forward_does_not_depend_on_workspace(tiny):
+    """unet_forward on a pattern-filled workspace gives the bits of the forward on a zero-filled one"""
+    cfg, w, net = tiny
+    B, H, W = 2, 24, 40
+    x = make_inputs(cfg, B, H, W, seed=83)
+    t = torch.tensor([10.0, 500.0])
+    outs = []
+    hip_failed = False
+    try:
+        for fill in FILLS:
+            net.plan(B, H, W)
+            fill_bytes(net.workspace, fill)
+            outs.append(net.unet_forward(x["lat"], t, x["ehs"], x["pooled"], x["tid"]))
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(outs[-1]).all()), f"fill 0x{fill:02X}"
+            assert same_bits(outs[-1], outs[0]), f"fill 0x{fill:02X}: the prediction differs from the clean workspace's"
+    except RuntimeError:      # a failed HIP call: no further GPU work
+        hip_failed = True
+        raise
+    finally:
+        if not hip_failed:
+            fill_bytes(net.workspace, 0)
