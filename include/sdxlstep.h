@@ -196,6 +196,28 @@ SDXL_API int sdxl_param_range(sdxl_handle* h, int i, size_t* elem_off, size_t* e
 /* copy one tensor in PyTorch layout ([out,in] / [cout,cin,kh,kw]) from device memory into the packed arena
  * (dtype: 0 = fp32, 1 = bf16).  Caller keeps ownership of src. */
 SDXL_API int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src_dev, int dtype, void* stream);
+/* ---- LoRA by merge and project: dtype SDXL_DTYPE_LORA of sdxl_load_weight / sdxl_export_grad (no entry point of its own) ----
+ * For a targeted weight W [out][in] with adapters A [rank][in], B [out][rank] and s = scale (alpha / rank):
+ *   sdxl_load_weight(h, NULL, &op, SDXL_DTYPE_LORA, stream)   merge:   W = bf16_rn(W0 + s B A), written into the bound weight arena;
+ *   sdxl_export_grad(h, NULL, &op, SDXL_DTYPE_LORA, stream)   project: dA = s B^T dW, dB = s dW A^T from the bound fp32 gradient arena.
+ * With this dtype the pointer argument is a HOST pointer to the struct below, read during the call, and `name` must be NULL.  The
+ * forward and the backward run unchanged between the two: dA and dB are exactly the LoRA gradients at the merged weight.
+ * merge: acc <- acc + B[o][k] A[k][i] for k = 0 .. rank - 1, every product and every sum rounded on its own in fp32 (no FMA), then
+ * t = s acc, W = bf16_rn(W0 + t) (round to nearest even), and W = W0 where t == 0: scale 0 or B = 0 give back W0 bit for bit.
+ * project: fp32, no atomics, OVERWRITES its outputs; the summation order is fixed by (out, in, rank) alone, so results are bitwise
+ * reproducible and a target's bits do not depend on the other targets of the call.  One launch merges, two launches project, whatever n.
+ * A target is a 2-D tensor in plain row layout, listed once: attention projections, proj_in / proj_out, ff.net.2, time_emb_proj, the
+ * embedding linears.  Bad arguments (1, before any launch, the message names the tensor): rank outside 1 .. 128, in % 8 != 0, a
+ * convolution or ff.net.0.proj (interleaved rows), a tensor listed twice, a non-NULL name, a NULL or misaligned (16 bytes) pointer.
+ * The handle keeps the device table of the last (target list, rank). */
+#define SDXL_DTYPE_LORA 2
+typedef struct {
+  int n; const int* param;   /* host [n]: state-dict indices (sdxl_param_info order) */
+  int rank; float scale;
+  const void* adapters;      /* device bf16: per target A [rank][in] then B [out][rank], each padded to 8 elements */
+  const void* base;          /* device bf16: the W0 copies, packed [out][in] in target order (load only) */
+  float* adapter_grads;      /* device fp32, laid out like adapters (export only) */
+} sdxl_lora_op;
 SDXL_API int sdxl_export_weight(sdxl_handle* h, const char* name, void* dst_dev, int dtype, void* stream);
 SDXL_API int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst_dev, int dtype, void* stream);
 

@@ -58,6 +58,13 @@ SDXL_API int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, co
 SDXL_API int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off,
                              long* ldb, int* K);
 
+/* the LoRA kernels of SDXL_DTYPE_LORA (csrc/lora.hip) on caller buffers, a table of one target, no handle: W0, w [out][in] bf16, A [rank][in],
+ * B [out][rank] bf16, dw [out][in] fp32, dA [rank][in], dB [out][rank] fp32 (overwritten).  Same argument checks: rank 1 .. 128, in % 8 == 0,
+ * out >= 1, every pointer 16-byte aligned. */
+SDXL_API int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* stream);
+SDXL_API int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale,
+                         void* stream);
+
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the

@@ -56,7 +56,7 @@ class TrainingConfig:                    # data/config.py:152-168
     clip_grad_norm: float = 1.0
     num_workers: int = 4
     save_final_model: bool = True        # data/config.py:170, config.yaml:39: main.py:108 saves on rank 0 after train() when set
-    shard_optimizer: bool = True         # build-only key: data parallel = ZeRO-1 (reduce-scatter -> sharded fused AdamW ->
+    shard_optimizer: Optional[bool] = None   # build-only key (None = not given = True): data parallel = ZeRO-1 (reduce-scatter -> sharded fused AdamW ->
                                          # all-gather) instead of all-reduce + a full update on every rank
     force_exchange: bool = False         # build-only key: drive the gradient exchange through the backend even at world size 1
                                          # (one-GPU RCCL test, tests/test_gpu_rccl.py); SDXL_FORCE_EXCHANGE=1 does the same
@@ -100,6 +100,13 @@ class TrainingConfig:                    # data/config.py:152-168
     validation_eta: float = 1.0          # euler_a only: the share of each step's noise that is drawn afresh (0 = euler), >= 0
     sampler_parameterization: str = "trained"   # ddpm: "trained" = the denoiser this build's loss trains, "reference" = the
                                          # reference's sample_with_ztsnr as written (inconsistent with its own training; sampler.py)
+    # build-only keys: LoRA adapters on a frozen UNet by merge and project (lora.py, csrc/lora.hip); create_trainer picks
+    # lora.NativeLoRATrainer when lora_rank > 0.  Not with use_ema, nor with shard_optimizer: true given explicitly.
+    lora_rank: int = 0                   # 0 = off, else 1 .. 128
+    lora_alpha: Optional[float] = None   # None = rank: s = alpha / rank = 1, the reference's default multiplier
+    lora_targets: Optional[List[str]] = None   # module-path suffixes; None = to_q, to_k, to_v, to_out.0
+    lora_seed: int = 0                   # seed of the A ~ N(0, (1 / rank)^2) initialisation (B = 0)
+    lora_save_merged: bool = False       # save_checkpoint also writes the merged UNet
 
 
 @dataclass

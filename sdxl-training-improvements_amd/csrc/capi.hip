@@ -16,9 +16,16 @@ struct StepState {  // what backward needs from the preceding forward
   float* d_ehs = nullptr;   // the conditioning gradients this micro-step asked for (sdxl_batch_ext): the caller's
   float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
 };
+struct LoraCache {  // device table of the last SDXL_DTYPE_LORA call, keyed by (target list, rank)
+  std::vector<int> params;
+  int rank = 0;
+  LoraTarget* dev = nullptr;
+  int tiles_m = 0, tiles_b = 0, tiles_a = 0;
+};
 struct sdxl_handle {
   Engine e;
   StepState step;
+  LoraCache lora;
 };
 
 #define H_CHECK(h) ARG_CHECK((h) != nullptr, "null handle")
@@ -98,6 +105,7 @@ int sdxl_destroy(sdxl_handle* h) {
   if (h->e.ev_hoist) (void)hipEventDestroy(h->e.ev_hoist);
   if (h->e.side) (void)hipStreamDestroy(h->e.side);
   if (h->e.small_ranges_dev) (void)hipFree(h->e.small_ranges_dev);
+  if (h->lora.dev) (void)hipFree(h->lora.dev);
   delete h;
   return 0;
 }
@@ -153,8 +161,72 @@ int sdxl_param_range(sdxl_handle* h, int i, size_t* elem_off, size_t* elems) {
   return 0;
 }
 
+// ---- LoRA by merge and project (SDXL_DTYPE_LORA): checks, the cached device table, the launches of csrc/lora.hip ----
+static int lora_check_shape(const char* who, int out, int in, int rank) {
+  ARG_CHECK(rank >= 1 && rank <= 128, "lora: rank %d outside 1 .. 128", rank);
+  ARG_CHECK(out >= 1 && in >= 8 && in % 8 == 0, "lora: '%s' is [%d][%d]: `in` must be a positive multiple of 8 (16-byte rows)", who, out, in);
+  return 0;
+}
+static bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
+
+static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q) {
+  ARG_CHECK(name == nullptr, "lora: `name` must be NULL with SDXL_DTYPE_LORA (the targets are listed in sdxl_lora_op.param)");
+  ARG_CHECK(op && op->n >= 1 && op->param, "lora: empty target list");
+  ARG_CHECK(op->rank >= 1 && op->rank <= 128, "lora: rank %d outside 1 .. 128", op->rank);
+  ARG_CHECK(isfinite(op->scale), "lora: scale is not finite");
+  ARG_CHECK(aligned16(op->adapters), "lora: adapters must be a 16-byte aligned device pointer");
+  if (merge) ARG_CHECK(aligned16(op->base), "lora: base must be a 16-byte aligned device pointer");
+  else ARG_CHECK(aligned16(op->adapter_grads), "lora: adapter_grads must be a 16-byte aligned device pointer");
+  Engine& e = h->e;
+  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lora: %s are not bound", merge ? "weights" : "grads");
+  LoraCache& c = h->lora;
+  std::vector<int> params(op->param, op->param + op->n);
+  if (!(c.dev && c.rank == op->rank && c.params == params)) {
+    std::vector<LoraTarget> tab(params.size());
+    std::vector<char> seen(e.src.size(), 0);
+    long a = 0, b = 0, tm = 0, tb = 0, ta = 0;
+    for (size_t i = 0; i < params.size(); ++i) {
+      const int pi = params[i];
+      ARG_CHECK(pi >= 0 && pi < (int)e.src.size(), "lora: parameter index %d out of range", pi);
+      const SrcParam& sp = e.src[pi];
+      ARG_CHECK(sp.ndim == 2 && sp.kind == 0, "lora: '%s' is not a 2-D weight in plain row layout (convolutions and the interleaved "
+                "ff.net.0.proj cannot be targets)", sp.name.c_str());
+      ARG_CHECK(!seen[pi], "lora: '%s' is listed twice", sp.name.c_str());
+      seen[pi] = 1;
+      const int out = (int)sp.shape[0], in = (int)sp.shape[1];
+      CHK(lora_check_shape(sp.name.c_str(), out, in, op->rank));
+      LoraTarget& t = tab[i];
+      t.w_off = (long)(sp.native.off + sp.elem_off);
+      ARG_CHECK(t.w_off % 8 == 0, "lora: '%s' does not start on a 16-byte boundary of the arena", sp.name.c_str());
+      t.base_off = b; b += (long)out * in;
+      t.a_off = t.ga_off = a; a += ((long)op->rank * in + 7) / 8 * 8;
+      t.b_off = t.gb_off = a; a += ((long)out * op->rank + 7) / 8 * 8;
+      t.out = out; t.in = in; t.pad = 0;
+      t.tile_m = (int)tm; t.tile_b = (int)tb; t.tile_a = (int)ta;
+      tm += lora_tiles_m(out, in); tb += lora_tiles_b(out, in); ta += lora_tiles_a(out, in);
+      ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "lora: too many tiles");
+    }
+    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
+    HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
+    HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
+    c.params = params; c.rank = op->rank;
+    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
+  }
+  memset(&q, 0, sizeof(q));
+  q.table = c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a;
+  q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = (const bf16*)op->adapters;
+  q.dw = e.grads; q.ga = q.gb = op->adapter_grads;
+  return 0;
+}
+
 int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtype, void* st) {
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LORA) {
+    LoraP q;
+    CHK(lora_prepare(h, name, (const sdxl_lora_op*)src, true, q));
+    return launch_lora_merge(q, (hipStream_t)st);
+  }
   ARG_CHECK(name && src, "null argument");
   return engine_load_weight(h->e, name, src, dtype, (hipStream_t)st);
 }
@@ -165,8 +237,38 @@ int sdxl_export_weight(sdxl_handle* h, const char* name, void* dst, int dtype, v
 }
 int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, void* st) {
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LORA) {
+    LoraP q;
+    CHK(lora_prepare(h, name, (const sdxl_lora_op*)dst, false, q));
+    return launch_lora_project(q, (hipStream_t)st);
+  }
   ARG_CHECK(name && dst, "null argument");
   return engine_export(h->e, name, dst, dtype, true, (hipStream_t)st);
+}
+
+static int lora_one(int out, int in, int rank, float scale, LoraP& q) {
+  CHK(lora_check_shape("the operand", out, in, rank));
+  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = scale;
+  q.one.out = out; q.one.in = in;
+  q.tiles_m = lora_tiles_m(out, in); q.tiles_b = lora_tiles_b(out, in); q.tiles_a = lora_tiles_a(out, in);
+  return 0;
+}
+int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* st) {
+  ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(lora_one(out, in, rank, scale, q));
+  q.w = (bf16*)w; q.base = (const bf16*)base; q.a = (const bf16*)A; q.b = (const bf16*)B;
+  return launch_lora_merge(q, (hipStream_t)st);
+}
+int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, void* st) {
+  ARG_CHECK(aligned16(dw) && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB),
+            "lora_project: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(lora_one(out, in, rank, scale, q));
+  q.dw = dw; q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
+  return launch_lora_project(q, (hipStream_t)st);
 }
 
 int sdxl_plan(sdxl_handle* h, int B, int H, int W, int ctx, size_t* ws_bytes) {

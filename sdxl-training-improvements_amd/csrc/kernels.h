@@ -478,3 +478,39 @@ struct CondDgradP {
 };
 size_t cond_dgrad_slab_floats(int n, const int* K, int M, int N);
 int launch_cond_dgrad(const CondDgradP& p, hipStream_t st);
+
+// ---- LoRA by merge and project (lora.hip): table-driven, one launch of each kernel covers every target ----
+#define LORA_M_ROWS 32    // merge tile
+#define LORA_M_COLS 64
+#define LORA_M_KC 32      // ranks staged per step
+#define LORA_B_ROWS 32    // dB: rows per workgroup
+#define LORA_B_COLS 256   //     columns staged per step
+#define LORA_B_KC 16      //     ranks per pass over the rows
+#define LORA_A_COLS 128   // dA: columns per workgroup
+#define LORA_A_ROWS 32    //     rows staged per step
+struct LoraTarget {       // one targeted weight [out][in]; element offsets from the launch's pointers
+  long w_off;             // weight / gradient arena
+  long base_off;          // packed W0
+  long a_off, b_off;      // adapter arena: A [rank][in], B [out][rank]
+  long ga_off, gb_off;    // adapter-gradient arena: dA, dB
+  int out, in;            // in % 8 == 0
+  int tile_m, tile_b, tile_a;   // first workgroup of this target in the merge / dB / dA launch
+  int pad;
+};
+struct LoraP {
+  const LoraTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
+  LoraTarget one;
+  int n, rank;                  // rank 1 .. 128
+  float scale;
+  int tiles_m, tiles_b, tiles_a;
+  bf16* w;                      // merge: out
+  const bf16* base;             // merge
+  const bf16 *a, *b;            // what a_off / b_off count from: the adapter arena twice, or the hook's A and B (offsets 0)
+  const float* dw;              // project
+  float *ga, *gb;               // project: out, overwritten; what ga_off / gb_off count from (the gradient arena twice, or dA and dB)
+};
+static inline int lora_tiles_m(int out, int in) { return cdiv(out, LORA_M_ROWS) * cdiv(in, LORA_M_COLS); }
+static inline int lora_tiles_b(int out, int in) { return cdiv(out, LORA_B_ROWS); }
+static inline int lora_tiles_a(int out, int in) { return cdiv(in, LORA_A_COLS); }
+int launch_lora_merge(const LoraP& p, hipStream_t st);
+int launch_lora_project(const LoraP& p, hipStream_t st);     // two launches: dB, dA

@@ -94,6 +94,15 @@ class CondGradBatch(SamplerBatch):
     _fields_ = [("d_prompt_embeds", C.c_void_p), ("d_pooled", C.c_void_p)]
 
 
+DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
+
+
+class LoraOp(C.Structure):
+    """sdxl_lora_op: the targets (state-dict indices), rank, scale and the adapter / base / adapter-gradient arenas of lora.LoRAAdapters"""
+    _fields_ = [("n", C.c_int), ("param", C.POINTER(C.c_int)), ("rank", C.c_int), ("scale", C.c_float),
+                ("adapters", C.c_void_p), ("base", C.c_void_p), ("adapter_grads", C.c_void_p)]
+
+
 LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
 MASK_NORMS = {"mean": 0, "masked_mean": 1}
 
@@ -183,6 +192,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_sampler_step": [_vp, _vp, _vp, _i, _i, _i, _P(SamplerStep), _vp],
     "sdxl_debug_cond_operands": [_vp, _i, _i, _P(_i), _P(_sz), _P(_l), _P(_sz), _P(_l), _P(_i)],
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
+    "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
 }
 # include/sdxlstep_diag.h part 2: experiment ABI, exported by libsdxlstep_diag.so only
 DIAG_SIGNATURES = {

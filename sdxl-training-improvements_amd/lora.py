@@ -1,0 +1,343 @@
+"""LoRA by merge and project: adapters on a frozen UNet without touching the engine, the plan or any existing kernel.
+
+For a targeted weight W [out, in] with adapters A [r, in], B [out, r] and s = alpha / r (the reference's `LoRAModuleWrapper`,
+src/models/adapters/lora.py: base(x) + alpha * up(down(x)), up = B, down = A):
+
+  merge    before the forward the weight arena holds W = bf16(W0 + s B A), W0 a frozen bf16 copy of the checkpoint's weight;
+  backward the existing forward and backward run unchanged and leave dW = dL/dW in the fp32 gradient arena;
+  project  dA = s B^T dW, dB = s dW A^T: exactly the LoRA gradients at the merged weight.
+
+Both steps are one call into libsdxlstep (csrc/lora.hip through dtype SDXL_DTYPE_LORA of sdxl_load_weight / sdxl_export_grad).
+LoRAAdapters owns the small arenas and looks to a fused optimizer like a net (weights, grads, L, zero_grads, param_ranges), so
+AdamWBF16 / AdamWScheduleFreeKahanBF16 update it unchanged.  NativeLoRATrainer is the trainer `training.lora_rank > 0` selects.
+What this does not save: the weight gradients of the frozen tensors are still computed (skipping them is the engine's business).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import logging
+from pathlib import Path
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import distributed as D
+from . import lib
+from .optimizer import FusedArenaOptimizer
+from .trainer import NativeSDXLTrainer, build_optimizer, checkpoint_dir
+
+logger = logging.getLogger(__name__)
+
+DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
+MAX_RANK = 128
+
+
+def _pad8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str]) -> List[str]:
+    """The `.weight` keys of `shapes` (state-dict order) whose module path is a pattern or ends in "." + pattern.  ValueError for a
+    pattern that matches nothing and for one that matches a tensor the kernels cannot take: a convolution, the row-interleaved
+    `ff.net.0.proj`, or an `in` that is no multiple of 8."""
+    patterns = [str(p) for p in patterns]
+    if not patterns:
+        raise ValueError("lora_targets: no pattern given")
+    out, hit = [], {p: 0 for p in patterns}
+    for key, shape in shapes.items():
+        if not key.endswith(".weight"):
+            continue
+        mod = key[: -len(".weight")]
+        ps = [p for p in patterns if mod == p or mod.endswith("." + p)]
+        if not ps:
+            continue
+        for p in ps:
+            hit[p] += 1
+        if len(shape) != 2:
+            raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key} {tuple(shape)}: only 2-D linear weights can carry an adapter")
+        if mod.endswith("ff.net.0.proj"):
+            raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key}: ff.net.0.proj is stored row-interleaved (GEGLU) and cannot "
+                             "carry an adapter")
+        if shape[1] % 8:
+            raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key} {tuple(shape)}: `in` must be a multiple of 8")
+        out.append(key)
+    missing = [p for p, n in hit.items() if n == 0]
+    if missing:
+        raise ValueError(f"lora_targets: pattern {missing[0]!r} matches no tensor")
+    return out
+
+
+def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int):
+    """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements"""
+    lay, cur = {}, 0
+    for k in targets:
+        o, i = (int(v) for v in shapes[k])
+        a, cur = cur, cur + _pad8(rank * i)
+        b, cur = cur, cur + _pad8(o * rank)
+        lay[k] = (a, b, o, i)
+    return lay, cur
+
+
+class LoRAAdapters:
+    """The adapters of one net: bf16 arena `.weights`, fp32 `.grads` laid out like it, and the packed bf16 copy of the targets' W0."""
+
+    def __init__(self, net, rank: int, alpha: Optional[float] = None, targets: Optional[Sequence[str]] = None, seed: int = 0):
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
+            raise ValueError(f"lora_rank must be an integer in 1 .. {MAX_RANK} (got {rank!r})")
+        self.net = net
+        self.L = getattr(net, "L", None)
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scale = self.alpha / rank
+        self.seed = int(seed)
+        shapes = net.param_shapes()
+        self.patterns = tuple(DEFAULT_TARGETS if targets is None else targets)
+        self.targets = resolve_targets(shapes, self.patterns)
+        names = list(shapes)
+        self.index = [names.index(k) for k in self.targets]
+        self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank)
+        dev = net.weights.device
+        self.weights = torch.zeros(self.param_elems, dtype=torch.bfloat16, device=dev)
+        self.grads = torch.zeros(self.param_elems, dtype=torch.float32, device=dev)
+        ranges = net.param_ranges()
+        self.base = torch.cat([net.weights[ranges[k][0]: ranges[k][0] + ranges[k][1]] for k in self.targets])
+        assert self.base.numel() == sum(o * i for _a, _b, o, i in self.layout.values())
+        g = torch.Generator().manual_seed(self.seed)          # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
+        for k in self.targets:
+            a, _b, _o, i = self.layout[k]
+            self.weights[a: a + rank * i] = (torch.randn(rank, i, generator=g) * (1.0 / rank)).to(torch.bfloat16).reshape(-1).to(dev)
+        self._param = (C.c_int * len(self.index))(*self.index)
+
+    # ---- what a fused optimizer asks of its net
+    def zero_grads(self) -> None:
+        self.grads.zero_()
+
+    def param_ranges(self) -> Dict[str, Tuple[int, int]]:
+        """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas"""
+        out = {}
+        for k, (a, b, o, i) in self.layout.items():
+            mod = k[: -len(".weight")]
+            out[f"{mod}.lora_A.weight"] = (a, _pad8(self.rank * i))
+            out[f"{mod}.lora_B.weight"] = (b, _pad8(o * self.rank))
+        return out
+
+    # ---- views
+    def A(self, key: str, grad: bool = False) -> torch.Tensor:
+        a, _b, _o, i = self.layout[key]
+        return (self.grads if grad else self.weights)[a: a + self.rank * i].view(self.rank, i)
+
+    def B(self, key: str, grad: bool = False) -> torch.Tensor:
+        _a, b, o, _i = self.layout[key]
+        return (self.grads if grad else self.weights)[b: b + o * self.rank].view(o, self.rank)
+
+    # ---- the two device steps
+    def _op(self, scale: float) -> lib.LoraOp:
+        return lib.LoraOp(len(self.index), self._param, self.rank, float(scale), self.weights.data_ptr(), self.base.data_ptr(),
+                          self.grads.data_ptr())
+
+    def _call(self, fn_name: str, scale: float) -> None:
+        if self.L is None:
+            raise lib.SdxlError(f"LoRAAdapters.{fn_name}: needs libsdxlstep.so (there is no PyTorch fallback)")
+        op = self._op(scale)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        lib.check(getattr(self.L, fn_name)(self.net.h, None, C.byref(op), lib.DTYPE_LORA, st), f"{fn_name} (lora)")
+
+    def merge(self, scale: Optional[float] = None) -> None:
+        """W = bf16(W0 + s B A) for every target, into the net's weight arena (one launch)"""
+        self._call("sdxl_load_weight", self.scale if scale is None else scale)
+
+    def restore(self) -> None:
+        """the checkpoint's weights back, bit for bit (a merge with scale 0)"""
+        self.merge(0.0)
+
+    def project(self) -> None:
+        """dA, dB of every target from the net's fp32 gradient arena into `.grads` (overwritten; two launches)"""
+        self._call("sdxl_export_grad", self.scale)
+
+    # ---- state
+    def _meta(self) -> Dict[str, Any]:
+        return {"rank": self.rank, "alpha": self.alpha, "seed": self.seed, "targets": list(self.targets),
+                "shapes": [[self.layout[k][2], self.layout[k][3]] for k in self.targets]}
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {**self._meta(), "weights": self.weights.detach().cpu().clone()}
+
+    def check_state_dict(self, sd: Dict[str, Any]) -> None:
+        mine = self._meta()
+        for key in ("rank", "targets", "shapes"):
+            if sd.get(key) != mine[key]:
+                raise ValueError(f"lora state: {key} differs from this trainer's ({_brief(sd.get(key))} vs {_brief(mine[key])})")
+        w = sd.get("weights")
+        if not (torch.is_tensor(w) and w.dtype == torch.bfloat16 and w.numel() == self.param_elems):
+            raise ValueError(f"lora state: the adapter arena must be {self.param_elems} bf16 elements")
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """bit-exact; ValueError, with nothing changed, when rank, targets or shapes differ"""
+        self.check_state_dict(sd)
+        self.alpha = float(sd.get("alpha", self.alpha))
+        self.scale = self.alpha / self.rank
+        self.weights.copy_(sd["weights"].reshape(-1))
+
+    def export_tensors(self) -> Dict[str, torch.Tensor]:
+        """{"unet.<module>.lora_A.weight", "unet.<module>.lora_B.weight"} in fp32 on the CPU, s folded into lora_B: a loader that
+        assumes alpha = rank (scale 1) reproduces the delta s B A"""
+        out = {}
+        for k in self.targets:
+            mod = k[: -len(".weight")]
+            out[f"unet.{mod}.lora_A.weight"] = self.A(k).float().cpu().contiguous()
+            out[f"unet.{mod}.lora_B.weight"] = (self.B(k).float().cpu() * torch.tensor(self.scale, dtype=torch.float32)).contiguous()
+        return out
+
+
+def _brief(v) -> str:
+    s = repr(v)
+    return s if len(s) <= 80 else s[:77] + "..."
+
+
+class _AdapterGradSync:
+    """What the base trainer asks of its gradient exchange, for a trainer whose full-size arena is never exchanged: the backward runs
+    without exchange and without emit mode (active is False), scaled by 1 / world; the adapter gradients are all-reduced after the
+    projection (NativeLoRATrainer._project)."""
+
+    def __init__(self):
+        self.world = D.get_world_size()
+        self.rank = 0
+        self.active = False
+        self.enabled = False
+        self.comm = None
+
+    def on_segment(self, k, offset, count) -> None:
+        pass
+
+    def finish(self) -> None:
+        pass
+
+    def reduced(self):
+        return None
+
+
+class NativeLoRATrainer(NativeSDXLTrainer):
+    """NativeSDXLTrainer with a frozen UNet and LoRA adapters (training.lora_rank > 0).  Per cycle: the micro-steps' backwards
+    accumulate dW in the fp32 arena as ever; optimizer_step() projects, all-reduces the adapter gradients (world > 1), clips on them,
+    steps the fused optimizer on the adapter arena and merges.  The weight arena always holds the merged model, so sample / validate /
+    evaluate work as they are.  A caller-owned loop may end its cycle with optimizer.step() as with the base trainer: the step projects first."""
+
+    name = "native_mi355x_lora"
+
+    def __init__(self, model, optimizer=None, train_dataloader=None, device=None, wandb_logger=None, config=None, **kwargs):
+        tc = config.training if config is not None else None
+        rank = getattr(tc, "lora_rank", 0)
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
+            raise ValueError(f"training.lora_rank must be an integer in 1 .. {MAX_RANK} for the LoRA trainer (got {rank!r})")
+        if bool(getattr(tc, "use_ema", False)):
+            raise ValueError("training.use_ema: an EMA of adapters is not supported (training.lora_rank > 0)")
+        if getattr(tc, "shard_optimizer", None):          # None = not given
+            raise ValueError("training.shard_optimizer: ZeRO-1 is not supported for adapters (training.lora_rank > 0); leave the key out")
+        if optimizer is not None:
+            logger.warning("NativeLoRATrainer builds its own fused optimizer on the adapter arena: the optimizer passed in is ignored")
+        super().__init__(model, None, train_dataloader, device, wandb_logger, config, **kwargs)
+        self._projected = False
+        # whoever steps the optimizer -- optimizer_step() below or a caller-owned loop's optimizer.step() -- steps it on the projected
+        # (and exchanged) gradients of the cycle, never on stale ones, and the merge follows the update
+        inner = self.optimizer.step
+
+        def step(*a, **k):
+            if a[:1] == (None,) or (not a and k.get("grads") is None):      # the adapters' own gradient arena
+                self._project()
+            return inner(*a, **k)
+
+        self.optimizer.step = step
+        self.optimizer.register_step_post_hook(lambda *_a, **_k: self.lora.merge())
+        if self.lora.L is not None:
+            self.lora.merge()
+
+    # the two builders of the base class: no full-model optimizer arenas, no full-size exchange buffers
+    def _build_optimizer(self, optimizer):
+        tc = self.config.training
+        alpha = getattr(tc, "lora_alpha", None)
+        targets = getattr(tc, "lora_targets", None)
+        if isinstance(targets, str):
+            targets = [targets]
+        self.lora = LoRAAdapters(self.net, int(tc.lora_rank), alpha, targets, int(getattr(tc, "lora_seed", 0)))
+        opt = build_optimizer(self.lora, self.config.optimizer)
+        assert isinstance(opt, FusedArenaOptimizer)
+        return opt
+
+    def _build_grad_sync(self):
+        return _AdapterGradSync()
+
+    # ---- the cycle's end
+    def _native_backward(self, grad_scale: float) -> None:
+        super()._native_backward(grad_scale)
+        self._projected = False
+
+    def _project(self) -> None:
+        if self._projected:
+            return
+        self.lora.project()
+        if self.sync.world > 1:      # the backward already scaled by 1 / world, and projection is linear
+            torch.distributed.all_reduce(self.lora.grads)
+        self._projected = True
+
+    def clip_grad_norm_(self, max_norm: float) -> float:
+        self._project()
+        g = self.lora.grads
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        buf = torch.empty(2, dtype=torch.float32, device=g.device)
+        lib.check(self.net.L.sdxl_sumsq(C.c_void_p(g.data_ptr()), 0, g.numel(), C.c_void_p(buf.data_ptr()), st), "sdxl_sumsq")
+        lib.check(self.net.L.sdxl_clip_coef(C.c_void_p(buf.data_ptr()), float(max_norm), C.c_void_p(buf.data_ptr() + 4), st),
+                  "sdxl_clip_coef")
+        self._clip_coef = buf[1:2]
+        return float(buf[0].sqrt())
+
+    def optimizer_step(self) -> Optional[float]:
+        self._project()
+        gn = None
+        if self.config.training.clip_grad_norm and self.config.training.clip_grad_norm > 0:
+            gn = self.clip_grad_norm_(float(self.config.training.clip_grad_norm))
+        self.optimizer.step(None, grad_scale=self._clip_coef)          # (its post hook merges)
+        self._clip_coef = None
+        self._end_cycle()
+        return gn
+
+    # ---- checkpoints
+    def sync_to_model(self, ema: bool = False) -> None:
+        if ema:
+            raise ValueError("sync_to_model(ema=True): the LoRA trainer keeps no EMA")
+        super().sync_to_model()
+
+    def save_checkpoint(self, epoch_or_path=0, is_final: bool = False) -> Optional[Path]:
+        """`pytorch_lora_weights.safetensors` (fp32, keys unet.<module>.lora_A.weight / .lora_B.weight, s folded into lora_B),
+        `lora_state.pt` (the bit-exact arena, settings and target list: load_lora_state), `optimizer.pt`, `config.json`; the merged
+        UNet only with training.lora_save_merged.  Rank 0 writes; no collective."""
+        if not D.is_main_process():
+            return None
+        from safetensors.torch import save_file
+        d = checkpoint_dir(epoch_or_path, is_final)
+        d.mkdir(parents=True, exist_ok=True)
+        save_file(self.lora.export_tensors(), str(d / "pytorch_lora_weights.safetensors"))
+        torch.save(self.lora.state_dict(), str(d / "lora_state.pt"))
+        with open(d / "config.json", "w") as f:
+            json.dump(self.config.to_dict(), f, indent=2)
+        torch.save(self._optimizer_state_for_save(), str(d / "optimizer.pt"))
+        if bool(getattr(self.config.training, "lora_save_merged", False)):
+            self.sync_to_model()
+            if self._torch_unet is not None and callable(getattr(self.model, "save_pretrained", None)):
+                self.model.save_pretrained(str(d), safe_serialization=True)
+            else:
+                (d / "unet").mkdir(exist_ok=True)
+                save_file({k: v.cpu().contiguous() for k, v in self.net.state_dict().items()},
+                          str(d / "unet" / "diffusion_pytorch_model.safetensors"))
+        return d
+
+    def load_lora_state(self, checkpoint_dir) -> None:
+        """resume from save_checkpoint's directory: the adapter arena bit for bit, optimizer.pt when it is there, then the merge.
+        ValueError, with the trainer's state as it was, for a state whose rank, targets or shapes differ."""
+        d = Path(checkpoint_dir)
+        sd = torch.load(str(d / "lora_state.pt"), map_location="cpu", weights_only=True)
+        self.lora.check_state_dict(sd)
+        if (d / "optimizer.pt").exists():
+            self.load_optimizer_state(d)
+        self.lora.load_state_dict(sd)
+        self.lora.merge()

@@ -126,16 +126,10 @@ class NativeSDXLTrainer:
             raise TypeError("model.unet must be a NativeUNet or a module with a diffusers-keyed state_dict(); got "
                             f"{type(unet).__name__}")
         self.noise_scheduler = NoiseScheduler(self.config, "cpu")
-        self.optimizer = optimizer if optimizer is not None else build_optimizer(self.net, self.config.optimizer)
+        self.optimizer = self._build_optimizer(optimizer)
         self.ema = build_ema(self.net, self.optimizer, self.config.training)     # None unless training.use_ema
         self._clip_coef = None
-        # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
-        want_sharded = bool(getattr(self.config.training, "shard_optimizer", True)) and isinstance(self.optimizer, FusedArenaOptimizer)
-        seg_sizes = [n for _off, n in self.net.segment_ranges()] if hasattr(self.net, "segment_ranges") else None
-        # force_exchange (build-only key / SDXL_FORCE_EXCHANGE=1): run the exchange through the backend even at world size 1
-        force = bool(getattr(self.config.training, "force_exchange", False)) or os.environ.get("SDXL_FORCE_EXCHANGE", "0") == "1"
-        self.sync = D.make_grad_sync(self.net.param_elems, self._cast, torch.bfloat16, getattr(self.net, "device", "cpu"),
-                                     sharded=want_sharded, segment_sizes=seg_sizes, force=force)
+        self.sync = self._build_grad_sync()
         self.sharded = isinstance(self.sync, D.ShardedGradSync)      # (falls back to all-reduce where the segments do not split)
         self._emit = False                   # this backward's weight-gradient GEMMs write the bf16 exchange arena themselves
         self._micro = 0                      # micro-step index inside the accumulation cycle
@@ -146,6 +140,22 @@ class NativeSDXLTrainer:
         hook = getattr(self.optimizer, "register_step_post_hook", None)
         if callable(hook):                   # an optimizer step ends the accumulation cycle, whoever calls it
             hook(lambda *_a, **_k: self._end_cycle())
+
+    # -------------------------------------------------------------------------------- the two builders a subclass may replace
+    def _build_optimizer(self, optimizer):
+        """the caller's optimizer, else the fused one the config names, on the net's arenas (lora.NativeLoRATrainer: on the adapters')"""
+        return optimizer if optimizer is not None else build_optimizer(self.net, self.config.optimizer)
+
+    def _build_grad_sync(self):
+        """the gradient exchange of the full arena, with its exchange buffers"""
+        # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
+        so = getattr(self.config.training, "shard_optimizer", None)          # None = not given: the default, sharded
+        want_sharded = (True if so is None else bool(so)) and isinstance(self.optimizer, FusedArenaOptimizer)
+        seg_sizes = [n for _off, n in self.net.segment_ranges()] if hasattr(self.net, "segment_ranges") else None
+        # force_exchange (build-only key / SDXL_FORCE_EXCHANGE=1): run the exchange through the backend even at world size 1
+        force = bool(getattr(self.config.training, "force_exchange", False)) or os.environ.get("SDXL_FORCE_EXCHANGE", "0") == "1"
+        return D.make_grad_sync(self.net.param_elems, self._cast, torch.bfloat16, getattr(self.net, "device", "cpu"),
+                                sharded=want_sharded, segment_sizes=seg_sizes, force=force)
 
     # -------------------------------------------------------------------------------- loss
     def _cast(self, off, n, dst):
@@ -855,4 +865,10 @@ def create_trainer(model, optimizer=None, train_dataloader=None, device=None, wa
     """BaseRouter.create equivalent for model_type == "sdxl" (base_router.py:48-84)."""
     if config is not None and str(config.model.model_type).lower() != "sdxl":
         raise ValueError(f"Unsupported model type: {config.model.model_type}")
+    rank = getattr(config.training, "lora_rank", 0) if config is not None else 0
+    if isinstance(rank, bool) or not isinstance(rank, int) or rank < 0:
+        raise ValueError(f"training.lora_rank must be an integer >= 0 (got {rank!r})")
+    if rank > 0:                       # LoRA adapters on a frozen UNet (lora.py)
+        from .lora import NativeLoRATrainer
+        return NativeLoRATrainer(model, optimizer, train_dataloader, device, wandb_logger, config, **kw)
     return NativeSDXLTrainer(model, optimizer, train_dataloader, device, wandb_logger, config, **kw)
