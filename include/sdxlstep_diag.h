@@ -65,6 +65,19 @@ SDXL_API int sdxl_op_lora_merge(const void* base, const void* A, const void* B, 
 SDXL_API int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale,
                          void* stream);
 
+/* which kernel a GEMM launch takes (csrc/gemm.hip, gemm_route: the single implementation of DESIGN.md section 4's table), without launching it and
+ * without a device.  The descriptor is what the problem's line in the launch log (SDXL_LAUNCH_LOG) carries, in the same order: emit_bf16 / delta /
+ * bias_grad are presence flags (GemmP::Cb, delta_out, bias_grad); Hm .. sd the 3x3 gather's image sizes and strides (taps != 1).  The same checks and normalisation as
+ * a launch are applied first (their errors are returned).  kernel: 0 the 128-row kernel (cfg 1, 2, 3, 13, 23, 5, 6), 1 the 256 x 256 kernel, 2 the
+ * co-resident 256-row kernel (cfg 31 .. 36), 3 the pipelined kernel (cfg 7, 8), 4 the long-reduction weight gradient, 5 the three-tap convolution
+ * weight gradient, 6 stream-K (diagnostics build); fast: the 128-row kernel's FAST staging; post: 0 none, 1 fp32 split-K reduce, 2 split-K sum +
+ * bf16 epilogue. */
+typedef struct sdxl_gemm_desc {
+  int form, taps, M, N, K, splitk, group, cfg, geglu, geglu_group, Hm, Wm, Hs, Ws, sm, sd, up2, emit_bf16, delta, bias_grad;
+} sdxl_gemm_desc;
+typedef struct sdxl_gemm_route { int kernel, cfg, fast, post; } sdxl_gemm_route;
+SDXL_API int sdxl_debug_gemm_route(const sdxl_gemm_desc* problem, sdxl_gemm_route* out);
+
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the

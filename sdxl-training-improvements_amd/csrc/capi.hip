@@ -888,7 +888,7 @@ int sdxl_op_gemm(int form, const void* A, const void* B, void* C, int M, int N, 
     CHK(test_slab(gemm_slab_floats(M, N, 1, splitk), &g.slab));
   }
   if (form == GEMM_TN) {
-    if (splitk <= 0) splitk = wgrad256_policy(M, N, K) ? wgrad256_pick_splitk(M, N, K) : gemm_pick_splitk(M, N, 1, K);     // the plan's choice
+    if (splitk <= 0) splitk = linear_wgrad_splitk(M, N, K);     // the plan's choice
     g.lda = M; g.ldb = N; g.out_f32 = 1; g.splitk = splitk;
     if (splitk > 1) CHK(test_slab(gemm_slab_floats(M, N, 1, splitk), &g.slab));
   }
@@ -948,20 +948,11 @@ int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, floa
 
 int sdxl_op_conv3x3_fwd(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
                         int stride, void* st) {
-  int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_NT;
+  GemmP g = conv3x3_fwd_problem(B, H, W, Cin, Cout, stride);
   g.A = (const bf16*)x; g.B = (const bf16*)w; g.C = y;
-  g.M = B * Ho * Wo; g.N = Cout; g.K = Cin;
-  g.lda = Cin; g.ldb = 9L * Cin; g.ldc = Cout;
-  g.taps = 9; g.Hm = Ho; g.Wm = Wo; g.Hs = H; g.Ws = W; g.sm = stride; g.sd = 1;
-  g.b_tap_stride = Cin;
   g.bias = (const bf16*)bias;
-  if (stride == 1 && Cin % 64 == 0) {     // as the plan does: small images split the (tap, channel) reduction
-    g.splitk = gemm_pick_splitk_small(g.M, Cout, 9 * Cin, 0);
-    if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cout, 1, g.splitk), &g.slab));
-  }
+  g.splitk = conv3x3_fwd_splitk(B, H, W, Cin, Cout, stride);
+  if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cout, 1, g.splitk), &g.slab));
   return launch_gemm(g, (hipStream_t)st);
 }
 // y = conv3x3(upsample2x(x)) and its input gradient without the upsampled image (GemmP::up2); weff [Cout][16][Cin] and planar
@@ -969,7 +960,7 @@ int sdxl_op_conv3x3_fwd(const void* x, const void* w, const void* bias, void* y,
 int sdxl_op_upconv3x3_fwd(const void* x, const void* w, const void* bias, void* weff, void* planar, void* y, int B, int H, int W,
                           int Cin, int Cout, void* st) {
   const int Mp = 4 * (int)upconv_plane_rows(B, H, W);
-  int splitk = gemm_pick_splitk_small(Mp, Cout, 4 * Cin, 0);
+  int splitk = upconv3x3_fwd_splitk(B, H, W, Cin, Cout);
   float* slab = nullptr;
   if (splitk > 1) CHK(test_slab(gemm_slab_floats(Mp, Cout, 1, splitk), &slab));
   return launch_upconv3x3_fwd((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)weff, (bf16*)planar, (bf16*)y, B, H, W, Cin, Cout,
@@ -977,7 +968,7 @@ int sdxl_op_upconv3x3_fwd(const void* x, const void* w, const void* bias, void* 
 }
 int sdxl_op_upconv3x3_dgrad(const void* dy, const void* weff, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
                             int Cout, void* st) {
-  int splitk = gemm_pick_splitk_small(B * H * W, Cin, 16 * Cout, 1);
+  int splitk = upconv3x3_dgrad_splitk(B, H, W, Cin, Cout);
   float* slab = nullptr;
   if (splitk > 1) CHK(test_slab(gemm_slab_floats(B * H * W, Cin, 1, splitk), &slab));
   return launch_upconv3x3_dgrad((const bf16*)dy, (const bf16*)weff, (bf16*)planar, (bf16*)dx, (const bf16*)addend, B, H, W, Cin, Cout, splitk,
@@ -1015,51 +1006,27 @@ int sdxl_op_upconv3x3_wgrad(const void* planar, const void* x, float* dweff, flo
 }
 int sdxl_op_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B, int H, int W, int Cin, int Cout, int stride,
                           void* st) {
-  int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_NN;
+  GemmP g = conv3x3_dgrad_problem(B, H, W, Cin, Cout, stride);
   g.A = (const bf16*)dy; g.B = (const bf16*)w; g.C = dx;
-  g.M = B * H * W; g.N = Cin; g.K = Cout;
-  g.lda = Cout; g.ldb = 9L * Cin; g.ldc = Cin;
-  g.taps = 9; g.Hm = H; g.Wm = W; g.Hs = Ho; g.Ws = Wo; g.sm = 1; g.sd = stride;
-  g.flip = 1; g.b_tap_stride = Cin;
-  if (stride == 1 && Cout % 64 == 0) {
-    g.splitk = gemm_pick_splitk_small(g.M, Cin, 9 * Cout, 1);
-    if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cin, 1, g.splitk), &g.slab));
-  }
+  g.splitk = conv3x3_dgrad_splitk(B, H, W, Cin, Cout, stride);
+  if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cin, 1, g.splitk), &g.slab));
   return launch_gemm(g, (hipStream_t)st);
 }
 int sdxl_op_conv3x3_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin, int Cout, int stride,
                           int splitk, void* st) {
-  int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_TN;
+  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
   g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
-  g.M = Cout; g.N = Cin; g.K = B * Ho * Wo;
-  g.lda = Cout; g.ldb = Cin; g.ldc = 9L * Cin;
-  g.taps = 9; g.Hm = Ho; g.Wm = Wo; g.Hs = H; g.Ws = W; g.sm = stride; g.sd = 1;
-  g.c_tap_stride = Cin;
-  g.out_f32 = 1; g.splitk = splitk; g.accumulate = 1;
+  g.splitk = splitk; g.accumulate = 1;
   if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
   return launch_gemm(g, (hipStream_t)st);
 }
 
 int sdxl_op_conv3x3_wgrad2(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout, int stride,
                            int splitk, int accumulate, void* st) {
-  int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_TN;
+  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
   g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
-  g.M = Cout; g.N = Cin; g.K = B * Ho * Wo;
-  g.lda = Cout; g.ldb = Cin; g.ldc = 9L * Cin;
-  g.taps = 9; g.Hm = Ho; g.Wm = Wo; g.Hs = H; g.Ws = W; g.sm = stride; g.sd = 1;
-  g.c_tap_stride = Cin;
-  g.out_f32 = 1; g.accumulate = accumulate; g.bias_grad = dbias;
-  // splitk <= 0: the plan's choice (the three-taps-per-workgroup kernel has its own)
-  if (splitk <= 0) splitk = conv_wgrad3_policy(Cout, Cin, g.K, Wo, stride) ? conv_wgrad3_pick_splitk(Cout, Cin, g.K) : gemm_pick_splitk(Cout, Cin, 9, g.K);
+  g.accumulate = accumulate; g.bias_grad = dbias;
+  if (splitk <= 0) splitk = conv3x3_wgrad_splitk(B, H, W, Cin, Cout, stride);      // the plan's choice
   g.splitk = splitk;
   if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
   return launch_gemm(g, (hipStream_t)st);
@@ -1316,6 +1283,42 @@ int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const void* o, con
   g.delta_nq = Nq; g.delta_heads = N / 64;
   g.cfg = 1;
   return launch_gemm(g, (hipStream_t)st);
+}
+// test hook (include/sdxlstep_diag.h part 1): what launch_gemm would run for the problem a launch-log line describes.  The operands gemm_route never
+// looks at are dense and stand on one aligned dummy word; no device is touched.
+int sdxl_debug_gemm_route(const sdxl_gemm_desc* d, sdxl_gemm_route* out) {
+  ARG_CHECK(d && out, "gemm_route: null argument");
+  alignas(16) static float word[4];
+  GemmP g;
+  gemm_defaults(&g);
+  g.form = d->form; g.taps = d->taps; g.M = d->M; g.N = d->N; g.K = d->K; g.cfg = d->cfg;
+  g.A = g.B = (const bf16*)word; g.C = word;
+  g.out_f32 = d->form == GEMM_TN;
+  g.lda = d->form == GEMM_TN ? d->M : d->K;
+  g.ldb = d->form == GEMM_NT ? (long)d->K * d->taps : (long)d->N * d->taps;
+  g.ldc = d->form == GEMM_TN ? (long)d->N * d->taps : d->N;
+  g.Hm = d->Hm; g.Wm = d->Wm; g.Hs = d->Hs; g.Ws = d->Ws; g.sm = d->sm; g.sd = d->sd;
+  g.up2 = d->up2;
+  if (d->up2) {      // the planar matrix's rows, from the side of the problem that walks them (GemmP::up2)
+    const int rows = d->form == GEMM_TN ? d->K : d->M;
+    const bool planar = d->up2 == 2 || (d->up2 == 1 && d->form == GEMM_NT);      // four planes of whole images + padding | the pixels themselves
+    ARG_CHECK(d->Hm > 0 && d->Wm > 0, "gemm_route: up2 needs the image size");
+    g.up_plane = planar ? rows / 4 : (int)upconv_plane_rows(1, 1, rows);
+    g.up_rows = planar ? g.up_plane / (d->Hm * d->Wm) * (d->Hm * d->Wm) : rows;
+  }
+  g.geglu = d->geglu; g.geglu_group = d->geglu_group;
+  if (d->geglu) { g.aux = (bf16*)word; g.ldaux = 8; }
+  g.splitk = d->splitk; g.slab = word;
+  if (d->group > 1) {
+    g.group = d->group;
+    for (int i = 0; i < d->group && i < GEMM_MAX_GROUP; ++i) { g.gA[i] = g.gB[i] = (const bf16*)word; g.gC[i] = word; g.gCb[i] = d->emit_bf16 ? (bf16*)word : nullptr; g.gbias_grad[i] = d->bias_grad ? word : nullptr; }
+  } else if (d->emit_bf16) g.Cb = (bf16*)word;
+  if (d->bias_grad) g.bias_grad = word;
+  if (d->delta) { g.delta_out = word; g.delta_o = (const bf16*)word; g.delta_nq = d->M; g.delta_heads = d->N / 64; }
+  GemmRoute r;
+  if (int e = gemm_route_checked(g, &r)) return e;
+  out->kernel = r.kernel; out->cfg = r.cfg; out->fast = r.fast; out->post = r.post;
+  return 0;
 }
 int sdxl_profile_gemm_begin(void) { return gemm_profile_begin(); }
 int sdxl_set_gemm_mode(int mode) {

@@ -197,7 +197,6 @@ bool Plan::grad_alias(Act* x, Act* y) {
 // ================================================================================================
 // Ops
 // ================================================================================================
-static int pick_splitk(long out_rows, long out_cols, int taps, long red) { return gemm_pick_splitk((int)out_rows, (int)out_cols, taps, red); }
 static void want_slab_main(Plan& p, int M, int N, int splitk) {     // slabs of the caller's-stream launches (forward, dgrad)
   size_t need = gemm_slab_floats(M, N, 1, splitk);
   if (need > p.slab_main_floats) p.slab_main_floats = need;
@@ -261,8 +260,7 @@ struct LinearOp : Op {
     }
     if (gu) dx = p.grad_dst(gu);           // the activation itself gets no gradient buffer: dgrad emits dU
     else if (x->need_grad) dx = p.grad_dst(x);
-    splitk = pick_splitk(N, K, 1, x->rows);
-    if (wgrad256_policy(N, K, x->rows)) splitk = wgrad256_pick_splitk(N, K, x->rows);
+    splitk = linear_wgrad_splitk(N, K, x->rows);
     wgroup = gemm_pick_group(N, K, 1, x->rows, splitk);
     want_slab(p, N, K, 1, splitk);
     crcfg = cr256_wgrad_cfg(N, K, x->rows, b.off != NONE);
@@ -385,14 +383,14 @@ struct ConvOp : Op {
     const long plane = upconv_plane_rows(Bn, H / 2, W / 2);
     weff_off = p.alloc(sizeof(bf16) * (size_t)Cout * 16 * Cin);
     planar_off = p.alloc(sizeof(bf16) * (size_t)4 * plane * (Cout > Cin ? Cout : Cin));
-    up_fs = gemm_pick_splitk_small((int)(4 * plane), Cout, 4 * Cin, 0);
+    up_fs = upconv3x3_fwd_splitk(Bn, H / 2, W / 2, Cin, Cout);
     want_slab_main(p, (int)(4 * plane), Cout, up_fs);
-    up_ds = gemm_pick_splitk_small(Bn * (H / 2) * (W / 2), Cin, 16 * Cout, 1);
+    up_ds = upconv3x3_dgrad_splitk(Bn, H / 2, W / 2, Cin, Cout);
     want_slab_main(p, Bn * (H / 2) * (W / 2), Cin, up_ds);
     up_wg = (Bn * (H / 2) * (W / 2)) % 64 == 0;
     if (up_wg) {
       dweff_off = p.alloc(sizeof(float) * (size_t)Cout * 16 * Cin);
-      up_ws = pick_splitk(Cout, Cin, 16, (long)Bn * (H / 2) * (W / 2));
+      up_ws = gemm_pick_splitk(Cout, Cin, 16, (long)Bn * (H / 2) * (W / 2));
       want_slab(p, Cout, Cin, 16, up_ws);
       cs_part_off = p.alloc(sizeof(float) * colsum_part_floats(1, Bn * H * W, Cout));      // (rowvec excludes up2: one buffer serves either)
     }
@@ -412,14 +410,8 @@ struct ConvOp : Op {
     if (up2())
       return launch_upconv3x3_fwd(p.P(x_low), p.eng->Wp(w), p.eng->Wp(b), (bf16*)p.F(weff_off), (bf16*)p.F(planar_off), p.P(y), Bn, H / 2,
                                   W / 2, Cin, Cout, up_fs, p.F(p.slab_main_off), st);
-    GemmP g;
-    gemm_defaults(&g);
-    g.form = GEMM_NT;
+    GemmP g = conv3x3_fwd_problem(Bn, H, W, Cin, Cout, stride);
     g.A = p.P(x); g.B = p.eng->Wp(w); g.C = p.P(y);
-    g.M = Bn * Ho * Wo; g.N = Cout; g.K = Cin;
-    g.lda = Cin; g.ldb = 9L * Cin; g.ldc = Cout;
-    g.taps = 9; g.Hm = Ho; g.Wm = Wo; g.Hs = H; g.Ws = W; g.sm = stride; g.sd = 1;
-    g.b_tap_stride = Cin;
     g.bias = p.eng->Wp(b);
     if (resid) { g.resid = p.P(resid); g.ldr = Cout; }
     if (rowvec) { g.rowvec = p.P(rowvec); g.ldv = rowvec->ld(); g.rows_per_batch = Ho * Wo; }
@@ -443,14 +435,11 @@ struct ConvOp : Op {
       s2x_off = p.alloc(sizeof(bf16) * (size_t)4 * upconv_plane_rows(Bn, Ho, Wo) * Cin);
     if (x->need_grad && stride == 2 && H % 2 == 0 && W % 2 == 0 && Cout % 64 == 0 && Cin % 8 == 0)
       s2_planar_off = p.alloc(sizeof(bf16) * (size_t)4 * upconv_plane_rows(Bn, Ho, Wo) * Cin);
-    splitk = pick_splitk(Cout, Cin, 9, (long)Bn * Ho * Wo);
-    if (conv_wgrad3_policy(Cout, Cin, (long)Bn * Ho * Wo, Wo, stride)) splitk = conv_wgrad3_pick_splitk(Cout, Cin, (long)Bn * Ho * Wo);
+    splitk = conv3x3_wgrad_splitk(Bn, H, W, Cin, Cout, stride);
     want_slab(p, Cout, Cin, 9, splitk);
-    if (stride == 1 && Cin % 64 == 0) {
-      fsplit = gemm_pick_splitk_small(Bn * Ho * Wo, Cout, 9 * Cin, 0);
-      want_slab_main(p, Bn * Ho * Wo, Cout, fsplit);
-      if (x->need_grad && Cout % 64 == 0) { dsplit = gemm_pick_splitk_small(Bn * H * W, Cin, 9 * Cout, 1); want_slab_main(p, Bn * H * W, Cin, dsplit); }
-    }
+    fsplit = conv3x3_fwd_splitk(Bn, H, W, Cin, Cout, stride);
+    want_slab_main(p, Bn * Ho * Wo, Cout, fsplit);
+    if (x->need_grad) { dsplit = conv3x3_dgrad_splitk(Bn, H, W, Cin, Cout, stride); want_slab_main(p, Bn * H * W, Cin, dsplit); }
   }
   int bwd(Plan& p, hipStream_t st, bool first) override {
     const bf16* dy = p.GP(dy_off);
@@ -476,15 +465,8 @@ struct ConvOp : Op {
       }));
     } else
     CHK(on_side(p, st, [&](hipStream_t s2) -> int {
-      GemmP g;
-      gemm_defaults(&g);
-      g.form = GEMM_TN;
+      GemmP g = conv3x3_wgrad_problem(Bn, H, W, Cin, Cout, stride);
       g.A = dy; g.B = p.P(x); g.C = p.eng->Gp(w);
-      g.M = Cout; g.N = Cin; g.K = (int)Mo;
-      g.lda = Cout; g.ldb = Cin; g.ldc = 9L * Cin;
-      g.taps = 9; g.Hm = Ho; g.Wm = Wo; g.Hs = H; g.Ws = W; g.sm = stride; g.sd = 1;
-      g.c_tap_stride = Cin;
-      g.out_f32 = 1;
       g.splitk = splitk;
       g.slab = p.F(p.slab_off);
       g.accumulate = first ? 0 : 1;
@@ -510,14 +492,8 @@ struct ConvOp : Op {
                                  p.F(p.slab_main_off), KNOB(0), st));
     } else
     if (x->need_grad) {
-      GemmP g;
-      gemm_defaults(&g);
-      g.form = GEMM_NN;
+      GemmP g = conv3x3_dgrad_problem(Bn, H, W, Cin, Cout, stride);
       g.A = dy; g.B = p.eng->Wp(w); g.C = p.GP(dx.out);
-      g.M = Bn * H * W; g.N = Cin; g.K = Cout;
-      g.lda = Cout; g.ldb = 9L * Cin; g.ldc = Cin;
-      g.taps = 9; g.Hm = H; g.Wm = W; g.Hs = Ho; g.Ws = Wo; g.sm = 1; g.sd = stride;
-      g.flip = 1; g.b_tap_stride = Cin;
       if (dx.addend != NONE) { g.resid = p.GP(dx.addend); g.ldr = Cin; }
       if (dsplit > 1) { g.splitk = dsplit; g.slab = p.F(p.slab_main_off); }
       g.prio = KNOB(0);

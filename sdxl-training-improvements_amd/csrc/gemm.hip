@@ -1264,33 +1264,31 @@ static int launch_k(const GemmP& p, hipStream_t st) {
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
-// the FAST staging forms only (reduction a multiple of BK; linear, or the same-size stride-1 3x3 gather): can this problem take them?
-static bool gemm_fast_ok(const GemmP& p, bool conv, int BK) {
+// the FAST staging forms only (reduction a multiple of BK; linear, or the same-size stride-1 3x3 gather -- all 3x3 convolutions but the two
+// downsamplers, their transposed dgrads and conv_in): can this problem take them?
+static bool gemm_fast_ok(const GemmP& p, int BK) {
   if (p.K % BK) return false;
-  if (!conv) return true;
+  if (p.taps == 1) return true;
   return (p.taps == 9 || p.up2) && p.sm == 1 && p.sd == 1 && p.Hm == p.Hs && p.Wm == p.Ws;
 }
 template <int FORM, bool CONV, int BN, int S, int BK, int NW, bool KSP = false, bool PL = false>
-static int launch_cfg(const GemmP& p, hipStream_t st) {
+static int launch_cfg(const GemmP& p, bool fast, hipStream_t st) {
   constexpr bool KS_OK = KSP && FORM != GEMM_TN;     // (the split-K groups exist for the FAST staging of the NT / NN forms)
-  constexpr bool PL_OK = PL && FORM != GEMM_TN;      // (the pipelined loop likewise; launch_one routes only FAST problems to it)
-  if (!CONV && p.K % BK == 0) return launch_k<FORM, false, BN, S, BK, true, NW, KS_OK, PL_OK>(p, st);
-  // same-size stride-1 3x3 convolutions (all but the two downsamplers, their transposed dgrads and conv_in)
-  if (CONV && (p.taps == 9 || p.up2) && p.sm == 1 && p.sd == 1 && p.Hm == p.Hs && p.Wm == p.Ws && p.K % BK == 0)
-    return launch_k<FORM, true, BN, S, BK, true, NW, KS_OK, PL_OK>(p, st);
+  constexpr bool PL_OK = PL && FORM != GEMM_TN;      // (the pipelined loop likewise; gemm_route sends only FAST problems to it)
+  if (fast) return launch_k<FORM, CONV, BN, S, BK, true, NW, KS_OK, PL_OK>(p, st);
   if constexpr (PL) { ARG_CHECK(false, "gemm: the pipelined configurations take FAST-staging problems only"); }
   else return launch_k<FORM, CONV, BN, S, BK, false, NW>(p, st);
 }
 
-// Tile / pipeline selection of the 128-row kernel.  Four configurations:
+// Tile / pipeline selection of the 128-row kernel (the `cfg` of a GemmRoute whose kernel is GEMM_K128).  Four configurations:
 //   1: 128x128, BK 64, 2-deep ring, 4 waves  (65 KiB LDS, 2 workgroups per CU)          -- default
 //   2: 128x128, BK 32, 2-deep ring, 4 waves  (34 KiB LDS, 3-4 per CU)                   -- large-grid dgrad
 //   3: 128x160, BK 64, 4-deep ring, 8 waves  (145 KiB LDS, 1 per CU, 3 K-steps of DMA in flight)
 //  13: 128x160, BK 64, 2-deep ring, 4 waves x (64x80)  (73 KiB, 2 per CU)               -- where 160-wide tiles fill the rounds
 // (Measured and dropped: 4-deep / 3-deep 128x128 rings, 6-deep BK 32 rings, a 64x160 tile, a 256x128 ping-pong schedule --
 //  DESIGN.md section 10.)
-template <int FORM, bool CONV>
-static int launch_one(const GemmP& p, hipStream_t st) {
+static int gemm_route_cfg128(const GemmP& p) {
+  const int FORM = p.form;
   int cfg = 1;
   // Tile-count quantisation decides most of it on this model's shapes: a launch of t workgroups runs in
   // ceil(t / 512) rounds of (256 CUs x 2 resident workgroups), so e.g. an N = 640 output at M = 16384 is 640 tiles of
@@ -1319,13 +1317,13 @@ static int launch_one(const GemmP& p, hipStream_t st) {
   // (forward only: in the backward a 145 KiB workgroup evicts the other stream from its CU -- dgrads on it: GEMM family
   //  -2 ms, step +2.4 ms, profiles/r02c)
   if (FORM == GEMM_NT && n160 && t160 <= 256 && (long)p.K * p.taps >= 2560) cfg = 23;
+  const bool fast64 = FORM != GEMM_TN && gemm_fast_ok(p, 64);
   // the pipelined one-wave-per-SIMD loop on the same tiles (configuration 5; 6 = 128-column tiles): knob 30 (kernels.h) selects where
   {
     const int k30 = KNOB(30);
     const bool one_round = (n160 ? t160 : blocks) <= 256 && (n160 ? t160 : blocks) > 128;
-    const bool fastp = FORM != GEMM_TN && gemm_fast_ok(p, CONV, 64) && p.splitk <= 1;
-    if (fastp && one_round) {
-      const bool fwd_conv = FORM == GEMM_NT && CONV, dg_conv = FORM == GEMM_NN && CONV;      // (linear problems: gemm_pl.hip, launch_gemm_impl)
+    if (fast64 && p.splitk <= 1 && one_round) {
+      const bool fwd_conv = FORM == GEMM_NT && p.taps != 1, dg_conv = FORM == GEMM_NN && p.taps != 1;      // (linear problems: gemm_pl.hip, gemm_route)
       if ((fwd_conv && (k30 & 4)) || (dg_conv && (k30 & 8))) cfg = n160 ? 5 : 6;
     }
   }
@@ -1340,21 +1338,27 @@ static int launch_one(const GemmP& p, hipStream_t st) {
   // FAST staging only
   if (cfg == 5 && !n160) cfg = 6;
   if (cfg == 6 && g80) cfg = 5;
-  if ((cfg == 5 || cfg == 6) && (FORM == GEMM_TN || !gemm_fast_ok(p, CONV, 64))) cfg = cfg == 5 ? 13 : 1;
+  if ((cfg == 5 || cfg == 6) && !fast64) cfg = cfg == 5 ? 13 : 1;
   if ((cfg == 3 || cfg == 13 || cfg == 23 || cfg == 43) && p.N % 160 != 0) cfg = 1;
   if (cfg == 23 && FORM == GEMM_TN) cfg = 13;
   if (p.geglu == 1 && cfg == 2) cfg = 1;                      // the BK = 32 configuration has no room for the GEGLU staging tile
-  switch (cfg) {
-    case 2: return launch_cfg<FORM, CONV, 128, 2, 32, 4>(p, st);
-    case 3: return launch_cfg<FORM, CONV, 160, 4, 64, 8>(p, st);
-    case 23: return launch_cfg<FORM, CONV, 160, 4, 64, 8, true>(p, st);   // split-K wave groups
-    case 13: return launch_cfg<FORM, CONV, 160, 2, 64, 4>(p, st);
-    case 5: return launch_cfg<FORM, CONV, 160, 4, 64, 4, false, true>(p, st);      // pipelined, one wave per SIMD, 145 KiB
-    case 6: return launch_cfg<FORM, CONV, 128, 4, 64, 4, false, true>(p, st);      // the same on 128 x 128 tiles, 128 KiB
+  for (int k : {2, 3, 23, 13, 5, 6, SDXL_DIAG_BUILD ? 43 : 1}) if (cfg == k) return cfg;
+  return 1;      // (whatever else was forced)
+}
+// configuration -> instantiation of the 128-row kernel
+template <int FORM, bool CONV>
+static int launch_one(const GemmP& p, const GemmRoute& r, hipStream_t st) {
+  switch (r.cfg) {
+    case 2: return launch_cfg<FORM, CONV, 128, 2, 32, 4>(p, r.fast, st);
+    case 3: return launch_cfg<FORM, CONV, 160, 4, 64, 8>(p, r.fast, st);
+    case 23: return launch_cfg<FORM, CONV, 160, 4, 64, 8, true>(p, r.fast, st);   // split-K wave groups
+    case 13: return launch_cfg<FORM, CONV, 160, 2, 64, 4>(p, r.fast, st);
+    case 5: return launch_cfg<FORM, CONV, 160, 4, 64, 4, false, true>(p, r.fast, st);      // pipelined, one wave per SIMD, 145 KiB
+    case 6: return launch_cfg<FORM, CONV, 128, 4, 64, 4, false, true>(p, r.fast, st);      // the same on 128 x 128 tiles, 128 KiB
 #ifdef SDXL_DIAG
-    case 43: return launch_cfg<FORM, CONV, 160, 4, 64, 4>(p, st);      // the 4-deep ring with FOUR waves (64 x 80 wave tiles: 74 KB of fragment reads per K-step against 115 with eight): 73.9 vs 67.3 us on NT 4096 x 1280 x 5120, not selected
+    case 43: return launch_cfg<FORM, CONV, 160, 4, 64, 4>(p, r.fast, st);      // the 4-deep ring with FOUR waves (64 x 80 wave tiles: 74 KB of fragment reads per K-step against 115 with eight): 73.9 vs 67.3 us on NT 4096 x 1280 x 5120, not selected
 #endif
-    default: return launch_cfg<FORM, CONV, 128, 2, 64, 4>(p, st);
+    default: return launch_cfg<FORM, CONV, 128, 2, 64, 4>(p, r.fast, st);
   }
 }
 
@@ -1473,8 +1477,73 @@ int gemm_pick_group(int M, int N, int taps, long red, int splitk) {
   const int g = KNOB(37) > 0 ? KNOB(37) : (int)(256 / tiles);      // (knob 37: problems per grouped launch, A/B runs)
   return g < 2 ? 1 : (g > GEMM_MAX_GROUP ? GEMM_MAX_GROUP : g);
 }
+// ---- the plan-time half of the policy, shared by the plan (engine.hip) and the single-kernel entry points (capi.hip): split-K factors ... ----
+int linear_wgrad_splitk(int Mo, int No, long rows) {      // dW [Mo][No] over `rows`: the long-reduction kernel has its own choice
+  return wgrad256_policy(Mo, No, rows) ? wgrad256_pick_splitk(Mo, No, rows) : gemm_pick_splitk(Mo, No, 1, rows);
+}
+int conv3x3_fwd_splitk(int B, int H, int W, int Cin, int Cout, int stride) {      // small images split the (tap, channel) reduction
+  return stride == 1 && Cin % 64 == 0 ? gemm_pick_splitk_small(B * H * W, Cout, 9 * Cin, 0) : 1;
+}
+int conv3x3_dgrad_splitk(int B, int H, int W, int Cin, int Cout, int stride) {
+  return stride == 1 && Cin % 64 == 0 && Cout % 64 == 0 ? gemm_pick_splitk_small(B * H * W, Cin, 9 * Cout, 1) : 1;
+}
+int conv3x3_wgrad_splitk(int B, int H, int W, int Cin, int Cout, int stride) {      // the three-taps-per-workgroup kernel has its own
+  const int Wo = (W - 1) / stride + 1;
+  const long red = (long)B * ((H - 1) / stride + 1) * Wo;
+  return conv_wgrad3_policy(Cout, Cin, red, Wo, stride) ? conv_wgrad3_pick_splitk(Cout, Cin, red) : gemm_pick_splitk(Cout, Cin, 9, red);
+}
+int upconv3x3_fwd_splitk(int B, int H, int W, int Cin, int Cout) { return gemm_pick_splitk_small((int)(4 * upconv_plane_rows(B, H, W)), Cout, 4 * Cin, 0); }
+int upconv3x3_dgrad_splitk(int B, int H, int W, int Cin, int Cout) { return gemm_pick_splitk_small(B * H * W, Cin, 16 * Cout, 1); }
+// ... and the geometry of the three problems of a 3x3 convolution (pad 1) x [B][H][W][Cin] -> y [B][Ho][Wo][Cout], w [Cout][9][Cin]: everything but the
+// operands, the epilogue inputs, the split and the launch options, which stay with the caller
+static GemmP conv3x3_problem(int form, int M, int N, int K, int Hm, int Wm, int Hs, int Ws, int sm, int sd) {
+  GemmP g;
+  gemm_defaults(&g);
+  g.form = form;
+  g.M = M; g.N = N; g.K = K;
+  g.taps = 9; g.Hm = Hm; g.Wm = Wm; g.Hs = Hs; g.Ws = Ws; g.sm = sm; g.sd = sd;
+  return g;
+}
+GemmP conv3x3_fwd_problem(int B, int H, int W, int Cin, int Cout, int stride) {
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  GemmP g = conv3x3_problem(GEMM_NT, B * Ho * Wo, Cout, Cin, Ho, Wo, H, W, stride, 1);
+  g.lda = Cin; g.ldb = 9L * Cin; g.ldc = Cout;
+  g.b_tap_stride = Cin;
+  return g;
+}
+GemmP conv3x3_dgrad_problem(int B, int H, int W, int Cin, int Cout, int stride) {      // dx = dy * w with the taps mirrored
+  GemmP g = conv3x3_problem(GEMM_NN, B * H * W, Cin, Cout, H, W, (H - 1) / stride + 1, (W - 1) / stride + 1, 1, stride);
+  g.lda = Cout; g.ldb = 9L * Cin; g.ldc = Cin;
+  g.flip = 1; g.b_tap_stride = Cin;
+  return g;
+}
+GemmP conv3x3_wgrad_problem(int B, int H, int W, int Cin, int Cout, int stride) {      // dw [Cout][9][Cin] fp32 = dy^T . gathered x
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  GemmP g = conv3x3_problem(GEMM_TN, Cout, Cin, B * Ho * Wo, Ho, Wo, H, W, stride, 1);
+  g.lda = Cout; g.ldb = Cin; g.ldc = 9L * Cin;
+  g.c_tap_stride = Cin;
+  g.out_f32 = 1;
+  return g;
+}
 void gemm_set_mode(int mode) { g_mode256 = mode & 3; g_force_cfg = mode >> 2; }
 static int launch_gemm_impl(const GemmP& pin, hipStream_t st);
+// the profiler's bracket: HIP events on the launch stream around `launch`, one record per call
+template <class F>
+static int profiled(hipStream_t st, double flops, const GemmProf::Rec& rec, F launch) {
+  if (!g_prof.on) return launch();
+  while (g_prof.ev.size() < g_prof.used + 2) {
+    hipEvent_t e;
+    HIP_CHECK_RET(hipEventCreate(&e));
+    g_prof.ev.push_back(e);
+  }
+  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used], st));
+  int rc = launch();
+  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used + 1], st));
+  g_prof.used += 2;
+  g_prof.flops.push_back(flops);
+  g_prof.recs.push_back(rec);
+  return rc;
+}
 #ifdef SDXL_DIAG
 void gemm_set_sk_mode(int mode) { g_sk_mode = mode; }
 int gemm_sk_mode() { return g_sk_mode; }
@@ -1488,48 +1557,32 @@ bool gemm_use_sk(const GemmP& p) {
 }
 // several problems in ONE stream-K launch (a layer's dgrad + wgrad); every problem must satisfy gemm_sk_applicable
 int launch_gemm_multi(const GemmP* ps, int n, hipStream_t st) {
-  if (!g_prof.on) return launch_gemm_sk(ps, n, st);
-  while (g_prof.ev.size() < g_prof.used + 2) {
-    hipEvent_t e;
-    HIP_CHECK_RET(hipEventCreate(&e));
-    g_prof.ev.push_back(e);
-  }
-  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used], st));
-  int rc = launch_gemm_sk(ps, n, st);
-  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used + 1], st));
-  g_prof.used += 2;
   double f = 0;
   for (int i = 0; i < n; ++i) f += 2.0 * (double)ps[i].M * (double)ps[i].N * (double)ps[i].K;
-  g_prof.flops.push_back(f);
-  g_prof.recs.push_back({n > 1 ? 3 : ps[0].form, n, ps[0].M, ps[0].N, ps[0].K, 1});
-  return rc;
+  return profiled(st, f, {n > 1 ? 3 : ps[0].form, n, ps[0].M, ps[0].N, ps[0].K, 1}, [&] { return launch_gemm_sk(ps, n, st); });
 }
 #endif
 // SDXL_LAUNCH_LOG=<path>: one line per GEMM / attention launch in host launch order (= rocprofv3's Dispatch_Id order), so that a
-// kernel trace can be joined with the problems' shapes (profiles/tools/phase_rate.py)
+// kernel trace can be joined with the problems' shapes (profiles/tools/phase_rate.py).  A GEMM line: form, taps, M, N, K, splitk, group, then
+// what else gemm_route reads (sdxl_debug_gemm_route takes the same): cfg, geglu, geglu group, Hm, Wm, Hs, Ws, sm, sd, up2, bf16 emit, Delta epilogue, bias gradient
 FILE* launch_log() {
   static FILE* f = []() -> FILE* { const char* p = getenv("SDXL_LAUNCH_LOG"); return p ? fopen(p, "w") : nullptr; }();
   return f;
 }
 int launch_gemm(const GemmP& p, hipStream_t st) {
-  if (FILE* f = launch_log()) { fprintf(f, "G,%d,%d,%d,%d,%d,%d,%d\n", p.form, p.taps, p.M, p.N, p.K, p.splitk, p.group > 1 ? p.group : 1); fflush(f); }
-  if (!g_prof.on) return launch_gemm_impl(p, st);
-  while (g_prof.ev.size() < g_prof.used + 2) {
-    hipEvent_t e;
-    HIP_CHECK_RET(hipEventCreate(&e));
-    g_prof.ev.push_back(e);
+  if (FILE* f = launch_log()) {
+    bool biasg = p.bias_grad;
+    for (int i = 0; i < p.group && i < GEMM_MAX_GROUP; ++i) biasg = biasg || p.gbias_grad[i];
+    fprintf(f, "G,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d\n", p.form, p.taps, p.M, p.N, p.K, p.splitk, p.group > 1 ? p.group : 1, p.cfg, p.geglu,
+            p.geglu_group, p.Hm, p.Wm, p.Hs, p.Ws, p.sm, p.sd, p.up2, p.Cb || (p.group > 1 && p.gCb[0]) ? 1 : 0, p.delta_out ? 1 : 0, biasg ? 1 : 0);
+    fflush(f);
   }
-  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used], st));
-  int rc = launch_gemm_impl(p, st);
-  HIP_CHECK_RET(hipEventRecord(g_prof.ev[g_prof.used + 1], st));
-  g_prof.used += 2;
-  g_prof.flops.push_back(2.0 * (double)p.M * (double)p.N * (double)p.K * (p.up2 == 2 ? 2.25 : (double)p.taps) * (p.group > 1 ? p.group : 1));      // (up2 == 2: 1 + 2 + 2 + 4 taps over four planes)
-  g_prof.recs.push_back({p.form, p.taps, p.M, p.N, p.K, p.splitk});
-  return rc;
+  const double flops = 2.0 * (double)p.M * (double)p.N * (double)p.K * (p.up2 == 2 ? 2.25 : (double)p.taps) * (p.group > 1 ? p.group : 1);      // (up2 == 2: 1 + 2 + 2 + 4 taps over four planes)
+  return profiled(st, flops, {p.form, p.taps, p.M, p.N, p.K, p.splitk}, [&] { return launch_gemm_impl(p, st); });
 }
 
-static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
-  GemmP p = pin;
+// Step 1 of a launch: the argument checks and the normalisation of a problem (what gemm_route and the kernels may then rely on)
+static int gemm_check(GemmP& p) {
   ARG_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
   ARG_CHECK(p.N % 8 == 0, "gemm: N=%d must be a multiple of 8", p.N);
   ARG_CHECK(p.lda % 8 == 0 && p.ldb % 8 == 0, "gemm: lda=%ld ldb=%ld must be multiples of 8", p.lda, p.ldb);
@@ -1552,8 +1605,7 @@ static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
     ARG_CHECK(p.K % 8 == 0, "gemm: K=%d must be a multiple of 8", p.K);
     ARG_CHECK(!p.out_f32, "gemm NT/NN: bf16 output");
     // split-K of the bf16-output forms: plain linear problems whose K is a whole number of 64-element steps
-    const bool conv_fast = (p.taps == 9 || p.up2) && p.sm == 1 && p.sd == 1 && p.Hm == p.Hs && p.Wm == p.Ws;
-    if (p.splitk > 1 && (!(p.taps == 1 || conv_fast) || p.geglu || p.K % 64 != 0 || p.N % 8 != 0)) p.splitk = 1;
+    if (p.splitk > 1 && (!gemm_fast_ok(p, 64) || p.geglu || p.N % 8 != 0)) p.splitk = 1;
     ARG_CHECK(p.ldc % 8 == 0, "gemm: ldc=%ld must be a multiple of 8", p.ldc);
     if (p.accumulate) { p.resid = (const bf16*)p.C; p.ldr = p.ldc; }
     if (p.geglu) {
@@ -1604,11 +1656,9 @@ static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
     if (p.form != GEMM_TN && p.splitk > p.K / 64 * p.taps) p.splitk = p.K / 64 * p.taps;
     p.slab_ld = p.form == GEMM_TN ? (long)p.N * p.taps : (long)p.N;
   }
-  const bool conv = p.taps != 1;
-  int rc;
   if (p.ln_x) {      // LayerNorm backward in the dgrad's epilogue (GemmP::ln_x)
     ARG_CHECK(SDXL_LN_EPILOGUE, "gemm: the LayerNorm-backward epilogue exists in the diagnostics build only");
-    ARG_CHECK(p.form == GEMM_NN && !conv && p.splitk == 1 && !p.geglu && !p.resid && !p.bias && !p.rowvec && !p.delta_out && !p.up2,
+    ARG_CHECK(p.form == GEMM_NN && p.taps == 1 && p.splitk == 1 && !p.geglu && !p.resid && !p.bias && !p.rowvec && !p.delta_out && !p.up2,
               "gemm: the LayerNorm-backward epilogue takes a plain NN problem");
     const int lc = gemm_ln_cfg(p.M, p.N, p.K);
     ARG_CHECK(lc != 0 && (p.cfg == lc || p.cfg == 0), "gemm: LayerNorm-backward epilogue: M=%d N=%d K=%d cfg=%d does not fit (gemm_ln_cfg)", p.M, p.N, p.K, p.cfg);
@@ -1616,16 +1666,30 @@ static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
     ARG_CHECK(p.ln_stats && p.ln_gamma && p.ln_dx && p.ln_part && p.ln_epoch > 0 && p.ln_ldx % 8 == 0 && p.ln_ldo % 8 == 0 && ((uintptr_t)p.ln_part & 15) == 0 &&
               (((uintptr_t)p.ln_x | (uintptr_t)p.ln_dx | (uintptr_t)p.ln_addend | (uintptr_t)p.ln_gamma) & 15) == 0,
               "gemm: LayerNorm-backward epilogue: missing or misaligned buffers");
-    return launch_one<GEMM_NN, false>(p, st);
   }
+  return 0;
+}
+
+// Step 2: THE selection policy of the GEMM family (DESIGN.md section 4's table) -- which kernel runs a checked and normalised problem, in which
+// configuration, followed by which split-K pass.  Pure: it reads p, the mode words (g_mode256, g_force_cfg, g_sk_mode; the two kernels' enable
+// switches through their _applicable / _policy) and the knobs, and calls nothing of HIP.  First match wins.
+GemmRoute gemm_route(const GemmP& p) {
+  const bool tn = p.form == GEMM_TN, split = p.splitk > 1;
+  const int fc = p.cfg > 0 ? p.cfg : g_force_cfg;      // the configuration forced for this launch / for the process
+  const int post = !split ? GEMM_POST_NONE : tn ? GEMM_POST_REDUCE : GEMM_POST_EPILOGUE;
+  auto k128 = [&]() -> GemmRoute {
+    const int c = gemm_route_cfg128(p);
+    const bool fast = gemm_fast_ok(p, c == 2 ? 32 : 64);
+    return {GEMM_K128, c == 23 && !fast ? 3 : c, fast, post};      // (the split-K wave groups exist for the FAST staging only: the same tile without them)
+  };
+  if (p.ln_x) return k128();      // LayerNorm backward in the dgrad's epilogue (GemmP::ln_x): the 128 x 128 tiles' epilogue only
   {   // software-pipelined one-wave-per-SIMD kernel (gemm_pl.hip): forced configuration 7, or the policy of knob 30 (linear problems whose tiles fit one round)
-    const int fc = p.cfg > 0 ? p.cfg : g_force_cfg;
     bool use = fc == 7 || fc == 8;                       // (8: WITH the L2 prefetch wave -- measured, not used: gemm_pl.hip)
     const bool pl_pf = fc == 8 || KNOB(31) == 1;            // diagnostics build only (the product has no such instantiation)
     // Policy (knob 30 = 0): the linear problems whose 128 x 160 tiles are ONE round of the chip (129 .. 256 workgroups: the 4096-token level's
     // 1280-column outputs) -- forward projections and dgrads.  In the step (profiles/r05e_*): NN 4096 x 1280 x 10240 162 -> 106 us, x 3840
     // 67 -> 46, NT x 5120 66 -> 59; step -0.6 ms (the weight-gradient stream loses its co-resident partner while such a dgrad runs).
-    if (!use && fc == 0 && KNOB(30) != 64 && p.taps == 1 && p.form != GEMM_TN) {
+    if (!use && fc == 0 && KNOB(30) != 64 && p.taps == 1 && !tn) {
       const int bnp = p.N % 160 == 0 ? 160 : 128;
       const long tiles = (long)cdiv(p.M, BM) * cdiv(p.N, bnp);
       const int k30 = KNOB(30) ? KNOB(30) : 3;
@@ -1633,83 +1697,80 @@ static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
       use = ((k30 & 1) && p.form == GEMM_NT && one_round) || ((k30 & 2) && p.form == GEMM_NN && one_round) || ((k30 & 512) && p.form == GEMM_NN && one_round && p.K >= 2560) ||
             ((k30 & 16) && tiles > 128 && tiles % 256 == 0) || ((k30 & 1024) && p.form == GEMM_NT && tiles > 256 && tiles % 256 == 0) || (k30 & 32);
     }
-    if (use && pl_applicable(p)) return launch_pl(p, 0, st, pl_pf);
+    if (use && pl_applicable(p)) return {GEMM_KPL, pl_pf ? 8 : 7, false, GEMM_POST_NONE};
   }
-  {   // co-resident 256-row kernel (gemm_cr256.hip): forced configurations 31 (160-column tiles) / 32 (128)
-    const int fc = p.cfg > 0 ? p.cfg : g_force_cfg;
-    if (fc >= 31 && fc <= 36 && !p.delta_out && cr256_applicable(p)) {      // (33 / 34: the exclusive 6-deep form, diagnostics build; 35 / 36: phased loop, 128 / 160 columns)
-      rc = launch_cr256(p, (fc == 31 || fc == 33 || fc == 36) ? 160 : 128, st, fc == 33 || fc == 34, fc == 35 || fc == 36);
-      if (rc == 0 && p.form == GEMM_TN && p.splitk > 1) {
-        const long nv = (long)p.M * (p.N / 4);
-        int g = (int)((nv + 255) / 256);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p.slab, (float*)p.C, p.M, p.N, p.ldc, p.slab_ld,
-                           p.splitk, p.accumulate, p.Cb, p.cb_scale, p.bias_grad);
-        HIP_CHECK_RET(hipGetLastError());
-      }
-      return rc;
-    }
+  // co-resident 256-row kernel (gemm_cr256.hip): forced configurations 31 (160-column tiles) / 32 (128); 33 / 34: the exclusive 6-deep form,
+  // diagnostics build; 35 / 36: phased loop, 128 / 160 columns
+  if (fc >= 31 && fc <= 36 && !p.delta_out && cr256_applicable(p)) {
+    bool biasg = tn && p.bias_grad;      // the lockstep loop carries a bias gradient on 128-column tiles only: 31 is 32 then
+    for (int i = 0; tn && i < p.group; ++i) biasg = biasg || p.gbias_grad[i];
+    return {GEMM_KCR256, fc == 31 && biasg ? 32 : fc, false, tn ? post : GEMM_POST_NONE};
   }
 #ifdef SDXL_DIAG
-  if (g_sk_mode && !p.delta_out && !(p.form != GEMM_TN && p.splitk > 1) && (g_sk_mode == 2 ? gemm_sk_applicable(p) : gemm_use_sk(p))) {
-    GemmP q = p;
-    q.splitk = 1;
-    return launch_gemm_sk(&q, 1, st);      // persistent stream-K kernel (gemm_sk.hip)
-  }
+  // persistent stream-K kernel (gemm_sk.hip)
+  if (g_sk_mode && !p.delta_out && !(!tn && split) && (g_sk_mode == 2 ? gemm_sk_applicable(p) : gemm_use_sk(p))) return {GEMM_KSK, 0, false, GEMM_POST_NONE};
 #endif
-  {   // 256 x 256 kernel (gemm256.hip)
-    if (g_mode256 && p.group <= 1 && !p.Cb && !p.delta_out && !(p.form != GEMM_TN && p.splitk > 1) && gemm256_applicable(p)) {      // (the Delta epilogue exists in the 128 x 128 4-wave kernel only)
-      // the forward GEGLU projection packed in groups of 64: the 256 x 256 kernel's register epilogue (value and gate of a channel
-      // in one lane) against the 128-row kernel's LDS-staged one -- 131 vs 156 us at 4096 x 10240 x 1280 although its 640 tiles
-      // fill only 2.5 rounds (profiles/r03_notes)
-      const bool geglu256 = p.geglu == 1 && p.geglu_group == 64 && (long)(p.M / 256) * (p.N / 256) >= 256;
-      if (g_mode256 == 2 || gemm_use256(p.form, p.M, p.N, p.K, p.splitk) || geglu256) {
-        rc = launch_gemm256(p, st);
-        if (rc == 0 && p.splitk > 1) {
-          const long nv = (long)p.M * (p.N / 4);
-          int g = (int)((nv + 255) / 256);
-          if (g > 2048) g = 2048;
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p.slab, (float*)p.C, p.M, p.N, p.ldc, p.slab_ld,
-                             p.splitk, p.accumulate, p.Cb, p.cb_scale, p.bias_grad);
-          HIP_CHECK_RET(hipGetLastError());
-        }
-        return rc;
-      }
-    }
+  // 256 x 256 kernel (gemm256.hip; the Delta epilogue exists in the 128 x 128 4-wave kernel only)
+  if (g_mode256 && p.group <= 1 && !p.Cb && !p.delta_out && !(!tn && split) && gemm256_applicable(p)) {
+    // the forward GEGLU projection packed in groups of 64: the 256 x 256 kernel's register epilogue (value and gate of a channel
+    // in one lane) against the 128-row kernel's LDS-staged one -- 131 vs 156 us at 4096 x 10240 x 1280 although its 640 tiles
+    // fill only 2.5 rounds (profiles/r03_notes)
+    const bool geglu256 = p.geglu == 1 && p.geglu_group == 64 && (long)(p.M / 256) * (p.N / 256) >= 256;
+    if (g_mode256 == 2 || gemm_use256(p.form, p.M, p.N, p.K, p.splitk) || geglu256) return {GEMM_K256, 0, false, post};
   }
-  if (p.form != GEMM_TN && p.splitk > 1) {     // partial tiles to the slabs, then the fixed-order sum + bf16 epilogue
-    const bf16* resid = p.resid; const long ldr = p.ldr;
-    if (conv) rc = p.form == GEMM_NT ? launch_one<GEMM_NT, true>(p, st) : launch_one<GEMM_NN, true>(p, st);
-    else rc = p.form == GEMM_NT ? launch_one<GEMM_NT, false>(p, st) : launch_one<GEMM_NN, false>(p, st);
-    if (rc) return rc;
-    const long nv = (long)p.M * (p.N / 8);
-    int g = (int)((nv + 255) / 256);
-    if (g > 2048) g = 2048;
+  if (tn && p.taps != 1 && conv_wgrad3_applicable(p) && conv_wgrad3_policy(p.M, p.N, p.K, p.Wm, p.sm)) return {GEMM_KCONV_WGRAD3, 0, false, post};
+  if (tn && p.taps == 1 && wgrad256_applicable(p) && wgrad256_policy(p.M, p.N, p.K)) return {GEMM_KWGRAD256, 0, false, post};
+  return k128();      // the 128-row kernel; a split reduction of the bf16-output forms leaves partial tiles in the slabs for the fixed-order sum + bf16 epilogue
+}
+int gemm_route_checked(GemmP p, GemmRoute* r) {      // (sdxl_debug_gemm_route)
+  if (int e = gemm_check(p)) return e;
+  *r = gemm_route(p);
+  return 0;
+}
+
+// Step 4: the pass over the split-K slabs
+static int launch_gemm_post(const GemmP& p, int post, hipStream_t st) {
+  if (post == GEMM_POST_NONE) return 0;
+  const int cols = post == GEMM_POST_REDUCE ? p.N * p.taps : p.N;      // the dense [M][taps N] weight gradient / a bf16 output
+  const long nv = (long)p.M * (cols / (post == GEMM_POST_REDUCE ? 4 : 8));
+  int g = (int)((nv + 255) / 256);
+  if (g > 2048) g = 2048;
+  if (post == GEMM_POST_REDUCE)
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p.slab, (float*)p.C, p.M, cols, p.ldc, p.slab_ld, p.splitk, p.accumulate, p.Cb,
+                       p.cb_scale, p.up2 == 1 ? nullptr : p.bias_grad);      // (up2 == 1: gemm_kernel's own adds)
+  else
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(g), dim3(256), 0, st, p.slab, (bf16*)p.C, p.M, p.N, p.ldc, p.slab_ld, p.splitk,
-                       p.bias, resid, ldr, p.rowvec, p.ldv, p.rows_per_batch > 0 ? p.rows_per_batch : 1);
-    HIP_CHECK_RET(hipGetLastError());
-    return 0;
+                       p.bias, p.resid, p.ldr, p.rowvec, p.ldv, p.rows_per_batch > 0 ? p.rows_per_batch : 1);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+static int launch_gemm_impl(const GemmP& pin, hipStream_t st) {
+  GemmP p = pin;
+  if (int e = gemm_check(p)) return e;
+  const GemmRoute r = gemm_route(p);
+  const bool conv = p.taps != 1;
+  int rc;
+  switch (r.kernel) {      // step 3
+    case GEMM_KPL: return launch_pl(p, 0, st, r.cfg == 8);
+    case GEMM_KCR256: rc = launch_cr256(p, (r.cfg == 31 || r.cfg == 33 || r.cfg == 36) ? 160 : 128, st, r.cfg == 33 || r.cfg == 34, r.cfg == 35 || r.cfg == 36); break;
+#ifdef SDXL_DIAG
+    case GEMM_KSK: {
+      GemmP q = p;
+      q.splitk = 1;
+      return launch_gemm_sk(&q, 1, st);
+    }
+#endif
+    case GEMM_K256: rc = launch_gemm256(p, st); break;
+    case GEMM_KCONV_WGRAD3: rc = launch_conv_wgrad3(p, st); break;
+    case GEMM_KWGRAD256: rc = launch_wgrad256(p, st); break;
+    default:
+      if (p.form == GEMM_NT) rc = conv ? launch_one<GEMM_NT, true>(p, r, st) : launch_one<GEMM_NT, false>(p, r, st);
+      else if (p.form == GEMM_TN) rc = conv ? launch_one<GEMM_TN, true>(p, r, st) : launch_one<GEMM_TN, false>(p, r, st);
+      else if (p.form == GEMM_NN) rc = conv ? launch_one<GEMM_NN, true>(p, r, st) : launch_one<GEMM_NN, false>(p, r, st);
+      else ARG_CHECK(false, "gemm: unknown form %d", p.form);
   }
-  switch (p.form) {
-    case GEMM_NT: return conv ? launch_one<GEMM_NT, true>(p, st) : launch_one<GEMM_NT, false>(p, st);
-    case GEMM_NN: return conv ? launch_one<GEMM_NN, true>(p, st) : launch_one<GEMM_NN, false>(p, st);
-    case GEMM_TN:
-      if (conv && conv_wgrad3_applicable(p) && conv_wgrad3_policy(p.M, p.N, p.K, p.Wm, p.sm)) rc = launch_conv_wgrad3(p, st);
-      else if (!conv && wgrad256_applicable(p) && wgrad256_policy(p.M, p.N, p.K)) rc = launch_wgrad256(p, st);
-      else
-      rc = conv ? launch_one<GEMM_TN, true>(p, st) : launch_one<GEMM_TN, false>(p, st);
-      if (rc == 0 && p.splitk > 1) {
-        const int cols = p.N * p.taps;
-        long nv = (long)p.M * (cols / 4);
-        int g = (int)((nv + 255) / 256);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p.slab, (float*)p.C, p.M, cols, p.ldc,
-                           p.slab_ld, p.splitk, p.accumulate, p.Cb, p.cb_scale, p.up2 == 1 ? nullptr : p.bias_grad);      // (up2 == 1: gemm_kernel's own adds)
-        HIP_CHECK_RET(hipGetLastError());
-      }
-      return rc;
-  }
-  ARG_CHECK(false, "gemm: unknown form %d", p.form);
+  return rc ? rc : launch_gemm_post(p, r.post, st);
 }
 
 // ---- 3x3 convolution of a nearest-2x upsampled image without the upsampled image (GemmP::up2) ----

@@ -46,10 +46,12 @@
 #ifdef SDXL_DIAG
 extern int g_knobs[SDXL_NKNOBS];
 #define KNOB(i) (g_knobs[(i)])
+constexpr bool SDXL_DIAG_BUILD = true;
 constexpr bool SDXL_UP2_3 = true;
 constexpr bool SDXL_LN_EPILOGUE = true;
 #else
 #define KNOB(i) 0
+constexpr bool SDXL_DIAG_BUILD = false;
 constexpr bool SDXL_UP2_3 = false;
 constexpr bool SDXL_LN_EPILOGUE = false;      // GemmP::ln_x (LayerNorm backward in the dgrad epilogue): measured, not shipped
 #endif
@@ -185,12 +187,34 @@ int gemm_pick_group(int M, int N, int taps, long red, int splitk);   // problems
 size_t gemm_slab_floats(int M, int N, int taps, int splitk);
 void gemm_defaults(GemmP* p);
 int launch_gemm(const GemmP& p, hipStream_t st);
+// What launch_gemm runs for a problem: decided by gemm_route (gemm.hip), the one place the selection policy lives; the launcher only obeys it.
+enum { GEMM_K128 = 0, GEMM_K256, GEMM_KCR256, GEMM_KPL, GEMM_KWGRAD256, GEMM_KCONV_WGRAD3, GEMM_KSK };      // gemm_kernel | gemm256 | cr256 | gemm_pl | wgrad256 | conv_wgrad3 | stream-K (diagnostics build)
+enum { GEMM_POST_NONE = 0, GEMM_POST_REDUCE, GEMM_POST_EPILOGUE };      // the pass over the split-K slabs: fp32 sum (weight gradients) | sum + bf16 epilogue
+struct GemmRoute {
+  int kernel;
+  int cfg;        // GEMM_K128: 1, 2, 3, 13, 23, 5, 6 (43); GEMM_KCR256: 31 .. 36; GEMM_KPL: 7, 8 (with the prefetch wave); else 0
+  bool fast;      // GEMM_K128: the FAST staging instantiation
+  int post;
+};
+GemmRoute gemm_route(const GemmP& p);                 // p checked and normalised (as launch_gemm does first); no HIP call
+int gemm_route_checked(GemmP p, GemmRoute* r);        // the same checks and normalisation as a launch, then gemm_route: 0, or the launch's argument error
 // 256 x 256 tile, 8-phase kernel (gemm256.hip): M, N multiples of 256, K of 64, no 3x3 gather
 bool gemm256_applicable(const GemmP& p);
 void gemm_set_mode(int mode);   // bits 0-1: 0 never / 1 policy / 2 wherever applicable; bits 2..: force a 128-row configuration
 bool gemm_use256(int form, int M, int N, int K, int splitk);   // the policy of mode 1
 int gemm_pick_splitk(int M, int N, int taps, long red);        // split-K factor the wgrad launchers should request
 int gemm_pick_splitk_small(int M, int N, int K, int kind = -1);               // split-K factor for NT / NN (bf16 output) launches of small problems
+// the plan-time choices of the layers' launches, once for the plan and the single-kernel entry points (gemm.hip): the split-K factor of each
+// launch WITH the condition under which it applies (1 = unsplit), and the geometry of a 3x3 convolution's three problems
+int linear_wgrad_splitk(int Mo, int No, long rows);
+int conv3x3_fwd_splitk(int B, int H, int W, int Cin, int Cout, int stride);
+int conv3x3_dgrad_splitk(int B, int H, int W, int Cin, int Cout, int stride);
+int conv3x3_wgrad_splitk(int B, int H, int W, int Cin, int Cout, int stride);
+int upconv3x3_fwd_splitk(int B, int H, int W, int Cin, int Cout);       // B, H, W: the LOW-resolution image
+int upconv3x3_dgrad_splitk(int B, int H, int W, int Cin, int Cout);
+GemmP conv3x3_fwd_problem(int B, int H, int W, int Cin, int Cout, int stride);
+GemmP conv3x3_dgrad_problem(int B, int H, int W, int Cin, int Cout, int stride);
+GemmP conv3x3_wgrad_problem(int B, int H, int W, int Cin, int Cout, int stride);
 int launch_gemm256(const GemmP& p, hipStream_t st);
 void gemm256_set_tail(bool on);     // half-height workgroups for the last partial round (default on; A/B runs)
 #ifdef SDXL_DIAG

@@ -194,7 +194,26 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
     "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
 }
+GEMM_DESC_FIELDS = ("form", "taps", "M", "N", "K", "splitk", "group", "cfg", "geglu", "geglu_group", "Hm", "Wm", "Hs", "Ws", "sm", "sd", "up2", "emit_bf16", "delta", "bias_grad")
+GEMM_ROUTE_FIELDS = ("kernel", "cfg", "fast", "post")
+GEMM_KERNELS = ("128-row", "256x256", "cr256", "pipelined", "wgrad256", "conv_wgrad3", "stream-K")
+GEMM_POSTS = ("none", "splitk_reduce", "splitk_epilogue")
+
+
+def gemm_route(**problem) -> dict:
+    """what launch_gemm would run for a problem (sdxl_debug_gemm_route; no device needed): kernel and post by name, cfg, fast.  Unnamed fields: a plain
+    unsplit linear problem."""
+    d = dict(dict.fromkeys(GEMM_DESC_FIELDS, 0), taps=1, splitk=1, group=1, sm=1, sd=1)
+    assert set(problem) <= set(d), set(problem) - set(d)
+    d.update(problem)
+    out = (_i * len(GEMM_ROUTE_FIELDS))()
+    check(load().sdxl_debug_gemm_route((_i * len(GEMM_DESC_FIELDS))(*[int(d[k]) for k in GEMM_DESC_FIELDS]), out), "sdxl_debug_gemm_route")
+    r = dict(zip(GEMM_ROUTE_FIELDS, out))
+    return dict(r, kernel=GEMM_KERNELS[r["kernel"]], post=GEMM_POSTS[r["post"]], fast=bool(r["fast"]))
+
+
 # include/sdxlstep_diag.h part 2: experiment ABI, exported by libsdxlstep_diag.so only
 DIAG_SIGNATURES = {
     "sdxl_op_linear_dgrad_ln_bwd": [_vp, _vp, _vp, _P(_f), _vp, _vp, _vp, _vp, _P(_f), _i, _i, _i, _vp],

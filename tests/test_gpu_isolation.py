@@ -85,15 +85,13 @@ def only(runs, names):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GEMM NT / NN
-def _gemm_route(M, N, K, cfg, mode):
-    """which kernel a forced configuration reaches, restated from launch_gemm_impl / launch_one (csrc/gemm.hip)"""
-    if cfg in (31, 32) and M % 8 == 0 and K % 32 == 0:
-        return f"co-resident 256 x {160 if cfg == 31 else 128} (gemm_cr256.hip)"
-    if mode == 2 and M % 256 == 0 and N % 256 == 0 and K % 64 == 0:
-        return "256 x 256 (gemm256.hip)"
-    if cfg in (3, 13, 23):
-        return f"128-row configuration {cfg if N % 160 == 0 else 1}"
-    return f"128-row configuration {cfg if cfg in (1, 2) else 'of the policy'}"
+def _gemm_route(L, form, M, N, K, cfg, mode, **more):
+    """which kernel the launch reaches under gemm mode `mode`: the library's own answer (sdxl_debug_gemm_route = gemm_route, csrc/gemm.hip)"""
+    lib.check(L.sdxl_set_gemm_mode(mode))
+    try:
+        return lib.gemm_route(form=form, M=M, N=N, K=K, cfg=cfg, **more)
+    finally:
+        lib.check(L.sdxl_set_gemm_mode(1))
 
 
 def _gemm_ld_case(L, form, M, N, K, cfg, mode=1, cross=False):
@@ -105,7 +103,7 @@ def _gemm_ld_case(L, form, M, N, K, cfg, mode=1, cross=False):
         lib.check(L.sdxl_op_gemm_ld(form, P(ar, "A"), P(ar, "B"), P(ar, "C"), M, N, K, ar.ld("A"), ar.ld("B"), ar.ld("C"), P(ar, "bias"),
                                     P(ar, "res"), ar.ld("res"), cfg, st()))
     what = f"gemm_ld form {form} {M}x{N}x{K} cfg {cfg} mode {mode}{' cross-row' if cross else ''}"
-    print(f"[isolation] {what}: {_gemm_route(M, N, K, cfg, mode)}")
+    print(f"[isolation] {what}: {_gemm_route(L, form, M, N, K, cfg, mode)}")
     lib.check(L.sdxl_set_gemm_mode(mode))
     try:
         runs = run(fn, specs, poison={"A": slice(150, M), "res": slice(150, M)} if cross else None)
@@ -130,7 +128,7 @@ def test_gemm_nt_nn_with_gaps_on_every_leading_dimension(L, form, M, N, K, cfg):
 @pytest.mark.parametrize("M,N,K,route", [(300, 256, 128, "128-row"), (256, 256, 128, "256 x 256"), (512, 256, 128, "256 x 256")])
 @pytest.mark.parametrize("form", [0, 1], ids=["nt", "nn"])
 def test_gemm_nt_nn_under_gemm_mode_2(L, form, M, N, K, route):
-    assert _gemm_route(M, N, K, 0, 2).startswith(route)
+    assert _gemm_route(L, form, M, N, K, 0, 2)["kernel"] == route.replace(" ", "")
     _gemm_ld_case(L, form, M, N, K, 0, mode=2)
 
 
@@ -428,7 +426,8 @@ def test_ff_geglu_fwd_bwd(L, M, K, C4, G, cross):
     what = f"ff geglu {M}x{K}x{C4} group {G}{' cross-row' if cross else ''}"
     h = M // 2
     mode = 2 if G == 64 else 1                                # as tests/test_gpu_ops.py::test_ff_geglu_fused_fwd_bwd
-    print(f"[isolation] {what}: forward {_gemm_route(M, 2 * C4, K, 0, mode)}, backward {_gemm_route(M, C4, K, 0, mode)}")
+    print(f"[isolation] {what}: forward {_gemm_route(L, 0, M, 2 * C4, K, 0, mode, geglu=1, geglu_group=G)}, "
+          f"backward {_gemm_route(L, 1, M, C4, K, 0, mode, geglu=2, geglu_group=G)}")
     lib.check(L.sdxl_set_gemm_mode(mode))
     try:
         runs = run(fn, specs, poison={"x": slice(h, M), "dy": slice(h, M)} if cross else None)
