@@ -218,6 +218,44 @@ typedef struct {
   const void* base;          /* device bf16: the W0 copies, packed [out][in] in target order (load only) */
   float* adapter_grads;      /* device fp32, laid out like adapters (export only) */
 } sdxl_lora_op;
+/* ---- gradient selection: dtype SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad (no entry point of its own) ----
+ *   sdxl_export_grad(h, NULL, &sel, SDXL_DTYPE_GRAD_SELECT, stream)
+ * tells the backward which state-dict tensors are trained.  `sel` is a HOST pointer, read during the call; `name` must be NULL; a NULL
+ * struct pointer = every tensor trainable (the state after sdxl_create).  Nothing is launched; the selection holds for every plan of the
+ * handle until it is changed, and a change drops the captured graphs.
+ * What is skipped: an op's parameter-gradient work -- the weight-gradient GEMM / convolution launch with its bias column sums, the
+ * zero-row memsets in front of it, the reduce of a norm's dgamma | dbeta -- if and only if EVERY tensor that maps into the op's native
+ * parameters is frozen.  State-dict tensors do not map 1:1 to ops: attn1.to_q | to_k | to_v of a block are one fused weight, attn2.to_k |
+ * to_v of ALL blocks of one width are one grouped weight, all time_emb_proj (weight and bias) are one op, a weight and its bias (a norm's
+ * weight and bias) are one op.  An op with at least one trainable tensor runs exactly as without a selection, and the frozen tensors that
+ * share it get their true gradient as a by-product.  A skipped op writes NOTHING into the fp32 gradient arena or the bf16 emit arena
+ * (sdxl_set_grad_emit): not a zero, not a partial -- its ranges keep what they held (its bias / norm vectors the zeros of
+ * sdxl_zero_grads).  The input-gradient side of the backward is untouched: every dgrad, the attention backward, the time-embedding
+ * column sums and the conditioning gradients (sdxl_batch_ext) run and give the same bits under any selection.  Of the weight gradients
+ * that still run, the linear ones that share a grouped launch may change their fp32 summation order with the group's composition.
+ * sdxl_zero_grads, segment ranges and join modes keep their meaning; sdxl_grad_sumsq sums the whole arena, stale values of frozen
+ * ranges included -- a caller with a selection takes its norm over its own tensors (sdxl_sumsq on their ranges).
+ * `lora` (NULL = none): adapters whose gradients the backward writes itself (csrc/lora_grad.hip).  A linear op that holds targets launches,
+ * in place of its weight-gradient launch (same stream, same place in the order), dA (+)= s (dY B)^T X and dB (+)= s dY^T (X A^T) for each of
+ * its targets, from the op's input X and output gradient dY: the LoRA gradients at the merged weight, without dW.  The intermediates X A^T
+ * and dY B are rounded once to bf16; fp32 accumulation, no atomics, the rows split across workgroups in chunks fixed by their number
+ * alone and the partial sums added in ascending order: bits are reproducible and a target's bits do not depend on the other targets.
+ * first_micro != 0 overwrites adapter_grads, otherwise the micro-step is added to them (the fp32 weight-gradient rule); `base` is not read.
+ * Rows of the op's weight that belong to no target get nothing, so EVERY tensor of an op that holds a target must be flagged 0 (its bias
+ * too).  The struct's rank, scale and the addresses of `adapters` / `adapter_grads` are taken at the call: they must stay valid until the
+ * selection changes, and the call is repeated when one of them changes.  The plans reserve the kernels' scratch, so a change of `lora`
+ * DROPS EVERY PLAN of the handle (it waits for the device first): call sdxl_plan and sdxl_bind_workspace again.
+ * Bad arguments (1, before anything changes, the message names the cause): n != sdxl_num_params(h), a flag other than 0 / 1, a non-NULL
+ * name; a selection that differs from the current one between sdxl_forward_loss and the end of its backward (a forward that is never
+ * differentiated, an evaluation, keeps that wait open; it ends with the next backward, with a plain sdxl_unet_forward, or with a call of
+ * sdxl_plan -- also for the shape that is current -- which is how a caller says that no backward will follow); with `lora`
+ * everything SDXL_DTYPE_LORA refuses, with its messages, a trainable tensor in an op that holds a target, and `lora` together with a
+ * bf16 emit arena (sdxl_set_grad_emit refuses the other order). */
+#define SDXL_DTYPE_GRAD_SELECT 3
+typedef struct {
+  int n; const unsigned char* trainable;   /* host [n], n == sdxl_num_params(h): 1 = the backward produces this tensor's gradient, 0 = frozen */
+  const sdxl_lora_op* lora;                /* NULL, or the adapters whose gradients the backward writes itself */
+} sdxl_grad_select;
 SDXL_API int sdxl_export_weight(sdxl_handle* h, const char* name, void* dst_dev, int dtype, void* stream);
 SDXL_API int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst_dev, int dtype, void* stream);
 

@@ -64,6 +64,13 @@ SDXL_API int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_g
 SDXL_API int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* stream);
 SDXL_API int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale,
                          void* stream);
+/* the direct adapter-gradient kernels of sdxl_grad_select.lora (csrc/lora_grad.hip) on caller buffers, a table of one target, no handle:
+ * x [M][in] (row stride ldx), dy [M][out] (row stride ldy: a column slice of a wider tensor is dy + offset), A [rank][in], B [out][rank] bf16;
+ * dA [rank][in], dB [out][rank] fp32 = (accumulate ? previous : 0) + scale * (dY B)^T X, scale * dY^T (X A^T).  Rows past M and columns outside
+ * the operands are never read.  Stream-ordered; its scratch is one buffer of the process, kept between calls and grown when a call needs
+ * more (one stream at a time). */
+SDXL_API int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out,
+                               int in, int rank, float scale, int accumulate, void* stream);
 
 /* which kernel a GEMM launch takes (csrc/gemm.hip, gemm_route: the single implementation of DESIGN.md section 4's table), without launching it and
  * without a device.  The descriptor is what the problem's line in the launch log (SDXL_LAUNCH_LOG) carries, in the same order: emit_bf16 / delta /

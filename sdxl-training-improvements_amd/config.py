@@ -107,6 +107,10 @@ class TrainingConfig:                    # data/config.py:152-168
     lora_targets: Optional[List[str]] = None   # module-path suffixes; None = to_q, to_k, to_v, to_out.0
     lora_seed: int = 0                   # seed of the A ~ N(0, (1 / rank)^2) initialisation (B = 0)
     lora_save_merged: bool = False       # save_checkpoint also writes the merged UNet
+    # what the backward computes for the adapters (lora.LORA_BACKWARDS): "project" = every weight gradient, then the projection (the
+    # default); "project_frozen" = only the ops that hold a target form their weight gradient, projected as before; "direct" = no weight
+    # gradient at all, dA and dB come out of the backward itself (csrc/lora_grad.hip)
+    lora_backward: str = "project"
 
 
 @dataclass

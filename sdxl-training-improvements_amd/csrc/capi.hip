@@ -15,6 +15,7 @@ struct StepState {  // what backward needs from the preceding forward
   bool valid = false;
   float* d_ehs = nullptr;   // the conditioning gradients this micro-step asked for (sdxl_batch_ext): the caller's
   float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
+  bool awaiting_bwd = false;   // a sdxl_forward_loss whose backward has not finished: the gradient selection may not change under it
 };
 struct LoraCache {  // device table of the last SDXL_DTYPE_LORA call, keyed by (target list, rank)
   std::vector<int> params;
@@ -106,6 +107,7 @@ int sdxl_destroy(sdxl_handle* h) {
   if (h->e.side) (void)hipStreamDestroy(h->e.side);
   if (h->e.small_ranges_dev) (void)hipFree(h->e.small_ranges_dev);
   if (h->lora.dev) (void)hipFree(h->lora.dev);
+  if (h->e.lora.dev) (void)hipFree(h->e.lora.dev);
   delete h;
   return 0;
 }
@@ -169,43 +171,57 @@ static int lora_check_shape(const char* who, int out, int in, int rank) {
 }
 static bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
 
-static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q) {
-  ARG_CHECK(name == nullptr, "lora: `name` must be NULL with SDXL_DTYPE_LORA (the targets are listed in sdxl_lora_op.param)");
+// the checks every user of a sdxl_lora_op shares (merge, project, the backward's own adapter gradients), before anything is launched
+static int lora_check_op(const sdxl_lora_op* op, bool need_base, bool need_grads) {
   ARG_CHECK(op && op->n >= 1 && op->param, "lora: empty target list");
   ARG_CHECK(op->rank >= 1 && op->rank <= 128, "lora: rank %d outside 1 .. 128", op->rank);
   ARG_CHECK(isfinite(op->scale), "lora: scale is not finite");
   ARG_CHECK(aligned16(op->adapters), "lora: adapters must be a 16-byte aligned device pointer");
-  if (merge) ARG_CHECK(aligned16(op->base), "lora: base must be a 16-byte aligned device pointer");
-  else ARG_CHECK(aligned16(op->adapter_grads), "lora: adapter_grads must be a 16-byte aligned device pointer");
+  if (need_base) ARG_CHECK(aligned16(op->base), "lora: base must be a 16-byte aligned device pointer");
+  if (need_grads) ARG_CHECK(aligned16(op->adapter_grads), "lora: adapter_grads must be a 16-byte aligned device pointer");
+  return 0;
+}
+// the targets of `params` in order: every target checked, its place in the weight arena and in the adapter / W0 arenas, its first tiles
+static int lora_table(Engine& e, const std::vector<int>& params, int rank, std::vector<LoraTarget>& tab, long* tm_, long* tb_, long* ta_) {
+  tab.assign(params.size(), LoraTarget());
+  std::vector<char> seen(e.src.size(), 0);
+  long a = 0, b = 0, tm = 0, tb = 0, ta = 0;
+  for (size_t i = 0; i < params.size(); ++i) {
+    const int pi = params[i];
+    ARG_CHECK(pi >= 0 && pi < (int)e.src.size(), "lora: parameter index %d out of range", pi);
+    const SrcParam& sp = e.src[pi];
+    ARG_CHECK(sp.ndim == 2 && sp.kind == 0, "lora: '%s' is not a 2-D weight in plain row layout (convolutions and the interleaved "
+              "ff.net.0.proj cannot be targets)", sp.name.c_str());
+    ARG_CHECK(!seen[pi], "lora: '%s' is listed twice", sp.name.c_str());
+    seen[pi] = 1;
+    const int out = (int)sp.shape[0], in = (int)sp.shape[1];
+    CHK(lora_check_shape(sp.name.c_str(), out, in, rank));
+    LoraTarget& t = tab[i];
+    t.w_off = (long)(sp.native.off + sp.elem_off);
+    ARG_CHECK(t.w_off % 8 == 0, "lora: '%s' does not start on a 16-byte boundary of the arena", sp.name.c_str());
+    t.base_off = b; b += (long)out * in;
+    t.a_off = t.ga_off = a; a += ((long)rank * in + 7) / 8 * 8;
+    t.b_off = t.gb_off = a; a += ((long)out * rank + 7) / 8 * 8;
+    t.out = out; t.in = in; t.pad = 0;
+    t.tile_m = (int)tm; t.tile_b = (int)tb; t.tile_a = (int)ta;
+    tm += lora_tiles_m(out, in); tb += lora_tiles_b(out, in); ta += lora_tiles_a(out, in);
+    ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "lora: too many tiles");
+  }
+  *tm_ = tm; *tb_ = tb; *ta_ = ta;
+  return 0;
+}
+
+static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q) {
+  ARG_CHECK(name == nullptr, "lora: `name` must be NULL with SDXL_DTYPE_LORA (the targets are listed in sdxl_lora_op.param)");
+  CHK(lora_check_op(op, merge, !merge));
   Engine& e = h->e;
   ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lora: %s are not bound", merge ? "weights" : "grads");
   LoraCache& c = h->lora;
   std::vector<int> params(op->param, op->param + op->n);
   if (!(c.dev && c.rank == op->rank && c.params == params)) {
-    std::vector<LoraTarget> tab(params.size());
-    std::vector<char> seen(e.src.size(), 0);
-    long a = 0, b = 0, tm = 0, tb = 0, ta = 0;
-    for (size_t i = 0; i < params.size(); ++i) {
-      const int pi = params[i];
-      ARG_CHECK(pi >= 0 && pi < (int)e.src.size(), "lora: parameter index %d out of range", pi);
-      const SrcParam& sp = e.src[pi];
-      ARG_CHECK(sp.ndim == 2 && sp.kind == 0, "lora: '%s' is not a 2-D weight in plain row layout (convolutions and the interleaved "
-                "ff.net.0.proj cannot be targets)", sp.name.c_str());
-      ARG_CHECK(!seen[pi], "lora: '%s' is listed twice", sp.name.c_str());
-      seen[pi] = 1;
-      const int out = (int)sp.shape[0], in = (int)sp.shape[1];
-      CHK(lora_check_shape(sp.name.c_str(), out, in, op->rank));
-      LoraTarget& t = tab[i];
-      t.w_off = (long)(sp.native.off + sp.elem_off);
-      ARG_CHECK(t.w_off % 8 == 0, "lora: '%s' does not start on a 16-byte boundary of the arena", sp.name.c_str());
-      t.base_off = b; b += (long)out * in;
-      t.a_off = t.ga_off = a; a += ((long)op->rank * in + 7) / 8 * 8;
-      t.b_off = t.gb_off = a; a += ((long)out * op->rank + 7) / 8 * 8;
-      t.out = out; t.in = in; t.pad = 0;
-      t.tile_m = (int)tm; t.tile_b = (int)tb; t.tile_a = (int)ta;
-      tm += lora_tiles_m(out, in); tb += lora_tiles_b(out, in); ta += lora_tiles_a(out, in);
-      ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "lora: too many tiles");
-    }
+    std::vector<LoraTarget> tab;
+    long tm = 0, tb = 0, ta = 0;
+    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta));
     if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
     HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
@@ -235,7 +251,99 @@ int sdxl_export_weight(sdxl_handle* h, const char* name, void* dst, int dtype, v
   ARG_CHECK(name && dst, "null argument");
   return engine_export(h->e, name, dst, dtype, false, (hipStream_t)st);
 }
+// ---- gradient selection (SDXL_DTYPE_GRAD_SELECT): host flags in, Engine::set_trainable; nothing is launched ----
+static int grad_select(sdxl_handle* h, const char* name, const sdxl_grad_select* sel) {
+  ARG_CHECK(name == nullptr, "grad select: `name` must be NULL with SDXL_DTYPE_GRAD_SELECT (the tensors are flagged in sdxl_grad_select.trainable)");
+  H_CHECK(h);
+  Engine& e = h->e;
+  std::vector<unsigned char> want;      // normal form: empty = every tensor trainable
+  if (sel) {
+    ARG_CHECK(sel->n == (int)e.src.size(), "grad select: n = %d, but the model has %d state-dict tensors (sdxl_num_params)", sel->n, (int)e.src.size());
+    ARG_CHECK(sel->trainable != nullptr, "grad select: trainable is NULL (pass a NULL struct for `every tensor trainable`)");
+    bool all = true;
+    for (int i = 0; i < sel->n; ++i) {
+      ARG_CHECK(sel->trainable[i] <= 1, "grad select: trainable[%d] ('%s') is %d (0 = frozen, 1 = trainable)", i, e.src[i].name.c_str(), (int)sel->trainable[i]);
+      all = all && sel->trainable[i] == 1;
+    }
+    if (!all) want.assign(sel->trainable, sel->trainable + sel->n);
+  }
+  // adapters whose gradients the backward writes itself: the same checks and messages as SDXL_DTYPE_LORA, then the targets by op
+  Engine::LoraSel L;
+  std::vector<LoraGradTarget> flat;
+  if (sel && sel->lora) {
+    const sdxl_lora_op* op = sel->lora;
+    CHK(lora_check_op(op, false, true));
+    ARG_CHECK(e.emit_base == nullptr, "lora: adapter gradients from the backward cannot be combined with a bf16 emit arena (sdxl_set_grad_emit)");
+    L.params.assign(op->param, op->param + op->n);
+    L.rank = op->rank; L.scale = op->scale; L.adapters = (const bf16*)op->adapters; L.grads = op->adapter_grads;
+    std::vector<LoraTarget> tab;
+    long tm = 0, tb = 0, ta = 0;
+    CHK(lora_table(e, L.params, op->rank, tab, &tm, &tb, &ta));
+    for (size_t i = 0; i < tab.size(); ++i) {
+      const SrcParam& sp = e.src[L.params[i]];
+      ARG_CHECK(sp.elem_off % (size_t)tab[i].in == 0, "lora: '%s' does not start on a row of its native weight", sp.name.c_str());
+      LoraGradTarget g;
+      memset(&g, 0, sizeof(g));
+      g.a_off = tab[i].a_off; g.b_off = tab[i].b_off; g.ga_off = tab[i].ga_off; g.gb_off = tab[i].gb_off;
+      g.out = tab[i].out; g.in = tab[i].in; g.dy_col = (int)(sp.elem_off / (size_t)tab[i].in);
+      L.ops[sp.native.off].host.push_back(g);
+    }
+    // every tensor of an op that holds a target is frozen: the op forms no dW, so it has no gradient to give them
+    for (size_t i = 0; i < e.src.size(); ++i) {
+      if (!sel->trainable[i]) continue;
+      const SrcParam& sp = e.src[i];
+      bool shares = L.ops.count(sp.native.off) != 0;
+      const size_t dot = sp.name.rfind('.');
+      if (!shares && dot != std::string::npos && sp.name.compare(dot, std::string::npos, ".bias") == 0) {      // the bias of a targeted layer
+        auto it = e.src_index.find(sp.name.substr(0, dot) + ".weight");
+        shares = it != e.src_index.end() && L.ops.count(e.src[it->second].native.off) != 0;
+      }
+      ARG_CHECK(!shares, "grad select: '%s' is flagged trainable but belongs to an op with adapter targets, whose dW is never formed: its flag must be 0",
+                sp.name.c_str());
+    }
+    for (auto& kv : L.ops) {
+      Engine::LoraOpSel& o = kv.second;
+      long tiles = 0, reds = 0, unit = 0;
+      for (LoraGradTarget& g : o.host) {
+        g.tile0 = (int)tiles; g.red0 = (int)reds; g.part_off = unit;
+        tiles += lora_grad_tiles(g.out, g.in); reds += lora_grad_reds(g.out, g.in, L.rank); unit += (long)L.rank * ((long)g.in + g.out);
+      }
+      ARG_CHECK(tiles < (1L << 24) && reds < (1L << 31), "lora: too many tiles");
+      o.tiles = (int)tiles; o.reds = (int)reds; o.part_unit = (size_t)unit;
+      flat.insert(flat.end(), o.host.begin(), o.host.end());
+    }
+  }
+  const bool same_lora = L.params == e.lora.params && L.rank == e.lora.rank && L.scale == e.lora.scale && L.adapters == e.lora.adapters &&
+                         L.grads == e.lora.grads;
+  if (want == e.trainable && same_lora) return 0;      // unchanged: captured graphs stay valid
+  ARG_CHECK(!h->step.awaiting_bwd, "grad select: the selection cannot change between sdxl_forward_loss and the end of its backward");
+  e.clear_graphs();                       // captured backwards hold the old selection's launches
+  if (!same_lora) {
+    // the plans reserve the adapter-gradient scratch of their targeted ops: dropped, the caller plans again (sdxl_plan, sdxl_bind_workspace)
+    HIP_CHECK_RET(hipDeviceSynchronize());
+    e.drop_pending();
+    e.plans.clear();
+    e.cur = nullptr;
+    if (e.lora.dev) { (void)hipFree(e.lora.dev); e.lora.dev = nullptr; }
+    if (!flat.empty()) {
+      HIP_CHECK_RET(hipMalloc((void**)&L.dev, flat.size() * sizeof(LoraGradTarget)));
+      if (hipMemcpy(L.dev, flat.data(), flat.size() * sizeof(LoraGradTarget), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(L.dev);
+        e.lora = Engine::LoraSel();      // (the old table is gone and the plans are dropped: no adapters until the next call)
+        sdxl_set_error("grad select: copying the target table to the device failed");
+        return 2;
+      }
+      size_t at = 0;
+      for (auto& kv : L.ops) { kv.second.dev = L.dev + at; at += kv.second.host.size(); }
+    }
+    e.lora = std::move(L);
+  }
+  e.set_trainable(want.empty() ? nullptr : want.data());
+  return 0;
+}
+
 int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, void* st) {
+  if (dtype == SDXL_DTYPE_GRAD_SELECT) return grad_select(h, name, (const sdxl_grad_select*)dst);
   H_CHECK(h);
   if (dtype == SDXL_DTYPE_LORA) {
     LoraP q;
@@ -271,6 +379,37 @@ int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* d
   return launch_lora_project(q, (hipStream_t)st);
 }
 
+int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out, int in,
+                      int rank, float scale, int accumulate, void* st) {
+  ARG_CHECK(x && dy && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB), "lora_grad: A, B, dA, dB must be 16-byte aligned, x and dy non-NULL");
+  CHK(lora_check_shape("the operand", out, in, rank));
+  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
+  ARG_CHECK(M >= 1 && ldx >= in && ldy >= out, "lora_grad: M = %d, ldx = %ld (in = %d), ldy = %ld (out = %d)", M, ldx, in, ldy, out);
+  LoraGradP q;
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = scale; q.accumulate = accumulate != 0;
+  q.one.out = out; q.one.in = in;
+  q.x = (const bf16*)x; q.ldx = ldx; q.dy = (const bf16*)dy; q.ldy = ldy;
+  q.M = M; q.Mp = lora_grad_mp(M); q.nchunk = lora_grad_chunks(M);
+  q.tiles = lora_grad_tiles(out, in); q.reds = lora_grad_reds(out, in, rank);
+  q.xvec = ((uintptr_t)x % 16 == 0 && ldx % 8 == 0) ? 1 : 0;
+  q.yvec = ((uintptr_t)dy % 16 == 0 && ldy % 8 == 0) ? 1 : 0;
+  q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
+  // scratch of the hook (the engine's is plan workspace): one buffer of the process, kept between calls and only ever grown (hipFree
+  // waits for the launches that use the old one), so that repeated calls of one shape enqueue three launches and nothing else
+  static char* scratch = nullptr;
+  static size_t scratch_cap = 0;
+  const size_t tu_bytes = (lora_grad_tu_elems(1, rank, M) * sizeof(bf16) + 255) / 256 * 256;
+  const size_t need = tu_bytes + lora_grad_part_floats(out, in, rank, M) * sizeof(float);
+  if (need > scratch_cap) {
+    if (scratch) { (void)hipFree(scratch); scratch = nullptr; scratch_cap = 0; }
+    HIP_CHECK_RET(hipMalloc((void**)&scratch, need));
+    scratch_cap = need;
+  }
+  q.tu = (bf16*)scratch; q.part = (float*)(scratch + tu_bytes);
+  return launch_lora_grad(q, (hipStream_t)st);
+}
+
 int sdxl_plan(sdxl_handle* h, int B, int H, int W, int ctx, size_t* ws_bytes) {
   H_CHECK(h);
   ARG_CHECK(B > 0 && H > 0 && W > 0 && ctx > 0, "bad plan shape B=%d H=%d W=%d ctx=%d", B, H, W, ctx);
@@ -287,6 +426,7 @@ int sdxl_plan(sdxl_handle* h, int B, int H, int W, int ctx, size_t* ws_bytes) {
   }
   if (e.cur != it->second.get()) e.drop_pending();
   e.cur = it->second.get();
+  h->step.awaiting_bwd = false;      // (the caller's way to say that the last sdxl_forward_loss gets no backward: sdxlstep.h, gradient selection)
   if (ws_bytes) *ws_bytes = e.cur->ws_bytes;
   return 0;
 }
@@ -586,6 +726,7 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
     HIP_CHECK_RET(hipMemcpyAsync(b->per_sample_loss, p.F(p.ps_loss_off), sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
   h->step.lc = full; h->step.b = sb; h->step.valid = true;
   h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
+  h->step.awaiting_bwd = true;
   return 0;
 }
 
@@ -679,6 +820,7 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
                         loss_cfg_bits2(h->step.lc, h->step.b) | cond_bits(h->step), loss_huber_bits(h->step.lc, h->step.b)};
     CHK(run_graphed(e, key, st, body));
   }
+  if (k == e.nseg - 1) h->step.awaiting_bwd = false;
   return k == e.nseg - 1 ? copy_cond_grads(h, st) : 0;
 }
 
@@ -700,6 +842,7 @@ int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* s
     for (int k = 0; k < e.nseg; ++k) CHK(run_backward_segment(e, k, first_micro != 0, s));
     return 0;
   }));
+  h->step.awaiting_bwd = false;
   return copy_cond_grads(h, st);
 }
 int sdxl_set_graph_mode(sdxl_handle* h, int on) {
@@ -777,6 +920,7 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   }
   CHK(upload_cond(e, cond, st));
   h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
+  h->step.awaiting_bwd = false;      // (this forward replaced the loss step's activations: nothing waits for that backward any more)
   size_t bytes = (size_t)p.B * p.H * p.W * 8 * sizeof(bf16);
   HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, bytes, hipMemcpyDeviceToDevice, st));
   CHK(run_forward_ops(e, st));
@@ -834,6 +978,7 @@ int sdxl_small_grads_to_bf16(sdxl_handle* h, size_t off, size_t n, void* dst, fl
 int sdxl_set_grad_emit(sdxl_handle* h, void* bf16_arena, float scale) {
   H_CHECK(h);
   ARG_CHECK(((uintptr_t)bf16_arena & 15) == 0, "bf16 gradient arena must be 16-byte aligned");
+  ARG_CHECK(bf16_arena == nullptr || h->e.lora.ops.empty(), "lora: a bf16 emit arena cannot be combined with adapter gradients from the backward (sdxl_grad_select.lora)");
   if (h->e.emit_base != (bf16*)bf16_arena || h->e.emit_scale != scale) h->e.clear_graphs();   // captured wgrad launches hold the old target
   h->e.emit_base = (bf16*)bf16_arena;
   h->e.emit_scale = scale;

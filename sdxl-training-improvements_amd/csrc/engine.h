@@ -10,6 +10,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -99,6 +100,9 @@ struct Plan {
   CondSrc cond_kv[2], cond_add;        // the hoisted K | V projections in forward order (at most one per attention width); add_embedding.linear_1
   int cond_nkv = 0;
   size_t dehs_off = NONE, dpool_off = NONE, cond_slab_off = NONE;
+  // direct adapter gradients (lora_grad.hip, Engine::lora): scratch of the widest targeted op, shared and stream-ordered (every launch
+  // is on the side stream, or all on the caller's); nothing is reserved -- no offset of the plan moves -- without adapters
+  size_t lg_tu_elems = 0, lg_part_floats = 0, lg_tu_off = NONE, lg_part_off = NONE;
 
   Act* new_act(long rows, int cols, bool need_grad = true, int pad_rows = 0);
   Act* view(Act* parent, int col0, int cols);   // columns [col0, col0 + cols) of parent
@@ -170,6 +174,35 @@ struct Engine {
   bool cond_ehs = false, cond_pool = false;   // this micro-step's backward also produces d prompt_embeds / d pooled (set by the C ABI)
   bool cond_gated = false;                    // ... behind a loss (its gate scalar is read), not behind sdxl_unet_backward
   int launch_cond_grads(Plan& p, hipStream_t st);
+  // Gradient selection (SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad, OFF after sdxl_create): one flag per state-dict tensor, 1 = the backward
+  // produces its gradient.  A native parameter is frozen when EVERY tensor that maps into it is (fused q | k | v, the grouped K | V and
+  // time-embedding projections: a tensor is a row range of the native weight), and an op skips its weight-gradient work -- the launch with
+  // its bias column sums, the zero-row memsets in front of it, the norm-parameter reduce -- when every native parameter it owns is frozen:
+  // nothing is written into the fp32 arena or the emit arena for it.  The dgrad side never looks at the selection.  Read at launch time
+  // (it holds for every plan); a change drops the captured graphs.
+  // Adapters whose gradients the backward writes itself (sdxl_grad_select.lora): the targets of one LinearOp, keyed by its weight's arena
+  // offset; that op launches lora_grad.hip's kernels in place of its weight gradient.  Plans reserve the scratch in plan_bwd, so the
+  // plans are dropped when this changes.
+  struct LoraOpSel { std::vector<LoraGradTarget> host; const LoraGradTarget* dev = nullptr; int tiles = 0, reds = 0; size_t part_unit = 0; };
+  struct LoraSel {
+    std::vector<int> params;
+    int rank = 0; float scale = 0.f;
+    const bf16* adapters = nullptr; float* grads = nullptr;
+    std::map<size_t, LoraOpSel> ops;
+    LoraGradTarget* dev = nullptr;           // one device table, the ops' targets back to back
+  } lora;
+  const LoraOpSel* lora_op(PRef w) const {
+    if (lora.ops.empty()) return nullptr;
+    auto it = lora.ops.find(w.off);
+    return it == lora.ops.end() ? nullptr : &it->second;
+  }
+  std::vector<unsigned char> trainable;      // [src.size()], empty = every tensor trainable
+  std::set<size_t> frozen_offs;              // PRef::off of the frozen native parameters (empty without a selection: one test per op)
+  void set_trainable(const unsigned char* flags);      // nullptr = all trainable
+  bool frozen(PRef a, PRef b) const {        // an op owning a (and b, unless NONE): skip its parameter gradients?
+    if (frozen_offs.empty()) return false;
+    return (a.off == NONE || frozen_offs.count(a.off)) && (b.off == NONE || frozen_offs.count(b.off));
+  }
   // hipGraph replay of the step (sdxl_set_graph_mode, OFF by default): forward (+ loss) and backward are captured once per
   // (plan, configuration) -- both streams, every event edge -- and replayed with one hipGraphLaunch, on an engine-owned
   // stream (the caller's may be the legacy default stream, which cannot be captured) fenced by two events.  Measured on

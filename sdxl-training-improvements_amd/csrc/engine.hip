@@ -266,6 +266,12 @@ struct LinearOp : Op {
     crcfg = cr256_wgrad_cfg(N, K, x->rows, b.off != NONE);
     if (crcfg) { crsplit = cr256_pick_splitk(N, K, x->rows, crcfg); want_slab(p, N, K, 1, crsplit); }
     if (!gact) { fsplit = gemm_pick_splitk_small((int)x->rows, N, K, 3); want_slab_main(p, (int)x->rows, N, fsplit); }
+    if (const Engine::LoraOpSel* lo = p.eng->lora_op(w)) {      // direct adapter gradients: the scratch of lora_grad.hip's launches
+      const size_t tu = lora_grad_tu_elems((int)lo->host.size(), p.eng->lora.rank, (int)x->rows);
+      const size_t pf = (size_t)lora_grad_chunks((int)x->rows) * lo->part_unit;
+      if (tu > p.lg_tu_elems) p.lg_tu_elems = tu;
+      if (pf > p.lg_part_floats) p.lg_part_floats = pf;
+    }
     if (delta_attn && !(!gu && x->need_grad)) attn_set_delta_fused(delta_attn, false);      // no dgrad launch: nobody would write Delta
     if (!gu && x->need_grad) {
       dsplit = gemm_pick_splitk_small((int)x->rows, K, N, 2);
@@ -300,7 +306,23 @@ struct LinearOp : Op {
     }
     if (gu && dx.addend != NONE) { sdxl_set_error("geglu: pre-activation gradient has another writer"); return 3; }
     if (resid && !resid_alias) CHK(launch_add(p.GP(dres.addend), dy, p.GP(dres.out), (long)M * N, st));
-    {
+    if (const Engine::LoraOpSel* lo = p.eng->lora_op(w)) {
+      // adapter targets in this op: dA, dB of each straight from X and dY, in place of the weight-gradient launch (same call site: the side
+      // stream, behind the queued leaves that produce a prompt-side dY).  Rows of the weight that belong to no target get nothing.
+      const Engine::LoraSel& L = p.eng->lora;
+      LoraGradP q;
+      memset(&q, 0, sizeof(q));
+      q.table = lo->dev; q.n = (int)lo->host.size(); q.rank = L.rank; q.scale = L.scale; q.accumulate = first ? 0 : 1;
+      q.x = p.P(x); q.ldx = x->ld(); q.dy = dy; q.ldy = y->ld();
+      q.M = M; q.Mp = lora_grad_mp(M); q.nchunk = lora_grad_chunks(M); q.tiles = lo->tiles; q.reds = lo->reds;
+      q.xvec = ((uintptr_t)q.x % 16 == 0 && q.ldx % 8 == 0) ? 1 : 0;
+      q.yvec = ((uintptr_t)q.dy % 16 == 0 && q.ldy % 8 == 0) ? 1 : 0;
+      q.a = q.b = L.adapters; q.ga = q.gb = L.grads;
+      if (p.lg_tu_off == NONE || p.lg_part_off == NONE) { sdxl_set_error("lora: the plan was built without adapter-gradient scratch"); return 3; }
+      q.tu = (bf16*)p.F(p.lg_tu_off); q.part = p.F(p.lg_part_off);
+      CHK(on_side(p, st, [&q](hipStream_t s2) -> int { return launch_lora_grad(q, s2); }));
+    } else
+    if (!p.eng->frozen(w, b)) {      // (a frozen op: no weight gradient, no bias column sums, no zero rows for them -- Engine::frozen)
       GemmP g;
       gemm_defaults(&g);
       g.form = GEMM_TN;
@@ -447,6 +469,8 @@ struct ConvOp : Op {
     if (resid && !resid_alias) CHK(launch_add(p.GP(dres.addend), dy, p.GP(dres.out), Mo * Cout, st));
     const bool upw = up2() && up_wg && KNOB(2) != 128;       // (knob 2 = 128: weight gradient on the upsampled image, A/B runs)
     if (up2()) CHK(launch_pixel_shuffle2(dy, (bf16*)p.F(planar_off), Bn, H / 2, W / 2, Cout, 0, st));      // dy in its four phases: dgrad and weight gradient read it
+    if (p.eng->frozen(w, b)) {      // frozen: no weight gradient, no bias gradient (the dgrad side below is the same)
+    } else
 #ifdef SDXL_DIAG
     if (s2x_off != NONE && KNOB(2) == 512) {
       CHK(on_side(p, st, [&](hipStream_t s2) -> int {
@@ -530,7 +554,7 @@ struct GroupNormOp : Op {
     if (KNOB(27) & 1) return 0;
     LnRedEntry r;      // dgamma | dbeta: B partial rows, added in a fixed order by the batched reduce (no atomics: bitwise reproducible)
     r.part = p.F(prow_off); r.dgamma = p.eng->Gp(gm); r.dbeta = p.eng->Gp(bt); r.C = C; r.nblk = Bn;
-    p.eng->ln_pending.push_back(r);
+    if (!p.eng->frozen(gm, bt)) p.eng->ln_pending.push_back(r);      // (frozen: the partial rows are written and never folded)
     return launch_groupnorm_bwd(p.P(x), p.GP(dy_off), p.eng->Wp(gm), p.eng->Wp(bt), p.F(stats_off), p.GP(dx.out),
                                 p.GP(dx.addend), p.eng->Gp(gm), p.eng->Gp(bt), p.F(p.gn_ws_off), Bn, HW, C, G, silu, st, p.F(prow_off));
   }
@@ -565,7 +589,9 @@ struct LayerNormOp : Op {
     // the lean dx kernel (120 VGPRs, no LDS) on the caller's stream + the parameter gradients as a leaf pass on the side stream (knob 10 = 1):
     // -0.7 ms then; with the side stream's passes costing the step their full duration now (210 x 5.8 us re-reading 21 MB each beside the GEMMs:
     // knob 25 = 1 is worth -1.2 ms) the one-pass form is -0.4 ms again, five alternations (profiles/r05w_ab_ln_fused.txt).
+    const bool frozen = p.eng->frozen(gm, bt);      // the same dx pass; its dgamma | dbeta partial sums are never folded into the arena
     if (fused) {      // dx is in place (or will be: this op runs after the consumer in the backward order); the parameter gradients:
+      if (frozen) return 0;
       if (fused == 2) {
         const bf16* xp = p.P(x); const bf16* dyp = p.GP(dy_off); const float* sp = p.F(stats_off);
         float* dg = p.eng->Gp(gm); float* db = p.eng->Gp(bt); const int Mr = (int)x->rows, Cc = C;
@@ -583,7 +609,7 @@ struct LayerNormOp : Op {
       CHK(launch_layernorm_bwd(p.P(x), p.GP(dy_off), p.eng->Wp(gm), p.F(stats_off), p.GP(dx.out), p.GP(dx.addend), nullptr, nullptr, (int)x->rows, C, st));
       const bf16* xp = p.P(x); const bf16* dyp = p.GP(dy_off); const float* sp = p.F(stats_off);
       const int Mr = (int)x->rows, Cc = C;
-      if (KNOB(25) == 1) return 0;
+      if (KNOB(25) == 1 || frozen) return 0;
       if (KNOB(10) == 3) {      // (A/B runs: the column-sum pass with one atomic per column and block)
         float* dg = p.eng->Gp(gm); float* db = p.eng->Gp(bt);
         return side_leaf(p, st, [=](hipStream_t s2) -> int { return launch_layernorm_param_grads(xp, dyp, sp, dg, db, Mr, Cc, s2); });
@@ -599,7 +625,7 @@ struct LayerNormOp : Op {
     r.part = p.F(part_off); r.dgamma = p.eng->Gp(gm); r.dbeta = p.eng->Gp(bt); r.C = C;
     CHK(launch_layernorm_bwd(p.P(x), p.GP(dy_off), p.eng->Wp(gm), p.F(stats_off), p.GP(dx.out), p.GP(dx.addend),
                              p.F(part_off), &r.nblk, (int)x->rows, C, st));
-    p.eng->ln_pending.push_back(r);
+    if (!frozen) p.eng->ln_pending.push_back(r);
     return 0;
   }
 };
@@ -805,6 +831,18 @@ void Engine::map_src(const std::string& name, std::vector<long> shape, PRef p, i
   s.ci_pad = ci_pad;
   src_index[name] = (int)src.size();
   src.push_back(s);
+}
+
+void Engine::set_trainable(const unsigned char* flags) {
+  trainable.clear();
+  frozen_offs.clear();
+  if (!flags) return;
+  trainable.assign(flags, flags + src.size());
+  std::set<size_t> live;
+  for (size_t i = 0; i < src.size(); ++i)
+    if (flags[i]) live.insert(src[i].native.off);
+  for (const SrcParam& s : src)
+    if (!live.count(s.native.off)) frozen_offs.insert(s.native.off);
 }
 
 int Engine::seg_of(size_t elem_off) const {
@@ -1225,6 +1263,10 @@ void Engine::build(Plan* plan) {
       const size_t slab2 = cond_dgrad_slab_floats(1, Ka, plan->B, c.pooled_dim);
       if (slab2 > slab) slab = slab2;
       plan->cond_slab_off = plan->alloc(sizeof(float) * (slab ? slab : 4));
+    }
+    if (plan->lg_tu_elems) {      // ... and, with adapters selected, lora_grad.hip's scratch
+      plan->lg_tu_off = plan->alloc(sizeof(bf16) * plan->lg_tu_elems);
+      plan->lg_part_off = plan->alloc(sizeof(float) * (plan->lg_part_floats ? plan->lg_part_floats : 4));
     }
     plan->seg_first_op.assign(nseg, -1);
     plan->seg_last_op.assign(nseg, -2);

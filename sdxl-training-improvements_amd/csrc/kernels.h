@@ -538,3 +538,40 @@ static inline int lora_tiles_b(int out, int in) { return cdiv(out, LORA_B_ROWS);
 static inline int lora_tiles_a(int out, int in) { return cdiv(in, LORA_A_COLS); }
 int launch_lora_merge(const LoraP& p, hipStream_t st);
 int launch_lora_project(const LoraP& p, hipStream_t st);     // two launches: dB, dA
+
+// ---- direct LoRA adapter gradients (lora_grad.hip): dA, dB of every target of ONE linear op from its X and dY, no dW ----
+#define LORA_G_CHUNK 512      // rows of M per partial block (a multiple of 32): the split of M is fixed by M alone
+struct LoraGradTarget {
+  long a_off, b_off;          // adapter arena: A [rank][in], B [out][rank]
+  long ga_off, gb_off;        // adapter-gradient arena: dA, dB
+  long part_off;              // this target's partial blocks [nchunk][rank][in + out] start at float part_off * nchunk of LoraGradP::part
+                              // (= rank * the earlier targets' in + out: the table does not depend on M)
+  int out, in;                // in % 8 == 0
+  int dy_col;                 // first column of the target inside the op's dY (its first row inside the op's native weight)
+  int tile0, red0;            // first 128-column tile of [in | out] / first workgroup of the reduce launch
+  int pad;
+};
+struct LoraGradP {
+  const LoraGradTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
+  LoraGradTarget one;
+  int n, rank;                      // rank 1 .. 128
+  float scale;
+  int accumulate;                   // 0: dA, dB are overwritten; 1: added to
+  const bf16* x; long ldx;          // [M][in], shared by the targets
+  const bf16* dy; long ldy;         // [M][...]: a target's columns start at dy_col
+  int M, Mp;                        // Mp = M rounded up to 64
+  int xvec, yvec;                   // x / dy rows are addressable in 16-byte vectors (pointer and row stride multiples of 16 bytes)
+  int nchunk, tiles, reds;          // cdiv(M, LORA_G_CHUNK); sum of the targets' tiles; of their reduce workgroups
+  const bf16 *a, *b;                // what a_off / b_off count from
+  float *ga, *gb;                   // what ga_off / gb_off count from
+  bf16* tu;                         // scratch: lora_grad_tu_elems(n, rank, M) bf16, 16-byte aligned
+  float* part;                      // scratch: the targets' partial blocks
+};
+static inline int lora_grad_rb(int rank) { return rank <= 16 ? 1 : rank <= 32 ? 2 : rank <= 64 ? 4 : 8; }      // 16-rank blocks the kernels are built for
+static inline int lora_grad_mp(int M) { return cdiv(M, 64) * 64; }
+static inline int lora_grad_chunks(int M) { return cdiv(M, LORA_G_CHUNK); }
+static inline size_t lora_grad_tu_elems(int n, int rank, int M) { return (size_t)n * 2 * 16 * lora_grad_rb(rank) * lora_grad_mp(M); }
+static inline size_t lora_grad_part_floats(int out, int in, int rank, int M) { return (size_t)lora_grad_chunks(M) * rank * ((size_t)in + out); }
+static inline int lora_grad_tiles(int out, int in) { return cdiv(in, 128) + cdiv(out, 128); }
+static inline int lora_grad_reds(int out, int in, int rank) { return cdiv((long)rank * ((long)in + out), 256); }
+int launch_lora_grad(const LoraGradP& p, hipStream_t st);     // three launches: T | U, partial blocks, reduce

@@ -103,6 +103,14 @@ class LoraOp(C.Structure):
                 ("adapters", C.c_void_p), ("base", C.c_void_p), ("adapter_grads", C.c_void_p)]
 
 
+DTYPE_GRAD_SELECT = 3  # SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad: the pointer is a host GradSelect* (NULL = every tensor trainable), name NULL
+
+
+class GradSelect(C.Structure):
+    """sdxl_grad_select: one flag per state-dict tensor (sdxl_param_info order), 1 = the backward produces its gradient"""
+    _fields_ = [("n", C.c_int), ("trainable", C.POINTER(C.c_ubyte)), ("lora", C.POINTER(LoraOp))]
+
+
 LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
 MASK_NORMS = {"mean": 0, "masked_mean": 1}
 
@@ -194,6 +202,7 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
     "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "sdxl_op_lora_grad": [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
 }
 GEMM_DESC_FIELDS = ("form", "taps", "M", "N", "K", "splitk", "group", "cfg", "geglu", "geglu_group", "Hm", "Wm", "Hs", "Ws", "sm", "sd", "up2", "emit_bf16", "delta", "bias_grad")

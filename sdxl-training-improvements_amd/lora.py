@@ -10,7 +10,12 @@ src/models/adapters/lora.py: base(x) + alpha * up(down(x)), up = B, down = A):
 Both steps are one call into libsdxlstep (csrc/lora.hip through dtype SDXL_DTYPE_LORA of sdxl_load_weight / sdxl_export_grad).
 LoRAAdapters owns the small arenas and looks to a fused optimizer like a net (weights, grads, L, zero_grads, param_ranges), so
 AdamWBF16 / AdamWScheduleFreeKahanBF16 update it unchanged.  NativeLoRATrainer is the trainer `training.lora_rank > 0` selects.
-What this does not save: the weight gradients of the frozen tensors are still computed (skipping them is the engine's business).
+training.lora_backward chooses how much of the full model's backward runs for that (LORA_BACKWARDS):
+  "project"         all of it, as above (the default);
+  "project_frozen"  the engine's gradient selection (NativeUNet.set_trainable) keeps only the ops that hold a target: every other op
+                    skips its weight / bias / norm-parameter gradient work; dW of the targets' ops is formed and projected as before;
+  "direct"          every tensor is frozen and the targets' ops write dA = s (dY B)^T X, dB = s dY^T (X A^T) themselves
+                    (csrc/lora_grad.hip): no dW anywhere, no projection pass.
 """
 from __future__ import annotations
 
@@ -31,6 +36,40 @@ logger = logging.getLogger(__name__)
 
 DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
 MAX_RANK = 128
+LORA_BACKWARDS = ("project", "project_frozen", "direct")
+
+
+def check_lora_backward(mode) -> str:
+    if mode not in LORA_BACKWARDS:
+        raise ValueError(f"training.lora_backward {mode!r}: expected one of {list(LORA_BACKWARDS)}")
+    return mode
+
+
+def op_of(key: str, shape: Tuple[int, ...]) -> str:
+    """The engine op that owns a state-dict tensor (include/sdxlstep.h, gradient selection), as a label: attn1.to_q | to_k | to_v of a
+    block are one fused weight, attn2.to_k | to_v of EVERY block of one width one grouped weight, every time_emb_proj (weights and
+    biases) one op; any other module is its own op, weight and bias together."""
+    mod, _dot, _leaf = key.rpartition(".")
+    head, _dot, name = mod.rpartition(".")
+    if head.endswith(".attn1") and name in ("to_q", "to_k", "to_v"):
+        return head + ".to_qkv"
+    if head.endswith(".attn2") and name in ("to_k", "to_v"):
+        return f"attn2.to_kv[{int(shape[0])}]"
+    if name == "time_emb_proj":
+        return "time_emb_proj"
+    return mod
+
+
+def trainable_for(mode: str, targets: Sequence[str], shapes: Dict[str, Tuple[int, ...]]):
+    """the names NativeUNet.set_trainable gets for a lora_backward mode: None (everything: "project"), every tensor of an op that
+    holds a target ("project_frozen"), nothing ("direct")"""
+    check_lora_backward(mode)
+    if mode == "project":
+        return None
+    if mode == "direct":
+        return []
+    ops = {op_of(k, shapes[k]) for k in targets}
+    return [k for k in shapes if op_of(k, shapes[k]) in ops]
 
 
 def _pad8(n: int) -> int:
@@ -155,6 +194,13 @@ class LoRAAdapters:
         """dA, dB of every target from the net's fp32 gradient arena into `.grads` (overwritten; two launches)"""
         self._call("sdxl_export_grad", self.scale)
 
+    def select(self, mode: str) -> None:
+        """apply a training.lora_backward mode to the net: its gradient selection and, for "direct", these adapters as the ones whose
+        gradients the backward writes into `.grads` (first micro-step: overwritten, later ones: added to).  The arenas' addresses and the
+        scale are read now: call again after either changes."""
+        names = trainable_for(mode, self.targets, self.net.param_shapes())
+        self.net.set_trainable(names, lora=self._op(self.scale) if mode == "direct" else None)
+
     # ---- state
     def _meta(self) -> Dict[str, Any]:
         return {"rank": self.rank, "alpha": self.alpha, "seed": self.seed, "targets": list(self.targets),
@@ -236,8 +282,11 @@ class NativeLoRATrainer(NativeSDXLTrainer):
             raise ValueError("training.shard_optimizer: ZeRO-1 is not supported for adapters (training.lora_rank > 0); leave the key out")
         if optimizer is not None:
             logger.warning("NativeLoRATrainer builds its own fused optimizer on the adapter arena: the optimizer passed in is ignored")
+        self.lora_backward = check_lora_backward(getattr(tc, "lora_backward", "project"))
         super().__init__(model, None, train_dataloader, device, wandb_logger, config, **kwargs)
         self._projected = False
+        if self.lora_backward != "project":
+            self.lora.select(self.lora_backward)
         # whoever steps the optimizer -- optimizer_step() below or a caller-owned loop's optimizer.step() -- steps it on the projected
         # (and exchanged) gradients of the cycle, never on stale ones, and the merge follows the update
         inner = self.optimizer.step
@@ -275,7 +324,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
     def _project(self) -> None:
         if self._projected:
             return
-        self.lora.project()
+        if self.lora_backward != "direct":      # ("direct": the backward wrote dA, dB itself)
+            self.lora.project()
         if self.sync.world > 1:      # the backward already scaled by 1 / world, and projection is linear
             torch.distributed.all_reduce(self.lora.grads)
         self._projected = True
@@ -340,4 +390,6 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         if (d / "optimizer.pt").exists():
             self.load_optimizer_state(d)
         self.lora.load_state_dict(sd)
+        if self.lora_backward == "direct":      # (the state's alpha is the scale the backward applies)
+            self.lora.select(self.lora_backward)
         self.lora.merge()

@@ -501,6 +501,8 @@ class NativeSDXLTrainer:
                 per = self.net.read_per_sample_loss().double()
                 sums[key] = sums.get(key, 0.0) + float(per.sum())
                 counts[key] = counts.get(key, 0) + B
+        if callable(getattr(self.net, "discard_forward", None)):        # no backward follows these forwards: the gradient selection is free again
+            self.net.discard_forward()
         per_t = {k: sums[k] / counts[k] for k in sums}
         n = sum(counts.values())
         return per_t, (sum(sums.values()) / n if n else float("nan"))

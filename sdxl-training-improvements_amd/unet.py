@@ -92,6 +92,17 @@ def loss_mask_bhw(m, latent_shape) -> torch.Tensor:
     return m
 
 
+def trainable_flags(all_names, names) -> list:
+    """[0 | 1] per entry of all_names for set_trainable's argument: an iterable of names (each must exist: KeyError) or a predicate"""
+    if callable(names):
+        return [1 if names(k) else 0 for k in all_names]
+    want = set(names)
+    unknown = sorted(want - set(all_names))
+    if unknown:
+        raise KeyError(f"set_trainable: unknown parameter names {unknown[:5]}{'...' if len(unknown) > 5 else ''}")
+    return [1 if k in want else 0 for k in all_names]
+
+
 class NativeUNet:
     """SDXL UNet + loss, forward and backward, on one MI355X.
 
@@ -120,6 +131,8 @@ class NativeUNet:
         self._plans: Dict[Tuple[int, int, int, int], int] = {}
         self._cur: Optional[Tuple[int, int, int, int]] = None
         self._keep = []          # tensors whose device pointers the library still references
+        self._trainable = None   # set_trainable's flag per state-dict tensor (None: no selection, every tensor trainable)
+        self._lora_sel = False   # ... and whether it handed adapters to the library
         self.param_table = self._read_param_table()
 
     # ------------------------------------------------------------------ parameters
@@ -178,6 +191,41 @@ class NativeUNet:
 
     def grad_dict(self, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         return {k: self.export(k, True, dtype) for k in self.param_table}
+
+    # ------------------------------------------------------------------ gradient selection
+    def set_trainable(self, names=None, lora=None) -> None:
+        """Tell the backward which tensors are trained: an iterable of state-dict keys, a predicate name -> bool, or None (every
+        tensor, the default).  An op whose tensors are ALL frozen skips its weight / bias / norm-parameter gradient work and writes
+        nothing into the gradient arena; an op with one trainable tensor runs as always, so the frozen tensors sharing it (to_q | to_k |
+        to_v of a block, attn2.to_k | to_v of every block of a width, all time_emb_proj, a weight and its bias) still get their
+        gradient.  Input gradients, the loss and the conditioning gradients do not change.  grad_norm() keeps summing the whole arena,
+        stale frozen ranges included: with a selection take the norm over grad_dict() / param_ranges() of trainable().
+        lora: a lib.LoraOp (lora.LoRAAdapters.select) whose targets' ops write the adapter gradients themselves in place of their
+        weight gradient; every tensor of such an op must be frozen.  Changing it drops the plans (the next step plans again).
+        Not allowed between forward_loss and its backward; after a forward that nothing differentiates, discard_forward() first."""
+        if names is None and lora is None:
+            lib.check(self.L.sdxl_export_grad(self.h, None, None, lib.DTYPE_GRAD_SELECT, _stream()), "set_trainable")
+            flags = None
+        else:
+            flags = trainable_flags(list(self.param_table), (lambda _k: True) if names is None else names)
+            sel = lib.GradSelect(len(flags), (C.c_ubyte * len(flags))(*flags), C.pointer(lora) if lora is not None else None)
+            lib.check(self.L.sdxl_export_grad(self.h, None, C.byref(sel), lib.DTYPE_GRAD_SELECT, _stream()), "set_trainable")
+            if all(flags):       # (the library's normal form of "every tensor": no selection)
+                flags = None
+        if lora is not None or self._lora_sel:      # the library dropped its plans
+            self._plans, self._cur = {}, None
+        self._lora_sel = lora is not None
+        self._trainable = flags
+
+    def trainable(self):
+        """the state-dict keys flagged trainable by the last set_trainable; every key when there is no selection"""
+        flags = self._trainable
+        return {k for i, k in enumerate(self.param_table) if flags is None or flags[i]}
+
+    def discard_forward(self) -> None:
+        """say that the last forward_loss gets no backward (an evaluation): the selection may change again (set_trainable)"""
+        if self._cur is not None:
+            lib.check(self.L.sdxl_plan(self.h, *self._cur, None), "sdxl_plan")
 
     # ------------------------------------------------------------------ plans
     def plan(self, B: int, H: int, W: int, ctx: int = 77) -> None:
