@@ -218,6 +218,23 @@ typedef struct {
   const void* base;          /* device bf16: the W0 copies, packed [out][in] in target order (load only) */
   float* adapter_grads;      /* device fp32, laid out like adapters (export only) */
 } sdxl_lora_op;
+/* ---- LoRA on the packed layouts: dtype SDXL_DTYPE_LORA_LAYOUTS of the same two calls, the same host struct ----
+ * SDXL_DTYPE_LORA keeps refusing what it refuses.  With this dtype a target may be ANY 2-D or 4-D weight: out = shape[0], in = the product
+ * of the other dimensions, A [rank][in] and B [out][rank] are indexed like the state-dict (PyTorch) tensor flattened to [out][in] -- so
+ * exported adapters are views -- and the kernels find source element (o, i) where the arena keeps it:
+ *   plain 2-D [out][in], 1x1 convolution [out][in][1][1]     o in + i
+ *   ff.net.0.proj [2 C4][in] (GEGLU, groups of G)             row (c / G) 2G + half G + c % G, column i;  half = o / C4, c = o % C4
+ *   3x3 convolution [cout][cin][3][3], i = c 9 + tap          (o 9 + tap) cin + c
+ * merge and project are SDXL_DTYPE_LORA's, element for element: the merge arithmetic depends on (o, i) alone; the projection's summation
+ * order is fixed by the target's shape and kind alone.  Still one launch to merge and two to project; a table without a packed target runs
+ * SDXL_DTYPE_LORA's kernels.  `base` is the packed copy of each target's sdxl_param_range elements, in target order (out * in of them for
+ * every accepted target).  conv_out: its 4 source rows are the first 4 of 8 native rows; the other 4 lie outside its sdxl_param_range and
+ * are neither read nor written.  Nothing outside the targets' ranges is written.
+ * Bad arguments (1, before any launch, the message names the tensor): everything SDXL_DTYPE_LORA refuses for other reasons (rank, a tensor
+ * listed twice, a non-NULL name, a NULL or misaligned pointer, an index out of range), a bias or a norm parameter, in % 8 != 0, a 3x3
+ * convolution whose input channels are padded in the arena -- together the last two refuse exactly conv_in.  sdxl_grad_select.lora keeps
+ * SDXL_DTYPE_LORA's rule.  The cached device table is keyed by the dtype too. */
+#define SDXL_DTYPE_LORA_LAYOUTS 4
 /* ---- gradient selection: dtype SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad (no entry point of its own) ----
  *   sdxl_export_grad(h, NULL, &sel, SDXL_DTYPE_GRAD_SELECT, stream)
  * tells the backward which state-dict tensors are trained.  `sel` is a HOST pointer, read during the call; `name` must be NULL; a NULL

@@ -64,6 +64,15 @@ SDXL_API int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_g
 SDXL_API int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* stream);
 SDXL_API int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale,
                          void* stream);
+/* ... and of SDXL_DTYPE_LORA_LAYOUTS: one target held in a packed layout (include/sdxlstep.h has the maps).  kind 0: plain rows; 1: a 3x3
+ * convolution, cg = cin and in == 9 cin; 2: GEGLU rows, cg = the group G, (out / 2) % G == 0.  W0, w (bf16) and dw (fp32) are NATIVE:
+ * [native_rows][in], native_rows >= out and == out unless kind is 1; A [rank][in], B [out][rank], dA, dB are indexed like the state-dict
+ * tensor.  merge writes every native row (W0's bits into the rows past `out`); project never reads those rows of dw.  These hooks always
+ * take the kind-aware kernels, kind 0 included. */
+SDXL_API int sdxl_op_lora_merge_layout(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, int kind,
+                              int cg, int native_rows, void* stream);
+SDXL_API int sdxl_op_lora_project_layout(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank,
+                                float scale, int kind, int cg, int native_rows, void* stream);
 /* the direct adapter-gradient kernels of sdxl_grad_select.lora (csrc/lora_grad.hip) on caller buffers, a table of one target, no handle:
  * x [M][in] (row stride ldx), dy [M][out] (row stride ldy: a column slice of a wider tensor is dy + offset), A [rank][in], B [out][rank] bf16;
  * dA [rank][in], dB [out][rank] fp32 = (accumulate ? previous : 0) + scale * (dY B)^T X, scale * dY^T (X A^T).  Rows past M and columns outside

@@ -2,9 +2,13 @@
 the default targets (csrc/lora.hip) and the fused update of the adapter arena at ranks 16 and 64, against the full-arena AdamWBF16 update
 of the same run.  HIP events, 20 repetitions after 3 warm-up calls, median and minimum.
 
-    python profiles/tools/lora_bench.py [--reps 20] [--out profiles/lora_timing.txt]
+    python profiles/tools/lora_bench.py [--reps 20] [--out profiles/lora_timing.txt] [--kinds all]
 
-The bar (rank 16): merge + project + adapter update <= the full-arena AdamW update measured here."""
+The bar (rank 16): merge + project + adapter update <= the full-arena AdamW update measured here.
+--kinds all (profiles/lora_layout_timing.txt): after the plain run, in the same process, the tables of SDXL_DTYPE_LORA_LAYOUTS -- every
+accepted tensor, the 3x3 convolutions only, ff.net.0.proj only, and the default (plain) targets through the new dtype -- with the arena
+bytes each launch moves per millisecond and the mapped kinds' rate as a fraction of the plain table's at the same rank.  The bar is
+reported for the all-kinds table too, not asserted: that table is 2.7x the default one."""
 import argparse
 import importlib
 import statistics
@@ -20,6 +24,10 @@ from sdxl_amd import unet as NU  # noqa: E402
 
 LORA = importlib.import_module("sdxl-training-improvements_amd.lora")
 O = importlib.import_module("sdxl-training-improvements_amd.optimizer")
+
+
+EVERY_MODULE = ["to_q", "to_k", "to_v", "to_out.0", "ff.net.0.proj", "ff.net.2", "proj_in", "proj_out", "conv1", "conv2", "conv_shortcut",
+                "downsamplers.0.conv", "upsamplers.0.conv", "conv_out", "time_emb_proj", "linear_1", "linear_2"]
 
 
 def timed(fn, reps, warmup=3):
@@ -41,6 +49,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kinds", choices=["plain", "all"], default="plain")
     args = ap.parse_args()
     lines = []
 
@@ -77,6 +86,41 @@ def main():
         ad.restore()
         del opt, ad
         torch.cuda.empty_cache()
+    if args.kinds == "all":
+        shapes = net.param_shapes()
+        every = LORA.resolve_targets(shapes, EVERY_MODULE, kinds="all")
+        conv3 = [k[: -len(".weight")] for k in every if len(shapes[k]) == 4 and tuple(shapes[k][2:]) == (3, 3)]
+        geglu = [k[: -len(".weight")] for k in every if k.endswith("ff.net.0.proj.weight")]
+        tables = [("plain (default targets)", None), ("all kinds", EVERY_MODULE), ("3x3 convolutions only", conv3), ("ff.net.0.proj only", geglu)]
+        say(f"--kinds all: SDXL_DTYPE_LORA_LAYOUTS; bytes moved = W0 read + W written (merge), dW read twice (project); rate = bytes / median")
+        for rank in (16, 64):
+            rates = {}
+            for label, targets in tables:
+                ad = LORA.LoRAAdapters(net, rank=rank, targets=targets, kinds="all")
+                for k in ad.targets:
+                    ad.B(k).normal_(0.0, 0.02, generator=g)
+                m = timed(ad.merge, args.reps)
+                p = timed(ad.project, args.reps)
+                n = ad.base.numel()
+                rates[label] = (2 * 2 * n / 1e6 / m[0], 2 * 4 * n / 1e6 / p[0])
+                line = (f"rank {rank} [{label}]: {len(ad.targets)} targets, {n} target weights ; merge {m[0]:.3f} / {m[1]:.3f} ms ({rates[label][0]:.0f} MB/ms) ; "
+                        f"project {p[0]:.3f} / {p[1]:.3f} ms ({rates[label][1]:.0f} MB/ms)")
+                if label == "all kinds":
+                    opt = O.AdamWBF16(ad, lr=1e-6, weight_decay=0.0)
+                    u = timed(lambda: opt.step(), args.reps)
+                    total = m[0] + p[0] + u[0]
+                    line += (f" ; adapter update {u[0]:.3f} ms ; merge + project + adapter update = {total:.3f} ms vs full-arena update {med_full:.3f} ms "
+                             f"({total / med_full:.2f}x, reported only)")
+                    del opt
+                say(line)
+                ad.restore()
+                del ad
+                torch.cuda.empty_cache()
+            base = rates["plain (default targets)"]
+            for label in ("3x3 convolutions only", "ff.net.0.proj only", "all kinds"):
+                rm, rp = rates[label][0] / base[0], rates[label][1] / base[1]
+                flag = "" if min(rm, rp) >= 2 / 3 else "  <- below two thirds of the plain rate"
+                say(f"rank {rank} [{label}] / plain: merge {rm:.2f}x, project {rp:.2f}x of the plain table's bytes per ms{flag}")
     net.close()
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)

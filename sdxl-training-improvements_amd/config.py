@@ -111,6 +111,9 @@ class TrainingConfig:                    # data/config.py:152-168
     # default); "project_frozen" = only the ops that hold a target form their weight gradient, projected as before; "direct" = no weight
     # gradient at all, dA and dB come out of the backward itself (csrc/lora_grad.hip)
     lora_backward: str = "project"
+    # which tensors may carry an adapter (lora.LORA_TARGET_KINDS): "plain" = 2-D linears stored as plain rows (the default); "all" = also
+    # ff.net.0.proj and the convolutions (3x3 and 1x1; LoCon), through SDXL_DTYPE_LORA_LAYOUTS.  Not conv_in; not with lora_backward "direct"
+    lora_target_kinds: str = "plain"
 
 
 @dataclass

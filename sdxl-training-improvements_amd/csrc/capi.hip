@@ -17,9 +17,9 @@ struct StepState {  // what backward needs from the preceding forward
   float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
   bool awaiting_bwd = false;   // a sdxl_forward_loss whose backward has not finished: the gradient selection may not change under it
 };
-struct LoraCache {  // device table of the last SDXL_DTYPE_LORA call, keyed by (target list, rank)
+struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS call, keyed by (target list, rank, dtype)
   std::vector<int> params;
-  int rank = 0;
+  int rank = 0, dtype = 0, mapped = 0;
   LoraTarget* dev = nullptr;
   int tiles_m = 0, tiles_b = 0, tiles_a = 0;
 };
@@ -182,55 +182,75 @@ static int lora_check_op(const sdxl_lora_op* op, bool need_base, bool need_grads
   return 0;
 }
 // the targets of `params` in order: every target checked, its place in the weight arena and in the adapter / W0 arenas, its first tiles
-static int lora_table(Engine& e, const std::vector<int>& params, int rank, std::vector<LoraTarget>& tab, long* tm_, long* tb_, long* ta_) {
+// layouts (SDXL_DTYPE_LORA_LAYOUTS): also the tensors held in a packed layout, by their kind; *mapped_ = some target needs the kind-aware kernels
+static int lora_table(Engine& e, const std::vector<int>& params, int rank, std::vector<LoraTarget>& tab, long* tm_, long* tb_, long* ta_,
+                      bool layouts = false, int* mapped_ = nullptr) {
   tab.assign(params.size(), LoraTarget());
+  int mapped = 0;
   std::vector<char> seen(e.src.size(), 0);
   long a = 0, b = 0, tm = 0, tb = 0, ta = 0;
   for (size_t i = 0; i < params.size(); ++i) {
     const int pi = params[i];
     ARG_CHECK(pi >= 0 && pi < (int)e.src.size(), "lora: parameter index %d out of range", pi);
     const SrcParam& sp = e.src[pi];
-    ARG_CHECK(sp.ndim == 2 && sp.kind == 0, "lora: '%s' is not a 2-D weight in plain row layout (convolutions and the interleaved "
-              "ff.net.0.proj cannot be targets)", sp.name.c_str());
+    if (!layouts)
+      ARG_CHECK(sp.ndim == 2 && sp.kind == 0, "lora: '%s' is not a 2-D weight in plain row layout (convolutions and the interleaved "
+                "ff.net.0.proj cannot be targets)", sp.name.c_str());
+    else
+      ARG_CHECK(sp.ndim == 2 || sp.ndim == 4, "lora: '%s' is not a weight (a bias or a norm parameter cannot be a target)", sp.name.c_str());
     ARG_CHECK(!seen[pi], "lora: '%s' is listed twice", sp.name.c_str());
     seen[pi] = 1;
-    const int out = (int)sp.shape[0], in = (int)sp.shape[1];
+    const int out = (int)sp.shape[0], in = (int)(sp.shape[1] * sp.shape[2] * sp.shape[3]);      // (shape is 1 past ndim)
     CHK(lora_check_shape(sp.name.c_str(), out, in, rank));
     LoraTarget& t = tab[i];
+    t.kind = LORA_KIND_PLAIN; t.cg = 0; t.nrows = out;
+    if (layouts && sp.kind == 1) {
+      ARG_CHECK(sp.shape[2] == 3 && sp.shape[3] == 3 && sp.ci_pad == (int)sp.shape[1], "lora: '%s' is stored with its input channels padded "
+                "from %ld to %d: it cannot be a target", sp.name.c_str(), sp.shape[1], sp.ci_pad);
+      t.kind = LORA_KIND_CONV3; t.cg = sp.ci_pad; mapped = 1;
+    } else if (layouts && sp.kind == 2) {
+      ARG_CHECK(sp.ndim == 2 && out % 2 == 0 && sp.ci_pad >= 1 && (out / 2) % sp.ci_pad == 0, "lora: '%s' [%d][%d] is not interleaved in whole "
+                "groups of %d", sp.name.c_str(), out, in, sp.ci_pad);
+      t.kind = LORA_KIND_GEGLU; t.cg = sp.ci_pad; mapped = 1;
+    } else if (layouts) {
+      ARG_CHECK(sp.kind == 0, "lora: '%s' is stored in a layout (%d) the adapter kernels do not know", sp.name.c_str(), sp.kind);
+    }
     t.w_off = (long)(sp.native.off + sp.elem_off);
     ARG_CHECK(t.w_off % 8 == 0, "lora: '%s' does not start on a 16-byte boundary of the arena", sp.name.c_str());
     t.base_off = b; b += (long)out * in;
     t.a_off = t.ga_off = a; a += ((long)rank * in + 7) / 8 * 8;
     t.b_off = t.gb_off = a; a += ((long)out * rank + 7) / 8 * 8;
-    t.out = out; t.in = in; t.pad = 0;
+    t.out = out; t.in = in;
     t.tile_m = (int)tm; t.tile_b = (int)tb; t.tile_a = (int)ta;
     tm += lora_tiles_m(out, in); tb += lora_tiles_b(out, in); ta += lora_tiles_a(out, in);
     ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "lora: too many tiles");
   }
   *tm_ = tm; *tb_ = tb; *ta_ = ta;
+  if (mapped_) *mapped_ = mapped;
   return 0;
 }
 
-static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q) {
+static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q, int dtype = SDXL_DTYPE_LORA) {
   ARG_CHECK(name == nullptr, "lora: `name` must be NULL with SDXL_DTYPE_LORA (the targets are listed in sdxl_lora_op.param)");
   CHK(lora_check_op(op, merge, !merge));
   Engine& e = h->e;
   ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lora: %s are not bound", merge ? "weights" : "grads");
   LoraCache& c = h->lora;
   std::vector<int> params(op->param, op->param + op->n);
-  if (!(c.dev && c.rank == op->rank && c.params == params)) {
+  if (!(c.dev && c.rank == op->rank && c.dtype == dtype && c.params == params)) {
     std::vector<LoraTarget> tab;
     long tm = 0, tb = 0, ta = 0;
-    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta));
+    int mapped = 0;
+    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, dtype == SDXL_DTYPE_LORA_LAYOUTS, &mapped));
     if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
     HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
-    c.params = params; c.rank = op->rank;
+    c.params = params; c.rank = op->rank; c.dtype = dtype; c.mapped = mapped;
     c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
   }
   memset(&q, 0, sizeof(q));
   q.table = c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
-  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a;
+  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
   q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = (const bf16*)op->adapters;
   q.dw = e.grads; q.ga = q.gb = op->adapter_grads;
   return 0;
@@ -238,9 +258,9 @@ static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
 
 int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtype, void* st) {
   H_CHECK(h);
-  if (dtype == SDXL_DTYPE_LORA) {
+  if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
-    CHK(lora_prepare(h, name, (const sdxl_lora_op*)src, true, q));
+    CHK(lora_prepare(h, name, (const sdxl_lora_op*)src, true, q, dtype));
     return launch_lora_merge(q, (hipStream_t)st);
   }
   ARG_CHECK(name && src, "null argument");
@@ -345,9 +365,9 @@ static int grad_select(sdxl_handle* h, const char* name, const sdxl_grad_select*
 int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, void* st) {
   if (dtype == SDXL_DTYPE_GRAD_SELECT) return grad_select(h, name, (const sdxl_grad_select*)dst);
   H_CHECK(h);
-  if (dtype == SDXL_DTYPE_LORA) {
+  if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
-    CHK(lora_prepare(h, name, (const sdxl_lora_op*)dst, false, q));
+    CHK(lora_prepare(h, name, (const sdxl_lora_op*)dst, false, q, dtype));
     return launch_lora_project(q, (hipStream_t)st);
   }
   ARG_CHECK(name && dst, "null argument");
@@ -359,9 +379,37 @@ static int lora_one(int out, int in, int rank, float scale, LoraP& q) {
   ARG_CHECK(isfinite(scale), "lora: scale is not finite");
   memset(&q, 0, sizeof(q));
   q.n = 1; q.rank = rank; q.scale = scale;
-  q.one.out = out; q.one.in = in;
+  q.one.out = out; q.one.in = in; q.one.kind = LORA_KIND_PLAIN; q.one.nrows = out;
   q.tiles_m = lora_tiles_m(out, in); q.tiles_b = lora_tiles_b(out, in); q.tiles_a = lora_tiles_a(out, in);
   return 0;
+}
+// ... and of one target held in a packed layout: always the kind-aware kernels, also for LORA_KIND_PLAIN
+static int lora_one_layout(int out, int in, int rank, float scale, int kind, int cg, int nrows, LoraP& q) {
+  CHK(lora_one(out, in, rank, scale, q));
+  ARG_CHECK(kind == LORA_KIND_PLAIN || kind == LORA_KIND_CONV3 || kind == LORA_KIND_GEGLU, "lora: kind %d (0 plain rows, 1 3x3 convolution, 2 GEGLU)", kind);
+  ARG_CHECK(nrows >= out && (nrows == out || kind == LORA_KIND_CONV3), "lora: %d native rows for out = %d (only a convolution has padded rows)", nrows, out);
+  if (kind == LORA_KIND_CONV3) ARG_CHECK(cg >= 1 && in == 9 * (long)cg, "lora: a 3x3 convolution with cin = %d has in = 9 cin, not %d", cg, in);
+  if (kind == LORA_KIND_GEGLU) ARG_CHECK(cg >= 1 && out % 2 == 0 && (out / 2) % cg == 0, "lora: GEGLU rows [%d] are not whole groups of %d", out, cg);
+  q.one.kind = kind; q.one.cg = kind == LORA_KIND_PLAIN ? 0 : cg; q.one.nrows = nrows; q.mapped = 1;
+  q.tiles_m = lora_tiles_m(nrows, in);
+  return 0;
+}
+int sdxl_op_lora_merge_layout(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, int kind, int cg,
+                              int native_rows, void* st) {
+  ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(lora_one_layout(out, in, rank, scale, kind, cg, native_rows, q));
+  q.w = (bf16*)w; q.base = (const bf16*)base; q.a = (const bf16*)A; q.b = (const bf16*)B;
+  return launch_lora_merge(q, (hipStream_t)st);
+}
+int sdxl_op_lora_project_layout(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, int kind,
+                                int cg, int native_rows, void* st) {
+  ARG_CHECK(aligned16(dw) && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB),
+            "lora_project: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(lora_one_layout(out, in, rank, scale, kind, cg, native_rows, q));
+  q.dw = dw; q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
+  return launch_lora_project(q, (hipStream_t)st);
 }
 int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* st) {
   ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");

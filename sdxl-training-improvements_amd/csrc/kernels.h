@@ -517,16 +517,34 @@ struct LoraTarget {       // one targeted weight [out][in]; element offsets from
   long base_off;          // packed W0
   long a_off, b_off;      // adapter arena: A [rank][in], B [out][rank]
   long ga_off, gb_off;    // adapter-gradient arena: dA, dB
-  int out, in;            // in % 8 == 0
+  int out, in;            // of the state-dict tensor flattened to [shape[0]][prod(shape[1:])]; in % 8 == 0
   int tile_m, tile_b, tile_a;   // first workgroup of this target in the merge / dB / dA launch
-  int pad;
+  // where source element (o, i) lives (SDXL_DTYPE_LORA_LAYOUTS; the arena's packed layouts, repack_kernel in engine.hip).  Native rows are
+  // `in` elements long for every kind, so the tiles walk native rows and columns and only the indices into A, B, dA, dB are mapped:
+  int kind;               // LORA_KIND_PLAIN: native (o, i).  LORA_KIND_CONV3: i = c * 9 + tap at native (o, tap * cg + c).
+                          // LORA_KIND_GEGLU: o = half * C4 + c at native row (c / cg) * 2 cg + half * cg + c % cg, C4 = out / 2
+  int cg;                 // CONV3: cin (in == 9 cin);  GEGLU: the group G (C4 % G == 0);  PLAIN: unused
+  int nrows;              // native rows, >= out: rows out .. nrows - 1 (CONV3 only) hold no source element; merge copies W0 there
 };
+#define LORA_KIND_PLAIN 0
+#define LORA_KIND_CONV3 1
+#define LORA_KIND_GEGLU 2
+__host__ __device__ static inline int lora_src_col(int kind, int cg, int j) {      // native column -> column of A / dA
+  return kind == LORA_KIND_CONV3 ? (j % cg) * 9 + j / cg : j;
+}
+__host__ __device__ static inline int lora_src_row(int kind, int cg, int c4, int r) {      // native row < out -> row of B / dB
+  if (kind != LORA_KIND_GEGLU) return r;
+  const int grp = r / (2 * cg), rem = r - grp * 2 * cg, half = rem / cg;
+  return half * c4 + grp * cg + rem - half * cg;
+}
 struct LoraP {
   const LoraTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
   LoraTarget one;
   int n, rank;                  // rank 1 .. 128
   float scale;
   int tiles_m, tiles_b, tiles_a;
+  int mapped;                   // 0: every target is LORA_KIND_PLAIN with nrows == out, and the launch takes the kernels that never look at
+                                // kind / cg / nrows; 1: the kind-aware instantiations (which also run the plain targets of a mixed table)
   bf16* w;                      // merge: out
   const bf16* base;             // merge
   const bf16 *a, *b;            // what a_off / b_off count from: the adapter arena twice, or the hook's A and B (offsets 0)

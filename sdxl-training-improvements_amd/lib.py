@@ -95,6 +95,7 @@ class CondGradBatch(SamplerBatch):
 
 
 DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
+DTYPE_LORA_LAYOUTS = 4  # SDXL_DTYPE_LORA_LAYOUTS: the same two calls and struct, targets in the arena's packed layouts accepted (lora.py, kinds="all")
 
 
 class LoraOp(C.Structure):
@@ -202,6 +203,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
     "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "sdxl_op_lora_merge_layout": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],
+    "sdxl_op_lora_project_layout": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],
     "sdxl_op_lora_grad": [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
 }

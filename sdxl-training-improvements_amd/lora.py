@@ -8,6 +8,9 @@ src/models/adapters/lora.py: base(x) + alpha * up(down(x)), up = B, down = A):
   project  dA = s B^T dW, dB = s dW A^T: exactly the LoRA gradients at the merged weight.
 
 Both steps are one call into libsdxlstep (csrc/lora.hip through dtype SDXL_DTYPE_LORA of sdxl_load_weight / sdxl_export_grad).
+training.lora_target_kinds (LORA_TARGET_KINDS) says which tensors may be targets: "plain" = 2-D linears stored as plain rows; "all" = every
+2-D or 4-D weight but conv_in -- also ff.net.0.proj and the convolutions, which the arena keeps in packed layouts -- through dtype
+SDXL_DTYPE_LORA_LAYOUTS.  There out = shape[0], in = prod(shape[1:]) and A, B are indexed like the state-dict tensor flattened to [out, in].
 LoRAAdapters owns the small arenas and looks to a fused optimizer like a net (weights, grads, L, zero_grads, param_ranges), so
 AdamWBF16 / AdamWScheduleFreeKahanBF16 update it unchanged.  NativeLoRATrainer is the trainer `training.lora_rank > 0` selects.
 training.lora_backward chooses how much of the full model's backward runs for that (LORA_BACKWARDS):
@@ -37,12 +40,24 @@ logger = logging.getLogger(__name__)
 DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
 MAX_RANK = 128
 LORA_BACKWARDS = ("project", "project_frozen", "direct")
+LORA_TARGET_KINDS = ("plain", "all")
 
 
 def check_lora_backward(mode) -> str:
     if mode not in LORA_BACKWARDS:
         raise ValueError(f"training.lora_backward {mode!r}: expected one of {list(LORA_BACKWARDS)}")
     return mode
+
+
+def check_target_kinds(kinds) -> str:
+    if kinds not in LORA_TARGET_KINDS:
+        raise ValueError(f"training.lora_target_kinds {kinds!r}: expected one of {list(LORA_TARGET_KINDS)}")
+    return kinds
+
+
+def is_plain_target(key: str, shape: Sequence[int]) -> bool:
+    """a tensor SDXL_DTYPE_LORA and the direct adapter gradients take: 2-D, stored as plain rows"""
+    return len(shape) == 2 and not key[: -len(".weight")].endswith("ff.net.0.proj")
 
 
 def op_of(key: str, shape: Tuple[int, ...]) -> str:
@@ -76,10 +91,12 @@ def _pad8(n: int) -> int:
     return (n + 7) // 8 * 8
 
 
-def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str]) -> List[str]:
+def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str], kinds: str = "plain") -> List[str]:
     """The `.weight` keys of `shapes` (state-dict order) whose module path is a pattern or ends in "." + pattern.  ValueError for a
-    pattern that matches nothing and for one that matches a tensor the kernels cannot take: a convolution, the row-interleaved
-    `ff.net.0.proj`, or an `in` that is no multiple of 8."""
+    pattern that matches nothing and for one that matches a tensor the kernels cannot take: with kinds "plain" a convolution, the
+    row-interleaved `ff.net.0.proj`, or an `in` that is no multiple of 8; with kinds "all" a tensor that is neither 2-D nor 4-D, or an
+    `in` = prod(shape[1:]) that is no multiple of 8 (conv_in)."""
+    check_target_kinds(kinds)
     patterns = [str(p) for p in patterns]
     if not patterns:
         raise ValueError("lora_targets: no pattern given")
@@ -93,6 +110,14 @@ def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str])
             continue
         for p in ps:
             hit[p] += 1
+        if kinds == "all":
+            if len(shape) not in (2, 4):
+                raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key} {tuple(shape)}: only 2-D and 4-D weights can carry an adapter")
+            if _prod(shape[1:]) % 8:
+                raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key} {tuple(shape)}: `in` = {_prod(shape[1:])} must be a multiple "
+                                 "of 8")
+            out.append(key)
+            continue
         if len(shape) != 2:
             raise ValueError(f"lora_targets: pattern {ps[0]!r} matches {key} {tuple(shape)}: only 2-D linear weights can carry an adapter")
         if mod.endswith("ff.net.0.proj"):
@@ -107,11 +132,19 @@ def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str])
     return out
 
 
+def _prod(dims) -> int:
+    n = 1
+    for v in dims:
+        n *= int(v)
+    return n
+
+
 def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int):
-    """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements"""
+    """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements;
+    out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions"""
     lay, cur = {}, 0
     for k in targets:
-        o, i = (int(v) for v in shapes[k])
+        o, i = int(shapes[k][0]), _prod(shapes[k][1:])
         a, cur = cur, cur + _pad8(rank * i)
         b, cur = cur, cur + _pad8(o * rank)
         lay[k] = (a, b, o, i)
@@ -121,7 +154,10 @@ def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], r
 class LoRAAdapters:
     """The adapters of one net: bf16 arena `.weights`, fp32 `.grads` laid out like it, and the packed bf16 copy of the targets' W0."""
 
-    def __init__(self, net, rank: int, alpha: Optional[float] = None, targets: Optional[Sequence[str]] = None, seed: int = 0):
+    def __init__(self, net, rank: int, alpha: Optional[float] = None, targets: Optional[Sequence[str]] = None, seed: int = 0,
+                 kinds: str = "plain"):
+        self.kinds = check_target_kinds(kinds)
+        self.dtype = lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA
         if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
             raise ValueError(f"lora_rank must be an integer in 1 .. {MAX_RANK} (got {rank!r})")
         self.net = net
@@ -132,7 +168,8 @@ class LoRAAdapters:
         self.seed = int(seed)
         shapes = net.param_shapes()
         self.patterns = tuple(DEFAULT_TARGETS if targets is None else targets)
-        self.targets = resolve_targets(shapes, self.patterns)
+        self.targets = resolve_targets(shapes, self.patterns, kinds)
+        self.shapes = {k: tuple(int(v) for v in shapes[k]) for k in self.targets}
         names = list(shapes)
         self.index = [names.index(k) for k in self.targets]
         self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank)
@@ -141,7 +178,7 @@ class LoRAAdapters:
         self.grads = torch.zeros(self.param_elems, dtype=torch.float32, device=dev)
         ranges = net.param_ranges()
         self.base = torch.cat([net.weights[ranges[k][0]: ranges[k][0] + ranges[k][1]] for k in self.targets])
-        assert self.base.numel() == sum(o * i for _a, _b, o, i in self.layout.values())
+        assert self.base.numel() == sum(ranges[k][1] for k in self.targets)      # (the targets' native ranges: out * in elements each)
         g = torch.Generator().manual_seed(self.seed)          # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
         for k in self.targets:
             a, _b, _o, i = self.layout[k]
@@ -180,7 +217,7 @@ class LoRAAdapters:
             raise lib.SdxlError(f"LoRAAdapters.{fn_name}: needs libsdxlstep.so (there is no PyTorch fallback)")
         op = self._op(scale)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        lib.check(getattr(self.L, fn_name)(self.net.h, None, C.byref(op), lib.DTYPE_LORA, st), f"{fn_name} (lora)")
+        lib.check(getattr(self.L, fn_name)(self.net.h, None, C.byref(op), self.dtype, st), f"{fn_name} (lora)")
 
     def merge(self, scale: Optional[float] = None) -> None:
         """W = bf16(W0 + s B A) for every target, into the net's weight arena (one launch)"""
@@ -198,19 +235,33 @@ class LoRAAdapters:
         """apply a training.lora_backward mode to the net: its gradient selection and, for "direct", these adapters as the ones whose
         gradients the backward writes into `.grads` (first micro-step: overwritten, later ones: added to).  The arenas' addresses and the
         scale are read now: call again after either changes."""
+        if mode == "direct":
+            self.check_direct()
         names = trainable_for(mode, self.targets, self.net.param_shapes())
         self.net.set_trainable(names, lora=self._op(self.scale) if mode == "direct" else None)
 
+    def check_direct(self) -> None:
+        """ValueError when a target is not one the direct adapter gradients (csrc/lora_grad.hip) take"""
+        bad = [k for k in self.targets if not is_plain_target(k, self.shapes[k])]
+        if bad:
+            raise ValueError(f"training.lora_backward 'direct': {bad[0]} {self.shapes[bad[0]]} is not a 2-D linear in plain row layout; the "
+                             "direct adapter gradients take no convolution and no ff.net.0.proj (use 'project' or 'project_frozen')")
+
     # ---- state
     def _meta(self) -> Dict[str, Any]:
-        return {"rank": self.rank, "alpha": self.alpha, "seed": self.seed, "targets": list(self.targets),
+        meta = {"rank": self.rank, "alpha": self.alpha, "seed": self.seed, "targets": list(self.targets),
                 "shapes": [[self.layout[k][2], self.layout[k][3]] for k in self.targets]}
+        if self.kinds != "plain":      # (a plain state is what it has always been, byte for byte)
+            meta["kinds"] = self.kinds
+        return meta
 
     def state_dict(self) -> Dict[str, Any]:
         return {**self._meta(), "weights": self.weights.detach().cpu().clone()}
 
     def check_state_dict(self, sd: Dict[str, Any]) -> None:
         mine = self._meta()
+        if sd.get("kinds", "plain") != self.kinds:
+            raise ValueError(f"lora state: kinds differs from this trainer's ({sd.get('kinds', 'plain')!r} vs {self.kinds!r})")
         for key in ("rank", "targets", "shapes"):
             if sd.get(key) != mine[key]:
                 raise ValueError(f"lora state: {key} differs from this trainer's ({_brief(sd.get(key))} vs {_brief(mine[key])})")
@@ -227,12 +278,18 @@ class LoRAAdapters:
 
     def export_tensors(self) -> Dict[str, torch.Tensor]:
         """{"unet.<module>.lora_A.weight", "unet.<module>.lora_B.weight"} in fp32 on the CPU, s folded into lora_B: a loader that
-        assumes alpha = rank (scale 1) reproduces the delta s B A"""
+        assumes alpha = rank (scale 1) reproduces the delta s B A.  PEFT's shapes: [r, in] / [out, r] for a linear, [r, cin, kh, kw] /
+        [out, r, 1, 1] for a convolution (the down convolution has the layer's kernel, the up convolution is 1 x 1)."""
         out = {}
         for k in self.targets:
             mod = k[: -len(".weight")]
-            out[f"unet.{mod}.lora_A.weight"] = self.A(k).float().cpu().contiguous()
-            out[f"unet.{mod}.lora_B.weight"] = (self.B(k).float().cpu() * torch.tensor(self.scale, dtype=torch.float32)).contiguous()
+            shape = self.shapes[k]
+            la = self.A(k).float().cpu().contiguous()
+            lb = (self.B(k).float().cpu() * torch.tensor(self.scale, dtype=torch.float32)).contiguous()
+            if len(shape) == 4:
+                la, lb = la.view(self.rank, *shape[1:]), lb.view(shape[0], self.rank, 1, 1)
+            out[f"unet.{mod}.lora_A.weight"] = la
+            out[f"unet.{mod}.lora_B.weight"] = lb
         return out
 
 
@@ -283,6 +340,7 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         if optimizer is not None:
             logger.warning("NativeLoRATrainer builds its own fused optimizer on the adapter arena: the optimizer passed in is ignored")
         self.lora_backward = check_lora_backward(getattr(tc, "lora_backward", "project"))
+        check_target_kinds(getattr(tc, "lora_target_kinds", "plain"))
         super().__init__(model, None, train_dataloader, device, wandb_logger, config, **kwargs)
         self._projected = False
         if self.lora_backward != "project":
@@ -308,7 +366,10 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         targets = getattr(tc, "lora_targets", None)
         if isinstance(targets, str):
             targets = [targets]
-        self.lora = LoRAAdapters(self.net, int(tc.lora_rank), alpha, targets, int(getattr(tc, "lora_seed", 0)))
+        self.lora = LoRAAdapters(self.net, int(tc.lora_rank), alpha, targets, int(getattr(tc, "lora_seed", 0)),
+                                 kinds=getattr(tc, "lora_target_kinds", "plain"))
+        if self.lora_backward == "direct":      # (before any arena of the optimizer is built)
+            self.lora.check_direct()
         opt = build_optimizer(self.lora, self.config.optimizer)
         assert isinstance(opt, FusedArenaOptimizer)
         return opt
