@@ -1,5 +1,6 @@
 /* libsdxlstep -- test hooks and experiment ABI.  NOT part of the drop-in boundary (include/sdxlstep.h is): nothing a caller of the
- * training step needs is declared here.
+ * training step needs is declared here.  Implemented in csrc/hooks.hip (with the sdxl_op_* entry points of sdxlstep.h): each builds its launch
+ * with the builders the plan uses (csrc/kernels.h) and takes scratch from one grow-only buffer of the process (one stream at a time).
  *
  * Part 1, exported by the product library too: hooks the parity tests and the measurement tools use to force one kernel
  * configuration or to look inside a plan.
@@ -98,7 +99,8 @@ SDXL_API int sdxl_debug_gemm_route(const sdxl_gemm_desc* problem, sdxl_gemm_rout
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the
  * LayerNorm's input gradient (+ addend, or null); dy_out (or null) [M][N] = dY W; pcol (or null) [cdiv(M, 128)][2][N] fp32 partial sums of
- * dgamma | dbeta per 128-row block.  N <= 1280, cdiv(M, 128) * cdiv(N, 128) <= 512.  Runs the launch three times (epochs 1, 2, 3) on one scratch buffer. */
+ * dgamma | dbeta per 128-row block.  N <= 1280, cdiv(M, 128) * cdiv(N, 128) <= 512.  Runs the launch three times (epochs 1, 2, 3) on one scratch
+ * buffer, zeroed on `stream` first; stream-ordered (it does not synchronise). */
 SDXL_API int sdxl_op_linear_dgrad_ln_bwd(const void* dy, const void* w, const void* x, const float* stats, const void* gamma, const void* addend,
                                 void* dx, void* dy_out, float* pcol, int M, int N, int K, void* stream);
 

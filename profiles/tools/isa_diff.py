@@ -52,6 +52,8 @@ def symbols(so):
                         text = f"s_add_u32 s{m[1]}, s{m[1]}, {where(pc.pop(m[1]) + (lit - (1 << 32) if lit >> 31 else lit))}"
                     if text != "...":      # (objdump's mark for the zero padding up to the next symbol)
                         out.append(text)
+                while out and out[-1] in ("s_nop 0", ""):      # (the filler behind the function's last instruction: its length depends on what follows
+                    out.pop()                            # the function in its code object -- the last one of a translation unit gets a long run)
                 funcs[name] = "\n".join(out).strip()
             notes = subprocess.run([LLVM / "llvm-readelf", "--notes", f], capture_output=True, text=True, check=True).stdout
             for blk in re.split(r"^\s*- (?=\.agpr_count:|\.args:)", notes, flags=re.M)[1:]:

@@ -1,40 +1,6 @@
 // extern "C" surface of libsdxlstep (see include/sdxlstep.h for the contract of every entry point).
-#include <math.h>
-#include "engine.h"
-#include "../../include/sdxlstep_diag.h"
+#include "capi.h"
 #include <functional>
-
-#include <stddef.h>
-#include <stdlib.h>
-
-const char* sdxl_get_error();
-
-struct StepState {  // what backward needs from the preceding forward
-  sdxl_loss_config lc;      // in full (read_loss_config), the flag cleared
-  sdxl_batch b;
-  bool valid = false;
-  float* d_ehs = nullptr;   // the conditioning gradients this micro-step asked for (sdxl_batch_ext): the caller's
-  float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
-  bool awaiting_bwd = false;   // a sdxl_forward_loss whose backward has not finished: the gradient selection may not change under it
-};
-struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS call, keyed by (target list, rank, dtype)
-  std::vector<int> params;
-  int rank = 0, dtype = 0, mapped = 0;
-  LoraTarget* dev = nullptr;
-  int tiles_m = 0, tiles_b = 0, tiles_a = 0;
-};
-struct sdxl_handle {
-  Engine e;
-  StepState step;
-  LoraCache lora;
-};
-
-#define H_CHECK(h) ARG_CHECK((h) != nullptr, "null handle")
-#define CHK(x)         \
-  do {                 \
-    int _r = (x);      \
-    if (_r) return _r; \
-  } while (0)
 
 extern "C" {
 
@@ -164,13 +130,6 @@ int sdxl_param_range(sdxl_handle* h, int i, size_t* elem_off, size_t* elems) {
 }
 
 // ---- LoRA by merge and project (SDXL_DTYPE_LORA): checks, the cached device table, the launches of csrc/lora.hip ----
-static int lora_check_shape(const char* who, int out, int in, int rank) {
-  ARG_CHECK(rank >= 1 && rank <= 128, "lora: rank %d outside 1 .. 128", rank);
-  ARG_CHECK(out >= 1 && in >= 8 && in % 8 == 0, "lora: '%s' is [%d][%d]: `in` must be a positive multiple of 8 (16-byte rows)", who, out, in);
-  return 0;
-}
-static bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
-
 // the checks every user of a sdxl_lora_op shares (merge, project, the backward's own adapter gradients), before anything is launched
 static int lora_check_op(const sdxl_lora_op* op, bool need_base, bool need_grads) {
   ARG_CHECK(op && op->n >= 1 && op->param, "lora: empty target list");
@@ -374,90 +333,6 @@ int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, voi
   return engine_export(h->e, name, dst, dtype, true, (hipStream_t)st);
 }
 
-static int lora_one(int out, int in, int rank, float scale, LoraP& q) {
-  CHK(lora_check_shape("the operand", out, in, rank));
-  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
-  memset(&q, 0, sizeof(q));
-  q.n = 1; q.rank = rank; q.scale = scale;
-  q.one.out = out; q.one.in = in; q.one.kind = LORA_KIND_PLAIN; q.one.nrows = out;
-  q.tiles_m = lora_tiles_m(out, in); q.tiles_b = lora_tiles_b(out, in); q.tiles_a = lora_tiles_a(out, in);
-  return 0;
-}
-// ... and of one target held in a packed layout: always the kind-aware kernels, also for LORA_KIND_PLAIN
-static int lora_one_layout(int out, int in, int rank, float scale, int kind, int cg, int nrows, LoraP& q) {
-  CHK(lora_one(out, in, rank, scale, q));
-  ARG_CHECK(kind == LORA_KIND_PLAIN || kind == LORA_KIND_CONV3 || kind == LORA_KIND_GEGLU, "lora: kind %d (0 plain rows, 1 3x3 convolution, 2 GEGLU)", kind);
-  ARG_CHECK(nrows >= out && (nrows == out || kind == LORA_KIND_CONV3), "lora: %d native rows for out = %d (only a convolution has padded rows)", nrows, out);
-  if (kind == LORA_KIND_CONV3) ARG_CHECK(cg >= 1 && in == 9 * (long)cg, "lora: a 3x3 convolution with cin = %d has in = 9 cin, not %d", cg, in);
-  if (kind == LORA_KIND_GEGLU) ARG_CHECK(cg >= 1 && out % 2 == 0 && (out / 2) % cg == 0, "lora: GEGLU rows [%d] are not whole groups of %d", out, cg);
-  q.one.kind = kind; q.one.cg = kind == LORA_KIND_PLAIN ? 0 : cg; q.one.nrows = nrows; q.mapped = 1;
-  q.tiles_m = lora_tiles_m(nrows, in);
-  return 0;
-}
-int sdxl_op_lora_merge_layout(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, int kind, int cg,
-                              int native_rows, void* st) {
-  ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");
-  LoraP q;
-  CHK(lora_one_layout(out, in, rank, scale, kind, cg, native_rows, q));
-  q.w = (bf16*)w; q.base = (const bf16*)base; q.a = (const bf16*)A; q.b = (const bf16*)B;
-  return launch_lora_merge(q, (hipStream_t)st);
-}
-int sdxl_op_lora_project_layout(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, int kind,
-                                int cg, int native_rows, void* st) {
-  ARG_CHECK(aligned16(dw) && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB),
-            "lora_project: every pointer must be 16-byte aligned and non-NULL");
-  LoraP q;
-  CHK(lora_one_layout(out, in, rank, scale, kind, cg, native_rows, q));
-  q.dw = dw; q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
-  return launch_lora_project(q, (hipStream_t)st);
-}
-int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* st) {
-  ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");
-  LoraP q;
-  CHK(lora_one(out, in, rank, scale, q));
-  q.w = (bf16*)w; q.base = (const bf16*)base; q.a = (const bf16*)A; q.b = (const bf16*)B;
-  return launch_lora_merge(q, (hipStream_t)st);
-}
-int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, void* st) {
-  ARG_CHECK(aligned16(dw) && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB),
-            "lora_project: every pointer must be 16-byte aligned and non-NULL");
-  LoraP q;
-  CHK(lora_one(out, in, rank, scale, q));
-  q.dw = dw; q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
-  return launch_lora_project(q, (hipStream_t)st);
-}
-
-int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out, int in,
-                      int rank, float scale, int accumulate, void* st) {
-  ARG_CHECK(x && dy && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB), "lora_grad: A, B, dA, dB must be 16-byte aligned, x and dy non-NULL");
-  CHK(lora_check_shape("the operand", out, in, rank));
-  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
-  ARG_CHECK(M >= 1 && ldx >= in && ldy >= out, "lora_grad: M = %d, ldx = %ld (in = %d), ldy = %ld (out = %d)", M, ldx, in, ldy, out);
-  LoraGradP q;
-  memset(&q, 0, sizeof(q));
-  q.n = 1; q.rank = rank; q.scale = scale; q.accumulate = accumulate != 0;
-  q.one.out = out; q.one.in = in;
-  q.x = (const bf16*)x; q.ldx = ldx; q.dy = (const bf16*)dy; q.ldy = ldy;
-  q.M = M; q.Mp = lora_grad_mp(M); q.nchunk = lora_grad_chunks(M);
-  q.tiles = lora_grad_tiles(out, in); q.reds = lora_grad_reds(out, in, rank);
-  q.xvec = ((uintptr_t)x % 16 == 0 && ldx % 8 == 0) ? 1 : 0;
-  q.yvec = ((uintptr_t)dy % 16 == 0 && ldy % 8 == 0) ? 1 : 0;
-  q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
-  // scratch of the hook (the engine's is plan workspace): one buffer of the process, kept between calls and only ever grown (hipFree
-  // waits for the launches that use the old one), so that repeated calls of one shape enqueue three launches and nothing else
-  static char* scratch = nullptr;
-  static size_t scratch_cap = 0;
-  const size_t tu_bytes = (lora_grad_tu_elems(1, rank, M) * sizeof(bf16) + 255) / 256 * 256;
-  const size_t need = tu_bytes + lora_grad_part_floats(out, in, rank, M) * sizeof(float);
-  if (need > scratch_cap) {
-    if (scratch) { (void)hipFree(scratch); scratch = nullptr; scratch_cap = 0; }
-    HIP_CHECK_RET(hipMalloc((void**)&scratch, need));
-    scratch_cap = need;
-  }
-  q.tu = (bf16*)scratch; q.part = (float*)(scratch + tu_bytes);
-  return launch_lora_grad(q, (hipStream_t)st);
-}
-
 int sdxl_plan(sdxl_handle* h, int B, int H, int W, int ctx, size_t* ws_bytes) {
   H_CHECK(h);
   ARG_CHECK(B > 0 && H > 0 && W > 0 && ctx > 0, "bad plan shape B=%d H=%d W=%d ctx=%d", B, H, W, ctx);
@@ -497,16 +372,6 @@ int sdxl_bind_workspace(sdxl_handle* h, void* ws, size_t bytes) {
     e.ws_cap = need; e.own_ws = true;
   }
   ARG_CHECK(((uintptr_t)e.ws & 255) == 0, "workspace must be 256-byte aligned");
-  return 0;
-}
-
-static int ready(Engine& e) {
-  if (!e.cur) { sdxl_set_error("no plan: call sdxl_plan first"); return 3; }
-  if (!e.weights || !e.grads) { sdxl_set_error("parameters are not bound: call sdxl_bind_params"); return 3; }
-  if (!e.ws || e.ws_cap < e.cur->ws_bytes) {
-    sdxl_set_error("workspace too small: have %zu bytes, plan needs %zu", e.ws_cap, e.cur->ws_bytes);
-    return 3;
-  }
   return 0;
 }
 
@@ -588,35 +453,6 @@ static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
   return 0;
 }
 
-// The caller's sdxl_loss_config is the short struct (everything before mask_norm) unless loss_type carries SDXL_LOSS_EXT: this is the
-// one place that reads it.  `out` is the struct in full with the flag cleared (loss_type = the element loss) and the fields the caller
-// did not pass zero / NULL; every other function here takes that copy.  loss_type's own errors come before any appended field is read.
-static int read_loss_config(const sdxl_loss_config* lc, sdxl_loss_config* out) {
-  const int lt = lc->loss_type;
-  ARG_CHECK(lt >= 0 && (lt & 0xff) <= 2 && (lt & ~(0xff | SDXL_LOSS_EXT)) == 0,
-            "loss_type %d (0 = l2, 1 = huber, 2 = smooth_l1, optionally | SDXL_LOSS_EXT)", lt);
-  memset(out, 0, sizeof(*out));
-  memcpy(out, lc, (lt & SDXL_LOSS_EXT) ? sizeof(*out) : offsetof(sdxl_loss_config, mask_norm));
-  out->loss_type = lt & 0xff;
-  ARG_CHECK(!out->loss_mask || (out->mask_norm >= 0 && out->mask_norm <= 1), "mask_norm %d (0 = mean, 1 = masked_mean)", out->mask_norm);
-  if (!out->loss_mask) out->mask_norm = 0;      // read only with a mask
-  return 0;
-}
-// the appended fields of sdxl_loss_config / sdxl_batch (element loss, per-sample weights / c / losses, mask, the input's noise), for
-// both places that fill a LossP; lc is read_loss_config's copy
-static void fill_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b, LossP& L) {
-  L.loss_type = lc->loss_type; L.huber_c = lc->huber_c;
-  L.sample_w = b->sample_weights; L.huber_cb = b->huber_c; L.ps_out = b->per_sample_loss;
-  L.mask = lc->loss_mask; L.mask_norm = lc->mask_norm;
-  L.noise_in = lc->noise_in ? lc->noise_in : b->noise;
-}
-// ... and their argument errors, reported before anything is copied or launched
-static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
-  ARG_CHECK(lc->loss_type == 0 || b->huber_c || lc->huber_c > 0.f, "loss_type %d needs huber_c > 0 (got %g) or a per-sample huber_c array",
-            lc->loss_type, (double)lc->huber_c);
-  return 0;
-}
-
 static void fill_loss(Engine& e, const sdxl_loss_config* lc, const sdxl_batch* b, float grad_scale, LossP& L) {
   Plan& p = *e.cur;
   memset(&L, 0, sizeof(L));
@@ -631,7 +467,6 @@ static void fill_loss(Engine& e, const sdxl_loss_config* lc, const sdxl_batch* b
   L.part = p.F(p.loss_part_off);
   L.mnorm = p.F(p.mask_norm_off);
 }
-
 
 // run `body(stream)` once eagerly (first call for a key: one-time function attributes), capture it on the second call, replay
 // the instantiated graph from then on; everything on the engine's graph stream, fenced against the caller's stream
@@ -915,36 +750,6 @@ int sdxl_read_loss(sdxl_handle* h, float out[8], void* stp) {
   return 0;
 }
 
-// sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters.  The caller's struct
-// ends at guidance_rescale unless init carries SDXL_SAMPLER_EXT: nothing behind it is read without the flag.
-static int fill_sampler(const sdxl_sampler_step* s, int image_batch, int HW, SamplerP& q) {
-  ARG_CHECK(s->x != nullptr, "sampler: x is NULL");
-  ARG_CHECK(!s->cfg || image_batch % 2 == 0, "sampler: cfg needs an even batch [cond; uncond] (got %d)", image_batch);
-  const float v[8] = {s->a_skip, s->a_out, s->p, s->q, s->a_in_next, s->clamp, s->guidance, s->guidance_rescale};
-  for (int i = 0; i < 8; ++i) ARG_CHECK(isfinite(v[i]), "sampler: scalar %d of (a_skip, a_out, p, q, a_in_next, clamp, guidance, guidance_rescale) is not finite", i);
-  ARG_CHECK((s->init & ~(1 | SDXL_SAMPLER_EXT)) == 0, "sampler: init %d (0 | 1, optionally | SDXL_SAMPLER_EXT)", s->init);
-  memset(&q, 0, sizeof(q));
-  q.x = s->x;
-  q.B = s->cfg ? image_batch / 2 : image_batch; q.HW = HW;
-  q.cfg = s->cfg != 0; q.init = (s->init & 1) != 0;
-  q.a_skip = s->a_skip; q.a_out = s->a_out; q.p = s->p; q.q = s->q; q.a_in_next = s->a_in_next; q.clamp = s->clamp;
-  q.guidance = s->guidance; q.rescale = s->guidance_rescale;
-  if (!(s->init & SDXL_SAMPLER_EXT)) return 0;
-  const sdxl_sampler_step_ext* e = (const sdxl_sampler_step_ext*)s;
-  const float w[5] = {e->r, e->u, e->s, e->k_a, e->k_b};
-  for (int i = 0; i < 5; ++i) ARG_CHECK(isfinite(w[i]), "sampler: scalar %d of (r, u, s, k_a, k_b) is not finite", i);
-  ARG_CHECK(e->save >= 0 && e->save <= 3, "sampler: save %d (bit 0: hist, bit 1: xsave)", e->save);
-  ARG_CHECK(e->hist || (e->r == 0.f && !(e->save & 1)), "sampler: hist is NULL but r != 0 or save bit 0 is set");
-  ARG_CHECK(e->xsave || (e->u == 0.f && !(e->save & 2)), "sampler: xsave is NULL but u != 0 or save bit 1 is set");
-  ARG_CHECK(e->noise || e->s == 0.f, "sampler: noise is NULL but s != 0");
-  ARG_CHECK(!e->mask || e->known, "sampler: mask needs known");
-  ARG_CHECK(e->knoise || e->k_b == 0.f, "sampler: knoise is NULL but k_b != 0");
-  q.ext = 1;
-  q.hist = e->hist; q.xsave = e->xsave; q.noise = e->noise; q.r = e->r; q.u = e->u; q.s = e->s; q.save = e->save;
-  q.mask = e->mask; q.known = e->known; q.knoise = e->knoise; q.k_a = e->k_a; q.k_b = e->k_b;
-  return 0;
-}
-
 int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond, void* pred, void* stp) {
   CHK(check_cond_request(cond));
   H_CHECK(h);
@@ -1052,310 +857,6 @@ int sdxl_clip_coef(const float* sumsq_dev, float max_norm, float* coef_dev, void
   return launch_clip_coef(sumsq_dev, max_norm, coef_dev, (hipStream_t)st);
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// single-kernel entry points
-// ------------------------------------------------------------------------------------------------------------
-static float* g_test_slab = nullptr;
-static size_t g_test_slab_floats = 0;
-static int test_slab(size_t floats, float** out) {   // scratch for the split-K slabs of the test entry points
-  if (floats > g_test_slab_floats) {
-    if (g_test_slab) (void)hipFree(g_test_slab);
-    HIP_CHECK_RET(hipMalloc((void**)&g_test_slab, floats * sizeof(float)));
-    g_test_slab_floats = floats;
-  }
-  *out = g_test_slab;
-  return 0;
-}
-
-int sdxl_op_gemm(int form, const void* A, const void* B, void* C, int M, int N, int K, const void* bias,
-                 const void* resid, int accumulate, int splitk, void* st) {
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = form;
-  g.A = (const bf16*)A; g.B = (const bf16*)B; g.C = C;
-  g.M = M; g.N = N; g.K = K;
-  if (form == GEMM_NT) { g.lda = K; g.ldb = K; }
-  else if (form == GEMM_NN) { g.lda = K; g.ldb = N; }
-  if (form != GEMM_TN && splitk > 1) {
-    g.splitk = splitk;
-    CHK(test_slab(gemm_slab_floats(M, N, 1, splitk), &g.slab));
-  }
-  if (form == GEMM_TN) {
-    if (splitk <= 0) splitk = linear_wgrad_splitk(M, N, K);     // the plan's choice
-    g.lda = M; g.ldb = N; g.out_f32 = 1; g.splitk = splitk;
-    if (splitk > 1) CHK(test_slab(gemm_slab_floats(M, N, 1, splitk), &g.slab));
-  }
-  g.ldc = N;
-  if (form == GEMM_TN) g.bias_grad = (float*)bias;
-  else g.bias = (const bf16*)bias;
-  if (resid) { g.resid = (const bf16*)resid; g.ldr = N; }
-  g.accumulate = accumulate;
-  return launch_gemm(g, (hipStream_t)st);
-}
-
-int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, const void* const* W, const long* ldb, const int* K, float* C, long ldc,
-                       int M, int N, void* st) {
-  ARG_CHECK(n >= 1 && n <= 2 && A && lda && W && ldb && K, "cond_dgrad: 1 or 2 groups, no null array");
-  CondDgradP q;
-  memset(&q, 0, sizeof(q));
-  q.n = n;
-  for (int g = 0; g < n; ++g) { q.A[g] = (const bf16*)A[g]; q.lda[g] = lda[g]; q.W[g] = (const bf16*)W[g]; q.ldb[g] = ldb[g]; q.K[g] = K[g]; }
-  q.C = C; q.ldc = ldc; q.M = M; q.N = N;
-  ARG_CHECK(M >= 1 && N >= 8, "cond_dgrad: M = %d, N = %d", M, N);
-  for (int g = 0; g < n; ++g) ARG_CHECK(K[g] >= 64 && K[g] % 64 == 0, "cond_dgrad: K[%d] = %d must be a positive multiple of 64", g, K[g]);
-  const size_t need = cond_dgrad_slab_floats(n, K, M, N);
-  if (need) CHK(test_slab(need, &q.slab));
-  return launch_cond_dgrad(q, (hipStream_t)st);
-}
-
-int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off, long* ldb,
-                             int* K) {
-  H_CHECK(h);
-  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
-  ARG_CHECK(n_groups && a_ws_byte_off && lda && w_elem_off && ldb && K, "null output");
-  const Plan& p = *h->e.cur;
-  const int n = which == 0 ? p.cond_nkv : 1;
-  ARG_CHECK((which == 0 || which == 1) && g >= 0 && g < n, "cond operands: which = %d, group %d of %d", which, g, n);
-  const Plan::CondSrc& cs = which == 0 ? p.cond_kv[g] : p.cond_add;
-  *n_groups = n; *a_ws_byte_off = cs.dy_off; *lda = cs.lda; *w_elem_off = cs.w.off; *ldb = cs.ldb; *K = cs.K;
-  return 0;
-}
-
-int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, float* const* dw, float* const* dbias, int Mo, int No,
-                        int rows, int accumulate, void* st) {
-  ARG_CHECK(n >= 1 && n <= GEMM_MAX_GROUP, "wgrad group of %d (1..%d)", n, GEMM_MAX_GROUP);
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_TN;
-  g.M = Mo; g.N = No; g.K = rows;
-  g.lda = Mo; g.ldb = No; g.ldc = No;
-  g.out_f32 = 1;
-  g.accumulate = accumulate;
-  g.A = (const bf16*)dy[0]; g.B = (const bf16*)x[0]; g.C = dw[0]; g.bias_grad = dbias ? dbias[0] : nullptr;
-  g.group = n;
-  for (int i = 0; i < n; ++i) {
-    g.gA[i] = (const bf16*)dy[i]; g.gB[i] = (const bf16*)x[i]; g.gC[i] = dw[i]; g.gbias_grad[i] = dbias ? dbias[i] : nullptr;
-  }
-  return launch_gemm(g, (hipStream_t)st);
-}
-
-int sdxl_op_conv3x3_fwd(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
-                        int stride, void* st) {
-  GemmP g = conv3x3_fwd_problem(B, H, W, Cin, Cout, stride);
-  g.A = (const bf16*)x; g.B = (const bf16*)w; g.C = y;
-  g.bias = (const bf16*)bias;
-  g.splitk = conv3x3_fwd_splitk(B, H, W, Cin, Cout, stride);
-  if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cout, 1, g.splitk), &g.slab));
-  return launch_gemm(g, (hipStream_t)st);
-}
-// y = conv3x3(upsample2x(x)) and its input gradient without the upsampled image (GemmP::up2); weff [Cout][16][Cin] and planar
-// [4 B H W][Cout] bf16 are scratch of the caller (weff written by the forward, read by the dgrad)
-int sdxl_op_upconv3x3_fwd(const void* x, const void* w, const void* bias, void* weff, void* planar, void* y, int B, int H, int W,
-                          int Cin, int Cout, void* st) {
-  const int Mp = 4 * (int)upconv_plane_rows(B, H, W);
-  int splitk = upconv3x3_fwd_splitk(B, H, W, Cin, Cout);
-  float* slab = nullptr;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(Mp, Cout, 1, splitk), &slab));
-  return launch_upconv3x3_fwd((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)weff, (bf16*)planar, (bf16*)y, B, H, W, Cin, Cout,
-                              splitk, slab, (hipStream_t)st);
-}
-int sdxl_op_upconv3x3_dgrad(const void* dy, const void* weff, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
-                            int Cout, void* st) {
-  int splitk = upconv3x3_dgrad_splitk(B, H, W, Cin, Cout);
-  float* slab = nullptr;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(B * H * W, Cin, 1, splitk), &slab));
-  return launch_upconv3x3_dgrad((const bf16*)dy, (const bf16*)weff, (bf16*)planar, (bf16*)dx, (const bf16*)addend, B, H, W, Cin, Cout, splitk,
-                                slab, 0, (hipStream_t)st);
-}
-#ifdef SDXL_DIAG
-// stride-2 3x3 convolution through the fast gather on the four phase planes of x (GemmP::up2 == 3); xplanar [4 * roundup(B*(H/2)*(W/2), 128)][Cin]
-// bf16: written by _fwd, read by _wgrad
-int sdxl_op_conv3x3_s2_fwd(const void* x, const void* w, const void* bias, void* xplanar, void* y, int B, int H, int W, int Cin, int Cout,
-                           void* st) {
-  return launch_conv3x3_s2_fwd((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)xplanar, (bf16*)y, B, H, W, Cin, Cout, (hipStream_t)st);
-}
-int sdxl_op_conv3x3_s2_wgrad(const void* dy, const void* xplanar, float* dw, float* dbias, int accumulate, int B, int H, int W, int Cin,
-                             int Cout, int splitk, void* st) {
-  float* slab = nullptr;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 9, splitk), &slab));
-  return launch_conv3x3_s2_wgrad((const bf16*)dy, (const bf16*)xplanar, dw, dbias, nullptr, 1.f, accumulate, B, H, W, Cin, Cout, splitk, slab,
-                                 (hipStream_t)st);
-}
-#endif
-// input gradient of the stride-2 3x3 convolution by output phase (GemmP::up2 == 2); planar [4 * roundup(B*(H/2)*(W/2), 128)][Cin] scratch
-int sdxl_op_conv3x3_s2_dgrad(const void* dy, const void* w, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
-                             int Cout, void* st) {
-  return launch_conv3x3_s2_dgrad((const bf16*)dy, (const bf16*)w, (bf16*)planar, (bf16*)dx, (const bf16*)addend, B, H, W, Cin, Cout, 0,
-                                 (hipStream_t)st);
-}
-// the weight / bias gradient of the same pair from `planar` as sdxl_op_upconv3x3_dgrad left it (the de-interleaved dy) and the
-// low-resolution x; dweff [Cout][16][Cin] fp32 scratch; dw [Cout][9][Cin] (= or +=), dbias += (may be NULL)
-int sdxl_op_upconv3x3_wgrad(const void* planar, const void* x, float* dweff, float* dw, float* dbias, int accumulate, int B, int H, int W,
-                            int Cin, int Cout, int splitk, void* st) {
-  float* slab = nullptr;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 16, splitk), &slab));
-  return launch_upconv3x3_wgrad((const bf16*)planar, (const bf16*)x, dweff, dw, dbias, nullptr, 1.f, accumulate, B, H, W, Cin, Cout, splitk,
-                                slab, (hipStream_t)st);
-}
-int sdxl_op_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B, int H, int W, int Cin, int Cout, int stride,
-                          void* st) {
-  GemmP g = conv3x3_dgrad_problem(B, H, W, Cin, Cout, stride);
-  g.A = (const bf16*)dy; g.B = (const bf16*)w; g.C = dx;
-  g.splitk = conv3x3_dgrad_splitk(B, H, W, Cin, Cout, stride);
-  if (g.splitk > 1) CHK(test_slab(gemm_slab_floats(g.M, Cin, 1, g.splitk), &g.slab));
-  return launch_gemm(g, (hipStream_t)st);
-}
-int sdxl_op_conv3x3_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin, int Cout, int stride,
-                          int splitk, void* st) {
-  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
-  g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
-  g.splitk = splitk; g.accumulate = 1;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
-  return launch_gemm(g, (hipStream_t)st);
-}
-
-int sdxl_op_conv3x3_wgrad2(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout, int stride,
-                           int splitk, int accumulate, void* st) {
-  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
-  g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
-  g.accumulate = accumulate; g.bias_grad = dbias;
-  if (splitk <= 0) splitk = conv3x3_wgrad_splitk(B, H, W, Cin, Cout, stride);      // the plan's choice
-  g.splitk = splitk;
-  if (splitk > 1) CHK(test_slab(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
-  return launch_gemm(g, (hipStream_t)st);
-}
-
-int sdxl_op_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int heads, int Nq,
-                          int Nk, long ldq, long ldk, long ldv, long ldo, void* st) {
-  AttnP a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)o; a.LSE = lse;
-  a.B = B; a.H = heads; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  return launch_attn_fwd(a, (hipStream_t)st);
-}
-int sdxl_op_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
-                          float* delta, void* dq, void* dk, void* dv, int B, int heads, int Nq, int Nk, long ldq,
-                          long ldk, long ldv, long ldo, void* st) {
-  AttnP a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)o; a.LSE = (float*)lse;
-  a.B = B; a.H = heads; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  a.dO = (const bf16*)d_o; a.lddo = ldo; a.Delta = delta;
-  a.dQ = (bf16*)dq; a.dK = (bf16*)dk; a.dV = (bf16*)dv; a.lddq = ldq; a.lddk = ldk; a.lddv = ldv;
-  a.qsplit = attn_pick_qsplit(B, heads, Nq, Nk);
-  if (a.qsplit > 1) CHK(test_slab(attn_part_floats(B, heads, Nk, a.qsplit), &a.part));
-  return launch_attn_bwd(a, (hipStream_t)st);
-}
-
-int sdxl_op_groupnorm_fwd(const void* x, void* y, const void* gamma, const void* beta, float* stats, float* ws, int B,
-                          int HW, int C, int G, float eps, int silu, void* st) {
-  return launch_groupnorm_fwd((const bf16*)x, (bf16*)y, (const bf16*)gamma, (const bf16*)beta, stats, ws, B, HW, C, G, eps,
-                              silu, (hipStream_t)st);
-}
-int sdxl_op_groupnorm_bwd(const void* x, const void* dy, const void* gamma, const void* beta, const float* stats, void* dx,
-                          float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int G, int silu, int accumulate,
-                          void* st) {
-  return launch_groupnorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, (const bf16*)beta, stats, (bf16*)dx,
-                              accumulate ? (const bf16*)dx : nullptr, dgamma, dbeta, ws, B, HW, C, G, silu, (hipStream_t)st);
-}
-int sdxl_op_layernorm_fwd(const void* x, void* y, const void* gamma, const void* beta, float* stats, int M, int C,
-                          float eps, void* st) {
-  return launch_layernorm_fwd((const bf16*)x, (bf16*)y, (const bf16*)gamma, (const bf16*)beta, stats, M, C, eps,
-                              (hipStream_t)st);
-}
-int sdxl_op_layernorm_bwd(const void* x, const void* dy, const void* gamma, const float* stats, void* dx, float* dgamma,
-                          float* dbeta, int M, int C, int accumulate, void* st) {
-  if (!dgamma)
-    return launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
-                                accumulate ? (const bf16*)dx : nullptr, nullptr, nullptr, M, C, (hipStream_t)st);
-  ARG_CHECK(dbeta, "layernorm bwd: dgamma and dbeta go together");
-  if (KNOB(10) == 1 || KNOB(10) == 3) {     // (A/B runs) lean dx kernel + parameter gradients as a pass of their own; the plan's default is the one-pass form below
-    CHK(launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
-                             accumulate ? (const bf16*)dx : nullptr, nullptr, nullptr, M, C, (hipStream_t)st));
-    if (KNOB(10) == 3) return launch_layernorm_param_grads((const bf16*)x, (const bf16*)dy, stats, dgamma, dbeta, M, C, (hipStream_t)st);
-    LnRedBatch b;
-    b.n = 1;
-    float* part;
-    CHK(test_slab(layernorm_bwd_part_floats(M, C), &part));
-    b.e[0].part = part; b.e[0].dgamma = dgamma; b.e[0].dbeta = dbeta; b.e[0].C = C; b.e[0].nblk = layernorm_param_partial_rows(M, C);
-    CHK(launch_layernorm_param_partials((const bf16*)x, (const bf16*)dy, stats, part, M, C, (hipStream_t)st));
-    return launch_ln_param_reduce(b, (hipStream_t)st);
-  }
-  LnRedBatch b;
-  b.n = 1;
-  float* part;
-  CHK(test_slab(layernorm_bwd_part_floats(M, C), &part));
-  b.e[0].part = part; b.e[0].dgamma = dgamma; b.e[0].dbeta = dbeta; b.e[0].C = C;
-  CHK(launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
-                           accumulate ? (const bf16*)dx : nullptr, part, &b.e[0].nblk, M, C, (hipStream_t)st));
-  return launch_ln_param_reduce(b, (hipStream_t)st);
-}
-int sdxl_op_ff_geglu_fwd(const void* x, const void* w1, const void* b1, void* u, void* g, int M, int K, int C4, int group,
-                         void* st) {
-  GemmP p;
-  gemm_defaults(&p);
-  p.form = GEMM_NT;
-  p.A = (const bf16*)x; p.B = (const bf16*)w1; p.C = u;
-  p.M = M; p.N = 2 * C4; p.K = K;
-  p.lda = K; p.ldb = K; p.ldc = 2L * C4;
-  p.bias = (const bf16*)b1;
-  p.geglu = 1; p.geglu_group = group; p.aux = (bf16*)g; p.ldaux = C4;
-  return launch_gemm(p, (hipStream_t)st);
-}
-int sdxl_op_ff_geglu_bwd(const void* dy, const void* w2, const void* u, void* du, int M, int C, int C4, int group,
-                         void* st) {
-  GemmP p;
-  gemm_defaults(&p);
-  p.form = GEMM_NN;
-  p.A = (const bf16*)dy; p.B = (const bf16*)w2; p.C = du;
-  p.M = M; p.N = C4; p.K = C;
-  p.lda = C; p.ldb = C4; p.ldc = 2L * C4;
-  p.geglu = 2; p.geglu_group = group; p.aux = (bf16*)u; p.ldaux = 2L * C4;
-  return launch_gemm(p, (hipStream_t)st);
-}
-
-int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in, const void* pred, void* dpred,
-                 float grad_scale, float* out8, int phase, void* st) {
-  ARG_CHECK(lc && b, "null argument");
-  sdxl_loss_config full;
-  CHK(read_loss_config(lc, &full));
-  lc = &full;
-  LossP L;
-  memset(&L, 0, sizeof(L));
-  L.method = lc->method; L.prediction_type = lc->prediction_type; L.use_min_snr = lc->use_min_snr;
-  L.min_snr_gamma = lc->min_snr_gamma; L.use_ztsnr = lc->use_ztsnr;
-  L.B = b->B; L.HW = b->H * b->W; L.C = 4;
-  L.latents = b->latents; L.noise = b->noise; L.sigma = b->sigma_or_t; L.tag_w = b->tag_weights;
-  L.unet_in = (bf16*)unet_in; L.pred = (const bf16*)pred; L.dpred = (bf16*)dpred;
-  L.grad_scale = grad_scale; L.out = out8;
-  CHK(check_loss_ext(lc, b));
-  fill_loss_ext(lc, b, L);
-  // the partial rows of phase 1, and behind them the [B] normaliser that masked_mean's phase 1 leaves for its phase 2
-  if (phase == 1 || (phase == 2 && L.mask && L.mask_norm == 1)) {
-    ARG_CHECK(L.B > 0 && L.HW > 0, "loss: empty batch");
-    CHK(test_slab(loss_part_floats(L.B, L.HW) + (size_t)L.B, &L.part));
-    L.mnorm = L.part + loss_part_floats(L.B, L.HW);
-  }
-  if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st);
-  if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);
-  if (phase == 2) return launch_loss_bwd(L, (hipStream_t)st);
-  ARG_CHECK(false, "phase %d", phase);
-}
-
-int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* st) {
-  ARG_CHECK(s, "null argument");
-  ARG_CHECK(B > 0 && H > 0 && W > 0, "sampler: empty batch");
-  sdxl_sampler_step_ext t;      // the caller's struct as far as its flag says it goes, with x set
-  memset(&t, 0, sizeof(t));
-  memcpy(&t, s, (s->init & SDXL_SAMPLER_EXT) ? sizeof(sdxl_sampler_step_ext) : sizeof(sdxl_sampler_step));
-  t.base.x = x;
-  SamplerP q;
-  CHK(fill_sampler(&t.base, s->cfg ? 2 * B : B, H * W, q));      // B = samples here: the images hold 2B rows of HW with cfg
-  q.pred = (const bf16*)pred; q.x_in = (bf16*)x_in;
-  if (!q.init && q.rescale != 0.f) CHK(test_slab(sampler_part_floats(B, H * W), &q.part));
-  return launch_sampler_step(q, (hipStream_t)st);
-}
-
 // ---- row f1: fused AdamW_BF16 ----
 static float bf16_round_host(float x) {
   unsigned u;
@@ -1438,204 +939,4 @@ int sdxl_adamw_decay(void* shift, const void* p, size_t n, float decay, void* st
   if (decay <= 0.f) return 0;
   return launch_adamw_decay((bf16*)shift, (const bf16*)p, n, bf16_round_host(-decay), (hipStream_t)st);
 }
-
-int sdxl_probe_layout(void* out, void* st) { return probe_layout(out, (hipStream_t)st); }
-int sdxl_op_exchange_shadow(void* buf, size_t bytes, int workgroups, int lds_bytes, float busy_us, void* st) {
-  return launch_exchange_shadow(buf, bytes, workgroups, lds_bytes, busy_us, (hipStream_t)st);
-}
-// test hook (include/sdxlstep_diag.h part 1): sdxl_op_gemm's NT / NN forms with explicit leading dimensions (padded activations, as the plan's
-// feed-forward hidden tensors are) and a forced configuration for this launch only (0: the policy)
-int sdxl_op_gemm_ld(int form, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, const void* bias,
-                    const void* resid, long ldr, int cfg, void* st) {
-  ARG_CHECK(form == GEMM_NT || form == GEMM_NN, "gemm_ld: NT / NN only (form %d)", form);
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = form;
-  g.A = (const bf16*)A; g.B = (const bf16*)B; g.C = C;
-  g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.bias = (const bf16*)bias;
-  if (resid) { g.resid = (const bf16*)resid; g.ldr = ldr; }
-  g.cfg = cfg;
-  return launch_gemm(g, (hipStream_t)st);
-}
-// test hook (include/sdxlstep_diag.h part 1): the NN dgrad with the Delta epilogue, as LinearOp::bwd launches it for a self-attention
-// layer's out-projection
-int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const void* o, const void* addend, void* d_o, float* delta, int B, int Nq,
-                               int N, int K, void* st) {
-  ARG_CHECK(dy && w && o && d_o && delta && B > 0 && Nq > 0 && N % 128 == 0 && K % 64 == 0, "linear_dgrad_delta: B=%d Nq=%d N=%d K=%d", B, Nq, N, K);
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_NN;
-  g.A = (const bf16*)dy; g.B = (const bf16*)w; g.C = d_o;
-  g.M = B * Nq; g.N = N; g.K = K;
-  g.lda = K; g.ldb = N; g.ldc = N;
-  if (addend) { g.resid = (const bf16*)addend; g.ldr = N; }
-  g.delta_o = (const bf16*)o; g.delta_ldo = N;
-  g.delta_out = delta;
-  g.delta_nq = Nq; g.delta_heads = N / 64;
-  g.cfg = 1;
-  return launch_gemm(g, (hipStream_t)st);
-}
-// test hook (include/sdxlstep_diag.h part 1): what launch_gemm would run for the problem a launch-log line describes.  The operands gemm_route never
-// looks at are dense and stand on one aligned dummy word; no device is touched.
-int sdxl_debug_gemm_route(const sdxl_gemm_desc* d, sdxl_gemm_route* out) {
-  ARG_CHECK(d && out, "gemm_route: null argument");
-  alignas(16) static float word[4];
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = d->form; g.taps = d->taps; g.M = d->M; g.N = d->N; g.K = d->K; g.cfg = d->cfg;
-  g.A = g.B = (const bf16*)word; g.C = word;
-  g.out_f32 = d->form == GEMM_TN;
-  g.lda = d->form == GEMM_TN ? d->M : d->K;
-  g.ldb = d->form == GEMM_NT ? (long)d->K * d->taps : (long)d->N * d->taps;
-  g.ldc = d->form == GEMM_TN ? (long)d->N * d->taps : d->N;
-  g.Hm = d->Hm; g.Wm = d->Wm; g.Hs = d->Hs; g.Ws = d->Ws; g.sm = d->sm; g.sd = d->sd;
-  g.up2 = d->up2;
-  if (d->up2) {      // the planar matrix's rows, from the side of the problem that walks them (GemmP::up2)
-    const int rows = d->form == GEMM_TN ? d->K : d->M;
-    const bool planar = d->up2 == 2 || (d->up2 == 1 && d->form == GEMM_NT);      // four planes of whole images + padding | the pixels themselves
-    ARG_CHECK(d->Hm > 0 && d->Wm > 0, "gemm_route: up2 needs the image size");
-    g.up_plane = planar ? rows / 4 : (int)upconv_plane_rows(1, 1, rows);
-    g.up_rows = planar ? g.up_plane / (d->Hm * d->Wm) * (d->Hm * d->Wm) : rows;
-  }
-  g.geglu = d->geglu; g.geglu_group = d->geglu_group;
-  if (d->geglu) { g.aux = (bf16*)word; g.ldaux = 8; }
-  g.splitk = d->splitk; g.slab = word;
-  if (d->group > 1) {
-    g.group = d->group;
-    for (int i = 0; i < d->group && i < GEMM_MAX_GROUP; ++i) { g.gA[i] = g.gB[i] = (const bf16*)word; g.gC[i] = word; g.gCb[i] = d->emit_bf16 ? (bf16*)word : nullptr; g.gbias_grad[i] = d->bias_grad ? word : nullptr; }
-  } else if (d->emit_bf16) g.Cb = (bf16*)word;
-  if (d->bias_grad) g.bias_grad = word;
-  if (d->delta) { g.delta_out = word; g.delta_o = (const bf16*)word; g.delta_nq = d->M; g.delta_heads = d->N / 64; }
-  GemmRoute r;
-  if (int e = gemm_route_checked(g, &r)) return e;
-  out->kernel = r.kernel; out->cfg = r.cfg; out->fast = r.fast; out->post = r.post;
-  return 0;
-}
-int sdxl_profile_gemm_begin(void) { return gemm_profile_begin(); }
-int sdxl_set_gemm_mode(int mode) {
-  const int cfg = mode >> 2;
-  ARG_CHECK(mode >= 0 && (mode & 3) <= 2 && (cfg == 0 || cfg == 1 || cfg == 2 || cfg == 3 || cfg == 5 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 13 || cfg == 23 || cfg == 43 || cfg == 31 || cfg == 32 || cfg == 33 || cfg == 34 || cfg == 35 || cfg == 36), "gemm mode %d", mode);
-  gemm_set_mode(mode);
-  return 0;
-}
-int sdxl_profile_gemm_end(double* flops, double* ms, int* launches) { return gemm_profile_end(flops, ms, launches); }
-#ifdef SDXL_DIAG     // ---- experiment ABI of the diagnostics build (include/sdxlstep_diag.h): not in the product library ----
-// dY [M][Kr] x W [Kr][N] (the NN dgrad form) with the LayerNorm backward of GemmP::ln_x in the epilogue: dx = LN_bwd(dY W | x, stats, gamma)
-// (+ addend), dy_out (or null) = dY W, pcol (or null) = [cdiv(M, 128)][2][N] dgamma | dbeta partial sums.  Scratch is allocated, zeroed and
-// freed per call (test hook; the plan shares its own); N <= 1280.
-int sdxl_op_linear_dgrad_ln_bwd(const void* dy, const void* w, const void* x, const float* stats, const void* gamma, const void* addend,
-                                void* dx, void* dy_out, float* pcol, int M, int N, int Kr, void* st) {
-  ARG_CHECK(gemm_ln_cfg(M, N, Kr) != 0, "linear_dgrad_ln_bwd: M=%d N=%d K=%d does not fit the fused epilogue", M, N, Kr);
-  float* part = nullptr;
-  const size_t pbytes = gemm_ln_part_floats(M, N) * sizeof(float);
-  HIP_CHECK_RET(hipMalloc((void**)&part, pbytes));
-  if (hipError_t e = hipMemsetAsync(part, 0, pbytes, (hipStream_t)st)) {      // (every exit path frees the scratch)
-    (void)hipFree(part);
-    sdxl_set_error("linear_dgrad_ln_bwd: hipMemsetAsync -> %s", hipGetErrorString(e));
-    return 2;
-  }
-  GemmP g;
-  gemm_defaults(&g);
-  g.form = GEMM_NN;
-  g.A = (const bf16*)dy; g.B = (const bf16*)w; g.C = dy_out;
-  g.M = M; g.N = N; g.K = Kr;
-  g.lda = Kr; g.ldb = N; g.ldc = N;
-  g.ln_x = (const bf16*)x; g.ln_ldx = N; g.ln_stats = stats; g.ln_gamma = (const bf16*)gamma;
-  g.ln_dx = (bf16*)dx; g.ln_addend = (const bf16*)addend; g.ln_ldo = N;
-  g.ln_part = part; g.ln_pcol = pcol;
-  int rc = 0;
-  for (int epoch = 1; epoch <= 3 && rc == 0; ++epoch) {      // three launches on the same scratch: later ones find the earlier epochs' granules
-    g.ln_epoch = epoch;
-    rc = launch_gemm(g, (hipStream_t)st);
-  }
-  const hipError_t se = hipStreamSynchronize((hipStream_t)st);
-  (void)hipFree(part);
-  if (se != hipSuccess) { sdxl_set_error("linear_dgrad_ln_bwd: hipStreamSynchronize -> %s", hipGetErrorString(se)); return 2; }
-  return rc;
-}
-// Knobs are process-global and read at plan-build, forward and backward time: set them BEFORE sdxl_plan / the first step of a handle and
-// leave them alone afterwards (A/B runs restart the process per setting, profiles/tools/ab.sh).
-int sdxl_set_knob(int id, int value) {
-  ARG_CHECK(id >= 0 && id < SDXL_NKNOBS, "knob %d out of range", id);
-  g_knobs[id] = value;
-  if (id == 9) wgrad256_set_enabled(value == 0);         // knob 9 = 1: long-reduction linear weight gradients on the 128 x 160 kernel
-  if (id == 12) conv_wgrad3_set_enabled(value == 0);    // knob 12 = 1: 3x3 weight gradients on the one-tap-per-workgroup kernel only
-  if (id == 15) gemm256_set_tail(value == 0);     // knob 15 = 1: no half-height tail workgroups in the 256 x 256 kernel
-  return 0;
-}
-int sdxl_set_sk_mode(int mode, int workers) {
-  ARG_CHECK(mode >= 0 && mode <= 2 && workers >= 0 && workers <= 256, "stream-K mode %d / workers %d", mode, workers);
-  gemm_set_sk_mode(mode);
-  gemm_sk_set_workers(workers);
-  return 0;
-}
-int sdxl_op_pl_prefetch_b(int form, const void* B, int M, int N, int K, long ldb, int parts, void* st) {
-  GemmP p;
-  gemm_defaults(&p);
-  p.form = form; p.B = (const bf16*)B; p.M = M; p.N = N; p.K = K; p.ldb = ldb;
-  return launch_pl_prefetch_b(p, parts, (hipStream_t)st);
-}
-int sdxl_ln_error(unsigned* out) {
-  ARG_CHECK(out != nullptr, "ln_error: null output");
-  return gemm_ln_error(out);
-}
-int sdxl_sk_error(void* st, unsigned* out) {
-  ARG_CHECK(out, "null output");
-  return gemm_sk_error((hipStream_t)st, out);
-}
-int sdxl_op_gemm_sk(int n, const int* form, const void* const* A, const void* const* B, void* const* C, const int* M, const int* N,
-                    const int* K, const void* const* bias, const void* const* resid, const int* accumulate, void* st) {
-  ARG_CHECK(n >= 1 && n <= 4 && form && A && B && C && M && N && K, "gemm_sk: bad arguments");
-  GemmP g[4];
-  for (int i = 0; i < n; ++i) {
-    gemm_defaults(&g[i]);
-    g[i].form = form[i];
-    g[i].A = (const bf16*)A[i]; g[i].B = (const bf16*)B[i]; g[i].C = C[i];
-    g[i].M = M[i]; g[i].N = N[i]; g[i].K = K[i];
-    if (form[i] == GEMM_NT) { g[i].lda = K[i]; g[i].ldb = K[i]; }
-    else if (form[i] == GEMM_NN) { g[i].lda = K[i]; g[i].ldb = N[i]; }
-    else { g[i].lda = M[i]; g[i].ldb = N[i]; g[i].out_f32 = 1; }
-    g[i].ldc = N[i];
-    if (form[i] == GEMM_TN) g[i].bias_grad = bias ? (float*)bias[i] : nullptr;
-    else g[i].bias = bias ? (const bf16*)bias[i] : nullptr;
-    if (resid && resid[i]) { g[i].resid = (const bf16*)resid[i]; g[i].ldr = N[i]; }
-    g[i].accumulate = accumulate ? accumulate[i] : 0;
-  }
-  return launch_gemm_multi(g, n, (hipStream_t)st);
-}
-#endif   // SDXL_DIAG
-
-// debug: order-independent checksum (sum of raw 16-bit patterns) of every activation of the current plan, in
-// creation order.  Synchronises.  Used to localise run-to-run differences.
-__global__ void checksum_kernel(const unsigned short* __restrict__ x, long n, unsigned long long* out) {
-  unsigned long long s = 0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    s += (unsigned long long)x[i] * (unsigned long long)((i % 251) + 1);
-  atomicAdd(out, s);
-}
-int sdxl_debug_act_checksums(sdxl_handle* h, unsigned long long* out_host, int cap, int* n_out, int grads) {
-  H_CHECK(h);
-  CHK(ready(h->e));
-  Plan& p = *h->e.cur;
-  int n = (int)p.acts.size();
-  if (n_out) *n_out = n;
-  if (n > cap) n = cap;
-  unsigned long long* d = nullptr;
-  HIP_CHECK_RET(hipMalloc((void**)&d, sizeof(unsigned long long) * (n > 0 ? n : 1)));
-  HIP_CHECK_RET(hipMemset(d, 0, sizeof(unsigned long long) * (n > 0 ? n : 1)));
-  for (int i = 0; i < n; ++i) {
-    Act* a = p.acts[i].get();
-    const bf16* src = grads ? p.G(a) : p.P(a);
-    if (!src || a->parent) continue;     // (column-slice views are covered by their parent)
-    long cnt = a->rows * a->cols;
-    hipLaunchKernelGGL(checksum_kernel, dim3(64), dim3(256), 0, 0, (const unsigned short*)src, cnt, d + i);
-  }
-  HIP_CHECK_RET(hipDeviceSynchronize());
-  HIP_CHECK_RET(hipMemcpy(out_host, d, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
-  (void)hipFree(d);
-  return 0;
-}
-
 }  // extern "C"

@@ -115,10 +115,7 @@ static int launch_wgrad_bucket(Plan& p, hipStream_t main, std::vector<GemmP>& v)
   GemmP g = v[0];
   if (v.size() > 1) {
     g.splitk = 1;
-    g.group = (int)v.size();
-    for (size_t i = 0; i < v.size(); ++i) {
-      g.gA[i] = v[i].A; g.gB[i] = v[i].B; g.gC[i] = (float*)v[i].C; g.gbias_grad[i] = v[i].bias_grad; g.gCb[i] = v[i].Cb;
-    }
+    gemm_fill_group(g, v.data(), (int)v.size());
   }
   v.clear();
   if (g.splitk > 1) g.anyorder = 0;      // (a straggler that keeps its split: the shared slab orders it)
@@ -206,6 +203,23 @@ static void want_slab(Plan& p, int M, int N, int taps, int splitk) {
   if (need > p.slab_floats) p.slab_floats = need;
 }
 
+// where an op's weight gradient goes: the fp32 arena (= on the first micro-step, += after) and the bias's accumulator, or with an emit arena
+// (sdxl_set_grad_emit) the final value as bf16 at the same element offset
+struct WgradDst {
+  float *C, *bias_grad;
+  int accumulate;
+  bf16* Cb;
+  float cb_scale;
+  void to(GemmP& g) const {
+    g.C = C; g.bias_grad = bias_grad; g.accumulate = accumulate;
+    if (Cb) { g.Cb = Cb; g.cb_scale = cb_scale; }
+  }
+};
+static WgradDst wgrad_dst(Plan& p, PRef w, PRef b, bool first) {
+  const Engine& e = *p.eng;
+  return {e.Gp(w), b.off != NONE ? e.Gp(b) : nullptr, first ? 0 : 1, e.emit_base ? e.emit_base + w.off : nullptr, e.emit_scale};
+}
+
 static int kv_pad_rows(int B, int ctx) { return (int)((64 - ((long)B * ctx) % 64) % 64); }   // B * 77 prompt tokens -> multiple of 64
 
 struct AttnOp;
@@ -240,15 +254,9 @@ struct LinearOp : Op {
   Act* gu = nullptr;     // second projection: the first projection's pre-activation u [rows][2K]
   LinearOp(Act* x_, Act* y_, PRef w_, PRef b_, int K_, int N_, Act* resid_) : x(x_), y(y_), resid(resid_), w(w_), b(b_), K(K_), N(N_) {}
   int fwd(Plan& p, hipStream_t st) override {
-    GemmP g;
-    gemm_defaults(&g);
-    g.form = GEMM_NT;
-    g.A = p.P(x); g.B = p.eng->Wp(w); g.C = p.P(y);
-    g.M = (int)x->rows; g.N = N; g.K = K;
-    g.lda = x->ld(); g.ldb = K; g.ldc = y->ld();
-    g.bias = b.off == NONE ? nullptr : p.eng->Wp(b);
-    if (resid) { g.resid = p.P(resid); g.ldr = resid->ld(); }
-    if (gact) { g.geglu = 1; g.geglu_group = ggroup; g.aux = p.P(gact); g.ldaux = gact->ld(); }
+    GemmP g = linear_fwd_problem(p.P(x), x->ld(), p.eng->Wp(w), p.P(y), y->ld(), (int)x->rows, N, K, b.off == NONE ? nullptr : p.eng->Wp(b),
+                                 resid ? p.P(resid) : nullptr, resid ? resid->ld() : 0);
+    if (gact) gemm_attach_geglu_fwd(g, ggroup, p.P(gact), gact->ld());
     if (fsplit > 1 && !hoist_fwd) { g.splitk = fsplit; g.slab = p.F(p.slab_main_off); }     // (the hoisted projection runs on the side stream)
     return launch_gemm(g, st);
   }
@@ -323,18 +331,10 @@ struct LinearOp : Op {
       CHK(on_side(p, st, [&q](hipStream_t s2) -> int { return launch_lora_grad(q, s2); }));
     } else
     if (!p.eng->frozen(w, b)) {      // (a frozen op: no weight gradient, no bias column sums, no zero rows for them -- Engine::frozen)
-      GemmP g;
-      gemm_defaults(&g);
-      g.form = GEMM_TN;
-      g.A = dy; g.B = p.P(x); g.C = p.eng->Gp(w);
-      g.M = N; g.N = K; g.K = M;
-      g.lda = y->ld(); g.ldb = x->ld(); g.ldc = K;
-      g.out_f32 = 1;
+      GemmP g = linear_wgrad_problem(dy, y->ld(), p.P(x), x->ld(), nullptr, N, K, M, nullptr);
+      wgrad_dst(p, w, b, first).to(g);      // dW, the bias's column sums, = or +=, the emit arena
       g.splitk = splitk;
       g.slab = p.F(p.slab_off);
-      g.accumulate = first ? 0 : 1;
-      g.bias_grad = b.off != NONE ? p.eng->Gp(b) : nullptr;   // column sums of dY ride along on the matrix pipe
-      if (p.eng->emit_base) { g.Cb = p.eng->emit_base + w.off; g.cb_scale = p.eng->emit_scale; }
       if (crcfg) { g.cfg = crcfg; if (wgroup <= 1) g.splitk = crsplit; }     // (a grouped launch's stragglers keep the 128-row policy's split)
       // knob 29 (experiment): no in-stream barrier for weight gradients whose operands were written on the caller's stream (everything but the
       // prompt-side K | V projection, whose dY the side stream's own dK / dV kernels produce) and that use no shared split-K slab
@@ -356,21 +356,15 @@ struct LinearOp : Op {
       else CHK(on_side(p, st, [&](hipStream_t s2) -> int { return launch_gemm(g, s2); }));
     }
     if (x->need_grad) {
-      GemmP g;
-      gemm_defaults(&g);
-      g.form = GEMM_NN;
-      g.A = dy; g.B = p.eng->Wp(w); g.C = p.GP(dx.out);
-      g.M = M; g.N = K; g.K = N;
-      g.lda = y->ld(); g.ldb = K; g.ldc = x->ld();
-      if (gu) { g.geglu = 2; g.geglu_group = ggroup; g.aux = p.P(gu); g.ldaux = gu->ld(); g.ldc = gu->ld(); }
-      else if (dx.addend != NONE) { g.resid = p.GP(dx.addend); g.ldr = x->ld(); }
+      GemmP g = linear_dgrad_problem(dy, y->ld(), p.eng->Wp(w), p.GP(dx.out), x->ld(), M, K, N, !gu && dx.addend != NONE ? p.GP(dx.addend) : nullptr, x->ld());
+      if (gu) gemm_attach_geglu_bwd(g, ggroup, p.P(gu), gu->ld());
       if (dsplit > 1) { g.splitk = dsplit; g.slab = p.F(p.slab_main_off); }
       g.prio = KNOB(0);
       if (KNOB(6) > 0 && !gu && (KNOB(8) <= 0 || N >= KNOB(8))) g.cfg = KNOB(6);     // experiment: configuration of the linear dgrads
       if (KNOB(22) > 0 && gu) g.cfg = KNOB(22);     // experiment: configuration of the GEGLU (FF2) dgrad
-      // (last: the epilogue that writes Delta exists on the 128 x 128 tiles of the 4-wave kernel only)
-      if (delta_on) { attn_delta_target(delta_attn, p, g); g.cfg = 1; }
-      if (ln_mode) { ln_fuse_target(ln_src, p, g, ln_mode); g.cfg = 0; g.resid = nullptr; }
+      // (last: the attached epilogues override the configuration -- Delta forces cfg 1; the LayerNorm backward cfg 0 and no resid)
+      if (delta_on) attn_delta_target(delta_attn, p, g);
+      if (ln_mode) ln_fuse_target(ln_src, p, g, ln_mode);
       CHK(launch_gemm(g, st));
     }
     return 0;
@@ -468,34 +462,32 @@ struct ConvOp : Op {
     const long Mo = (long)Bn * Ho * Wo;
     if (resid && !resid_alias) CHK(launch_add(p.GP(dres.addend), dy, p.GP(dres.out), Mo * Cout, st));
     const bool upw = up2() && up_wg && KNOB(2) != 128;       // (knob 2 = 128: weight gradient on the upsampled image, A/B runs)
+    const WgradDst wd = wgrad_dst(p, w, b, first);
     if (up2()) CHK(launch_pixel_shuffle2(dy, (bf16*)p.F(planar_off), Bn, H / 2, W / 2, Cout, 0, st));      // dy in its four phases: dgrad and weight gradient read it
     if (p.eng->frozen(w, b)) {      // frozen: no weight gradient, no bias gradient (the dgrad side below is the same)
     } else
 #ifdef SDXL_DIAG
     if (s2x_off != NONE && KNOB(2) == 512) {
       CHK(on_side(p, st, [&](hipStream_t s2) -> int {
-        return launch_conv3x3_s2_wgrad(dy, (const bf16*)p.F(s2x_off), p.eng->Gp(w), p.eng->Gp(b), p.eng->emit_base ? p.eng->emit_base + w.off : nullptr,
-                                       p.eng->emit_scale, first ? 0 : 1, Bn, H, W, Cin, Cout, splitk, p.F(p.slab_off), s2);
+        return launch_conv3x3_s2_wgrad(dy, (const bf16*)p.F(s2x_off), wd.C, wd.bias_grad, wd.Cb, wd.cb_scale, wd.accumulate, Bn, H, W, Cin, Cout, splitk,
+                                       p.F(p.slab_off), s2);
       }));
     } else
 #endif
     if (upw) {
       CHK(on_side(p, st, [&](hipStream_t s2) -> int {
         // (bias gradient: the four phase planes would add in launch order -- a fixed-order column sum of dy instead, 10 - 20 us on this stream)
-        CHK(launch_colsum_f32_batched(dy, p.eng->Gp(b), 1, (int)Mo, Cout, Cout, 0, p.F(cs_part_off), s2));
-        return launch_upconv3x3_wgrad((const bf16*)p.F(planar_off), p.P(x_low), p.F(dweff_off), p.eng->Gp(w), nullptr,
-                                      p.eng->emit_base ? p.eng->emit_base + w.off : nullptr, p.eng->emit_scale, first ? 0 : 1, Bn, H / 2, W / 2,
-                                      Cin, Cout, up_ws, p.F(p.slab_off), s2);
+        CHK(launch_colsum_f32_batched(dy, wd.bias_grad, 1, (int)Mo, Cout, Cout, 0, p.F(cs_part_off), s2));
+        return launch_upconv3x3_wgrad((const bf16*)p.F(planar_off), p.P(x_low), p.F(dweff_off), wd.C, nullptr, wd.Cb, wd.cb_scale, wd.accumulate, Bn, H / 2,
+                                      W / 2, Cin, Cout, up_ws, p.F(p.slab_off), s2);
       }));
     } else
     CHK(on_side(p, st, [&](hipStream_t s2) -> int {
       GemmP g = conv3x3_wgrad_problem(Bn, H, W, Cin, Cout, stride);
-      g.A = dy; g.B = p.P(x); g.C = p.eng->Gp(w);
+      g.A = dy; g.B = p.P(x);
+      wd.to(g);
       g.splitk = splitk;
       g.slab = p.F(p.slab_off);
-      g.accumulate = first ? 0 : 1;
-      g.bias_grad = p.eng->Gp(b);
-      if (p.eng->emit_base) { g.Cb = p.eng->emit_base + w.off; g.cb_scale = p.eng->emit_scale; }
       CHK(launch_gemm(g, s2));
       return 0;
     }));
@@ -640,13 +632,9 @@ static bool ln_fuse_plan(LayerNormOp* ln, Plan& p, int mode) {
   return true;
 }
 static void ln_fuse_target(LayerNormOp* ln, Plan& p, GemmP& g, int mode) {
-  g.ln_x = p.P(ln->x); g.ln_ldx = ln->x->ld();
-  g.ln_stats = p.F(ln->stats_off);
-  g.ln_gamma = p.eng->Wp(ln->gm);
-  g.ln_dx = p.GP(ln->dx.out); g.ln_addend = p.GP(ln->dx.addend); g.ln_ldo = ln->x->ld();
-  g.ln_part = p.F(p.ln_part_off);
-  g.ln_epoch = ++p.ln_epoch;
-  if (mode == 1) { g.ln_pcol = p.F(ln->part_off); g.C = nullptr; }      // dy itself is not stored
+  gemm_attach_ln_bwd(g, p.P(ln->x), ln->x->ld(), p.F(ln->stats_off), p.eng->Wp(ln->gm), p.GP(ln->dx.out), p.GP(ln->dx.addend), p.F(p.ln_part_off),
+                     ++p.ln_epoch, mode == 1 ? p.F(ln->part_off) : nullptr);
+  if (mode == 1) g.C = nullptr;      // dy itself is not stored
 }
 
 // self attention: qkv [B*N][3C]; cross attention: q [B*N][C], kv [B*ctx][2C]
@@ -729,9 +717,7 @@ struct AttnOp : Op {
 static bool attn_delta_wanted(const AttnOp* a) { return a->self && a->qsplit <= 1 && a->Nk >= 256 && a->C % 128 == 0 && a->delta_fused; }
 static void attn_set_delta_fused(AttnOp* a, bool on) { a->delta_fused = on; }
 static void attn_delta_target(AttnOp* a, Plan& p, GemmP& g) {
-  g.delta_o = p.P(a->o); g.delta_ldo = a->o->ld();
-  g.delta_out = p.F(a->delta_off);
-  g.delta_nq = a->Nq; g.delta_heads = a->heads;
+  gemm_attach_delta(g, p.P(a->o), a->o->ld(), p.F(a->delta_off), a->Nq, a->heads);
 }
 
 struct SiluOp : Op {

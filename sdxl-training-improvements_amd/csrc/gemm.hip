@@ -1477,7 +1477,7 @@ int gemm_pick_group(int M, int N, int taps, long red, int splitk) {
   const int g = KNOB(37) > 0 ? KNOB(37) : (int)(256 / tiles);      // (knob 37: problems per grouped launch, A/B runs)
   return g < 2 ? 1 : (g > GEMM_MAX_GROUP ? GEMM_MAX_GROUP : g);
 }
-// ---- the plan-time half of the policy, shared by the plan (engine.hip) and the single-kernel entry points (capi.hip): split-K factors ... ----
+// ---- the plan-time half of the policy, shared by the plan (engine.hip) and the single-kernel entry points (hooks.hip): split-K factors ... ----
 int linear_wgrad_splitk(int Mo, int No, long rows) {      // dW [Mo][No] over `rows`: the long-reduction kernel has its own choice
   return wgrad256_policy(Mo, No, rows) ? wgrad256_pick_splitk(Mo, No, rows) : gemm_pick_splitk(Mo, No, 1, rows);
 }
@@ -1524,6 +1524,52 @@ GemmP conv3x3_wgrad_problem(int B, int H, int W, int Cin, int Cout, int stride) 
   g.c_tap_stride = Cin;
   g.out_f32 = 1;
   return g;
+}
+// ---- ... and the three problems of a linear layer y [M][N] = x [M][K] . w [N][K]^T + bias (+ resid), for LinearOp and the hooks alike: operands,
+// shape, leading dimensions (activations may be padded or column slices; the weight is dense) and the epilogue inputs.  The split, the slab, the
+// configuration, accumulate and the launch options stay with the caller; the attachable epilogues follow.
+static GemmP linear_problem(int form, const bf16* A, long lda, const bf16* B, long ldb, void* C, long ldc, int M, int N, int K) {
+  GemmP g;
+  gemm_defaults(&g);
+  g.form = form;
+  g.A = A; g.B = B; g.C = C;
+  g.M = M; g.N = N; g.K = K;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  return g;
+}
+GemmP linear_fwd_problem(const bf16* x, long ldx, const bf16* w, void* y, long ldy, int M, int N, int K, const bf16* bias, const bf16* resid, long ldr) {
+  GemmP g = linear_problem(GEMM_NT, x, ldx, w, K, y, ldy, M, N, K);
+  g.bias = bias;
+  if (resid) { g.resid = resid; g.ldr = ldr; }
+  return g;
+}
+GemmP linear_dgrad_problem(const bf16* dy, long ldy, const bf16* w, void* dx, long ldx, int M, int N, int K, const bf16* addend, long ldr) {      // dx [M][N] = dy [M][K] . w [K][N]
+  GemmP g = linear_problem(GEMM_NN, dy, ldy, w, N, dx, ldx, M, N, K);
+  if (addend) { g.resid = addend; g.ldr = ldr; }
+  return g;
+}
+GemmP linear_wgrad_problem(const bf16* dy, long ldy, const bf16* x, long ldx, float* dw, int Mo, int No, int rows, float* bias_grad) {      // dw [Mo][No] fp32 = dy^T . x over `rows`
+  GemmP g = linear_problem(GEMM_TN, dy, ldy, x, ldx, dw, No, Mo, No, rows);
+  g.out_f32 = 1;
+  g.bias_grad = bias_grad;      // column sums of dY ride along on the matrix pipe
+  return g;
+}
+void gemm_attach_geglu_fwd(GemmP& g, int group, bf16* gact, long ldgact) { g.geglu = 1; g.geglu_group = group; g.aux = gact; g.ldaux = ldgact; }
+void gemm_attach_geglu_bwd(GemmP& g, int group, bf16* u, long ldu) { g.geglu = 2; g.geglu_group = group; g.aux = u; g.ldaux = ldu; g.ldc = ldu; }      // C = dU, as wide as u
+void gemm_attach_delta(GemmP& g, const bf16* o, long ldo, float* delta, int nq, int heads) {
+  g.delta_o = o; g.delta_ldo = ldo; g.delta_out = delta; g.delta_nq = nq; g.delta_heads = heads;
+  g.cfg = 1;      // the epilogue that writes Delta exists on the 128 x 128 tiles of the 4-wave kernel only
+}
+void gemm_attach_ln_bwd(GemmP& g, const bf16* x, long ldx, const float* stats, const bf16* gamma, bf16* dx, const bf16* addend, float* part, int epoch,
+                        float* pcol) {
+  g.ln_x = x; g.ln_ldx = ldx; g.ln_stats = stats; g.ln_gamma = gamma;
+  g.ln_dx = dx; g.ln_addend = addend; g.ln_ldo = ldx;
+  g.ln_part = part; g.ln_epoch = epoch; g.ln_pcol = pcol;
+  g.cfg = 0; g.resid = nullptr;      // the launcher picks gemm_ln_cfg; the addend goes through ln_addend
+}
+void gemm_fill_group(GemmP& g, const GemmP* v, int n) {      // v: n weight gradients of one shape; g = v[0] as a grouped launch
+  g.group = n;
+  for (int i = 0; i < n; ++i) { g.gA[i] = v[i].A; g.gB[i] = v[i].B; g.gC[i] = (float*)v[i].C; g.gbias_grad[i] = v[i].bias_grad; g.gCb[i] = v[i].Cb; }
 }
 void gemm_set_mode(int mode) { g_mode256 = mode & 3; g_force_cfg = mode >> 2; }
 static int launch_gemm_impl(const GemmP& pin, hipStream_t st);

@@ -1,0 +1,527 @@
+// Single-kernel entry points: the test hooks and the experiment ABI of include/sdxlstep_diag.h, and the sdxl_op_* part of include/sdxlstep.h.
+// One launch (or one op's few) on caller buffers; problems come from the same builders the plan uses (kernels.h), scratch from hook_scratch.
+#include "capi.h"
+
+// The hooks' scratch (the engine's is plan workspace): one buffer of the process, at least `bytes` and 256-byte aligned, kept between calls and
+// only ever grown (hipFree waits for the launches that use the old one) -- a repeated call of one shape allocates nothing.  One stream at a
+// time (a later hook reuses the bytes of an earlier one: only stream order keeps them apart); a hook that needs two regions carves them from
+// one request.
+static int hook_scratch(size_t bytes, void** out) {
+  static char* buf = nullptr;
+  static size_t cap = 0;
+  if (bytes > cap) {
+    if (buf) { (void)hipFree(buf); buf = nullptr; cap = 0; }
+    HIP_CHECK_RET(hipMalloc((void**)&buf, bytes));
+    cap = bytes;
+  }
+  *out = buf;
+  return 0;
+}
+static int hook_floats(size_t n, float** out) { return hook_scratch(n * sizeof(float), (void**)out); }      // (split-K slabs, partial sums)
+// the dense problem of sdxl_op_gemm / sdxl_op_gemm_sk / sdxl_debug_gemm_route from the plan's builders: every leading dimension is the row
+// length; `bias` is the fp32 bias gradient of a TN problem
+static int dense_problem(int form, const void* A, const void* B, void* C, int M, int N, int K, const void* bias, const void* resid, int accumulate,
+                         GemmP* g) {
+  const bf16 *a = (const bf16*)A, *b = (const bf16*)B, *r = (const bf16*)resid;
+  ARG_CHECK(form == GEMM_NT || form == GEMM_NN || form == GEMM_TN, "gemm: unknown form %d", form);
+  if (form == GEMM_NT) *g = linear_fwd_problem(a, K, b, C, N, M, N, K, (const bf16*)bias, r, N);
+  else if (form == GEMM_NN) { *g = linear_dgrad_problem(a, K, b, C, N, M, N, K, r, N); g->bias = (const bf16*)bias; }
+  else { *g = linear_wgrad_problem(a, M, b, N, (float*)C, M, N, K, (float*)bias); if (r) { g->resid = r; g->ldr = N; } }
+  g->accumulate = accumulate;
+  return 0;
+}
+
+extern "C" {
+
+// ---- LoRA on caller buffers: the descriptor of one target (the device table of SDXL_DTYPE_LORA holds many) ----
+static int lora_one(int out, int in, int rank, float scale, LoraP& q) {
+  CHK(lora_check_shape("the operand", out, in, rank));
+  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = scale;
+  q.one.out = out; q.one.in = in; q.one.kind = LORA_KIND_PLAIN; q.one.nrows = out;
+  q.tiles_m = lora_tiles_m(out, in); q.tiles_b = lora_tiles_b(out, in); q.tiles_a = lora_tiles_a(out, in);
+  return 0;
+}
+// ... and of one target held in a packed layout: always the kind-aware kernels, also for LORA_KIND_PLAIN
+static int lora_one_layout(int out, int in, int rank, float scale, int kind, int cg, int nrows, LoraP& q) {
+  CHK(lora_one(out, in, rank, scale, q));
+  ARG_CHECK(kind == LORA_KIND_PLAIN || kind == LORA_KIND_CONV3 || kind == LORA_KIND_GEGLU, "lora: kind %d (0 plain rows, 1 3x3 convolution, 2 GEGLU)", kind);
+  ARG_CHECK(nrows >= out && (nrows == out || kind == LORA_KIND_CONV3), "lora: %d native rows for out = %d (only a convolution has padded rows)", nrows, out);
+  if (kind == LORA_KIND_CONV3) ARG_CHECK(cg >= 1 && in == 9 * (long)cg, "lora: a 3x3 convolution with cin = %d has in = 9 cin, not %d", cg, in);
+  if (kind == LORA_KIND_GEGLU) ARG_CHECK(cg >= 1 && out % 2 == 0 && (out / 2) % cg == 0, "lora: GEGLU rows [%d] are not whole groups of %d", out, cg);
+  q.one.kind = kind; q.one.cg = kind == LORA_KIND_PLAIN ? 0 : cg; q.one.nrows = nrows; q.mapped = 1;
+  q.tiles_m = lora_tiles_m(nrows, in);
+  return 0;
+}
+// one body each for merge and project: `layout` = {kind, cg, native rows} of the _layout entry points (the kind-aware kernels, also for kind 0),
+// NULL for the plain ones (q.mapped == 0: the MAPPED = false kernels)
+static int lora_merge_hook(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, const int* layout, void* st) {
+  ARG_CHECK(aligned16(base) && aligned16(A) && aligned16(B) && aligned16(w), "lora_merge: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(layout ? lora_one_layout(out, in, rank, scale, layout[0], layout[1], layout[2], q) : lora_one(out, in, rank, scale, q));
+  q.w = (bf16*)w; q.base = (const bf16*)base; q.a = (const bf16*)A; q.b = (const bf16*)B;
+  return launch_lora_merge(q, (hipStream_t)st);
+}
+static int lora_project_hook(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, const int* layout,
+                             void* st) {
+  ARG_CHECK(aligned16(dw) && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB),
+            "lora_project: every pointer must be 16-byte aligned and non-NULL");
+  LoraP q;
+  CHK(layout ? lora_one_layout(out, in, rank, scale, layout[0], layout[1], layout[2], q) : lora_one(out, in, rank, scale, q));
+  q.dw = dw; q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
+  return launch_lora_project(q, (hipStream_t)st);
+}
+int sdxl_op_lora_merge_layout(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, int kind, int cg,
+                              int native_rows, void* st) {
+  const int layout[3] = {kind, cg, native_rows};
+  return lora_merge_hook(base, A, B, w, out, in, rank, scale, layout, st);
+}
+int sdxl_op_lora_project_layout(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, int kind,
+                                int cg, int native_rows, void* st) {
+  const int layout[3] = {kind, cg, native_rows};
+  return lora_project_hook(dw, A, B, dA, dB, out, in, rank, scale, layout, st);
+}
+int sdxl_op_lora_merge(const void* base, const void* A, const void* B, void* w, int out, int in, int rank, float scale, void* st) {
+  return lora_merge_hook(base, A, B, w, out, in, rank, scale, nullptr, st);
+}
+int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank, float scale, void* st) {
+  return lora_project_hook(dw, A, B, dA, dB, out, in, rank, scale, nullptr, st);
+}
+
+int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out, int in,
+                      int rank, float scale, int accumulate, void* st) {
+  ARG_CHECK(x && dy && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB), "lora_grad: A, B, dA, dB must be 16-byte aligned, x and dy non-NULL");
+  CHK(lora_check_shape("the operand", out, in, rank));
+  ARG_CHECK(isfinite(scale), "lora: scale is not finite");
+  ARG_CHECK(M >= 1 && ldx >= in && ldy >= out, "lora_grad: M = %d, ldx = %ld (in = %d), ldy = %ld (out = %d)", M, ldx, in, ldy, out);
+  LoraGradP q;
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = scale; q.accumulate = accumulate != 0;
+  q.one.out = out; q.one.in = in;
+  q.x = (const bf16*)x; q.ldx = ldx; q.dy = (const bf16*)dy; q.ldy = ldy;
+  q.M = M; q.Mp = lora_grad_mp(M); q.nchunk = lora_grad_chunks(M);
+  q.tiles = lora_grad_tiles(out, in); q.reds = lora_grad_reds(out, in, rank);
+  q.xvec = ((uintptr_t)x % 16 == 0 && ldx % 8 == 0) ? 1 : 0;
+  q.yvec = ((uintptr_t)dy % 16 == 0 && ldy % 8 == 0) ? 1 : 0;
+  q.a = (const bf16*)A; q.b = (const bf16*)B; q.ga = dA; q.gb = dB;
+  // scratch of the hook (the engine's is plan workspace): one buffer of the process, kept between calls and only ever grown (hipFree
+  // waits for the launches that use the old one), so that repeated calls of one shape enqueue three launches and nothing else
+  const size_t tu_bytes = (lora_grad_tu_elems(1, rank, M) * sizeof(bf16) + 255) / 256 * 256;
+  char* scratch;
+  CHK(hook_scratch(tu_bytes + lora_grad_part_floats(out, in, rank, M) * sizeof(float), (void**)&scratch));
+  q.tu = (bf16*)scratch; q.part = (float*)(scratch + tu_bytes);
+  return launch_lora_grad(q, (hipStream_t)st);
+}
+
+int sdxl_op_gemm(int form, const void* A, const void* B, void* C, int M, int N, int K, const void* bias,
+                 const void* resid, int accumulate, int splitk, void* st) {
+  GemmP g;
+  CHK(dense_problem(form, A, B, C, M, N, K, bias, resid, accumulate, &g));
+  if (form == GEMM_TN) g.splitk = splitk <= 0 ? linear_wgrad_splitk(M, N, K) : splitk;     // (<= 0: the plan's choice)
+  else if (splitk > 1) g.splitk = splitk;
+  if (g.splitk > 1) CHK(hook_floats(gemm_slab_floats(M, N, 1, g.splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+
+int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, const void* const* W, const long* ldb, const int* K, float* C, long ldc,
+                       int M, int N, void* st) {
+  ARG_CHECK(n >= 1 && n <= 2 && A && lda && W && ldb && K, "cond_dgrad: 1 or 2 groups, no null array");
+  CondDgradP q;
+  memset(&q, 0, sizeof(q));
+  q.n = n;
+  for (int g = 0; g < n; ++g) { q.A[g] = (const bf16*)A[g]; q.lda[g] = lda[g]; q.W[g] = (const bf16*)W[g]; q.ldb[g] = ldb[g]; q.K[g] = K[g]; }
+  q.C = C; q.ldc = ldc; q.M = M; q.N = N;
+  ARG_CHECK(M >= 1 && N >= 8, "cond_dgrad: M = %d, N = %d", M, N);
+  for (int g = 0; g < n; ++g) ARG_CHECK(K[g] >= 64 && K[g] % 64 == 0, "cond_dgrad: K[%d] = %d must be a positive multiple of 64", g, K[g]);
+  const size_t need = cond_dgrad_slab_floats(n, K, M, N);
+  if (need) CHK(hook_floats(need, &q.slab));
+  return launch_cond_dgrad(q, (hipStream_t)st);
+}
+
+int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off, long* ldb,
+                             int* K) {
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(n_groups && a_ws_byte_off && lda && w_elem_off && ldb && K, "null output");
+  const Plan& p = *h->e.cur;
+  const int n = which == 0 ? p.cond_nkv : 1;
+  ARG_CHECK((which == 0 || which == 1) && g >= 0 && g < n, "cond operands: which = %d, group %d of %d", which, g, n);
+  const Plan::CondSrc& cs = which == 0 ? p.cond_kv[g] : p.cond_add;
+  *n_groups = n; *a_ws_byte_off = cs.dy_off; *lda = cs.lda; *w_elem_off = cs.w.off; *ldb = cs.ldb; *K = cs.K;
+  return 0;
+}
+
+int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, float* const* dw, float* const* dbias, int Mo, int No,
+                        int rows, int accumulate, void* st) {
+  ARG_CHECK(n >= 1 && n <= GEMM_MAX_GROUP, "wgrad group of %d (1..%d)", n, GEMM_MAX_GROUP);
+  GemmP v[GEMM_MAX_GROUP];
+  for (int i = 0; i < n; ++i) v[i] = linear_wgrad_problem((const bf16*)dy[i], Mo, (const bf16*)x[i], No, dw[i], Mo, No, rows, dbias ? dbias[i] : nullptr);
+  GemmP g = v[0];
+  g.accumulate = accumulate;
+  gemm_fill_group(g, v, n);
+  return launch_gemm(g, (hipStream_t)st);
+}
+
+int sdxl_op_conv3x3_fwd(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                        int stride, void* st) {
+  GemmP g = conv3x3_fwd_problem(B, H, W, Cin, Cout, stride);
+  g.A = (const bf16*)x; g.B = (const bf16*)w; g.C = y;
+  g.bias = (const bf16*)bias;
+  g.splitk = conv3x3_fwd_splitk(B, H, W, Cin, Cout, stride);
+  if (g.splitk > 1) CHK(hook_floats(gemm_slab_floats(g.M, Cout, 1, g.splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+// y = conv3x3(upsample2x(x)) and its input gradient without the upsampled image (GemmP::up2); weff [Cout][16][Cin] and planar
+// [4 B H W][Cout] bf16 are scratch of the caller (weff written by the forward, read by the dgrad)
+int sdxl_op_upconv3x3_fwd(const void* x, const void* w, const void* bias, void* weff, void* planar, void* y, int B, int H, int W,
+                          int Cin, int Cout, void* st) {
+  const int Mp = 4 * (int)upconv_plane_rows(B, H, W);
+  int splitk = upconv3x3_fwd_splitk(B, H, W, Cin, Cout);
+  float* slab = nullptr;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(Mp, Cout, 1, splitk), &slab));
+  return launch_upconv3x3_fwd((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)weff, (bf16*)planar, (bf16*)y, B, H, W, Cin, Cout,
+                              splitk, slab, (hipStream_t)st);
+}
+int sdxl_op_upconv3x3_dgrad(const void* dy, const void* weff, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
+                            int Cout, void* st) {
+  int splitk = upconv3x3_dgrad_splitk(B, H, W, Cin, Cout);
+  float* slab = nullptr;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(B * H * W, Cin, 1, splitk), &slab));
+  return launch_upconv3x3_dgrad((const bf16*)dy, (const bf16*)weff, (bf16*)planar, (bf16*)dx, (const bf16*)addend, B, H, W, Cin, Cout, splitk,
+                                slab, 0, (hipStream_t)st);
+}
+#ifdef SDXL_DIAG
+// stride-2 3x3 convolution through the fast gather on the four phase planes of x (GemmP::up2 == 3); xplanar [4 * roundup(B*(H/2)*(W/2), 128)][Cin]
+// bf16: written by _fwd, read by _wgrad
+int sdxl_op_conv3x3_s2_fwd(const void* x, const void* w, const void* bias, void* xplanar, void* y, int B, int H, int W, int Cin, int Cout,
+                           void* st) {
+  return launch_conv3x3_s2_fwd((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)xplanar, (bf16*)y, B, H, W, Cin, Cout, (hipStream_t)st);
+}
+int sdxl_op_conv3x3_s2_wgrad(const void* dy, const void* xplanar, float* dw, float* dbias, int accumulate, int B, int H, int W, int Cin,
+                             int Cout, int splitk, void* st) {
+  float* slab = nullptr;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(Cout, Cin, 9, splitk), &slab));
+  return launch_conv3x3_s2_wgrad((const bf16*)dy, (const bf16*)xplanar, dw, dbias, nullptr, 1.f, accumulate, B, H, W, Cin, Cout, splitk, slab,
+                                 (hipStream_t)st);
+}
+#endif
+// input gradient of the stride-2 3x3 convolution by output phase (GemmP::up2 == 2); planar [4 * roundup(B*(H/2)*(W/2), 128)][Cin] scratch
+int sdxl_op_conv3x3_s2_dgrad(const void* dy, const void* w, void* planar, void* dx, const void* addend, int B, int H, int W, int Cin,
+                             int Cout, void* st) {
+  return launch_conv3x3_s2_dgrad((const bf16*)dy, (const bf16*)w, (bf16*)planar, (bf16*)dx, (const bf16*)addend, B, H, W, Cin, Cout, 0,
+                                 (hipStream_t)st);
+}
+// the weight / bias gradient of the same pair from `planar` as sdxl_op_upconv3x3_dgrad left it (the de-interleaved dy) and the
+// low-resolution x; dweff [Cout][16][Cin] fp32 scratch; dw [Cout][9][Cin] (= or +=), dbias += (may be NULL)
+int sdxl_op_upconv3x3_wgrad(const void* planar, const void* x, float* dweff, float* dw, float* dbias, int accumulate, int B, int H, int W,
+                            int Cin, int Cout, int splitk, void* st) {
+  float* slab = nullptr;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(Cout, Cin, 16, splitk), &slab));
+  return launch_upconv3x3_wgrad((const bf16*)planar, (const bf16*)x, dweff, dw, dbias, nullptr, 1.f, accumulate, B, H, W, Cin, Cout, splitk,
+                                slab, (hipStream_t)st);
+}
+int sdxl_op_conv3x3_dgrad(const void* dy, const void* w, void* dx, int B, int H, int W, int Cin, int Cout, int stride,
+                          void* st) {
+  GemmP g = conv3x3_dgrad_problem(B, H, W, Cin, Cout, stride);
+  g.A = (const bf16*)dy; g.B = (const bf16*)w; g.C = dx;
+  g.splitk = conv3x3_dgrad_splitk(B, H, W, Cin, Cout, stride);
+  if (g.splitk > 1) CHK(hook_floats(gemm_slab_floats(g.M, Cin, 1, g.splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+int sdxl_op_conv3x3_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int Cin, int Cout, int stride,
+                          int splitk, void* st) {
+  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
+  g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
+  g.splitk = splitk; g.accumulate = 1;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+
+int sdxl_op_conv3x3_wgrad2(const void* x, const void* dy, float* dw, float* dbias, int B, int H, int W, int Cin, int Cout, int stride,
+                           int splitk, int accumulate, void* st) {
+  GemmP g = conv3x3_wgrad_problem(B, H, W, Cin, Cout, stride);
+  g.A = (const bf16*)dy; g.B = (const bf16*)x; g.C = dw;
+  g.accumulate = accumulate; g.bias_grad = dbias;
+  if (splitk <= 0) splitk = conv3x3_wgrad_splitk(B, H, W, Cin, Cout, stride);      // the plan's choice
+  g.splitk = splitk;
+  if (splitk > 1) CHK(hook_floats(gemm_slab_floats(Cout, Cin, 9, splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+
+int sdxl_op_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int heads, int Nq,
+                          int Nk, long ldq, long ldk, long ldv, long ldo, void* st) {
+  AttnP a;
+  memset(&a, 0, sizeof(a));
+  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)o; a.LSE = lse;
+  a.B = B; a.H = heads; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+  return launch_attn_fwd(a, (hipStream_t)st);
+}
+int sdxl_op_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                          float* delta, void* dq, void* dk, void* dv, int B, int heads, int Nq, int Nk, long ldq,
+                          long ldk, long ldv, long ldo, void* st) {
+  AttnP a;
+  memset(&a, 0, sizeof(a));
+  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)o; a.LSE = (float*)lse;
+  a.B = B; a.H = heads; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+  a.dO = (const bf16*)d_o; a.lddo = ldo; a.Delta = delta;
+  a.dQ = (bf16*)dq; a.dK = (bf16*)dk; a.dV = (bf16*)dv; a.lddq = ldq; a.lddk = ldk; a.lddv = ldv;
+  a.qsplit = attn_pick_qsplit(B, heads, Nq, Nk);
+  if (a.qsplit > 1) CHK(hook_floats(attn_part_floats(B, heads, Nk, a.qsplit), &a.part));
+  return launch_attn_bwd(a, (hipStream_t)st);
+}
+
+int sdxl_op_groupnorm_fwd(const void* x, void* y, const void* gamma, const void* beta, float* stats, float* ws, int B,
+                          int HW, int C, int G, float eps, int silu, void* st) {
+  return launch_groupnorm_fwd((const bf16*)x, (bf16*)y, (const bf16*)gamma, (const bf16*)beta, stats, ws, B, HW, C, G, eps,
+                              silu, (hipStream_t)st);
+}
+int sdxl_op_groupnorm_bwd(const void* x, const void* dy, const void* gamma, const void* beta, const float* stats, void* dx,
+                          float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int G, int silu, int accumulate,
+                          void* st) {
+  return launch_groupnorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, (const bf16*)beta, stats, (bf16*)dx,
+                              accumulate ? (const bf16*)dx : nullptr, dgamma, dbeta, ws, B, HW, C, G, silu, (hipStream_t)st);
+}
+int sdxl_op_layernorm_fwd(const void* x, void* y, const void* gamma, const void* beta, float* stats, int M, int C,
+                          float eps, void* st) {
+  return launch_layernorm_fwd((const bf16*)x, (bf16*)y, (const bf16*)gamma, (const bf16*)beta, stats, M, C, eps,
+                              (hipStream_t)st);
+}
+int sdxl_op_layernorm_bwd(const void* x, const void* dy, const void* gamma, const float* stats, void* dx, float* dgamma,
+                          float* dbeta, int M, int C, int accumulate, void* st) {
+  if (!dgamma)
+    return launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
+                                accumulate ? (const bf16*)dx : nullptr, nullptr, nullptr, M, C, (hipStream_t)st);
+  ARG_CHECK(dbeta, "layernorm bwd: dgamma and dbeta go together");
+  if (KNOB(10) == 1 || KNOB(10) == 3) {     // (A/B runs) lean dx kernel + parameter gradients as a pass of their own; the plan's default is the one-pass form below
+    CHK(launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
+                             accumulate ? (const bf16*)dx : nullptr, nullptr, nullptr, M, C, (hipStream_t)st));
+    if (KNOB(10) == 3) return launch_layernorm_param_grads((const bf16*)x, (const bf16*)dy, stats, dgamma, dbeta, M, C, (hipStream_t)st);
+    LnRedBatch b;
+    b.n = 1;
+    float* part;
+    CHK(hook_floats(layernorm_bwd_part_floats(M, C), &part));
+    b.e[0].part = part; b.e[0].dgamma = dgamma; b.e[0].dbeta = dbeta; b.e[0].C = C; b.e[0].nblk = layernorm_param_partial_rows(M, C);
+    CHK(launch_layernorm_param_partials((const bf16*)x, (const bf16*)dy, stats, part, M, C, (hipStream_t)st));
+    return launch_ln_param_reduce(b, (hipStream_t)st);
+  }
+  LnRedBatch b;
+  b.n = 1;
+  float* part;
+  CHK(hook_floats(layernorm_bwd_part_floats(M, C), &part));
+  b.e[0].part = part; b.e[0].dgamma = dgamma; b.e[0].dbeta = dbeta; b.e[0].C = C;
+  CHK(launch_layernorm_bwd((const bf16*)x, (const bf16*)dy, (const bf16*)gamma, stats, (bf16*)dx,
+                           accumulate ? (const bf16*)dx : nullptr, part, &b.e[0].nblk, M, C, (hipStream_t)st));
+  return launch_ln_param_reduce(b, (hipStream_t)st);
+}
+int sdxl_op_ff_geglu_fwd(const void* x, const void* w1, const void* b1, void* u, void* g, int M, int K, int C4, int group,
+                         void* st) {
+  GemmP p = linear_fwd_problem((const bf16*)x, K, (const bf16*)w1, u, 2L * C4, M, 2 * C4, K, (const bf16*)b1, nullptr, 0);
+  gemm_attach_geglu_fwd(p, group, (bf16*)g, C4);
+  return launch_gemm(p, (hipStream_t)st);
+}
+int sdxl_op_ff_geglu_bwd(const void* dy, const void* w2, const void* u, void* du, int M, int C, int C4, int group,
+                         void* st) {
+  GemmP p = linear_dgrad_problem((const bf16*)dy, C, (const bf16*)w2, du, C4, M, C4, C, nullptr, 0);
+  gemm_attach_geglu_bwd(p, group, (bf16*)u, 2L * C4);
+  return launch_gemm(p, (hipStream_t)st);
+}
+
+int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in, const void* pred, void* dpred,
+                 float grad_scale, float* out8, int phase, void* st) {
+  ARG_CHECK(lc && b, "null argument");
+  sdxl_loss_config full;
+  CHK(read_loss_config(lc, &full));
+  lc = &full;
+  LossP L;
+  memset(&L, 0, sizeof(L));
+  L.method = lc->method; L.prediction_type = lc->prediction_type; L.use_min_snr = lc->use_min_snr;
+  L.min_snr_gamma = lc->min_snr_gamma; L.use_ztsnr = lc->use_ztsnr;
+  L.B = b->B; L.HW = b->H * b->W; L.C = 4;
+  L.latents = b->latents; L.noise = b->noise; L.sigma = b->sigma_or_t; L.tag_w = b->tag_weights;
+  L.unet_in = (bf16*)unet_in; L.pred = (const bf16*)pred; L.dpred = (bf16*)dpred;
+  L.grad_scale = grad_scale; L.out = out8;
+  CHK(check_loss_ext(lc, b));
+  fill_loss_ext(lc, b, L);
+  // the partial rows of phase 1, and behind them the [B] normaliser that masked_mean's phase 1 leaves for its phase 2
+  if (phase == 1 || (phase == 2 && L.mask && L.mask_norm == 1)) {
+    ARG_CHECK(L.B > 0 && L.HW > 0, "loss: empty batch");
+    CHK(hook_floats(loss_part_floats(L.B, L.HW) + (size_t)L.B, &L.part));
+    L.mnorm = L.part + loss_part_floats(L.B, L.HW);
+  }
+  if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st);
+  if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);
+  if (phase == 2) return launch_loss_bwd(L, (hipStream_t)st);
+  ARG_CHECK(false, "phase %d", phase);
+}
+
+int sdxl_op_sampler_step(float* x, const void* pred, void* x_in, int B, int H, int W, const sdxl_sampler_step* s, void* st) {
+  ARG_CHECK(s, "null argument");
+  ARG_CHECK(B > 0 && H > 0 && W > 0, "sampler: empty batch");
+  sdxl_sampler_step_ext t;      // the caller's struct as far as its flag says it goes, with x set
+  memset(&t, 0, sizeof(t));
+  memcpy(&t, s, (s->init & SDXL_SAMPLER_EXT) ? sizeof(sdxl_sampler_step_ext) : sizeof(sdxl_sampler_step));
+  t.base.x = x;
+  SamplerP q;
+  CHK(fill_sampler(&t.base, s->cfg ? 2 * B : B, H * W, q));      // B = samples here: the images hold 2B rows of HW with cfg
+  q.pred = (const bf16*)pred; q.x_in = (bf16*)x_in;
+  if (!q.init && q.rescale != 0.f) CHK(hook_floats(sampler_part_floats(B, H * W), &q.part));
+  return launch_sampler_step(q, (hipStream_t)st);
+}
+int sdxl_probe_layout(void* out, void* st) { return probe_layout(out, (hipStream_t)st); }
+int sdxl_op_exchange_shadow(void* buf, size_t bytes, int workgroups, int lds_bytes, float busy_us, void* st) {
+  return launch_exchange_shadow(buf, bytes, workgroups, lds_bytes, busy_us, (hipStream_t)st);
+}
+// test hook (include/sdxlstep_diag.h part 1): sdxl_op_gemm's NT / NN forms with explicit leading dimensions (padded activations, as the plan's
+// feed-forward hidden tensors are) and a forced configuration for this launch only (0: the policy)
+int sdxl_op_gemm_ld(int form, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, const void* bias,
+                    const void* resid, long ldr, int cfg, void* st) {
+  ARG_CHECK(form == GEMM_NT || form == GEMM_NN, "gemm_ld: NT / NN only (form %d)", form);
+  GemmP g;
+  if (form == GEMM_NT) g = linear_fwd_problem((const bf16*)A, lda, (const bf16*)B, C, ldc, M, N, K, (const bf16*)bias, (const bf16*)resid, ldr);
+  else { g = linear_dgrad_problem((const bf16*)A, lda, (const bf16*)B, C, ldc, M, N, K, (const bf16*)resid, ldr); g.bias = (const bf16*)bias; }
+  g.ldb = ldb;      // (the hook's weight may have padded rows too)
+  g.cfg = cfg;
+  return launch_gemm(g, (hipStream_t)st);
+}
+// test hook (include/sdxlstep_diag.h part 1): the NN dgrad with the Delta epilogue, as LinearOp::bwd launches it for a self-attention
+// layer's out-projection
+int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const void* o, const void* addend, void* d_o, float* delta, int B, int Nq,
+                               int N, int K, void* st) {
+  ARG_CHECK(dy && w && o && d_o && delta && B > 0 && Nq > 0 && N % 128 == 0 && K % 64 == 0, "linear_dgrad_delta: B=%d Nq=%d N=%d K=%d", B, Nq, N, K);
+  GemmP g = linear_dgrad_problem((const bf16*)dy, K, (const bf16*)w, d_o, N, B * Nq, N, K, (const bf16*)addend, N);
+  gemm_attach_delta(g, (const bf16*)o, N, delta, Nq, N / 64);
+  return launch_gemm(g, (hipStream_t)st);
+}
+// test hook (include/sdxlstep_diag.h part 1): what launch_gemm would run for the problem a launch-log line describes.  The operands gemm_route never
+// looks at are dense and stand on one aligned dummy word; no device is touched.
+int sdxl_debug_gemm_route(const sdxl_gemm_desc* d, sdxl_gemm_route* out) {
+  ARG_CHECK(d && out, "gemm_route: null argument");
+  alignas(16) static float word[4];
+  GemmP g;
+  CHK(dense_problem(d->form, word, word, word, d->M, d->N, d->K, nullptr, nullptr, 0, &g));      // taps == 1: the linear builders' leading dimensions
+  g.taps = d->taps; g.cfg = d->cfg;
+  g.ldb *= d->taps;      // the weight's (NT / NN) or the gathered image's rows hold every tap, and so do the weight gradient's
+  if (d->form == GEMM_TN) g.ldc *= d->taps;
+  g.Hm = d->Hm; g.Wm = d->Wm; g.Hs = d->Hs; g.Ws = d->Ws; g.sm = d->sm; g.sd = d->sd;
+  g.up2 = d->up2;
+  if (d->up2) {      // the planar matrix's rows, from the side of the problem that walks them (GemmP::up2)
+    const int rows = d->form == GEMM_TN ? d->K : d->M;
+    const bool planar = d->up2 == 2 || (d->up2 == 1 && d->form == GEMM_NT);      // four planes of whole images + padding | the pixels themselves
+    ARG_CHECK(d->Hm > 0 && d->Wm > 0, "gemm_route: up2 needs the image size");
+    g.up_plane = planar ? rows / 4 : (int)upconv_plane_rows(1, 1, rows);
+    g.up_rows = planar ? g.up_plane / (d->Hm * d->Wm) * (d->Hm * d->Wm) : rows;
+  }
+  g.geglu = d->geglu; g.geglu_group = d->geglu_group;
+  if (d->geglu) { g.aux = (bf16*)word; g.ldaux = 8; }
+  g.splitk = d->splitk; g.slab = word;
+  if (d->group > 1) {
+    g.group = d->group;
+    for (int i = 0; i < d->group && i < GEMM_MAX_GROUP; ++i) { g.gA[i] = g.gB[i] = (const bf16*)word; g.gC[i] = word; g.gCb[i] = d->emit_bf16 ? (bf16*)word : nullptr; g.gbias_grad[i] = d->bias_grad ? word : nullptr; }
+  } else if (d->emit_bf16) g.Cb = (bf16*)word;
+  if (d->bias_grad) g.bias_grad = word;
+  if (d->delta) { g.delta_out = word; g.delta_o = (const bf16*)word; g.delta_nq = d->M; g.delta_heads = d->N / 64; }
+  GemmRoute r;
+  if (int e = gemm_route_checked(g, &r)) return e;
+  out->kernel = r.kernel; out->cfg = r.cfg; out->fast = r.fast; out->post = r.post;
+  return 0;
+}
+int sdxl_profile_gemm_begin(void) { return gemm_profile_begin(); }
+int sdxl_set_gemm_mode(int mode) {
+  const int cfg = mode >> 2;
+  ARG_CHECK(mode >= 0 && (mode & 3) <= 2 && (cfg == 0 || cfg == 1 || cfg == 2 || cfg == 3 || cfg == 5 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 13 || cfg == 23 || cfg == 43 || cfg == 31 || cfg == 32 || cfg == 33 || cfg == 34 || cfg == 35 || cfg == 36), "gemm mode %d", mode);
+  gemm_set_mode(mode);
+  return 0;
+}
+int sdxl_profile_gemm_end(double* flops, double* ms, int* launches) { return gemm_profile_end(flops, ms, launches); }
+#ifdef SDXL_DIAG     // ---- experiment ABI of the diagnostics build (include/sdxlstep_diag.h): not in the product library ----
+// dY [M][Kr] x W [Kr][N] (the NN dgrad form) with the LayerNorm backward of GemmP::ln_x in the epilogue: dx = LN_bwd(dY W | x, stats, gamma)
+// (+ addend), dy_out (or null) = dY W, pcol (or null) = [cdiv(M, 128)][2][N] dgamma | dbeta partial sums.  The granule scratch is the hooks'
+// (the plan shares its own), zeroed on the stream before the launches; stream-ordered like every other hook.  N <= 1280.
+int sdxl_op_linear_dgrad_ln_bwd(const void* dy, const void* w, const void* x, const float* stats, const void* gamma, const void* addend,
+                                void* dx, void* dy_out, float* pcol, int M, int N, int Kr, void* st) {
+  ARG_CHECK(gemm_ln_cfg(M, N, Kr) != 0, "linear_dgrad_ln_bwd: M=%d N=%d K=%d does not fit the fused epilogue", M, N, Kr);
+  float* part;
+  const size_t pbytes = gemm_ln_part_floats(M, N) * sizeof(float);
+  CHK(hook_scratch(pbytes, (void**)&part));
+  HIP_CHECK_RET(hipMemsetAsync(part, 0, pbytes, (hipStream_t)st));
+  GemmP g = linear_dgrad_problem((const bf16*)dy, Kr, (const bf16*)w, dy_out, N, M, N, Kr, nullptr, 0);
+  for (int epoch = 1; epoch <= 3; ++epoch) {      // three launches on the same scratch: later ones find the earlier epochs' granules
+    gemm_attach_ln_bwd(g, (const bf16*)x, N, stats, (const bf16*)gamma, (bf16*)dx, (const bf16*)addend, part, epoch, pcol);
+    CHK(launch_gemm(g, (hipStream_t)st));
+  }
+  return 0;
+}
+// Knobs are process-global and read at plan-build, forward and backward time: set them BEFORE sdxl_plan / the first step of a handle and
+// leave them alone afterwards (A/B runs restart the process per setting, profiles/tools/ab.sh).
+int sdxl_set_knob(int id, int value) {
+  ARG_CHECK(id >= 0 && id < SDXL_NKNOBS, "knob %d out of range", id);
+  g_knobs[id] = value;
+  if (id == 9) wgrad256_set_enabled(value == 0);         // knob 9 = 1: long-reduction linear weight gradients on the 128 x 160 kernel
+  if (id == 12) conv_wgrad3_set_enabled(value == 0);    // knob 12 = 1: 3x3 weight gradients on the one-tap-per-workgroup kernel only
+  if (id == 15) gemm256_set_tail(value == 0);     // knob 15 = 1: no half-height tail workgroups in the 256 x 256 kernel
+  return 0;
+}
+int sdxl_set_sk_mode(int mode, int workers) {
+  ARG_CHECK(mode >= 0 && mode <= 2 && workers >= 0 && workers <= 256, "stream-K mode %d / workers %d", mode, workers);
+  gemm_set_sk_mode(mode);
+  gemm_sk_set_workers(workers);
+  return 0;
+}
+int sdxl_op_pl_prefetch_b(int form, const void* B, int M, int N, int K, long ldb, int parts, void* st) {
+  GemmP p;
+  gemm_defaults(&p);
+  p.form = form; p.B = (const bf16*)B; p.M = M; p.N = N; p.K = K; p.ldb = ldb;
+  return launch_pl_prefetch_b(p, parts, (hipStream_t)st);
+}
+int sdxl_ln_error(unsigned* out) {
+  ARG_CHECK(out != nullptr, "ln_error: null output");
+  return gemm_ln_error(out);
+}
+int sdxl_sk_error(void* st, unsigned* out) {
+  ARG_CHECK(out, "null output");
+  return gemm_sk_error((hipStream_t)st, out);
+}
+int sdxl_op_gemm_sk(int n, const int* form, const void* const* A, const void* const* B, void* const* C, const int* M, const int* N,
+                    const int* K, const void* const* bias, const void* const* resid, const int* accumulate, void* st) {
+  ARG_CHECK(n >= 1 && n <= 4 && form && A && B && C && M && N && K, "gemm_sk: bad arguments");
+  GemmP g[4];
+  for (int i = 0; i < n; ++i) {
+    CHK(dense_problem(form[i], A[i], B[i], C[i], M[i], N[i], K[i], bias ? bias[i] : nullptr, resid ? resid[i] : nullptr, accumulate ? accumulate[i] : 0, &g[i]));
+  }
+  return launch_gemm_multi(g, n, (hipStream_t)st);
+}
+#endif   // SDXL_DIAG
+
+// debug: order-independent checksum (sum of raw 16-bit patterns) of every activation of the current plan, in
+// creation order.  Synchronises.  Used to localise run-to-run differences.
+__global__ void checksum_kernel(const unsigned short* __restrict__ x, long n, unsigned long long* out) {
+  unsigned long long s = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    s += (unsigned long long)x[i] * (unsigned long long)((i % 251) + 1);
+  atomicAdd(out, s);
+}
+int sdxl_debug_act_checksums(sdxl_handle* h, unsigned long long* out_host, int cap, int* n_out, int grads) {
+  H_CHECK(h);
+  CHK(ready(h->e));
+  Plan& p = *h->e.cur;
+  int n = (int)p.acts.size();
+  if (n_out) *n_out = n;
+  if (n > cap) n = cap;
+  unsigned long long* d;
+  HIP_CHECK_RET(hipDeviceSynchronize());      // the hooks' scratch is used on the null stream here: no hook of another stream may still be running on it
+  CHK(hook_scratch(sizeof(unsigned long long) * (n > 0 ? n : 1), (void**)&d));
+  HIP_CHECK_RET(hipMemset(d, 0, sizeof(unsigned long long) * (n > 0 ? n : 1)));
+  for (int i = 0; i < n; ++i) {
+    Act* a = p.acts[i].get();
+    const bf16* src = grads ? p.G(a) : p.P(a);
+    if (!src || a->parent) continue;     // (column-slice views are covered by their parent)
+    long cnt = a->rows * a->cols;
+    hipLaunchKernelGGL(checksum_kernel, dim3(64), dim3(256), 0, 0, (const unsigned short*)src, cnt, d + i);
+  }
+  HIP_CHECK_RET(hipDeviceSynchronize());
+  HIP_CHECK_RET(hipMemcpy(out_host, d, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"

@@ -215,6 +215,18 @@ int upconv3x3_dgrad_splitk(int B, int H, int W, int Cin, int Cout);
 GemmP conv3x3_fwd_problem(int B, int H, int W, int Cin, int Cout, int stride);
 GemmP conv3x3_dgrad_problem(int B, int H, int W, int Cin, int Cout, int stride);
 GemmP conv3x3_wgrad_problem(int B, int H, int W, int Cin, int Cout, int stride);
+// ... and a linear layer's three problems (w [N][K] dense; ld*: row strides of the activations), the epilogues that attach to them and the grouped
+// weight gradient: the one place a GemmP of the linear family is assembled (LinearOp and the single-kernel entry points call these).  Pure: no
+// HIP call, no policy -- split-K, slab, group size, cfg and accumulate are the caller's.
+GemmP linear_fwd_problem(const bf16* x, long ldx, const bf16* w, void* y, long ldy, int M, int N, int K, const bf16* bias, const bf16* resid, long ldr);
+GemmP linear_dgrad_problem(const bf16* dy, long ldy, const bf16* w, void* dx, long ldx, int M, int N, int K, const bf16* addend, long ldr);      // dx [M][N] = dy [M][K] . w [K][N]
+GemmP linear_wgrad_problem(const bf16* dy, long ldy, const bf16* x, long ldx, float* dw, int Mo, int No, int rows, float* bias_grad);      // dw [Mo][No] = dy [rows][Mo]^T . x [rows][No]
+void gemm_attach_geglu_fwd(GemmP& g, int group, bf16* gact, long ldgact);      // GemmP::geglu == 1
+void gemm_attach_geglu_bwd(GemmP& g, int group, bf16* u, long ldu);            // GemmP::geglu == 2: also ldc = ldu
+void gemm_attach_delta(GemmP& g, const bf16* o, long ldo, float* delta, int nq, int heads);      // GemmP::delta_out: also cfg = 1
+void gemm_attach_ln_bwd(GemmP& g, const bf16* x, long ldx, const float* stats, const bf16* gamma, bf16* dx, const bf16* addend, float* part, int epoch,
+                        float* pcol);      // GemmP::ln_x: also cfg = 0 and no resid
+void gemm_fill_group(GemmP& g, const GemmP* v, int n);      // GemmP::group: g (= v[0]) launches the n problems of v in one grid
 int launch_gemm256(const GemmP& p, hipStream_t st);
 void gemm256_set_tail(bool on);     // half-height workgroups for the last partial round (default on; A/B runs)
 #ifdef SDXL_DIAG
