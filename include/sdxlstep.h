@@ -27,7 +27,7 @@ typedef struct sdxl_handle sdxl_handle;
 /* UNet2DConditionModel config (the fields of diffusers' unet/config.json that determine the arithmetic;
  * loaded by the reference at models/sdxl.py:25-40). */
 typedef struct {
-  int in_channels, out_channels;       /* 4, 4 */
+  int in_channels, out_channels;       /* 4, 4; in_channels 4 .. 16 (extra input channels, below), out_channels 4 only */
   int block_out_channels[3];           /* 320, 640, 1280 */
   int layers_per_block;                /* 2 */
   int transformer_layers[3];           /* 0, 2, 10 */
@@ -83,7 +83,8 @@ typedef struct {
  *   F       = guidance_rescale * (F * std(F_c) / std(F)) + (1 - guidance_rescale) * F      per sample over C.H.W; skipped when 0
  *   den     = a_skip * x + a_out * F
  *   x       = p * x + q * den                                                              the state, in place
- *   input   = bf16(clamp(a_in_next * x, +-clamp))                                          clamp <= 0: none; channels 4..7 zero
+ *   input   = bf16(clamp(a_in_next * x, +-clamp))                                          clamp <= 0: none; channels 4.. zero, or
+ *                                                                                          bf16(input_cond) (sdxl_batch_cond)
  * fp32, every operation rounded on its own in this order (no FMA), the rescale sums in a fixed order: bitwise reproducible.  The scalars
  * are the caller's (sampler.py derives them for the trained ddpm denoiser, the reference's Karras scalings and flow matching).
  * The struct sdxl_sampler_step_ext below appends the terms of the second-order and stochastic solvers and of inpainting. */
@@ -174,6 +175,32 @@ typedef struct {
   float* d_pooled;             /* optional OUT [B,pooled_dim] fp32; NULL = none */
 } sdxl_batch_ext;
 #define SDXL_BATCH_EXT 0x10000   /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_ext */
+
+/* Extra input channels: a UNet whose conv_in reads more than the 4 latent channels (sdxl_unet_config.in_channels 5 .. 16: the inpainting
+ * UNet has 9 = latents | mask | masked-image latents, the InstructPix2Pix one 8 = latents | source-image latents).  Channels 0..3 of the
+ * UNet input stay what the loss preparation / the sampler step build from the latents; channels 4 .. in_channels - 1 are the caller's
+ * `input_cond`, rounded to bf16 (nearest even) and concatenated behind them in the given order (diffusers' channel order is the caller's).
+ * The batch that carries it is sdxl_batch_ext with the fields below appended (`base` IS that struct), passed as a sdxl_batch* with
+ * SDXL_BATCH_COND or-ed into base.base.ctx_len: the flag says that the struct passed is this one, so its d_prompt_embeds / d_pooled are
+ * read as well (they may be NULL) and SDXL_BATCH_EXT need not be set beside it.  Nothing behind `sampler` is read without a flag.
+ * A pixel of the plan's input buffer is stored Cs = 8 channels wide for in_channels <= 8, else 16 ([B*H*W][Cs] bf16, the channels past
+ * in_channels zero), and conv_in as [cout][9][Cs] with zero pad channels; callers only ever see [cout, in_channels, 3, 3]
+ * (sdxl_load_weight, sdxl_export_weight, sdxl_export_grad, sdxl_param_info).  input_cond is read by the loss preparation / the sampler
+ * step only: the backward never reads it (conv_in has no input gradient, and there is no gradient with respect to input_cond).  In graph
+ * mode it is staged inside the plan like the latents, and whether it is present is part of the capture key.
+ * sdxl_forward_loss, sdxl_loss_fwd_bwd, sdxl_op_loss phase 0 and a sampler step (sdxl_unet_forward with `sampler`, init included) read
+ * it; with cfg the plan's batch is 2B and row b of input_cond goes to the conditional half, row b + B to the unconditional one.
+ * sdxl_unet_forward without `sampler` ignores it: the caller's sample already carries every channel ([B*H*W][Cs]).
+ * cond_channels: 0 = in_channels - 4 of the handle; any other value must equal it.  sdxl_op_loss has no handle: there cond_channels IS
+ * the number of extra channels (0 .. 12; unet_in is then [B*H*W][Cs] for in_channels = 4 + cond_channels).
+ * Bad arguments (1, before any launch, the message names input_cond): in_channels > 4 (sdxl_op_loss: cond_channels > 0) without a
+ * non-NULL input_cond on one of the readers above; in_channels == 4 with a non-NULL input_cond; a cond_channels that does not match. */
+typedef struct {
+  sdxl_batch_ext base;
+  const float* input_cond;     /* device [Bplan, in_channels - 4, H, W] fp32 NCHW; NULL = none */
+  int cond_channels;           /* 0, or in_channels - 4 (above) */
+} sdxl_batch_cond;
+#define SDXL_BATCH_COND 0x20000  /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_cond */
 
 SDXL_API const char* sdxl_last_error(void);
 SDXL_API int sdxl_version(void);
@@ -310,14 +337,14 @@ SDXL_API int sdxl_loss_fwd_bwd(sdxl_handle* h, const sdxl_loss_config* lc, const
 SDXL_API int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* stream);
 /* hipGraph replay of forward / backward (default OFF: measured slower than eager two-stream launches on ROCm 7.2, see
  * DESIGN.md): the second call with a given (plan, loss configuration including loss_type / huber_c and which per-sample arrays are
- * present, the loss mask / noise_in and mask_norm, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
+ * present, the loss mask / noise_in and mask_norm, whether input_cond is present, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
  * kernel by kernel.  Inputs are staged at fixed addresses inside the plan, so the caller's tensors may move between steps. */
 SDXL_API int sdxl_set_graph_mode(sdxl_handle* h, int on);
 /* synchronises `stream`; out[0]=loss out[1]=sum s*w*l(pred-target) (s = 1, l = square unless set otherwise) out[2]=sum|pred| out[3]=sum pred^2
  * out[4]=sum|noise| out[5]=sum noise^2 (x0) out[6]=sum latents^2 (x1) out[7]=gradient gate */
 SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
 
-/* UNet only: sample_nhwc8 [B*H*W][8] bf16 in (channels 4..7 ignored) -> pred [B*H*W][8] bf16 out.
+/* UNet only: sample_nhwc8 [B*H*W][Cs] bf16 in (Cs = 8, or 16 with in_channels > 8; channels past in_channels ignored) -> pred [B*H*W][8] bf16 out.
  * (replaces unet(sample, t, ehs, added_cond_kwargs).sample, ddpm_trainer.py:320-325) */
 /* With cond->sampler set, sample_nhwc8 and pred_nhwc8 must be NULL: the call uploads the conditioning, runs the forward on what the
  * plan's input buffer holds (B, or 2B = [cond; uncond] with cfg: both halves hold the same latent), then the step kernel, which leaves
@@ -417,6 +444,7 @@ SDXL_API int sdxl_op_ff_geglu_bwd(const void* dy, const void* w2, const void* u,
  * noise_in only: the mask, mask_norm and that scratch are nothing to it. */
 SDXL_API int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in, const void* pred, void* dpred,
                  float grad_scale, float* out8_dev, int phase /*0 prepare,1 loss,2 dpred*/, void* stream);
+/* (phase 0 with a sdxl_batch_cond: unet_in is [B*H*W][Cs] for 4 + cond_channels input channels; phases 1 and 2 ignore input_cond) */
 /* ---- row f1: fused AdamW_BF16 step (replaces AdamWBF16.step / _make_step,
  * reference src/training/optimizers/adamw_bfloat16/__init__.py:87-197 and stochastic/__init__.py:46-124).
  * One launch over flat arrays (the packed weight / gradient arenas, or any 16-byte aligned slice of them):

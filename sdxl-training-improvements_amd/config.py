@@ -85,6 +85,11 @@ class TrainingConfig:                    # data/config.py:152-168
     noise_offset: float = 0.0            # >= 0: noise += noise_offset * randn(B,4,1,1); the target uses the offset noise (diffusers)
     input_perturbation: float = 0.0      # >= 0: the UNet input is built from noise + gamma * randn(B,4,H,W), the target from noise
     cond_dropout_prob: float = 0.0       # in [0,1]: per sample, prompt_embeds / pooled_prompt_embeds zeroed on a copy (time_ids kept)
+    # build-only keys: extra UNet input channels (model in_channels > 4; trainer.py::NativeSDXLTrainer._input_cond): what fills channels 4..
+    input_conditioning: str = "none"     # "none" (in_channels 4) | "inpaint" (9): cat(batch["inpaint_mask"] [B,1,H,W] / [B,H,W],
+                                         # batch["masked_latents"] [B,4,H,W]), diffusers' channel order | "concat": batch["cond_latents"]
+                                         # [B, in_channels - 4, H, W] (InstructPix2Pix: the source-image latents, in_channels 8)
+    input_cond_dropout_prob: float = 0.0 # in [0,1]: per sample, the extra channels zeroed on a copy (training only; drawn after every other draw)
     # build-only key: conditioning gradients (csrc/cond_dgrad.hip).  "auto": a batch["prompt_embeds"] / batch["pooled_prompt_embeds"] that
     # requires grad gets d loss / d itself back through compute_loss(...)["loss"].backward() (text encoders, textual inversion); "off": never
     conditioning_grads: str = "auto"

@@ -84,6 +84,16 @@ static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
   return 0;
 }
 
+// sdxl_batch_cond's two fields (extra UNet input channels), read only behind SDXL_BATCH_COND: a caller without the flag passes a shorter
+// struct.  SDXL_BATCH_FLAGS: what the flags leave of ctx_len; either flag says that sdxl_batch_ext's fields are there.
+#define SDXL_BATCH_FLAGS (SDXL_BATCH_EXT | SDXL_BATCH_COND)
+static void read_input_cond(const sdxl_batch* b, const float** cond, int* channels) {
+  *cond = nullptr; *channels = 0;
+  if (!(b->ctx_len & SDXL_BATCH_COND)) return;
+  const sdxl_batch_cond* x = (const sdxl_batch_cond*)b;
+  *cond = x->input_cond; *channels = x->cond_channels;
+}
+
 // sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters.  The caller's struct
 // ends at guidance_rescale unless init carries SDXL_SAMPLER_EXT: nothing behind it is read without the flag.
 static int fill_sampler(const sdxl_sampler_step* s, int image_batch, int HW, SamplerP& q) {

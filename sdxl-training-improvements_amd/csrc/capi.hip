@@ -22,7 +22,8 @@ int sdxl_default_config(sdxl_unet_config* c) {
 int sdxl_create(const sdxl_unet_config* cfg, int device, sdxl_handle** out) {
   ARG_CHECK(cfg && out, "null argument");
   ARG_CHECK(cfg->head_dim == 64, "head_dim must be 64 (got %d)", cfg->head_dim);
-  ARG_CHECK(cfg->in_channels == 4 && cfg->out_channels == 4, "in/out channels must be 4");
+  ARG_CHECK(cfg->in_channels >= 4 && cfg->in_channels <= 16, "in_channels must be 4 .. 16 (got %d)", cfg->in_channels);
+  ARG_CHECK(cfg->out_channels == 4, "out_channels must be 4 (got %d)", cfg->out_channels);
   ARG_CHECK(cfg->transformer_layers[0] == 0, "level 0 must not have attention");
   for (int i = 0; i < 3; ++i) {
     int c = cfg->block_out_channels[i];
@@ -397,7 +398,7 @@ int sdxl_zero_grads(sdxl_handle* h, void* st) {
 static int check_batch(Engine& e, const sdxl_batch* b) {
   Plan& p = *e.cur;
   ARG_CHECK(b, "null batch");
-  const int ctx = b->ctx_len & ~SDXL_BATCH_EXT;
+  const int ctx = b->ctx_len & ~SDXL_BATCH_FLAGS;
   ARG_CHECK(b->B == p.B && b->H == p.H && b->W == p.W && ctx == p.ctx,
             "batch shape (B=%d,H=%d,W=%d,ctx=%d) does not match the current plan (B=%d,H=%d,W=%d,ctx=%d)", b->B, b->H,
             b->W, ctx, p.B, p.H, p.W, p.ctx);
@@ -408,14 +409,14 @@ static int check_batch(Engine& e, const sdxl_batch* b) {
 // The conditioning-gradient request of a micro-step: sdxl_batch_ext's two fields, read only behind SDXL_BATCH_EXT (a caller without the
 // flag passes a shorter struct).  The one error that needs no plan comes first, before the handle is looked at or anything is launched.
 static int check_cond_request(const sdxl_batch* b) {
-  if (!b || !(b->ctx_len & SDXL_BATCH_EXT)) return 0;
+  if (!b || !(b->ctx_len & SDXL_BATCH_FLAGS)) return 0;
   const sdxl_batch_ext* x = (const sdxl_batch_ext*)b;
   ARG_CHECK(!(b->sampler && (x->d_prompt_embeds || x->d_pooled)), "d_prompt_embeds / d_pooled cannot be combined with a sampler step");
   return 0;
 }
 static int read_cond_request(Engine& e, const sdxl_batch* b, float** d_ehs, float** d_pool) {
   *d_ehs = *d_pool = nullptr;
-  if (!(b->ctx_len & SDXL_BATCH_EXT)) return 0;
+  if (!(b->ctx_len & SDXL_BATCH_FLAGS)) return 0;
   const sdxl_batch_ext* x = (const sdxl_batch_ext*)b;
   if (x->d_prompt_embeds) {
     for (int g = 0; g < e.cur->cond_nkv; ++g)
@@ -423,6 +424,17 @@ static int read_cond_request(Engine& e, const sdxl_batch* b, float** d_ehs, floa
   }
   if (x->d_pooled) ARG_CHECK(e.cur->cond_add.K >= 64 && e.cur->cond_add.K % 64 == 0, "d_pooled: time-embedding width %d is not a multiple of 64", e.cur->cond_add.K);
   *d_ehs = x->d_prompt_embeds; *d_pool = x->d_pooled;
+  return 0;
+}
+// The extra input channels of a batch (sdxl_batch_cond) against the handle's in_channels, before anything is copied or launched.
+// reader: this call builds the UNet input itself (loss preparation, sampler step), so in_channels > 4 needs the array.
+static int check_input_cond(const Engine& e, const sdxl_batch* b, bool reader, const float** cond) {
+  const int n = e.cfg.in_channels - 4;
+  int ch;
+  read_input_cond(b, cond, &ch);
+  ARG_CHECK(n > 0 || !*cond, "input_cond must be NULL: the UNet has in_channels = 4");
+  ARG_CHECK(ch == 0 || ch == n, "input_cond: cond_channels %d does not match in_channels - 4 = %d", ch, n);
+  ARG_CHECK(n == 0 || !reader || *cond, "input_cond is missing: the UNet has in_channels = %d, channels 4.. of its input come from input_cond", e.cfg.in_channels);
   return 0;
 }
 // which of them the backward of this micro-step produces: part of the capture key of its graphs (the launch sequence differs)
@@ -560,6 +572,8 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   CHK(read_loss_config(lc, &full));
   lc = &full;
   CHK(check_loss_ext(lc, b));
+  const float* icond;
+  CHK(check_input_cond(e, b, true, &icond));
   float *d_ehs, *d_pool;
   CHK(read_cond_request(e, b, &d_ehs, &d_pool));
   CHK(upload_cond(e, b, st));
@@ -593,14 +607,20 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
       HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_nin_off), full.noise_in, nlat, hipMemcpyDeviceToDevice, st));
       full.noise_in = p.F(p.in_nin_off);
     }
+    if (icond) {
+      HIP_CHECK_RET(hipMemcpyAsync(p.F(p.in_cond_off), icond, sizeof(float) * (size_t)p.B * (e.cfg.in_channels - 4) * p.H * p.W, hipMemcpyDeviceToDevice, st));
+      icond = p.F(p.in_cond_off);
+    }
   }
   // the per-sample losses are produced inside the plan (a fixed address for a captured graph) and copied out below
   if (b->per_sample_loss) sb.per_sample_loss = p.F(p.ps_loss_off);
   LossP L;
   fill_loss(e, lc, &sb, 1.f, L);
-  Engine::GraphKey key{&p, 0, 0, 0, 0, 0u, loss_cfg_bits(*lc, b->tag_weights != nullptr), loss_cfg_bits2(*lc, *b), loss_huber_bits(*lc, *b)};
+  const int ncond = icond ? e.cfg.in_channels - 4 : 0;      // (the preparation only: the backward never reads input_cond)
+  Engine::GraphKey key{&p, 0, 0, 0, 0, 0u, loss_cfg_bits(*lc, b->tag_weights != nullptr), loss_cfg_bits2(*lc, *b) | ((unsigned)(icond != nullptr) << 10),
+                      loss_huber_bits(*lc, *b)};
   CHK(run_graphed(e, key, st, [&](hipStream_t s) -> int {
-    CHK(launch_loss_prepare(L, s));
+    CHK(launch_loss_prepare(L, s, icond, ncond));
     CHK(run_forward_ops(e, s));
     CHK(launch_loss_fwd(L, s));
     return 0;
@@ -758,6 +778,8 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   CHK(ready(e));
   CHK(check_batch(e, cond));
   Plan& p = *e.cur;
+  const float* icond;
+  CHK(check_input_cond(e, cond, cond->sampler != nullptr, &icond));
   float *d_ehs, *d_pool;
   CHK(read_cond_request(e, cond, &d_ehs, &d_pool));
   if (cond->sampler) {      // a sampling step: the forward runs on what the plan's input buffer holds, the step kernel writes the next input there
@@ -769,15 +791,15 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
       CHK(upload_cond(e, cond, st));
       CHK(run_forward_ops(e, st));
     }
-    return launch_sampler_step(q, st);
+    return launch_sampler_step(q, st, icond, icond ? e.cfg.in_channels - 4 : 0);
   }
   CHK(upload_cond(e, cond, st));
   h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
   h->step.awaiting_bwd = false;      // (this forward replaced the loss step's activations: nothing waits for that backward any more)
-  size_t bytes = (size_t)p.B * p.H * p.W * 8 * sizeof(bf16);
-  HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, bytes, hipMemcpyDeviceToDevice, st));
+  const size_t rows = (size_t)p.B * p.H * p.W;      // (input_cond is not read here: the caller's sample carries every channel)
+  HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, rows * input_cs(e.cfg.in_channels) * sizeof(bf16), hipMemcpyDeviceToDevice, st));
   CHK(run_forward_ops(e, st));
-  if (pred) HIP_CHECK_RET(hipMemcpyAsync(pred, p.P(p.pred), bytes, hipMemcpyDeviceToDevice, st));
+  if (pred) HIP_CHECK_RET(hipMemcpyAsync(pred, p.P(p.pred), rows * 8 * sizeof(bf16), hipMemcpyDeviceToDevice, st));
   return 0;
 }
 

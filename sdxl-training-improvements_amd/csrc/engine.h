@@ -82,6 +82,7 @@ struct Plan {
   size_t in_sw_off = NONE, in_hc_off = NONE;   // ... of the optional per-sample weights and per-sample Huber c ([B] each)
   size_t ps_loss_off = NONE;                   // [B] per-sample losses, copied to the caller's pointer after the loss kernels
   size_t in_mask_off = NONE, in_nin_off = NONE; // staged copies of the optional loss mask [B*H*W] and input noise [B*4*H*W]
+  size_t in_cond_off = NONE;                   // staged copy of the extra input channels [B][in_channels - 4][H*W] (in_channels > 4 only)
   size_t mask_norm_off = NONE;                 // [B] masked_mean normaliser M_b: loss_finalize_kernel -> loss_bwd_kernel
   size_t samp_part_off = NONE;                 // sampler_part_floats(B, HW): the guidance-rescale partial sums of a sampler step
   size_t gn_ws_off = NONE, gn_ws_floats = 0;  // GroupNorm scratch shared by all (stream-ordered) norm ops

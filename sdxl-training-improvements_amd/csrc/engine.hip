@@ -1017,7 +1017,7 @@ struct Builder {
     const int add_in = c.pooled_dim + 6 * c.addition_time_embed_dim;
     Act *x_in = nullptr, *ehs = nullptr, *te_sin = nullptr, *aug_in = nullptr;
     if (pl) {
-      pl->x_in = x_in = pl->new_act((long)B * H * W, 8, false);
+      pl->x_in = x_in = pl->new_act((long)B * H * W, input_cs(c.in_channels), false);
       pl->ehs = ehs = pl->new_act((long)B * ctx, c.cross_attention_dim, false, kv_pad_rows(B, ctx));
       pl->te_sin = te_sin = pl->new_act(B, ch[0], false);
       pl->tid_emb = pl->new_act((long)B * 6, c.addition_time_embed_dim, false);
@@ -1114,7 +1114,7 @@ struct Builder {
       op->dy32_off = pl->tp32_off;
     }
 
-    Act* x = conv("conv_in", x_in, H, W, 8, ch[0], 1, nullptr, nullptr, c.in_channels, ch[0]);
+    Act* x = conv("conv_in", x_in, H, W, input_cs(c.in_channels), ch[0], 1, nullptr, nullptr, c.in_channels, ch[0]);
     struct Skip { Act* a; int c; };
     std::vector<Skip> skips;
     skips.push_back({x, ch[0]});
@@ -1250,6 +1250,8 @@ void Engine::build(Plan* plan) {
       if (slab2 > slab) slab = slab2;
       plan->cond_slab_off = plan->alloc(sizeof(float) * (slab ? slab : 4));
     }
+    // ... and, with extra input channels, the staged input_cond (nothing is reserved -- no offset of the plan moves -- for in_channels = 4)
+    if (cfg.in_channels > 4) plan->in_cond_off = plan->alloc(sizeof(float) * (size_t)plan->B * (cfg.in_channels - 4) * plan->H * plan->W);
     if (plan->lg_tu_elems) {      // ... and, with adapters selected, lora_grad.hip's scratch
       plan->lg_tu_off = plan->alloc(sizeof(bf16) * plan->lg_tu_elems);
       plan->lg_part_off = plan->alloc(sizeof(float) * (plan->lg_part_floats ? plan->lg_part_floats : 4));

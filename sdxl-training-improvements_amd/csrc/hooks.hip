@@ -343,13 +343,21 @@ int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void* unet_in,
   L.grad_scale = grad_scale; L.out = out8;
   CHK(check_loss_ext(lc, b));
   fill_loss_ext(lc, b, L);
+  const float* icond = nullptr;
+  int ncond = 0;
+  if (phase == 0) {      // extra input channels: no handle here, so cond_channels is their number (unet_in is [B*HW][input_cs(4 + ncond)])
+    read_input_cond(b, &icond, &ncond);
+    ARG_CHECK(ncond >= 0 && ncond <= 12, "input_cond: cond_channels %d outside 0 .. 12", ncond);
+    ARG_CHECK(ncond == 0 || icond, "input_cond is missing: cond_channels = %d", ncond);
+    ARG_CHECK(ncond > 0 || !icond, "input_cond must be NULL with cond_channels = 0 (in_channels = 4)");
+  }
   // the partial rows of phase 1, and behind them the [B] normaliser that masked_mean's phase 1 leaves for its phase 2
   if (phase == 1 || (phase == 2 && L.mask && L.mask_norm == 1)) {
     ARG_CHECK(L.B > 0 && L.HW > 0, "loss: empty batch");
     CHK(hook_floats(loss_part_floats(L.B, L.HW) + (size_t)L.B, &L.part));
     L.mnorm = L.part + loss_part_floats(L.B, L.HW);
   }
-  if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st);
+  if (phase == 0) return launch_loss_prepare(L, (hipStream_t)st, icond, ncond);
   if (phase == 1) return launch_loss_fwd(L, (hipStream_t)st);
   if (phase == 2) return launch_loss_bwd(L, (hipStream_t)st);
   ARG_CHECK(false, "phase %d", phase);

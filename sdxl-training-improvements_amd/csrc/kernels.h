@@ -401,7 +401,7 @@ struct LossP {
   const float* noise;     // noise (ddpm) / x0 (flow)
   const float* sigma;     // ddpm: [B] sigma ; flow: [B] t
   const float* tag_w;     // optional [B]
-  bf16* unet_in;          // [B*HW][8] (channels 4..7 zero)
+  bf16* unet_in;          // [B*HW][8] (channels 4..7 zero; wider and filled with ncond > 0, below)
   const bf16* pred;       // [B*HW][8]
   bf16* dpred;            // [B*HW][8]
   float grad_scale;       // multiplies d(loss)/d(pred) (1/grad_accum, 1/world)
@@ -421,13 +421,21 @@ struct LossP {
   int mask_norm;          // with mask: 0 = mean (divide by numel), 1 = masked_mean (per sample by 4 M_b, M_b = sum_hw m)
   float* mnorm;           // masked_mean: [B] scratch, M_b left by loss_finalize_kernel for loss_bwd_kernel
 };
+// ---- extra UNet input channels (in_channels > 4): what the COND instantiations of loss_prepare_kernel take; LossP itself, and with it
+// every kernel of the 4-channel UNet, stays as it is.  Read by the preparation only (conv_in has no input gradient). ----
+struct LossCondP : LossP {
+  const float* cond;      // [B][ncond][HW] fp32 NCHW: channels 4 .. 4 + ncond - 1 of the UNet input, bf16(cond) round to nearest even
+  int ncond;              // in_channels - 4, 1 .. 12; unet_in is [B*HW][Cs] with Cs = input_cs(4 + ncond), the channels behind zero
+};
+// stored width of an input pixel: one 16-byte vector up to 8 channels, two above (conv_in's Cin and the row stride of the plan's input buffer)
+static inline __host__ __device__ int input_cs(int in_channels) { return in_channels <= 8 ? 8 : 16; }
 // A 256-pixel block of the flat [B*HW] range touches at most loss_ps_slots samples (it straddles a sample boundary whenever
 // HW % 256 != 0, several when HW < 256).  The scratch holds the blocks' six batch sums first, then one partial of the weighted
 // element loss per (block, sample slot); slot j of block r belongs to sample (r * 256) / HW + j.  masked_mean adds a second such
 // column behind it: the block's partial of the mask sum M_b per slot.
 static inline __host__ __device__ int loss_ps_slots(int B, int HW) { const int s = 255 / HW + 2; return s < B ? s : B; }
 static inline size_t loss_part_floats(int B, int HW) { return (6 + 2 * (size_t)loss_ps_slots(B, HW)) * (((size_t)B * HW + 255) / 256); }
-int launch_loss_prepare(const LossP& p, hipStream_t st);
+int launch_loss_prepare(const LossP& p, hipStream_t st, const float* cond = nullptr, int ncond = 0);
 int launch_loss_fwd(const LossP& p, hipStream_t st);
 int launch_loss_bwd(const LossP& p, hipStream_t st);
 
@@ -452,8 +460,13 @@ struct SamplerP {
   const float* knoise;    // [B][4][HW] fp32: read with k_b != 0
   float k_a, k_b;
 };
+// ---- extra UNet input channels (the COND instantiations of sampler_step_kernel): x_in is [rows][Cs], Cs = input_cs(4 + ncond); pred stays [rows][8] ----
+struct SamplerCondP : SamplerP {
+  const float* cond;      // [(cfg ? 2B : B)][ncond][HW] fp32 NCHW: row b goes to the conditional half, row b + B to the unconditional one
+  int ncond;
+};
 static inline size_t sampler_part_floats(int B, int HW) { return 4 * (size_t)B * (((size_t)HW + 255) / 256); }
-int launch_sampler_step(const SamplerP& p, hipStream_t st);
+int launch_sampler_step(const SamplerP& p, hipStream_t st, const float* cond = nullptr, int ncond = 0);
 
 // ---- the fused optimizer updates (optimizer.hip): one launch over an arena slice ----
 // what both algorithms' kernels read

@@ -24,7 +24,10 @@
 //
 // Inputs arrive as the reference hands them over: NCHW fp32 latents / noise.  The UNet consumes and
 // produces token-major [B*HW][8] bf16 (4 real channels + 4 zero pad so every row is one 16-byte vector).
+// Extra input channels (in_channels 5 .. 16, LossCondP): the input image is [B*HW][Cs], Cs = 8 up to 8 channels, else 16 (one or two
+// 16-byte vectors per pixel); channels 4 .. hold bf16(cond), the rest zero.  Only loss_prepare_kernel knows: pred / dpred stay 8 wide.
 #include "kernels.h"
+#include <type_traits>
 
 // a * b + c and friends with every operation rounded on its own, as separate torch ops do (hipcc contracts a * b + c into
 // an FMA by default, and __fmul_rn / __fadd_rn are plain operators to it)
@@ -52,7 +55,10 @@ __device__ __forceinline__ void loss_target(const LossP& p, int b, float x, floa
   }
 }
 
-__global__ void loss_prepare_kernel(const LossP p) {
+// CS = the stored width of an input pixel (8 | 16, input_cs); COND: channels 4 .. 4 + ncond - 1 hold bf16(cond), the rest zero.
+// <8, false> is the kernel of the 4-channel UNet, instruction for instruction; channels 0..3 are the same operations in every instantiation.
+template <int CS, bool COND>
+__global__ void loss_prepare_kernel(const std::conditional_t<COND, LossCondP, LossP> p) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // over B*HW
   if (i >= (long)p.B * p.HW) return;
   int b = (int)(i / p.HW), hw = (int)(i - (long)b * p.HW);
@@ -74,7 +80,25 @@ __global__ void loss_prepare_kernel(const LossP p) {
     o[c] = (bf16)v;
     o[c + 4] = (bf16)0.f;
   }
-  *(bf16x8*)(p.unet_in + i * 8) = o;
+  if constexpr (COND) {      // (a wave reads 64 consecutive pixels of each cond plane: one 256-byte run per channel, like latents / noise)
+    const float* cp = p.cond + (long)b * p.ncond * p.HW + hw;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < p.ncond) o[c + 4] = (bf16)cp[(long)c * p.HW];
+  }
+  *(bf16x8*)(p.unet_in + i * CS) = o;
+  if (CS == 16) {
+    bf16x8 o2;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o2[c] = (bf16)0.f;
+    if constexpr (COND) {
+      const float* cp = p.cond + (long)b * p.ncond * p.HW + hw;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        if (c + 4 < p.ncond) o2[c] = (bf16)cp[(long)(c + 4) * p.HW];
+    }
+    *(bf16x8*)(p.unet_in + i * CS + 8) = o2;
+  }
 }
 
 // sqrt(d^2 + c^2) - c without the cancellation
@@ -254,11 +278,18 @@ static int check_loss(const LossP& p) {
   ARG_CHECK(!p.mask || (p.mask_norm >= 0 && p.mask_norm <= 1), "loss: mask_norm %d (0 = mean, 1 = masked_mean)", p.mask_norm);
   return 0;
 }
-int launch_loss_prepare(const LossP& p, hipStream_t st) {
+int launch_loss_prepare(const LossP& p, hipStream_t st, const float* cond, int ncond) {
   if (int e = check_loss(p)) return e;
   long n = (long)p.B * p.HW;
   ARG_CHECK(p.noise_in != nullptr, "loss: missing noise_in (the callers set it to noise)");
-  hipLaunchKernelGGL(loss_prepare_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p);
+  ARG_CHECK(ncond >= 0 && ncond <= 12 && (ncond == 0 || cond), "loss: input_cond is missing for %d extra input channels (0 .. 12)", ncond);
+  const dim3 grid(cdiv(n, 256)), block(256);
+  LossCondP q;
+  static_cast<LossP&>(q) = p;
+  q.cond = cond; q.ncond = ncond;
+  if (ncond == 0) hipLaunchKernelGGL((loss_prepare_kernel<8, false>), grid, block, 0, st, p);
+  else if (input_cs(4 + ncond) == 8) hipLaunchKernelGGL((loss_prepare_kernel<8, true>), grid, block, 0, st, q);
+  else hipLaunchKernelGGL((loss_prepare_kernel<16, true>), grid, block, 0, st, q);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -18,6 +18,8 @@
 // tests/_sampler_ref.py restates it in separate fp32 torch ops and the kernel is held to it bit for bit.  x is the caller's fp32 NCHW
 // state, updated in place; F_c / F_u are read from, and in_next is written to, token-major [rows][8] bf16 images (the plan's prediction and
 // input buffers: one 16-byte vector per pixel, channels 4..7 written as zero).  With cfg both halves of the input image receive in_next.
+// Extra input channels (SamplerCondP): in_next is [rows][Cs], Cs = 8 | 16, channels 4.. = bf16(cond) from row b (conditional half) and
+// row B + b (unconditional half) of cond [rows][ncond][HW], the rest zero; the prediction images stay 8 wide.
 //
 // Access pattern: one thread per pixel, the sample in blockIdx.y.  A wave reads 64 consecutive pixels: four 256-byte runs of x (one per
 // channel plane) and one 1-KiB run of 16-byte vectors per prediction half, and writes the same shapes back, so every access is a full
@@ -29,6 +31,7 @@
 // model outputs, whose mean is small against their spread (it cancels when |mean| >> std).  A sample whose variance is not positive keeps
 // r = 1.
 #include "kernels.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -75,8 +78,9 @@ __global__ __launch_bounds__(256) void sampler_stats_kernel(const SamplerP p) {
   if (threadIdx.x < 4) p.part[((long)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = v[threadIdx.x];
 }
 
-template <int RESCALE, int EXT>
-__global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerP p) {
+// CS / COND as in loss_prepare_kernel (loss.hip): <.., 8, false> are the kernels of the 4-channel UNet, instruction for instruction
+template <int RESCALE, int EXT, int CS, bool COND>
+__global__ __launch_bounds__(256) void sampler_step_kernel(const std::conditional_t<COND, SamplerCondP, SamplerP> p) {
   __shared__ float sm[4][4];
   const int b = blockIdx.y;
   const long hw = (long)blockIdx.x * 256 + threadIdx.x;
@@ -142,24 +146,56 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerP p) {
     o[c] = (bf16)v;
     o[c + 4] = (bf16)0.f;
   }
-  *(bf16x8*)(p.x_in + ic) = o;
-  if (p.cfg) *(bf16x8*)(p.x_in + iu) = o;
+  if constexpr (!COND) {
+    *(bf16x8*)(p.x_in + ic) = o;
+    if (p.cfg) *(bf16x8*)(p.x_in + iu) = o;
+  } else {
+    // extra input channels: the halves share channels 0..3 and take 4.. from their own rows of cond (b: conditional, B + b: unconditional)
+    for (int half = 0; half < (p.cfg ? 2 : 1); ++half) {
+      const long row = half ? p.B + b : b;
+      const float* cp = p.cond + row * p.ncond * p.HW + hw;
+      bf16x8 oh = o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < p.ncond) oh[c + 4] = (bf16)cp[(long)c * p.HW];
+      bf16* dst = p.x_in + (row * p.HW + hw) * CS;
+      *(bf16x8*)dst = oh;
+      if (CS == 16) {
+        bf16x8 o2;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) o2[c] = (c + 4 < p.ncond) ? (bf16)cp[(long)(c + 4) * p.HW] : (bf16)0.f;
+        *(bf16x8*)(dst + 8) = o2;
+      }
+    }
+  }
 }
 
-int launch_sampler_step(const SamplerP& p, hipStream_t st) {
+template <int CS, bool COND>
+static int launch_sampler_cs(const std::conditional_t<COND, SamplerCondP, SamplerP>& p, bool rescale, bool ext, dim3 grid, dim3 block, hipStream_t st) {
+  if (ext) {
+    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 1, CS, COND>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((sampler_step_kernel<0, 1, CS, COND>), grid, block, 0, st, p);
+  } else {
+    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 0, CS, COND>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((sampler_step_kernel<0, 0, CS, COND>), grid, block, 0, st, p);
+  }
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+int launch_sampler_step(const SamplerP& p, hipStream_t st, const float* cond, int ncond) {
   ARG_CHECK(p.B > 0 && p.HW > 0, "sampler: empty batch");
   ARG_CHECK(p.x && p.x_in && (p.init || p.pred), "sampler: missing buffers");
   const bool rescale = !p.init && p.rescale != 0.f;
   ARG_CHECK(!rescale || p.part, "sampler: guidance rescale needs the partial-row scratch (sampler_part_floats)");
+  ARG_CHECK(ncond >= 0 && ncond <= 12 && (ncond == 0 || cond), "sampler: input_cond is missing for %d extra input channels (0 .. 12)", ncond);
   const dim3 grid(cdiv(p.HW, 256), p.B), block(256);
   if (rescale) hipLaunchKernelGGL(sampler_stats_kernel, grid, block, 0, st, p);
-  if (p.ext && !p.init) {      // (init writes the input image only: the plain kernel)
-    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((sampler_step_kernel<0, 1>), grid, block, 0, st, p);
-  } else {
-    if (rescale) hipLaunchKernelGGL((sampler_step_kernel<1, 0>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((sampler_step_kernel<0, 0>), grid, block, 0, st, p);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  const bool ext = p.ext && !p.init;      // (init writes the input image only: the plain kernel)
+  if (ncond == 0) return launch_sampler_cs<8, false>(p, rescale, ext, grid, block, st);
+  SamplerCondP q;
+  static_cast<SamplerP&>(q) = p;
+  q.cond = cond; q.ncond = ncond;
+  if (input_cs(4 + ncond) == 8) return launch_sampler_cs<8, true>(q, rescale, ext, grid, block, st);
+  return launch_sampler_cs<16, true>(q, rescale, ext, grid, block, st);
 }

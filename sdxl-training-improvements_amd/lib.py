@@ -94,6 +94,15 @@ class CondGradBatch(SamplerBatch):
     _fields_ = [("d_prompt_embeds", C.c_void_p), ("d_pooled", C.c_void_p)]
 
 
+BATCH_COND = 0x20000   # SDXL_BATCH_COND, or-ed into Batch.ctx_len: the struct passed is an InputCondBatch
+
+
+class InputCondBatch(CondGradBatch):
+    """sdxl_batch_cond: CondGradBatch + the extra UNet input channels (in_channels > 4) [B, in_channels - 4, H, W] fp32, read only
+    when ctx_len carries BATCH_COND; cond_channels 0 = the handle's in_channels - 4 (sdxl_op_loss, which has no handle: their number)"""
+    _fields_ = [("input_cond", C.c_void_p), ("cond_channels", C.c_int)]
+
+
 DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
 DTYPE_LORA_LAYOUTS = 4  # SDXL_DTYPE_LORA_LAYOUTS: the same two calls and struct, targets in the arena's packed layouts accepted (lora.py, kinds="all")
 

@@ -16,7 +16,9 @@ its `param_groups`).  The fused class follows `optimizer.optimizer_type` (traine
 class is the reference's `AdamWScheduleFreeKahan` selects the fused schedule-free Kahan AdamW as well, with `warmup_steps` and
 `kahan_sum` also read from its `param_groups`.  The build-only keys of `training` (EMA, `loss_type` / `huber_c` / `huber_schedule`,
 `snr_weighting`, `tag_weights_per_sample`, `log_per_sample_loss`, `masked_loss`, `noise_offset`, `input_perturbation`,
-`cond_dropout_prob`, `conditioning_grads`: INTEGRATION.md section 1) are copied like every other key."""
+`cond_dropout_prob`, `conditioning_grads`, `input_conditioning`, `input_cond_dropout_prob`: INTEGRATION.md section 1) are copied like
+every other key.  `in_channels` is the model's (an inpainting UNet's 9, an image-conditioned one's 8): widening SDXL-base is the
+caller's job before constructing (unet.widen_conv_in)."""
 from __future__ import annotations
 
 import copy

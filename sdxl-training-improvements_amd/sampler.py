@@ -314,7 +314,8 @@ class NativeSampler:
                generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None, sigmas=None,
                timesteps=None, solver: str = "euler", eta: float = 1.0, step_noise: Optional[torch.Tensor] = None,
                init_latents: Optional[torch.Tensor] = None, strength: float = 1.0,
-               inpaint_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+               inpaint_mask: Optional[torch.Tensor] = None, input_cond: Optional[torch.Tensor] = None,
+               neg_input_cond: Optional[torch.Tensor] = None) -> torch.Tensor:
         """height / width are the latent's.  Negative conditioning that is missing with guidance_scale != 1 is zeros of the same
         shape (neg_time_ids: the positive ones).  `noise` [B,4,H,W] overrides the draw from `generator` (CPU, as in training).  The
         loop enqueues every forward and step without a host synchronisation; the result is stream-ordered.
@@ -323,7 +324,10 @@ class NativeSampler:
         torch.randn((n,B,4,H,W)) from `generator` behind the initial noise; `step_noise` [n,B,4,H,W] overrides that draw.
         `init_latents` [B,4,H,W] with 0 < strength <= 1 (img2img) runs the last max(1, round(strength N)) of the N grid points from
         init + sigma_start n (ddpm) or (1 - t_start) n + t_start init (flow); strength = 1 is pure noise, the call without
-        init_latents.  `inpaint_mask` [B,H,W] or [B,1,H,W] in [0,1] (1 = generate, 0 = keep) needs init_latents, the latent kept."""
+        init_latents.  `inpaint_mask` [B,H,W] or [B,1,H,W] in [0,1] (1 = generate, 0 = keep) needs init_latents, the latent kept.
+        `input_cond` [B, in_channels - 4, H, W] (a UNet with in_channels > 4: inpainting, image conditioning): channels 4.. of every
+        forward's input, rounded to bf16 by the step kernel.  With guidance the unconditional half reuses it unless `neg_input_cond`
+        (same shape) is given.  The keyword reaches the net only when it is given."""
         net = self.unet
         dev = net.device
         B = int(prompt_embeds.shape[0])
@@ -368,13 +372,24 @@ class NativeSampler:
             nti = ti if neg_time_ids is None else neg_time_ids.to(dev, torch.float32).reshape(B, 6)
             pe, po, ti = torch.cat([pe, npe]), torch.cat([po, npo]), torch.cat([ti, nti])
         PB = self.plan_batch(B, guidance_scale)
+        ic = {}
+        if neg_input_cond is not None and input_cond is None:
+            raise ValueError("neg_input_cond needs input_cond")
+        if input_cond is not None:
+            for name, t in (("input_cond", input_cond), ("neg_input_cond", neg_input_cond)):
+                if t is not None and (t.dim() != 4 or tuple(t.shape) != (B, int(input_cond.shape[1]), H, W)):
+                    raise ValueError(f"{name}: expected shape {(B, int(input_cond.shape[1]), H, W)}, got {tuple(t.shape)}")
+            c = input_cond.detach().to(dev, torch.float32)
+            if cfg:
+                c = torch.cat([c, c if neg_input_cond is None else neg_input_cond.detach().to(dev, torch.float32)])
+            ic = dict(input_cond=c.contiguous())
         if plain:
             # the time inputs of all forwards, uploaded once: row j is forward j's [PB] values
             tall = torch.tensor([[s[6]] * PB for s in steps], dtype=torch.float32).to(dev)
             ks = kernel_steps(steps, guidance_scale, guidance_rescale, cfg)
-            net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5])
+            net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5], **ic)
             for j, k in enumerate(ks):
-                net.sample_step(x, pe, po, ti, tall[j], **k)
+                net.sample_step(x, pe, po, ti, tall[j], **k, **ic)
             return x
         # every buffer of the extended steps is made and uploaded here, before the loop: no torch op runs between forwards
         tall = torch.tensor([[t] * PB for t in tin], dtype=torch.float32).to(dev)
@@ -393,7 +408,7 @@ class NativeSampler:
         if mask is not None:
             blend = dict(mask=mask.to(dev).contiguous(), known=known.to(dev).contiguous(),
                          knoise=noise.to(torch.float32).to(dev).contiguous())
-        net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5])
+        net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5], **ic)
         d = 0
         for f, k in enumerate(ks):
             ex = dict(blend)
@@ -403,7 +418,7 @@ class NativeSampler:
                 ex["xsave"] = xsave
             if k.get("s", 0) != 0:
                 ex["noise"], d = draws[d], d + 1
-            net.sample_step(x, pe, po, ti, tall[f], **k, **ex)
+            net.sample_step(x, pe, po, ti, tall[f], **k, **ex, **ic)
         return x
 
     def _start(self, n: int, B: int, H: int, W: int, init_latents, strength, inpaint_mask):

@@ -57,6 +57,7 @@ HUBER_SCHEDULES = ("constant", "snr")
 SNR_WEIGHTINGS = ("reference", "debiased")
 WEIGHT_SETS = ("trained", "ema")
 MASKED_LOSSES = ("off", "mean", "masked_mean")
+INPUT_CONDITIONINGS = ("none", "inpaint", "concat")
 CONDITIONING_GRADS = ("auto", "off")
 
 
@@ -125,6 +126,7 @@ class NativeSDXLTrainer:
         else:
             raise TypeError("model.unet must be a NativeUNet or a module with a diffusers-keyed state_dict(); got "
                             f"{type(unet).__name__}")
+        self._check_input_conditioning()
         self.noise_scheduler = NoiseScheduler(self.config, "cpu")
         self.optimizer = self._build_optimizer(optimizer)
         self.ema = build_ema(self.net, self.optimizer, self.config.training)     # None unless training.use_ema
@@ -200,6 +202,54 @@ class NativeSDXLTrainer:
                 raise ValueError("training.snr_weighting: 'debiased' is a ddpm weighting (flow matching has no snr)")
         elif self.snr_weighting == "debiased" and self.config.model.min_snr_gamma is None:
             raise ValueError("training.snr_weighting: 'debiased' divides min(snr, gamma) by the snr: it needs model.min_snr_gamma")
+
+    def _check_input_conditioning(self) -> None:
+        """training.input_conditioning / input_cond_dropout_prob against the net's in_channels, once the net exists (ValueError names the key)"""
+        tc = self.config.training
+        ic = getattr(tc, "input_conditioning", "none")
+        self.input_conditioning = ic.lower() if isinstance(ic, str) else ic
+        if self.input_conditioning not in INPUT_CONDITIONINGS:
+            raise ValueError(f"training.input_conditioning: unknown value {ic!r} (expected one of {', '.join(INPUT_CONDITIONINGS)})")
+        v = getattr(tc, "input_cond_dropout_prob", 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"training.input_cond_dropout_prob must be a number in [0, 1] (got {v!r})")
+        self.input_cond_dropout_prob = float(v)
+        cfg = getattr(self.net, "cfg", None)
+        cin = cfg.get("in_channels", 4) if isinstance(cfg, dict) else getattr(cfg, "in_channels", 4)
+        self.in_channels = int(cin)
+        want = {"none": "4", "inpaint": "9", "concat": "5 .. 16"}[self.input_conditioning]
+        ok = {"none": cin == 4, "inpaint": cin == 9, "concat": 5 <= cin <= 16}[self.input_conditioning]
+        if not ok:
+            raise ValueError(f"training.input_conditioning: {self.input_conditioning!r} needs a UNet with in_channels = {want}, this one has {cin}")
+        if self.input_conditioning == "none" and self.input_cond_dropout_prob > 0.0:
+            raise ValueError("training.input_cond_dropout_prob: needs training.input_conditioning 'inpaint' or 'concat'")
+
+    def _input_cond(self, batch, B: int, H: int, W: int) -> torch.Tensor:
+        """the extra input channels [B, in_channels - 4, H, W] fp32 of a batch, a new tensor (ValueError names a missing key or a wrong shape)"""
+        def get(key, shapes):
+            if key not in batch or batch[key] is None:
+                raise ValueError(f"training.input_conditioning {self.input_conditioning!r}: the batch has no {key!r}")
+            t = torch.as_tensor(batch[key])
+            if tuple(t.shape) not in shapes:
+                raise ValueError(f"batch[{key!r}]: expected shape {' or '.join(str(s) for s in shapes)}, got {tuple(t.shape)}")
+            return t.detach().to(torch.float32)
+        if self.input_conditioning == "inpaint":        # diffusers' order: latents | mask | masked-image latents
+            m = get("inpaint_mask", ((B, 1, H, W), (B, H, W))).reshape(B, 1, H, W)
+            ml = get("masked_latents", ((B, 4, H, W),))
+            return torch.cat([m, ml.to(m.device)], dim=1)
+        return get("cond_latents", ((B, self.in_channels - 4, H, W),)).clone()
+
+    def _input_cond_ext(self, batch, lat, generator, augment: bool, ext: Dict[str, Any]) -> None:
+        """forward_loss's input_cond, when the key is on; with augment (a training step) the per-sample dropout, drawn after every
+        other draw of the step and only when its key is on"""
+        if self.input_conditioning == "none":
+            return
+        B, _c, H, W = lat.shape
+        ic = self._input_cond(batch, B, H, W)
+        if augment and self.input_cond_dropout_prob > 0.0:
+            drop = torch.rand(B, generator=generator) < self.input_cond_dropout_prob
+            ic[drop.to(ic.device)] = 0
+        ext["input_cond"] = ic
 
     def _check_sampler_keys(self) -> None:
         """the validation / sampler keys, checked when the trainer is built (ValueError names the key)"""
@@ -277,14 +327,16 @@ class NativeSDXLTrainer:
                width: int, num_steps: Optional[int] = None, guidance_scale: Optional[float] = None,
                guidance_rescale: Optional[float] = None, generator: Optional[torch.Generator] = None, noise=None, sigmas=None,
                timesteps=None, weights: Optional[str] = None, solver: Optional[str] = None, eta: Optional[float] = None,
-               step_noise=None, init_latents=None, strength: float = 1.0, inpaint_mask=None) -> torch.Tensor:
+               step_noise=None, init_latents=None, strength: float = 1.0, inpaint_mask=None, input_cond=None,
+               neg_input_cond=None) -> torch.Tensor:
         """Latents [B,4,height,width] fp32 on the device, sampled natively (sampler.py::NativeSampler) from the trained weights or
         the EMA; what is not given comes from the training.validation_* keys (solver / eta: validation_sampler / validation_eta;
-        step_noise, init_latents, strength and inpaint_mask are NativeSampler.sample's).  Decoding is the caller's.  Nothing of the training
+        step_noise, init_latents, strength, inpaint_mask, input_cond and neg_input_cond are NativeSampler.sample's).  Decoding is the caller's.  Nothing of the training
         state changes: the next step has the bits it would have had without the call."""
         tc = self.config.training
         sampler = NativeSampler(self.net, self.method, str(tc.prediction_type), bool(self.config.model.use_ztsnr),
                                 self.sampler_parameterization, config=self.config, t_bf16=str(tc.mixed_precision) == "bf16")
+        ic = {} if input_cond is None else dict(input_cond=input_cond, neg_input_cond=neg_input_cond)      # (only when given)
         with self._weights(self.validation_weights if weights is None else weights):
             return sampler.sample(prompt_embeds, pooled, time_ids, neg_prompt_embeds, neg_pooled, neg_time_ids, height=height,
                                   width=width, num_steps=int(tc.validation_num_steps if num_steps is None else num_steps),
@@ -293,7 +345,7 @@ class NativeSDXLTrainer:
                                   generator=generator, noise=noise, sigmas=sigmas, timesteps=timesteps,
                                   solver=self.validation_sampler if solver is None else solver,
                                   eta=float(getattr(tc, "validation_eta", 1.0) if eta is None else eta), step_noise=step_noise,
-                                  init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask)
+                                  init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, **ic)
 
     def validate(self, step: int, validation_batches, on_validation=None):
         """sample every conditioning batch of `validation_batches` (dicts with "prompt_embeds", "pooled_prompt_embeds", "time_ids",
@@ -310,10 +362,15 @@ class NativeSDXLTrainer:
                 h, w = int(b["height"]), int(b["width"])
             else:
                 h, w = (int(v) for v in b["vae_latents"].shape[-2:])
+            blend_mask, ic = b.get("inpaint_mask"), {}
+            if self.input_conditioning != "none":      # the extra input channels, built as in training (no dropout); "neg_input_cond" as given
+                ic = dict(input_cond=self._input_cond(b, int(b["prompt_embeds"].shape[0]), h, w), neg_input_cond=b.get("neg_input_cond"))
+                if self.input_conditioning == "inpaint" and b.get("init_latents") is None:
+                    blend_mask = None                  # the mask is the UNet's input channel; the latent blend also needs init_latents
             lat = self.sample(b["prompt_embeds"], b["pooled_prompt_embeds"], b["time_ids"], b.get("neg_prompt_embeds"),
                               b.get("neg_pooled_prompt_embeds"), b.get("neg_time_ids"), height=h, width=w, generator=gen,
                               init_latents=b.get("init_latents"), strength=float(b.get("strength", 1.0)),
-                              inpaint_mask=b.get("inpaint_mask"))
+                              inpaint_mask=blend_mask, **ic)
             outs.append(lat)
             if on_validation is not None:
                 on_validation(step, lat)
@@ -408,6 +465,7 @@ class NativeSDXLTrainer:
             if augment:
                 batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
                 ext.update(aug)
+            self._input_cond_ext(batch, lat, generator, augment, ext)
             if cond_grads:
                 batch = dict(batch)
                 self._cond_request(batch, ext)
@@ -428,6 +486,7 @@ class NativeSDXLTrainer:
         if augment:
             batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
             ext.update(aug)
+        self._input_cond_ext(batch, lat, generator, augment, ext)
         if cond_grads:
             batch = dict(batch)
             self._cond_request(batch, ext)

@@ -65,10 +65,33 @@ def config_from_unet(unet, sd=None) -> lib.UNetConfig:
     add_in = get("projection_class_embeddings_input_dim", None) or sd["add_embedding.linear_1.weight"].shape[1]
     head = get("attention_head_dim", 64)
     head = 64 if isinstance(head, (list, tuple)) else head           # SDXL: heads = C / 64 at every level
-    return make_config(block_out_channels=tuple(int(x) for x in ch), transformer_layers=tuple(int(x) for x in tl),
+    cin = get("in_channels")          # 4; 9 inpainting, 8 image-conditioned (InstructPix2Pix)
+    if cin is None:
+        cin = sd["conv_in.weight"].shape[1]
+    return make_config(in_channels=int(cin), block_out_channels=tuple(int(x) for x in ch), transformer_layers=tuple(int(x) for x in tl),
                        layers_per_block=int(get("layers_per_block", 2)), cross_attention_dim=int(cross),
                        addition_time_embed_dim=int(ad), pooled_dim=int(add_in) - 6 * int(ad),
                        norm_num_groups=int(get("norm_num_groups", 32)), head_dim=64 if head in (5, 10, 20) else int(head))
+
+
+def input_cs(in_channels: int) -> int:
+    """stored width of a pixel of the library's UNet input ([B*H*W][Cs] bf16): 8 up to 8 input channels, 16 above"""
+    return 8 if int(in_channels) <= 8 else 16
+
+
+def widen_conv_in(state_dict, in_channels: int) -> dict:
+    """A copy of a diffusers-keyed UNet state dict whose conv_in.weight [cout, c, 3, 3] is zero-extended along dim 1 to in_channels:
+    the usual start of inpainting (9) or InstructPix2Pix (8) training from SDXL-base -- the widened UNet computes what the original
+    does whatever the extra channels hold.  Every other tensor is the same object; the original slice is kept bit for bit."""
+    w = state_dict["conv_in.weight"]
+    c = int(w.shape[1])
+    if not c <= int(in_channels) <= 16:
+        raise ValueError(f"widen_conv_in: in_channels {in_channels} must lie in {c} .. 16 (conv_in.weight has {c})")
+    out = dict(state_dict)
+    wide = torch.zeros(w.shape[0], int(in_channels), *w.shape[2:], dtype=w.dtype, device=w.device)
+    wide[:, :c] = w
+    out["conv_in.weight"] = wide
+    return out
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -306,6 +329,31 @@ class NativeUNet:
         x.d_pooled = None if self._d_pooled is None else self._d_pooled.data_ptr()
         return x
 
+    def _input_cond_batch(self, b, input_cond, latent_shape, what: str, rows: Optional[int] = None, convert: bool = True):
+        """b as a lib.InputCondBatch carrying input_cond (flagged), or b itself when input_cond is None: without it every call is
+        the one a 4-channel UNet makes.  input_cond is [rows, in_channels - 4, H, W] (rows = the plan's batch) fp32 on the device,
+        kept alive with the batch's other tensors; convert=False (the sampler path) checks instead of converting."""
+        if input_cond is None:
+            return b
+        B, _c, H, W = latent_shape
+        rows = B if rows is None else rows
+        n = int(self.cfg.in_channels) - 4
+        if input_cond.dim() != 4 or tuple(input_cond.shape) != (rows, int(input_cond.shape[1]), H, W) or (n > 0 and input_cond.shape[1] != n):
+            raise ValueError(f"{what}: input_cond must be [{rows}, {n}, {H}, {W}] (in_channels - 4 = {n} extra channels), got {tuple(input_cond.shape)}")
+        if convert:
+            input_cond = input_cond.to(self.device, torch.float32).contiguous()
+        elif input_cond.dtype != torch.float32 or not input_cond.is_cuda or not input_cond.is_contiguous():
+            raise ValueError(f"{what}: input_cond must be a contiguous torch.float32 device tensor")
+        self._keep = list(self._keep) + [input_cond]
+        x = lib.InputCondBatch(*[getattr(b, f[0]) for f in lib.Batch._fields_])
+        for f in ("sampler", "d_prompt_embeds", "d_pooled"):
+            if hasattr(b, f):
+                setattr(x, f, getattr(b, f))
+        x.ctx_len |= lib.BATCH_COND
+        x.input_cond = input_cond.data_ptr()
+        x.cond_channels = int(input_cond.shape[1])
+        return x
+
     def read_cond_grads(self):
         """(d_prompt_embeds [B,ctx,cross_attention_dim] | None, d_pooled [B,pooled_dim] | None) of the last micro-step that asked for
         them (forward_loss / unet_forward with cond_grads) and whose backward has been enqueued: fp32, on the device, stream-ordered
@@ -316,8 +364,10 @@ class NativeUNet:
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
                      use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
                      per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean",
-                     cond_grads=None) -> None:
+                     cond_grads=None, input_cond=None) -> None:
         """loss preparation + UNet forward + loss; results stay on the device until read_loss().
+        input_cond: [B, in_channels - 4, H, W], channels 4.. of the UNet input (rounded to bf16) of a UNet with in_channels > 4:
+        required there, refused (by the library) with in_channels = 4.  Read by this call only; the backward does not need it.
         sample_weights: optional [B] s_b multiplied into each sample's loss and gradient.  loss_type "l2" | "huber" |
         "smooth_l1" (include/sdxlstep.h), with huber_c a float (every sample) or [B] values (per sample).
         per_sample_loss: also produce the [B] per-sample losses, read with read_per_sample_loss() after read_loss().
@@ -357,7 +407,7 @@ class NativeUNet:
         b.huber_c = None if hc is None else hc.data_ptr()
         b.per_sample_loss = None if self._ps_loss is None else self._ps_loss.data_ptr()
         self._cond_request(cond_grads, B, b.ctx_len)
-        b = self._cond_batch(b)
+        b = self._input_cond_batch(self._cond_batch(b), input_cond, latents.shape, "forward_loss")
         lib.check(self.L.sdxl_forward_loss(self.h, C.byref(lc), C.byref(b), _stream()), "sdxl_forward_loss")
 
     def backward(self, grad_scale: float = 1.0, first_micro: bool = True, on_segment=None, segment_stream: bool = False) -> None:
@@ -428,14 +478,17 @@ class NativeUNet:
         b = lib.SamplerBatch(*[getattr(tb, f[0]) for f in lib.Batch._fields_])      # sdxl_batch in full, sampler = NULL
         self._cond_request(cond_grads, B, tb.ctx_len)
         b = self._cond_batch(b)
-        x8 = torch.zeros(B * H * W, 8, dtype=torch.bfloat16, device=d)
-        x8[:, :4] = sample.to(d).permute(0, 2, 3, 1).reshape(B * H * W, 4).to(torch.bfloat16)
-        out8 = torch.empty_like(x8)
+        cin = int(self.cfg.in_channels)      # the sample carries every input channel, packed into Cs columns
+        if Cc != cin:
+            raise ValueError(f"unet_forward: sample has {Cc} channels, the UNet has in_channels = {cin}")
+        x8 = torch.zeros(B * H * W, input_cs(cin), dtype=torch.bfloat16, device=d)
+        x8[:, :cin] = sample.to(d).permute(0, 2, 3, 1).reshape(B * H * W, cin).to(torch.bfloat16)
+        out8 = torch.empty(B * H * W, 8, dtype=torch.bfloat16, device=d)
         lib.check(self.L.sdxl_unet_forward(self.h, _ptr(x8), C.byref(b), _ptr(out8), _stream()), "sdxl_unet_forward")
         return out8[:, :4].float().reshape(B, H, W, 4).permute(0, 3, 1, 2).contiguous()
 
     # ------------------------------------------------------------------ sampling (sampler.py drives these)
-    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str, planes=()) -> None:
+    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str, planes=(), input_cond=None) -> None:
         """sdxl_unet_forward with sdxl_batch.sampler set.  Every tensor is already on the device in the library's dtype and
         contiguous (checked, not converted: no torch arithmetic or copy runs here); the plan's batch is prompt_embeds' (B, or
         2B = [cond; uncond] with cfg), x is [B,4,H,W] fp32.  `planes`: (name, tensor, elements) of an extended step's buffers."""
@@ -456,16 +509,20 @@ class NativeUNet:
         b = lib.SamplerBatch(PB, H, W, ctx, None, None, None, timestep.data_ptr(), prompt_embeds.data_ptr(), pooled.data_ptr(),
                              time_ids.data_ptr(), None)
         b.sampler = C.cast(C.pointer(step), C.POINTER(lib.SamplerStep))      # (a SamplerStepExt goes through the same pointer)
+        b = self._input_cond_batch(b, input_cond, x.shape, what, rows=PB, convert=False)      # [PB, in_channels - 4, H, W]: the uncond half has rows of its own
         lib.check(self.L.sdxl_unet_forward(self.h, None, C.byref(b), None, _stream()), what)
 
-    def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0) -> None:
-        """write the first UNet input of a sampling loop, bf16(clamp(a_in * x, +-clamp)), into the plan's input buffer (no forward)"""
+    def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0,
+                    input_cond=None) -> None:
+        """write the first UNet input of a sampling loop, bf16(clamp(a_in * x, +-clamp)), into the plan's input buffer (no forward).
+        input_cond (in_channels > 4): [PB, in_channels - 4, H, W] fp32 on the device, PB = prompt_embeds' batch -- channels 4.. of
+        the input, row b for the conditional half and row b + B for the unconditional one; the same for sample_step."""
         s = lib.SamplerStep(None, int(cfg), 1, 0.0, 0.0, 0.0, 0.0, float(a_in), float(clamp), 1.0, 0.0)
-        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init")
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init", input_cond=input_cond)
 
     def sample_step(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg, a_skip, a_out, p, q, a_in_next=1.0, clamp=0.0,
                     guidance=1.0, guidance_rescale=0.0, init=0, hist=None, xsave=None, noise=None, r=0.0, u=0.0, s=0.0, save=0,
-                    mask=None, known=None, knoise=None, k_a=0.0, k_b=0.0) -> None:
+                    mask=None, known=None, knoise=None, k_a=0.0, k_b=0.0, input_cond=None) -> None:
         """one forward on the plan's input buffer + the fused sampler step (include/sdxlstep.h sdxl_sampler_step): x is updated in
         place and the next input is left in the plan; stream-ordered, no synchronisation.  hist ... k_b are the fields of
         sdxl_sampler_step_ext ([B,4,H,W] fp32 device tensors, mask [B,H,W]); the extended struct and its flag are passed only when
@@ -474,14 +531,14 @@ class NativeUNet:
                 float(guidance), float(guidance_rescale))
         tensors = (("hist", hist), ("xsave", xsave), ("noise", noise), ("mask", mask), ("known", known), ("knoise", knoise))
         if all(t is None for _n, t in tensors) and not any((r, u, s, save, k_a, k_b)):
-            self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, lib.SamplerStep(*base), "sample_step")
+            self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, lib.SamplerStep(*base), "sample_step", input_cond=input_cond)
             return
         st = lib.SamplerStepExt(*base)
         st.init |= lib.SAMPLER_EXT
         st.r, st.u, st.s, st.save, st.k_a, st.k_b = float(r), float(u), float(s), int(save), float(k_a), float(k_b)
         n = x.numel()
         planes = tuple((name, t, n // 4 if name == "mask" else n) for name, t in tensors if t is not None)
-        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, st, "sample_step", planes)
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, st, "sample_step", planes, input_cond=input_cond)
 
     def unet_backward(self, dpred_nchw: torch.Tensor, first_micro: bool = True) -> None:
         B, Cc, H, W = dpred_nchw.shape
