@@ -202,6 +202,45 @@ typedef struct {
 } sdxl_batch_cond;
 #define SDXL_BATCH_COND 0x20000  /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_cond */
 
+/* Additional skip residuals (diffusers' down_block_additional_residuals / mid_block_additional_residual: how a ControlNet attaches to the
+ * UNet), with gradients.  The batch that carries them is sdxl_batch_cond with one host pointer appended (`base` IS that struct), passed as
+ * a sdxl_batch* with SDXL_BATCH_RES or-ed into base.base.base.ctx_len: the flag says that the struct passed is this one, so every field of
+ * sdxl_batch_ext and sdxl_batch_cond is read as well and their flags need not be set beside it.  Nothing behind `sampler` is read without a flag.
+ * Forward.  The UNet saves n = 1 + 3 * layers_per_block + 2 skips (SDXL-base: 9) in forward order: conv_in's output, then per down block
+ * each layer's output and then its downsampler's; the up path joins them, last first, to its hidden state by a channel concat.  For
+ * down[i] the skip half of its concat becomes bf16_rn(float(skip) + float(r)): one fp32 add, one round to nearest even; where r == 0 the
+ * skip's bits pass unchanged.  `mid` is added the same way to the hidden half of the first concat (the mid block's output).  The saved skip
+ * itself is NOT modified: the down path, its weight gradients and the backward read the plain skip, as diffusers adds the residuals
+ * after the whole down path has run.  Scaling the residuals (conditioning_scale) is the caller's.  The residuals are read by the forward
+ * only; the backward never reads them.  sdxl_forward_loss, sdxl_loss_fwd_bwd and sdxl_unet_forward (with and without `sampler`; init runs no
+ * forward and reads none) honour the struct; with cfg the plan's batch is 2B and row b + B feeds the unconditional half, as for input_cond.
+ * Gradients.  A given d_down[i] / d_mid is written by the backward of that micro-step: float(g) of the concat's bf16 output gradient for
+ * that column range, transposed to NCHW.  The values follow that micro-step's parameter gradients' grad_scale and gradient gate (a
+ * closed gate stores exact zeros; sdxl_unet_backward: of <dpred, pred>, no scale, no gate); always OVERWRITTEN, never accumulated.  A d_*
+ * pointer may be given without the matching residual (the gradient at r = 0).  The writes go straight from the backward's kernels into the
+ * caller's buffers (no plan copies), stream-ordered, complete once the last-executed backward segment has been enqueued; the caller keeps
+ * the buffers alive until then.  d_* together with `sampler` is a bad argument.
+ * Graph mode.  A call that carries a sdxl_residuals launches kernel by kernel even in graph mode (sdxl_set_graph_mode), as the sampler
+ * path does -- its forward and the backward of that micro-step: the residuals (SDXL-base, B = 4, 128 x 128, fp32: about 430 MB) would
+ * otherwise have to be staged at fixed addresses inside the plan.
+ * Bad arguments (1, before any launch, the message names `residuals` and the index): n other than the handle's number of skips, a dtype
+ * outside 0..1, a pointer that is not 16-byte aligned, d_* with `sampler`.  Without the flag or with residuals == NULL the launch
+ * sequence, every workspace offset and every bit are those of a call without this struct. */
+typedef struct {
+  int n;                    /* number of skips of the handle: 1 + 3 * layers_per_block + 2 (SDXL-base: 9); any other value = bad argument */
+  int dtype;                /* of down[] / mid: 0 = fp32, 1 = bf16 */
+  const void* const* down;  /* HOST array [n] of device pointers, forward (diffusers) order; down[i] is [Bplan, C_i, h_i, w_i] NCHW contiguous;
+                               an entry may be NULL (no residual at that skip); down == NULL = none */
+  const void* mid;          /* device [Bplan, C_last, H/4, W/4] NCHW; NULL = none */
+  float* const* d_down;     /* HOST array [n] of device fp32 OUT pointers, same shapes; entries may be NULL; NULL = none */
+  float* d_mid;             /* device fp32 OUT; NULL = none */
+} sdxl_residuals;
+typedef struct {
+  sdxl_batch_cond base;
+  const sdxl_residuals* residuals;   /* HOST pointer, read during the call; NULL = none */
+} sdxl_batch_res;
+#define SDXL_BATCH_RES 0x40000   /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_res */
+
 SDXL_API const char* sdxl_last_error(void);
 SDXL_API int sdxl_version(void);
 
@@ -338,7 +377,8 @@ SDXL_API int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro
 /* hipGraph replay of forward / backward (default OFF: measured slower than eager two-stream launches on ROCm 7.2, see
  * DESIGN.md): the second call with a given (plan, loss configuration including loss_type / huber_c and which per-sample arrays are
  * present, the loss mask / noise_in and mask_norm, whether input_cond is present, first_micro, grad_scale) captures the launch sequence of both streams, later calls replay it with one hipGraphLaunch.  0 = launch
- * kernel by kernel.  Inputs are staged at fixed addresses inside the plan, so the caller's tensors may move between steps. */
+ * kernel by kernel.  Inputs are staged at fixed addresses inside the plan, so the caller's tensors may move between steps.
+ * A micro-step that carries a sdxl_residuals is never captured: its forward and backward launch kernel by kernel (above). */
 SDXL_API int sdxl_set_graph_mode(sdxl_handle* h, int on);
 /* synchronises `stream`; out[0]=loss out[1]=sum s*w*l(pred-target) (s = 1, l = square unless set otherwise) out[2]=sum|pred| out[3]=sum pred^2
  * out[4]=sum|noise| out[5]=sum noise^2 (x0) out[6]=sum latents^2 (x1) out[7]=gradient gate */
@@ -353,7 +393,7 @@ SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
  * path always launches kernel by kernel, also in graph mode. */
 SDXL_API int sdxl_unet_forward(sdxl_handle* h, const void* sample_nhwc8, const sdxl_batch* cond, void* pred_nhwc8, void* stream);
 /* d(pred) in -> runs every backward segment; d(sample) is not produced.  The conditioning gradients are, when the preceding
- * sdxl_unet_forward asked for them (sdxl_batch_ext): of <dpred, pred>, no scale, no gate */
+ * sdxl_unet_forward asked for them (sdxl_batch_ext): of <dpred, pred>, no scale, no gate; so are the residual gradients (sdxl_residuals) */
 SDXL_API int sdxl_unet_backward(sdxl_handle* h, const void* dpred_nhwc8, int first_micro, void* stream);
 
 /* fp32 grads -> bf16 (scaled) for the gradient exchange; global L2 norm of the fp32 grads */

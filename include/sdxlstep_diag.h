@@ -82,6 +82,15 @@ SDXL_API int sdxl_op_lora_project_layout(const float* dw, const void* A, const v
 SDXL_API int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out,
                                int in, int rank, float scale, int accumulate, void* stream);
 
+/* the two kernels of the additional skip residuals (sdxl_residuals; csrc/residual.hip) on caller buffers, as ConcatOp launches them:
+ * o [B * HW][Ca + Cb] bf16 = a [B * HW][Ca] | b [B * HW][Cb], with ra [B][Ca][HW] / rb [B][Cb][HW] (rdtype 0 = fp32, 1 = bf16; either may be NULL,
+ * both NULL = the plain concat) added to its half as bf16_rn(float(x) + float(r)), the bits of x where r == 0;
+ * dra [B][Ca][HW] / drb [B][Cb][HW] fp32 (either may be NULL) = float(g [B * HW][Ca + Cb]) of their column range, exact zeros when
+ * gate_dev (may be NULL) reads 0.  Ca, Cb multiples of 8, B <= 65535, every non-NULL pointer 16-byte aligned. */
+SDXL_API int sdxl_op_concat_residual(const void* a, int Ca, const void* b, int Cb, const void* ra, const void* rb, int rdtype, void* o, int B, int HW,
+                            void* stream);
+SDXL_API int sdxl_op_concat_residual_grad(const void* g, int Ca, int Cb, float* dra, float* drb, const float* gate_dev, int B, int HW, void* stream);
+
 /* which kernel a GEMM launch takes (csrc/gemm.hip, gemm_route: the single implementation of DESIGN.md section 4's table), without launching it and
  * without a device.  The descriptor is what the problem's line in the launch log (SDXL_LAUNCH_LOG) carries, in the same order: emit_bf16 / delta /
  * bias_grad are presence flags (GemmP::Cb, delta_out, bias_grad); Hm .. sd the 3x3 gather's image sizes and strides (taps != 1).  The same checks and normalisation as

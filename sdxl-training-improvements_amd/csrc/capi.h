@@ -16,6 +16,7 @@ struct StepState {  // what backward needs from the preceding forward
   float* d_ehs = nullptr;   // the conditioning gradients this micro-step asked for (sdxl_batch_ext): the caller's
   float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
   bool awaiting_bwd = false;   // a sdxl_forward_loss whose backward has not finished: the gradient selection may not change under it
+  ResidualReq res;             // the additional skip residuals this micro-step carried (sdxl_batch_res): the backward writes res.d_*
 };
 struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS call, keyed by (target list, rank, dtype)
   std::vector<int> params;
@@ -86,12 +87,37 @@ static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
 
 // sdxl_batch_cond's two fields (extra UNet input channels), read only behind SDXL_BATCH_COND: a caller without the flag passes a shorter
 // struct.  SDXL_BATCH_FLAGS: what the flags leave of ctx_len; either flag says that sdxl_batch_ext's fields are there.
-#define SDXL_BATCH_FLAGS (SDXL_BATCH_EXT | SDXL_BATCH_COND)
+#define SDXL_BATCH_FLAGS (SDXL_BATCH_EXT | SDXL_BATCH_COND | SDXL_BATCH_RES)
 static void read_input_cond(const sdxl_batch* b, const float** cond, int* channels) {
   *cond = nullptr; *channels = 0;
-  if (!(b->ctx_len & SDXL_BATCH_COND)) return;
+  if (!(b->ctx_len & (SDXL_BATCH_COND | SDXL_BATCH_RES))) return;      // (sdxl_batch_res holds a sdxl_batch_cond in full)
   const sdxl_batch_cond* x = (const sdxl_batch_cond*)b;
   *cond = x->input_cond; *channels = x->cond_channels;
+}
+// sdxl_batch_res's one field (additional skip residuals), read only behind SDXL_BATCH_RES, with its argument errors -- reported before
+// anything is copied or launched.  `out` is a copy of the caller's host arrays (they are read during the call only); nskip = the handle's
+// number of skips.  Without the flag or with a NULL pointer: out->present is false and nothing else of it is looked at.
+static int read_residuals(const sdxl_batch* b, int nskip, ResidualReq* out) {
+  *out = ResidualReq();
+  if (!b || !(b->ctx_len & SDXL_BATCH_RES)) return 0;
+  const sdxl_residuals* r = ((const sdxl_batch_res*)b)->residuals;
+  if (!r) return 0;
+  ARG_CHECK(r->n == nskip, "residuals: n = %d, the UNet saves %d skips (1 + 3 * layers_per_block + 2)", r->n, nskip);
+  ARG_CHECK(r->dtype == 0 || r->dtype == 1, "residuals: dtype %d (0 = fp32, 1 = bf16)", r->dtype);
+  for (int i = 0; i < nskip; ++i) {
+    ARG_CHECK(!r->down || ((uintptr_t)r->down[i] & 15) == 0, "residuals: down[%d] is not 16-byte aligned", i);
+    ARG_CHECK(!r->d_down || ((uintptr_t)r->d_down[i] & 15) == 0, "residuals: d_down[%d] is not 16-byte aligned", i);
+  }
+  ARG_CHECK(((uintptr_t)r->mid & 15) == 0, "residuals: mid is not 16-byte aligned");
+  ARG_CHECK(((uintptr_t)r->d_mid & 15) == 0, "residuals: d_mid is not 16-byte aligned");
+  out->present = true; out->dtype = r->dtype; out->mid = r->mid; out->d_mid = r->d_mid;
+  if (r->down) out->down.assign(r->down, r->down + nskip);
+  if (r->d_down) out->d_down.assign(r->d_down, r->d_down + nskip);
+  if (b->sampler) {
+    for (int i = 0; i < nskip; ++i) ARG_CHECK(!r->d_down || !r->d_down[i], "residuals: d_down[%d] cannot be combined with a sampler step", i);
+    ARG_CHECK(!r->d_mid, "residuals: d_mid cannot be combined with a sampler step");
+  }
+  return 0;
 }
 
 // sdxl_sampler_step's argument errors (reported before anything is copied or launched) and its kernel parameters.  The caller's struct

@@ -451,6 +451,7 @@ static int copy_cond_grads(sdxl_handle* h, hipStream_t st) {
 }
 static void set_cond_request(sdxl_handle* h, bool gated) {
   h->e.cond_ehs = h->step.d_ehs != nullptr; h->e.cond_pool = h->step.d_pool != nullptr; h->e.cond_gated = gated;
+  h->e.res_bwd = h->step.res.wants_grads() ? &h->step.res : nullptr; h->e.res_gated = gated;      // (the residual gradients: ConcatOp::bwd)
 }
 
 static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
@@ -576,6 +577,8 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   CHK(check_input_cond(e, b, true, &icond));
   float *d_ehs, *d_pool;
   CHK(read_cond_request(e, b, &d_ehs, &d_pool));
+  ResidualReq res;
+  CHK(read_residuals(b, e.num_skips(), &res));
   CHK(upload_cond(e, b, st));
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
   // kernels must not)
@@ -619,16 +622,25 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   const int ncond = icond ? e.cfg.in_channels - 4 : 0;      // (the preparation only: the backward never reads input_cond)
   Engine::GraphKey key{&p, 0, 0, 0, 0, 0u, loss_cfg_bits(*lc, b->tag_weights != nullptr), loss_cfg_bits2(*lc, *b) | ((unsigned)(icond != nullptr) << 10),
                       loss_huber_bits(*lc, *b)};
-  CHK(run_graphed(e, key, st, [&](hipStream_t s) -> int {
+  auto body = [&](hipStream_t s) -> int {
     CHK(launch_loss_prepare(L, s, icond, ncond));
     CHK(run_forward_ops(e, s));
     CHK(launch_loss_fwd(L, s));
     return 0;
-  }));
+  };
+  if (res.present) {      // additional residuals: kernel by kernel also in graph mode (the caller's tensors are read where they lie)
+    e.res_fwd = &res;
+    const int rc = body(st);
+    e.res_fwd = nullptr;
+    CHK(rc);
+  } else {
+    CHK(run_graphed(e, key, st, body));
+  }
   if (b->per_sample_loss)
     HIP_CHECK_RET(hipMemcpyAsync(b->per_sample_loss, p.F(p.ps_loss_off), sizeof(float) * p.B, hipMemcpyDeviceToDevice, st));
   h->step.lc = full; h->step.b = sb; h->step.valid = true;
   h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
+  h->step.res = std::move(res);
   h->step.awaiting_bwd = true;
   return 0;
 }
@@ -714,7 +726,7 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
     return run_backward_segment(e, k, first_micro != 0, s);
   };
   // a segment can only be captured on its own when it ends with the side stream joined (per-segment join mode, or the last one)
-  if (e.join_last_only) {
+  if (e.join_last_only || h->step.res.present) {      // (a micro-step that carried residuals: kernel by kernel, as its forward)
     CHK(body(st));
   } else {
     unsigned sbits;
@@ -738,13 +750,15 @@ int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* s
   set_cond_request(h, true);
   Engine::GraphKey key{e.cur, 2, 0, first_micro != 0, e.join_last_only, sbits, loss_cfg_bits(h->step.lc, h->step.b.tag_weights != nullptr),
                       loss_cfg_bits2(h->step.lc, h->step.b) | cond_bits(h->step), loss_huber_bits(h->step.lc, h->step.b)};
-  CHK(run_graphed(e, key, st, [&](hipStream_t s) -> int {
+  auto body = [&](hipStream_t s) -> int {
     LossP L;
     fill_loss(e, &h->step.lc, &h->step.b, grad_scale, L);
     CHK(launch_loss_bwd(L, s));
     for (int k = 0; k < e.nseg; ++k) CHK(run_backward_segment(e, k, first_micro != 0, s));
     return 0;
-  }));
+  };
+  if (h->step.res.present) CHK(body(st));      // (a micro-step that carried residuals: kernel by kernel, as its forward)
+  else CHK(run_graphed(e, key, st, body));
   h->step.awaiting_bwd = false;
   return copy_cond_grads(h, st);
 }
@@ -782,6 +796,8 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   CHK(check_input_cond(e, cond, cond->sampler != nullptr, &icond));
   float *d_ehs, *d_pool;
   CHK(read_cond_request(e, cond, &d_ehs, &d_pool));
+  ResidualReq res;
+  CHK(read_residuals(cond, e.num_skips(), &res));
   if (cond->sampler) {      // a sampling step: the forward runs on what the plan's input buffer holds, the step kernel writes the next input there
     SamplerP q;
     CHK(fill_sampler(cond->sampler, p.B, p.H * p.W, q));
@@ -789,7 +805,10 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
     q.pred = p.P(p.pred); q.x_in = p.P(p.x_in); q.part = p.F(p.samp_part_off);
     if (!q.init) {
       CHK(upload_cond(e, cond, st));
-      CHK(run_forward_ops(e, st));
+      e.res_fwd = res.present ? &res : nullptr;
+      const int rc = run_forward_ops(e, st);
+      e.res_fwd = nullptr;
+      CHK(rc);
     }
     return launch_sampler_step(q, st, icond, icond ? e.cfg.in_channels - 4 : 0);
   }
@@ -798,7 +817,11 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   h->step.awaiting_bwd = false;      // (this forward replaced the loss step's activations: nothing waits for that backward any more)
   const size_t rows = (size_t)p.B * p.H * p.W;      // (input_cond is not read here: the caller's sample carries every channel)
   HIP_CHECK_RET(hipMemcpyAsync(p.P(p.x_in), sample, rows * input_cs(e.cfg.in_channels) * sizeof(bf16), hipMemcpyDeviceToDevice, st));
-  CHK(run_forward_ops(e, st));
+  e.res_fwd = res.present ? &res : nullptr;
+  const int rc = run_forward_ops(e, st);
+  e.res_fwd = nullptr;
+  CHK(rc);
+  h->step.res = std::move(res);
   if (pred) HIP_CHECK_RET(hipMemcpyAsync(pred, p.P(p.pred), rows * 8 * sizeof(bf16), hipMemcpyDeviceToDevice, st));
   return 0;
 }

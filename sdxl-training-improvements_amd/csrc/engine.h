@@ -53,6 +53,22 @@ struct SrcParam {  // one diffusers state-dict tensor and where it lives in the 
 struct Engine;
 struct Plan;
 
+// The additional skip residuals of one micro-step (sdxl_residuals): a copy of the caller's host arrays, taken at the forward call and kept
+// (StepState) for that micro-step's backward.  Index = the skip in forward order; a null entry = nothing at that skip.
+struct ResidualReq {
+  bool present = false;      // the call carried a sdxl_residuals: its forward and backward launch kernel by kernel, also in graph mode
+  int dtype = 0;             // of down / mid: 0 fp32, 1 bf16
+  std::vector<const void*> down;
+  const void* mid = nullptr;
+  std::vector<float*> d_down;
+  float* d_mid = nullptr;
+  bool wants_grads() const {
+    if (d_mid) return true;
+    for (float* d : d_down) if (d) return true;
+    return false;
+  }
+};
+
 struct Op {
   int seg = 0;
   bool hoist_fwd = false;   // forward depends on the inputs only (cross-attention K/V projections of the prompt
@@ -175,6 +191,12 @@ struct Engine {
   bool cond_ehs = false, cond_pool = false;   // this micro-step's backward also produces d prompt_embeds / d pooled (set by the C ABI)
   bool cond_gated = false;                    // ... behind a loss (its gate scalar is read), not behind sdxl_unet_backward
   int launch_cond_grads(Plan& p, hipStream_t st);
+  // additional skip residuals (residual.hip), consulted by ConcatOp: res_fwd is set by the C ABI for the duration of a forward that carries
+  // them (the backward never reads the residuals), res_bwd before a backward whose micro-step asked for their gradients; res_gated as cond_gated
+  const ResidualReq* res_fwd = nullptr;
+  const ResidualReq* res_bwd = nullptr;
+  bool res_gated = false;
+  int num_skips() const { return 3 * cfg.layers_per_block + 3; }
   // Gradient selection (SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad, OFF after sdxl_create): one flag per state-dict tensor, 1 = the backward
   // produces its gradient.  A native parameter is frozen when EVERY tensor that maps into it is (fused q | k | v, the grouped K | V and
   // time-embedding projections: a tensor is a row range of the native weight), and an op skips its weight-gradient work -- the launch with

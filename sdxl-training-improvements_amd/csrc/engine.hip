@@ -736,12 +736,31 @@ struct ConcatOp : Op {
   Act *a, *b, *o;
   size_t do_off = NONE;
   Plan::GradDst da, db;
-  ConcatOp(Act* a_, Act* b_, Act* o_) : a(a_), b(b_), o(o_) {}
-  int fwd(Plan& p, hipStream_t st) override { return launch_concat(p.P(a), a->cols, p.P(b), b->cols, p.P(o), a->rows, st); }
+  int skip;       // index of b among the saved skips, forward order (sdxl_residuals.down)
+  bool first;     // the first concat of the up path: a is the mid block's output (sdxl_residuals.mid)
+  ConcatOp(Act* a_, Act* b_, Act* o_, int skip_, bool first_) : a(a_), b(b_), o(o_), skip(skip_), first(first_) {}
+  int fwd(Plan& p, hipStream_t st) override {
+    // an additional residual changes what the up path reads, never the saved skip: the down path and the backward keep the plain one
+    if (const ResidualReq* r = p.eng->res_fwd) {
+      const void* ra = first ? r->mid : nullptr;
+      const void* rb = skip < (int)r->down.size() ? r->down[skip] : nullptr;
+      if (ra || rb) return launch_concat_residual(p.P(a), a->cols, p.P(b), b->cols, ra, rb, r->dtype, p.P(o), p.B, (int)(a->rows / p.B), st);
+    }
+    return launch_concat(p.P(a), a->cols, p.P(b), b->cols, p.P(o), a->rows, st);
+  }
   void plan_bwd(Plan& p) override { do_off = o->goff; da = p.grad_dst(a); db = p.grad_dst(b); }
   int bwd(Plan& p, hipStream_t st, bool) override {
-    return launch_split_add(p.GP(do_off), p.GP(da.out), a->cols, p.GP(da.addend), p.GP(db.out), b->cols, p.GP(db.addend),
-                            a->rows, st);
+    CHK(launch_split_add(p.GP(do_off), p.GP(da.out), a->cols, p.GP(da.addend), p.GP(db.out), b->cols, p.GP(db.addend), a->rows, st));
+    // the gradient of a residual is its column range of the concat's output gradient (write-once: no ordering beyond the stream's),
+    // written straight into the caller's buffer
+    if (const ResidualReq* r = p.eng->res_bwd) {
+      float* dra = first ? r->d_mid : nullptr;
+      float* drb = skip < (int)r->d_down.size() ? r->d_down[skip] : nullptr;
+      if (dra || drb)
+        return launch_residual_grad(p.GP(do_off), a->cols, b->cols, dra, drb, p.eng->res_gated ? p.F(p.loss_off) + 7 : nullptr, p.B,
+                                    (int)(a->rows / p.B), st);
+    }
+    return 0;
   }
 };
 
@@ -1150,7 +1169,7 @@ struct Builder {
         Act* cat = nullptr;
         if (pl) {
           cat = pl->new_act(x->rows, prev + s.c);
-          tagseg(pl->add<ConcatOp>(x, s.a, cat), PRef());
+          tagseg(pl->add<ConcatOp>(x, s.a, cat, (int)skips.size(), ui == 0 && j == 0), PRef());      // (s is popped: its index is the new size)
         }
         x = resnet(p + ".resnets." + std::to_string(j), cat, h, w, prev + s.c, ch[lvl]);
         prev = ch[lvl];

@@ -139,6 +139,14 @@ int sdxl_op_cond_dgrad(int n, const void* const* A, const long* lda, const void*
   return launch_cond_dgrad(q, (hipStream_t)st);
 }
 
+// ---- additional skip residuals (residual.hip) on caller buffers: the two launches of ConcatOp with a residual request ----
+int sdxl_op_concat_residual(const void* a, int Ca, const void* b, int Cb, const void* ra, const void* rb, int rdtype, void* o, int B, int HW, void* st) {
+  return launch_concat_residual((const bf16*)a, Ca, (const bf16*)b, Cb, ra, rb, rdtype, (bf16*)o, B, HW, (hipStream_t)st);
+}
+int sdxl_op_concat_residual_grad(const void* g, int Ca, int Cb, float* dra, float* drb, const float* gate_dev, int B, int HW, void* st) {
+  return launch_residual_grad((const bf16*)g, Ca, Cb, dra, drb, gate_dev, B, HW, (hipStream_t)st);
+}
+
 int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off, long* ldb,
                              int* K) {
   H_CHECK(h);

@@ -355,6 +355,12 @@ int launch_colsum_partials(const bf16* x, float* out, int batches, int rows, int
 int launch_concat(const bf16* a, int Ca, const bf16* b, int Cb, bf16* o, long rows, hipStream_t st);
 int launch_split_add(const bf16* g, bf16* ga, int Ca, const bf16* add_a, bf16* gb, int Cb, const bf16* add_b,
                      long rows, hipStream_t st);                                                  // concat backward
+// residual.hip: the concat with an NCHW residual ra [B][Ca][HW] / rb [B][Cb][HW] (rdtype 0 fp32, 1 bf16; either may be null, both null =
+// launch_concat) added to its half, and the fp32 NCHW gradient of such a residual: columns of the concat's output gradient g [B * HW][Ca + Cb]
+// (exact zeros when *gate == 0; gate may be null).  Every non-null pointer 16-byte aligned.
+int launch_concat_residual(const bf16* a, int Ca, const bf16* b, int Cb, const void* ra, const void* rb, int rdtype, bf16* o, int B, int HW,
+                           hipStream_t st);
+int launch_residual_grad(const bf16* g, int Ca, int Cb, float* da, float* db, const float* gate, int B, int HW, hipStream_t st);
 int launch_upsample2x(const bf16* x, bf16* y, int B, int H, int W, int C, hipStream_t st);
 // GemmP::up2 companions: the [Cout][16][Cin] stencil weights of a [Cout][9][Cin] kernel; planar phase-major <-> high-resolution layout
 int launch_upconv_fold_weights(const bf16* w, bf16* weff, int Cout, int Cin, hipStream_t st);

@@ -103,6 +103,22 @@ class InputCondBatch(CondGradBatch):
     _fields_ = [("input_cond", C.c_void_p), ("cond_channels", C.c_int)]
 
 
+BATCH_RES = 0x40000    # SDXL_BATCH_RES, or-ed into Batch.ctx_len: the struct passed is a ResidualBatch
+
+
+class Residuals(C.Structure):
+    """sdxl_residuals: the additional skip residuals of one call (diffusers' down_block_additional_residuals / mid_block_additional_residual)
+    and the fp32 outputs of their gradients.  down / d_down are HOST arrays [n] of device pointers, entries may be NULL"""
+    _fields_ = [("n", C.c_int), ("dtype", C.c_int), ("down", C.POINTER(C.c_void_p)), ("mid", C.c_void_p),
+                ("d_down", C.POINTER(C.c_void_p)), ("d_mid", C.c_void_p)]
+
+
+class ResidualBatch(InputCondBatch):
+    """sdxl_batch_res: InputCondBatch + the host pointer to a Residuals, read only when ctx_len carries BATCH_RES (which also says that
+    every field of CondGradBatch and InputCondBatch is there)"""
+    _fields_ = [("residuals", C.POINTER(Residuals))]
+
+
 DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
 DTYPE_LORA_LAYOUTS = 4  # SDXL_DTYPE_LORA_LAYOUTS: the same two calls and struct, targets in the arena's packed layouts accepted (lora.py, kinds="all")
 
@@ -210,6 +226,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_sampler_step": [_vp, _vp, _vp, _i, _i, _i, _P(SamplerStep), _vp],
     "sdxl_debug_cond_operands": [_vp, _i, _i, _P(_i), _P(_sz), _P(_l), _P(_sz), _P(_l), _P(_i)],
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
+    "sdxl_op_concat_residual": [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "sdxl_op_concat_residual_grad": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_merge_layout": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],

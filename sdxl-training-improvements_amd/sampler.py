@@ -258,13 +258,16 @@ class NativeSampler:
     """sample(...) -> latents [B,4,H,W] fp32 on the device.  `unet` is a NativeUNet (its bound weight arena is what is sampled)."""
 
     def __init__(self, unet, method: str = "ddpm", prediction_type: str = "v_prediction", use_ztsnr: bool = True,
-                 parameterization: str = "trained", config=None, t_bf16: bool = True):
+                 parameterization: str = "trained", config=None, t_bf16: bool = True, control=None):
         method, prediction_type, parameterization = str(method).lower(), str(prediction_type).lower(), str(parameterization).lower()
         for key, val, known in (("method", method, METHODS), ("prediction_type", prediction_type, PREDICTION_TYPES),
                                 ("parameterization", parameterization, PARAMETERIZATIONS)):
             if val not in known:
                 raise ValueError(f"sampler {key}: unknown value {val!r} (expected one of {', '.join(known)})")
         self.unet = unet
+        # control(sample, timestep, batch) -> (down, mid), as NativeSDXLTrainer's: called before every forward with that forward's input
+        # (a_in x, clamped; the plan's batch: 2B rows with guidance) and time input; its outputs are added to the UNet's skips / mid output
+        self.control = control
         self.method, self.prediction_type, self.parameterization = method, prediction_type, parameterization
         self.use_ztsnr, self.t_bf16 = bool(use_ztsnr), bool(t_bf16)
         if config is None:
@@ -307,6 +310,21 @@ class NativeSampler:
     def plan_batch(B: int, guidance_scale: float) -> int:
         """the batch of the UNet plan: B without guidance (guidance_scale == 1), else 2B = [cond; uncond]"""
         return int(B) if float(guidance_scale) == 1.0 else 2 * int(B)
+
+    def _residuals(self, x, a_in: float, clamp: float, t_row, cfg: bool, cond) -> dict:
+        """the residuals keyword of one forward ({} without a control module: the call is then the one made without this feature)"""
+        if self.control is None:
+            return {}
+        dev = self.unet.device
+        with torch.no_grad():
+            s = x if float(a_in) == 1.0 else torch.tensor(float(a_in), dtype=torch.float32, device=x.device) * x
+            if float(clamp) > 0.0:
+                s = s.clamp(-float(clamp), float(clamp))
+            down, mid = self.control(torch.cat([s, s]) if cfg else s, t_row, cond)
+        outs = list(down) + [mid]
+        dt = torch.bfloat16 if all(t is None or t.dtype == torch.bfloat16 for t in outs) else torch.float32
+        conv = lambda t: None if t is None else t.detach().to(dev, dt).contiguous()
+        return dict(residuals=([conv(t) for t in down], conv(mid)))
 
     # ------------------------------------------------------------------ the loop
     def sample(self, prompt_embeds, pooled, time_ids, neg_prompt_embeds=None, neg_pooled=None, neg_time_ids=None, *,
@@ -383,13 +401,16 @@ class NativeSampler:
             if cfg:
                 c = torch.cat([c, c if neg_input_cond is None else neg_input_cond.detach().to(dev, torch.float32)])
             ic = dict(input_cond=c.contiguous())
+        cond = {"prompt_embeds": pe, "pooled_prompt_embeds": po, "time_ids": ti}      # what `control` gets as its batch (the plan's rows)
+        # forward f reads bf16(clamp(a_in x)): the first from sample_init, the others from the step before them
+        scale_of = lambda f, ks: (steps[0][0], steps[0][5]) if f == 0 else (ks[f - 1]["a_in_next"], ks[f - 1]["clamp"])
         if plain:
             # the time inputs of all forwards, uploaded once: row j is forward j's [PB] values
             tall = torch.tensor([[s[6]] * PB for s in steps], dtype=torch.float32).to(dev)
             ks = kernel_steps(steps, guidance_scale, guidance_rescale, cfg)
             net.sample_init(x, pe, po, ti, tall[0], cfg=cfg, a_in=steps[0][0], clamp=steps[0][5], **ic)
             for j, k in enumerate(ks):
-                net.sample_step(x, pe, po, ti, tall[j], **k, **ic)
+                net.sample_step(x, pe, po, ti, tall[j], **k, **ic, **self._residuals(x, *scale_of(j, ks), tall[j], cfg, cond))
             return x
         # every buffer of the extended steps is made and uploaded here, before the loop: no torch op runs between forwards
         tall = torch.tensor([[t] * PB for t in tin], dtype=torch.float32).to(dev)
@@ -418,7 +439,7 @@ class NativeSampler:
                 ex["xsave"] = xsave
             if k.get("s", 0) != 0:
                 ex["noise"], d = draws[d], d + 1
-            net.sample_step(x, pe, po, ti, tall[f], **k, **ex, **ic)
+            net.sample_step(x, pe, po, ti, tall[f], **k, **ex, **ic, **self._residuals(x, *scale_of(f, ks), tall[f], cfg, cond))
         return x
 
     def _start(self, n: int, B: int, H: int, W: int, init_latents, strength, inpaint_mask):

@@ -65,12 +65,15 @@ class _NativeLoss(torch.autograd.Function):
     """0-d loss whose backward runs the HIP backward with the incoming scale (so `(loss / N).backward()` works).
     prompt_embeds / pooled: the conditioning tensors the UNet read (after conditioning dropout) when one of them requires grad, else
     None.  Their gradients come back from the device (NativeUNet.read_cond_grads) in each input's device and dtype, so the caller's
-    autograd graph -- text encoders, an embedding table -- continues from here."""
+    autograd graph -- text encoders, an embedding table -- continues from here.
+    residuals: the additional skip residuals a `control` module produced (down ..., mid; None where nothing requires grad): their
+    gradients come back the same way (NativeUNet.read_residual_grads), so the control module trains through the loss."""
 
     @staticmethod
-    def forward(ctx, anchor, trainer, value, prompt_embeds=None, pooled=None):
+    def forward(ctx, anchor, trainer, value, prompt_embeds=None, pooled=None, *residuals):
         ctx.trainer = trainer
         ctx.cond = [None if t is None else (t.shape, t.dtype, t.device) for t in (prompt_embeds, pooled)]
+        ctx.res = [None if t is None else (t.shape, t.dtype, t.device) for t in residuals]
         return anchor.new_tensor(value)
 
     @staticmethod
@@ -87,7 +90,17 @@ class _NativeLoss(torch.autograd.Function):
                     shape, dtype, device = ctx.cond[i]
                     g = dev[i] if world == 1.0 else dev[i] * world
                     grads[i] = g.reshape(shape).to(device=device, dtype=dtype)
-        return None, None, None, grads[0], grads[1]
+        res = [None] * len(ctx.res)
+        if ctx.res and any(ctx.needs_input_grad[5:]):      # the same world-size factor as the conditioning gradients, for the same reason
+            world = float(ctx.trainer.sync.world)
+            d_down, d_mid = ctx.trainer.net.read_residual_grads()
+            dev = list(d_down or [None] * (len(ctx.res) - 1)) + [d_mid]
+            for i, meta in enumerate(ctx.res):
+                if meta is not None and ctx.needs_input_grad[5 + i] and dev[i] is not None:
+                    shape, dtype, device = meta
+                    g = dev[i] if world == 1.0 else dev[i] * world
+                    res[i] = g.reshape(shape).to(device=device, dtype=dtype)
+        return (None, None, None, grads[0], grads[1], *res)
 
 
 class NativeSDXLTrainer:
@@ -109,6 +122,9 @@ class NativeSDXLTrainer:
         self._check_loss_keys()
         self._check_sampler_keys()
         self.gradient_accumulation_steps = int(self.config.training.gradient_accumulation_steps)
+        # control(sample, timestep, batch) -> (down, mid): a module outside the UNet (a ControlNet) whose outputs are added to the skips and
+        # to the mid block's output (diffusers' down_block_additional_residuals / mid_block_additional_residual); None = none
+        self.control = kwargs.pop("control", None)
         unet = model.unet if hasattr(model, "unet") else model
         native_attrs = ("forward_loss", "backward", "read_loss", "zero_grads", "param_elems")
         self._torch_unet = None
@@ -335,7 +351,8 @@ class NativeSDXLTrainer:
         state changes: the next step has the bits it would have had without the call."""
         tc = self.config.training
         sampler = NativeSampler(self.net, self.method, str(tc.prediction_type), bool(self.config.model.use_ztsnr),
-                                self.sampler_parameterization, config=self.config, t_bf16=str(tc.mixed_precision) == "bf16")
+                                self.sampler_parameterization, config=self.config, t_bf16=str(tc.mixed_precision) == "bf16",
+                                **({} if self.control is None else dict(control=self.control)))      # (only when set)
         ic = {} if input_cond is None else dict(input_cond=input_cond, neg_input_cond=neg_input_cond)      # (only when given)
         with self._weights(self.validation_weights if weights is None else weights):
             return sampler.sample(prompt_embeds, pooled, time_ids, neg_prompt_embeds, neg_pooled, neg_time_ids, height=height,
@@ -448,11 +465,45 @@ class NativeSDXLTrainer:
             for k in ("prompt_embeds", "pooled_prompt_embeds"):
                 batch[k] = batch[k].detach() if torch.is_tensor(batch[k]) else batch[k]
 
+    def _control_ext(self, batch, lat, noise, sig_or_t, timestep, ext: Dict[str, Any], grads: bool) -> None:
+        """forward_loss's residuals from `control`, when one is set: the UNet input is built the way the loss preparation builds it
+        (scheduler.add_noise for ddpm, the optimal-transport path for flow matching; from noise_in under input perturbation),
+        control(sample, timestep, batch) runs under autograd (grads: compute_loss) or no_grad (evaluate), and the net gets the detached
+        residuals.  With grads, the residuals that require grad are kept for _NativeLoss and their gradients requested."""
+        self._res_inputs = ()
+        if self.control is None:
+            return
+        nin = ext.get("noise_in", noise).float()
+        dev = getattr(self.net, "device", None)
+        if self.method == "ddpm":
+            sample = lat + sig_or_t.view(-1, 1, 1, 1).to(lat.device) * nin.to(lat.device)
+            if self.config.model.use_ztsnr:
+                sample = torch.clamp(sample, -20000.0, 20000.0)
+        else:
+            t = sig_or_t.view(-1, 1, 1, 1).to(lat.device)
+            sample = (1 - t) * nin.to(lat.device) + t * lat
+        if dev is not None:
+            sample, timestep = sample.to(dev), timestep.to(dev)
+        with torch.enable_grad() if grads else torch.no_grad():
+            down, mid = self.control(sample, timestep, batch)
+        outs = list(down) + [mid]
+        bf = all(t is None or t.dtype == torch.bfloat16 for t in outs)
+        conv = lambda t: None if t is None else t.detach().to(dev if dev is not None else t.device, torch.bfloat16 if bf else torch.float32).contiguous()
+        ext["residuals"] = ([conv(t) for t in down], conv(mid))
+        if grads:
+            self._res_inputs = tuple(t if t is not None and t.requires_grad else None for t in outs)
+            want = [("mid" if i == len(outs) - 1 else i) for i, t in enumerate(self._res_inputs) if t is not None]
+            if want:
+                ext["residual_grads"] = want
+            else:
+                self._res_inputs = ()
+
     def _forward(self, batch, lat, noise, timesteps, generator, ext_over: Optional[Dict[str, Any]] = None, augment: bool = False,
-                 cond_grads: bool = False):
+                 cond_grads: bool = False, control_grads: bool = False):
         """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used.
         augment: apply the training-only recipes (noise offset, input perturbation, conditioning dropout; _augment).
-        cond_grads: compute_loss found a conditioning tensor that requires grad (_cond_request)"""
+        cond_grads: compute_loss found a conditioning tensor that requires grad (_cond_request)
+        control_grads: compute_loss under autograd: `control` runs with a graph and its residuals get their gradients (_control_ext)"""
         B = lat.shape[0]
         cm = self.config.model
         tag = batch.get("tag_weights")
@@ -469,6 +520,7 @@ class NativeSDXLTrainer:
             if cond_grads:
                 batch = dict(batch)
                 self._cond_request(batch, ext)
+            self._control_ext(batch, lat, noise, sig, ts, ext, control_grads)
             self.net.forward_loss("ddpm", lat, noise, sig, ts.float(), batch["prompt_embeds"],
                                   batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag,
                                   prediction_type=self.config.training.prediction_type,
@@ -490,6 +542,7 @@ class NativeSDXLTrainer:
         if cond_grads:
             batch = dict(batch)
             self._cond_request(batch, ext)
+        self._control_ext(batch, lat, noise, t, t_unet, ext, control_grads)
         self.net.forward_loss("flow_matching", lat, noise, t, t_unet, batch["prompt_embeds"],
                               batch["pooled_prompt_embeds"], batch["time_ids"], None if per_sample_tag else tag, **ext)
         return t
@@ -513,7 +566,8 @@ class NativeSDXLTrainer:
         cond = (self.conditioning_grads != "off" and torch.is_grad_enabled() and
                 any(torch.is_tensor(batch[k]) and batch[k].requires_grad for k in ("prompt_embeds", "pooled_prompt_embeds")))
         self._cond_inputs = (None, None)
-        ts = self._forward(batch, lat, noise, timesteps, generator, augment=True, cond_grads=cond)
+        self._res_inputs = ()
+        ts = self._forward(batch, lat, noise, timesteps, generator, augment=True, cond_grads=cond, control_grads=torch.is_grad_enabled())
         o = self.net.read_loss()                                        # the single host sync of the step
         numel = lat.numel()
         lr = self.optimizer.param_groups[0]["lr"] if self.optimizer is not None else 0.0
@@ -526,7 +580,7 @@ class NativeSDXLTrainer:
             metrics = {"loss": o[0], "x0_norm": math.sqrt(o[5]), "x1_norm": math.sqrt(o[6]),
                        "time_mean": float(ts.mean()), "time_std": float(ts.std()) if B > 1 else float("nan"),
                        "velocity_norm": math.sqrt(o[3]), "batch_size": B, "lr": lr}
-        loss = _NativeLoss.apply(self._anchor, self, o[0], *self._cond_inputs)
+        loss = _NativeLoss.apply(self._anchor, self, o[0], *self._cond_inputs, *self._res_inputs)
         out = {"loss": loss, "metrics": metrics}
         if bool(getattr(self.config.training, "log_per_sample_loss", False)):
             out["per_sample_loss"] = self.net.read_per_sample_loss()    # (after read_loss's sync: the copy only)

@@ -354,6 +354,69 @@ class NativeUNet:
         x.cond_channels = int(input_cond.shape[1])
         return x
 
+    def residual_shapes(self, B: int, H: int, W: int):
+        """([(B, C_i, h_i, w_i)] of the saved skips in forward (diffusers) order, the mid block's (B, C, h, w)): the shapes of
+        down_block_additional_residuals / mid_block_additional_residual for a plan of batch B and latent size H x W"""
+        ch, lpb = [int(c) for c in self.cfg.block_out_channels], int(self.cfg.layers_per_block)
+        out, h, w = [(B, ch[0], H, W)], H, W
+        for i in range(3):
+            out += [(B, ch[i], h, w)] * lpb
+            if i < 2:
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+                out.append((B, ch[i], h, w))
+        return out, (B, ch[2], h, w)
+
+    def _residual_batch(self, b, residuals, residual_grads, shape, what: str):
+        """b as a lib.ResidualBatch carrying the additional skip residuals and / or the request for their gradients (flagged), or b
+        itself when neither is given: without them every call is the one made before they existed.  residuals = (down, mid): down a
+        list of one tensor (or None) per skip or None, mid a tensor or None; each a contiguous fp32 or bf16 (one dtype for all) device
+        tensor of residual_shapes()'s shape -- checked, not converted (430 MB at SDXL-base B = 4 128 x 128: no silent copy).
+        residual_grads: True (every skip and mid), None, or a collection of skip indices and / or "mid"."""
+        self._d_down, self._d_mid = None, None
+        if residuals is None and not residual_grads:
+            return b
+        shapes, mid_shape = self.residual_shapes(*shape)
+        n = len(shapes)
+        down, mid = (None, None) if residuals is None else residuals
+        if down is not None and len(down) != n:
+            raise ValueError(f"{what}: residuals: expected {n} down residuals (one per skip, None allowed), got {len(down)}")
+        given = [(f"down[{i}]", t, shapes[i]) for i, t in enumerate(down or ()) if t is not None]
+        if mid is not None:
+            given.append(("mid", mid, mid_shape))
+        dt = given[0][1].dtype if given else torch.float32
+        for name, t, shp in given:
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{what}: residuals: {name} must be {shp}, got {tuple(t.shape)}")
+            if t.dtype not in (torch.float32, torch.bfloat16) or t.dtype != dt:
+                raise ValueError(f"{what}: residuals: {name} is {t.dtype}; every residual must be torch.float32 or every one torch.bfloat16")
+            if t.device.type != torch.device(self.device).type or not t.is_contiguous():
+                raise ValueError(f"{what}: residuals: {name} must be a contiguous device tensor")
+        want = set(range(n)) | {"mid"} if residual_grads is True else set(residual_grads or ())
+        if want - (set(range(n)) | {"mid"}):
+            raise ValueError(f"{what}: residual_grads {residual_grads!r}: expected True, None or a collection of skip indices 0..{n - 1} and 'mid'")
+        z = lambda shp: torch.empty(shp, dtype=torch.float32, device=self.device)
+        if want:
+            self._d_down = [z(shapes[i]) if i in want else None for i in range(n)]
+            self._d_mid = z(mid_shape) if "mid" in want else None
+        ptrs = lambda ts: None if ts is None else (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+        arr_down, arr_d = ptrs(None if down is None else list(down)), ptrs(self._d_down)
+        r = lib.Residuals(n, 0 if dt == torch.float32 else 1, arr_down, None if mid is None else mid.data_ptr(), arr_d,
+                          None if self._d_mid is None else self._d_mid.data_ptr())
+        self._keep = list(self._keep) + [t for _n, t, _s in given] + [arr_down, arr_d, r]
+        x = lib.ResidualBatch(*[getattr(b, f[0]) for f in lib.Batch._fields_])
+        for f in ("sampler", "d_prompt_embeds", "d_pooled", "input_cond", "cond_channels"):
+            if hasattr(b, f):
+                setattr(x, f, getattr(b, f))
+        x.ctx_len |= lib.BATCH_RES
+        x.residuals = C.pointer(r)
+        return x
+
+    def read_residual_grads(self):
+        """([d_down[i] | None per skip], d_mid | None) of the last call that asked for them (residual_grads) and whose backward has
+        been enqueued: fp32 NCHW, on the device, stream-ordered (no synchronisation); (None, None) when nothing was asked.  The
+        gradient of grad_scale x loss, as the parameter gradients of that micro-step (unet_backward: of <dpred, pred>)."""
+        return getattr(self, "_d_down", None), getattr(self, "_d_mid", None)
+
     def read_cond_grads(self):
         """(d_prompt_embeds [B,ctx,cross_attention_dim] | None, d_pooled [B,pooled_dim] | None) of the last micro-step that asked for
         them (forward_loss / unet_forward with cond_grads) and whose backward has been enqueued: fp32, on the device, stream-ordered
@@ -364,8 +427,12 @@ class NativeUNet:
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
                      use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
                      per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean",
-                     cond_grads=None, input_cond=None) -> None:
+                     cond_grads=None, input_cond=None, residuals=None, residual_grads=None) -> None:
         """loss preparation + UNet forward + loss; results stay on the device until read_loss().
+        residuals: (down, mid), diffusers' down_block_additional_residuals / mid_block_additional_residual (a ControlNet's outputs,
+        already scaled): added to the skips where the up path reads them and to the mid block's output (_residual_batch has the
+        shapes and dtypes).  residual_grads: True, None or a collection of skip indices / "mid": the backward of this micro-step also
+        produces the gradient with respect to those residuals, read with read_residual_grads().
         input_cond: [B, in_channels - 4, H, W], channels 4.. of the UNet input (rounded to bf16) of a UNet with in_channels > 4:
         required there, refused (by the library) with in_channels = 4.  Read by this call only; the backward does not need it.
         sample_weights: optional [B] s_b multiplied into each sample's loss and gradient.  loss_type "l2" | "huber" |
@@ -408,6 +475,7 @@ class NativeUNet:
         b.per_sample_loss = None if self._ps_loss is None else self._ps_loss.data_ptr()
         self._cond_request(cond_grads, B, b.ctx_len)
         b = self._input_cond_batch(self._cond_batch(b), input_cond, latents.shape, "forward_loss")
+        b = self._residual_batch(b, residuals, residual_grads, (B, latents.shape[2], latents.shape[3]), "forward_loss")
         lib.check(self.L.sdxl_forward_loss(self.h, C.byref(lc), C.byref(b), _stream()), "sdxl_forward_loss")
 
     def backward(self, grad_scale: float = 1.0, first_micro: bool = True, on_segment=None, segment_stream: bool = False) -> None:
@@ -469,15 +537,16 @@ class NativeUNet:
         return self._ps_loss.cpu()
 
     # UNet only (sample NCHW fp32/bf16 in, NCHW fp32 out) -- for parity tests and validation sampling
-    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids, cond_grads=None) -> torch.Tensor:
-        """cond_grads as in forward_loss: the following unet_backward also produces d prompt_embeds / d pooled of <dpred, pred>"""
+    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids, cond_grads=None, residuals=None, residual_grads=None) -> torch.Tensor:
+        """cond_grads as in forward_loss: the following unet_backward also produces d prompt_embeds / d pooled of <dpred, pred>;
+        residuals / residual_grads as in forward_loss (the gradients: of <dpred, pred>)"""
         B, Cc, H, W = sample.shape
         d = self.device
         dummy = torch.zeros(B, 4, H, W, device=d)
         tb = self._batch(dummy, dummy, torch.zeros(B), timestep, prompt_embeds, pooled, time_ids, None)
         b = lib.SamplerBatch(*[getattr(tb, f[0]) for f in lib.Batch._fields_])      # sdxl_batch in full, sampler = NULL
         self._cond_request(cond_grads, B, tb.ctx_len)
-        b = self._cond_batch(b)
+        b = self._residual_batch(self._cond_batch(b), residuals, residual_grads, (B, H, W), "unet_forward")
         cin = int(self.cfg.in_channels)      # the sample carries every input channel, packed into Cs columns
         if Cc != cin:
             raise ValueError(f"unet_forward: sample has {Cc} channels, the UNet has in_channels = {cin}")
@@ -488,7 +557,7 @@ class NativeUNet:
         return out8[:, :4].float().reshape(B, H, W, 4).permute(0, 3, 1, 2).contiguous()
 
     # ------------------------------------------------------------------ sampling (sampler.py drives these)
-    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str, planes=(), input_cond=None) -> None:
+    def _sampler_call(self, x, prompt_embeds, pooled, time_ids, timestep, step: "lib.SamplerStep", what: str, planes=(), input_cond=None, residuals=None) -> None:
         """sdxl_unet_forward with sdxl_batch.sampler set.  Every tensor is already on the device in the library's dtype and
         contiguous (checked, not converted: no torch arithmetic or copy runs here); the plan's batch is prompt_embeds' (B, or
         2B = [cond; uncond] with cfg), x is [B,4,H,W] fp32.  `planes`: (name, tensor, elements) of an extended step's buffers."""
@@ -510,35 +579,37 @@ class NativeUNet:
                              time_ids.data_ptr(), None)
         b.sampler = C.cast(C.pointer(step), C.POINTER(lib.SamplerStep))      # (a SamplerStepExt goes through the same pointer)
         b = self._input_cond_batch(b, input_cond, x.shape, what, rows=PB, convert=False)      # [PB, in_channels - 4, H, W]: the uncond half has rows of its own
+        b = self._residual_batch(b, residuals, None, (PB, H, W), what)      # [PB, C_i, h_i, w_i]: rows b + B feed the unconditional half
         lib.check(self.L.sdxl_unet_forward(self.h, None, C.byref(b), None, _stream()), what)
 
     def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0,
-                    input_cond=None) -> None:
+                    input_cond=None, residuals=None) -> None:
         """write the first UNet input of a sampling loop, bf16(clamp(a_in * x, +-clamp)), into the plan's input buffer (no forward).
         input_cond (in_channels > 4): [PB, in_channels - 4, H, W] fp32 on the device, PB = prompt_embeds' batch -- channels 4.. of
         the input, row b for the conditional half and row b + B for the unconditional one; the same for sample_step."""
         s = lib.SamplerStep(None, int(cfg), 1, 0.0, 0.0, 0.0, 0.0, float(a_in), float(clamp), 1.0, 0.0)
-        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init", input_cond=input_cond)
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, s, "sample_init", input_cond=input_cond, residuals=residuals)
 
     def sample_step(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg, a_skip, a_out, p, q, a_in_next=1.0, clamp=0.0,
                     guidance=1.0, guidance_rescale=0.0, init=0, hist=None, xsave=None, noise=None, r=0.0, u=0.0, s=0.0, save=0,
-                    mask=None, known=None, knoise=None, k_a=0.0, k_b=0.0, input_cond=None) -> None:
+                    mask=None, known=None, knoise=None, k_a=0.0, k_b=0.0, input_cond=None, residuals=None) -> None:
         """one forward on the plan's input buffer + the fused sampler step (include/sdxlstep.h sdxl_sampler_step): x is updated in
         place and the next input is left in the plan; stream-ordered, no synchronisation.  hist ... k_b are the fields of
         sdxl_sampler_step_ext ([B,4,H,W] fp32 device tensors, mask [B,H,W]); the extended struct and its flag are passed only when
-        one of them is given, otherwise the call is the plain step's."""
+        one of them is given, otherwise the call is the plain step's.  residuals: (down, mid) as in forward_loss, for the plan's batch
+        (2B rows with cfg); read by this step's forward only."""
         base = (None, int(cfg), int(init), float(a_skip), float(a_out), float(p), float(q), float(a_in_next), float(clamp),
                 float(guidance), float(guidance_rescale))
         tensors = (("hist", hist), ("xsave", xsave), ("noise", noise), ("mask", mask), ("known", known), ("knoise", knoise))
         if all(t is None for _n, t in tensors) and not any((r, u, s, save, k_a, k_b)):
-            self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, lib.SamplerStep(*base), "sample_step", input_cond=input_cond)
+            self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, lib.SamplerStep(*base), "sample_step", input_cond=input_cond, residuals=residuals)
             return
         st = lib.SamplerStepExt(*base)
         st.init |= lib.SAMPLER_EXT
         st.r, st.u, st.s, st.save, st.k_a, st.k_b = float(r), float(u), float(s), int(save), float(k_a), float(k_b)
         n = x.numel()
         planes = tuple((name, t, n // 4 if name == "mask" else n) for name, t in tensors if t is not None)
-        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, st, "sample_step", planes, input_cond=input_cond)
+        self._sampler_call(x, prompt_embeds, pooled, time_ids, timestep, st, "sample_step", planes, input_cond=input_cond, residuals=residuals)
 
     def unet_backward(self, dpred_nchw: torch.Tensor, first_micro: bool = True) -> None:
         B, Cc, H, W = dpred_nchw.shape
