@@ -186,7 +186,7 @@ typedef struct {
  * A pixel of the plan's input buffer is stored Cs = 8 channels wide for in_channels <= 8, else 16 ([B*H*W][Cs] bf16, the channels past
  * in_channels zero), and conv_in as [cout][9][Cs] with zero pad channels; callers only ever see [cout, in_channels, 3, 3]
  * (sdxl_load_weight, sdxl_export_weight, sdxl_export_grad, sdxl_param_info).  input_cond is read by the loss preparation / the sampler
- * step only: the backward never reads it (conv_in has no input gradient, and there is no gradient with respect to input_cond).  In graph
+ * step only: the backward never reads it (its gradient is channels 4 .. of the input gradient, on request: sdxl_batch_din).  In graph
  * mode it is staged inside the plan like the latents, and whether it is present is part of the capture key.
  * sdxl_forward_loss, sdxl_loss_fwd_bwd, sdxl_op_loss phase 0 and a sampler step (sdxl_unet_forward with `sampler`, init included) read
  * it; with cfg the plan's batch is 2B and row b of input_cond goes to the conditional half, row b + B to the unconditional one.
@@ -240,6 +240,37 @@ typedef struct {
   const sdxl_residuals* residuals;   /* HOST pointer, read during the call; NULL = none */
 } sdxl_batch_res;
 #define SDXL_BATCH_RES 0x40000   /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_res */
+
+/* Input gradient: the gradient with respect to the UNet input, the one tensor input that had none (prompt_embeds / pooled: sdxl_batch_ext;
+ * the additional residuals: sdxl_residuals).  The batch that asks for it is sdxl_batch_res with one output pointer appended (`base` IS that
+ * struct), passed as a sdxl_batch* with SDXL_BATCH_DIN or-ed into base.base.base.base.ctx_len: the flag says that the struct passed is this
+ * one, so every field of sdxl_batch_ext, sdxl_batch_cond and sdxl_batch_res is read as well and their flags need not be set beside it.
+ * Nothing behind `sampler` is read without a flag.
+ * sdxl_forward_loss, sdxl_loss_fwd_bwd and sdxl_unet_forward (without `sampler`) read the pointer and remember the request for that
+ * micro-step; the backward of that micro-step writes the buffer: sdxl_backward_segment of the segment that holds conv_in (executed last),
+ * sdxl_backward_all, sdxl_loss_fwd_bwd, sdxl_unet_backward.  The write goes straight from conv_in's backward (csrc/input_dgrad.hip) into the
+ * caller's buffer (nothing is allocated in the plan), stream-ordered, complete once the last-executed segment has been enqueued; the
+ * caller keeps the buffer alive until then.
+ * The value is the gradient of grad_scale x loss with respect to the UNet input as the UNet read it -- the bf16 [B*H*W][Cs] buffer the
+ * loss preparation wrote, or the caller's sample (sdxl_unet_forward) -- for channels 0 .. in_channels - 1 (the four latent channels, then
+ * the input_cond channels), in fp32, transposed to NCHW: dx[b][c][y][x] = sum over the nine taps and conv_in's output channels o of
+ * dy[b][y + 1 - ky][x + 1 - kx][o] * w[o][3 ky + kx][c], pixels outside the image contributing nothing, fp32 sums in a fixed order that
+ * depends on the shape alone (no atomics: bitwise reproducible).  The same scale and gradient gate as that micro-step's parameter
+ * gradients (a closed gate stores exact zeros; sdxl_unet_backward: of <dpred, pred>, no scale, no gate).  Always OVERWRITTEN, never
+ * accumulated: first_micro does not matter.  The chain rule through the loss preparation (x_t from latents and noise, a_in, the bf16
+ * rounding) is the caller's: INTEGRATION.md section 1 "Input gradients" has the formulas per method.
+ * The request changes no other bit (loss, parameter, conditioning and residual gradients) and combines with d_prompt_embeds, d_pooled,
+ * input_cond, residuals, d_down / d_mid and any sdxl_grad_select, an all-frozen UNet included.
+ * Graph mode.  The backward of a micro-step that asked for d_input launches kernel by kernel (the caller's buffer is written where it
+ * lies), as one that carried residuals does; its forward is the unflagged call's.
+ * Bad arguments (1, before any launch, the message names d_input): d_input together with `sampler`, a pointer that is not 16-byte
+ * aligned, a conv_in whose output width is not a multiple of 32 (SDXL-base: 320).  Without the flag or with d_input == NULL the launch
+ * sequence, every workspace offset and every bit are those of a call without this struct. */
+typedef struct {
+  sdxl_batch_res base;
+  float* d_input;   /* optional OUT, device fp32 [B, in_channels, H, W] NCHW contiguous, 16-byte aligned; NULL = none */
+} sdxl_batch_din;
+#define SDXL_BATCH_DIN 0x80000   /* or-ed into sdxl_batch.ctx_len: the struct passed is a sdxl_batch_din */
 
 SDXL_API const char* sdxl_last_error(void);
 SDXL_API int sdxl_version(void);
@@ -392,8 +423,8 @@ SDXL_API int sdxl_read_loss(sdxl_handle* h, float out[8], void* stream);
  * of a loop.  cfg with an odd plan batch, x == NULL or a non-finite scalar is a bad argument (1), reported before any launch.  The sampler
  * path always launches kernel by kernel, also in graph mode. */
 SDXL_API int sdxl_unet_forward(sdxl_handle* h, const void* sample_nhwc8, const sdxl_batch* cond, void* pred_nhwc8, void* stream);
-/* d(pred) in -> runs every backward segment; d(sample) is not produced.  The conditioning gradients are, when the preceding
- * sdxl_unet_forward asked for them (sdxl_batch_ext): of <dpred, pred>, no scale, no gate; so are the residual gradients (sdxl_residuals) */
+/* d(pred) in -> runs every backward segment.  The conditioning gradients are produced when the preceding sdxl_unet_forward asked for them
+ * (sdxl_batch_ext): of <dpred, pred>, no scale, no gate; so are the residual gradients (sdxl_residuals) and d(sample) (sdxl_batch_din) */
 SDXL_API int sdxl_unet_backward(sdxl_handle* h, const void* dpred_nhwc8, int first_micro, void* stream);
 
 /* fp32 grads -> bf16 (scaled) for the gradient exchange; global L2 norm of the fp32 grads */

@@ -91,6 +91,18 @@ SDXL_API int sdxl_op_concat_residual(const void* a, int Ca, const void* b, int C
                             void* stream);
 SDXL_API int sdxl_op_concat_residual_grad(const void* g, int Ca, int Cb, float* dra, float* drb, const float* gate_dev, int B, int HW, void* stream);
 
+/* the input-gradient kernel (csrc/input_dgrad.hip; the request: sdxl_batch_din) on caller buffers, through the launcher conv_in's backward calls:
+ * dx [B][in_channels][H][W] fp32 (overwritten) = sum over ky, kx, o of dy [B * H * W][Cout] bf16 at pixel (y + 1 - ky, x + 1 - kx) times
+ * w [Cout][9][Cs] bf16 (the arena's layout: Cs = 8 for in_channels <= 8, else 16; pad channels zero), pixels outside the image contributing
+ * nothing; fp32 sums in a fixed order (no atomics).  Exact zeros, dy not read, when gate_dev (may be NULL) reads 0.  Cout % 32 == 0,
+ * in_channels 1 .. 16, any B, H, W >= 1; dy, w, dx 16-byte aligned. */
+SDXL_API int sdxl_op_input_dgrad(const void* dy, const void* w, float* dx, const float* gate_dev, int B, int H, int W, int in_channels, int Cout,
+                        void* stream);
+/* where the current plan's input-gradient launch finds its operands, so that a test can hand the same buffers to sdxl_op_input_dgrad:
+ * dy = workspace + *dy_ws_byte_off (bf16 [B * H * W][*Cout], conv_in's output gradient, intact once a backward has finished), w = weight
+ * arena + *w_elem_off (bf16 [*Cout][9][Cs]). */
+SDXL_API int sdxl_debug_input_dgrad_operands(sdxl_handle* h, size_t* dy_ws_byte_off, size_t* w_elem_off, int* Cout);
+
 /* which kernel a GEMM launch takes (csrc/gemm.hip, gemm_route: the single implementation of DESIGN.md section 4's table), without launching it and
  * without a device.  The descriptor is what the problem's line in the launch log (SDXL_LAUNCH_LOG) carries, in the same order: emit_bf16 / delta /
  * bias_grad are presence flags (GemmP::Cb, delta_out, bias_grad); Hm .. sd the 3x3 gather's image sizes and strides (taps != 1).  The same checks and normalisation as

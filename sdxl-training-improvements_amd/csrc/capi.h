@@ -17,6 +17,7 @@ struct StepState {  // what backward needs from the preceding forward
   float* d_pool = nullptr;  // buffers, written behind the backward from the plan's
   bool awaiting_bwd = false;   // a sdxl_forward_loss whose backward has not finished: the gradient selection may not change under it
   ResidualReq res;             // the additional skip residuals this micro-step carried (sdxl_batch_res): the backward writes res.d_*
+  float* d_input = nullptr;    // the input gradient this micro-step asked for (sdxl_batch_din): the caller's buffer, written by conv_in's backward
 };
 struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS call, keyed by (target list, rank, dtype)
   std::vector<int> params;
@@ -87,10 +88,10 @@ static int check_loss_ext(const sdxl_loss_config* lc, const sdxl_batch* b) {
 
 // sdxl_batch_cond's two fields (extra UNet input channels), read only behind SDXL_BATCH_COND: a caller without the flag passes a shorter
 // struct.  SDXL_BATCH_FLAGS: what the flags leave of ctx_len; either flag says that sdxl_batch_ext's fields are there.
-#define SDXL_BATCH_FLAGS (SDXL_BATCH_EXT | SDXL_BATCH_COND | SDXL_BATCH_RES)
+#define SDXL_BATCH_FLAGS (SDXL_BATCH_EXT | SDXL_BATCH_COND | SDXL_BATCH_RES | SDXL_BATCH_DIN)
 static void read_input_cond(const sdxl_batch* b, const float** cond, int* channels) {
   *cond = nullptr; *channels = 0;
-  if (!(b->ctx_len & (SDXL_BATCH_COND | SDXL_BATCH_RES))) return;      // (sdxl_batch_res holds a sdxl_batch_cond in full)
+  if (!(b->ctx_len & (SDXL_BATCH_COND | SDXL_BATCH_RES | SDXL_BATCH_DIN))) return;      // (sdxl_batch_res / sdxl_batch_din hold a sdxl_batch_cond in full)
   const sdxl_batch_cond* x = (const sdxl_batch_cond*)b;
   *cond = x->input_cond; *channels = x->cond_channels;
 }
@@ -99,7 +100,7 @@ static void read_input_cond(const sdxl_batch* b, const float** cond, int* channe
 // number of skips.  Without the flag or with a NULL pointer: out->present is false and nothing else of it is looked at.
 static int read_residuals(const sdxl_batch* b, int nskip, ResidualReq* out) {
   *out = ResidualReq();
-  if (!b || !(b->ctx_len & SDXL_BATCH_RES)) return 0;
+  if (!b || !(b->ctx_len & (SDXL_BATCH_RES | SDXL_BATCH_DIN))) return 0;      // (sdxl_batch_din holds a sdxl_batch_res in full)
   const sdxl_residuals* r = ((const sdxl_batch_res*)b)->residuals;
   if (!r) return 0;
   ARG_CHECK(r->n == nskip, "residuals: n = %d, the UNet saves %d skips (1 + 3 * layers_per_block + 2)", r->n, nskip);
@@ -117,6 +118,20 @@ static int read_residuals(const sdxl_batch* b, int nskip, ResidualReq* out) {
     for (int i = 0; i < nskip; ++i) ARG_CHECK(!r->d_down || !r->d_down[i], "residuals: d_down[%d] cannot be combined with a sampler step", i);
     ARG_CHECK(!r->d_mid, "residuals: d_mid cannot be combined with a sampler step");
   }
+  return 0;
+}
+
+// sdxl_batch_din's one field (the input gradient's output), read only behind SDXL_BATCH_DIN, with its argument errors -- reported before
+// anything is copied or launched.  conv_in_cout: the width of conv_in's output (input_dgrad.hip reduces it in steps of 32).
+static int read_input_grad(const sdxl_batch* b, int conv_in_cout, float** d_input) {
+  *d_input = nullptr;
+  if (!b || !(b->ctx_len & SDXL_BATCH_DIN)) return 0;
+  float* d = ((const sdxl_batch_din*)b)->d_input;
+  if (!d) return 0;
+  ARG_CHECK(!b->sampler, "d_input cannot be combined with a sampler step");
+  ARG_CHECK(((uintptr_t)d & 15) == 0, "d_input is not 16-byte aligned");
+  ARG_CHECK(conv_in_cout % 32 == 0, "d_input: conv_in's output width %d is not a multiple of 32", conv_in_cout);
+  *d_input = d;
   return 0;
 }
 

@@ -452,6 +452,7 @@ static int copy_cond_grads(sdxl_handle* h, hipStream_t st) {
 static void set_cond_request(sdxl_handle* h, bool gated) {
   h->e.cond_ehs = h->step.d_ehs != nullptr; h->e.cond_pool = h->step.d_pool != nullptr; h->e.cond_gated = gated;
   h->e.res_bwd = h->step.res.wants_grads() ? &h->step.res : nullptr; h->e.res_gated = gated;      // (the residual gradients: ConcatOp::bwd)
+  h->e.din = h->step.d_input; h->e.din_gated = gated;                                              // (the input gradient: conv_in's ConvOp::bwd)
 }
 
 static int upload_cond(Engine& e, const sdxl_batch* b, hipStream_t st) {
@@ -579,6 +580,8 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   CHK(read_cond_request(e, b, &d_ehs, &d_pool));
   ResidualReq res;
   CHK(read_residuals(b, e.num_skips(), &res));
+  float* d_input;
+  CHK(read_input_grad(b, e.cfg.block_out_channels[0], &d_input));
   CHK(upload_cond(e, b, st));
   // the step's inputs are staged at fixed addresses inside the plan (the caller's tensors move from step to step; the captured
   // kernels must not)
@@ -641,6 +644,7 @@ int sdxl_forward_loss(sdxl_handle* h, const sdxl_loss_config* lc, const sdxl_bat
   h->step.lc = full; h->step.b = sb; h->step.valid = true;
   h->step.d_ehs = d_ehs; h->step.d_pool = d_pool;
   h->step.res = std::move(res);
+  h->step.d_input = d_input;
   h->step.awaiting_bwd = true;
   return 0;
 }
@@ -726,7 +730,7 @@ int sdxl_backward_segment(sdxl_handle* h, int k, float grad_scale, int first_mic
     return run_backward_segment(e, k, first_micro != 0, s);
   };
   // a segment can only be captured on its own when it ends with the side stream joined (per-segment join mode, or the last one)
-  if (e.join_last_only || h->step.res.present) {      // (a micro-step that carried residuals: kernel by kernel, as its forward)
+  if (e.join_last_only || h->step.res.present || h->step.d_input) {      // (a micro-step that carried residuals: kernel by kernel, as its forward; one that asked for d_input: its kernel writes the caller's buffer)
     CHK(body(st));
   } else {
     unsigned sbits;
@@ -757,7 +761,7 @@ int sdxl_backward_all(sdxl_handle* h, float grad_scale, int first_micro, void* s
     for (int k = 0; k < e.nseg; ++k) CHK(run_backward_segment(e, k, first_micro != 0, s));
     return 0;
   };
-  if (h->step.res.present) CHK(body(st));      // (a micro-step that carried residuals: kernel by kernel, as its forward)
+  if (h->step.res.present || h->step.d_input) CHK(body(st));      // (a micro-step that carried residuals or asked for d_input: kernel by kernel)
   else CHK(run_graphed(e, key, st, body));
   h->step.awaiting_bwd = false;
   return copy_cond_grads(h, st);
@@ -798,6 +802,8 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   CHK(read_cond_request(e, cond, &d_ehs, &d_pool));
   ResidualReq res;
   CHK(read_residuals(cond, e.num_skips(), &res));
+  float* d_input;
+  CHK(read_input_grad(cond, e.cfg.block_out_channels[0], &d_input));
   if (cond->sampler) {      // a sampling step: the forward runs on what the plan's input buffer holds, the step kernel writes the next input there
     SamplerP q;
     CHK(fill_sampler(cond->sampler, p.B, p.H * p.W, q));
@@ -822,6 +828,7 @@ int sdxl_unet_forward(sdxl_handle* h, const void* sample, const sdxl_batch* cond
   e.res_fwd = nullptr;
   CHK(rc);
   h->step.res = std::move(res);
+  h->step.d_input = d_input;
   if (pred) HIP_CHECK_RET(hipMemcpyAsync(pred, p.P(p.pred), rows * 8 * sizeof(bf16), hipMemcpyDeviceToDevice, st));
   return 0;
 }

@@ -116,6 +116,7 @@ struct Plan {
   struct CondSrc { size_t dy_off = NONE; long lda = 0; PRef w; long ldb = 0; int K = 0; };
   CondSrc cond_kv[2], cond_add;        // the hoisted K | V projections in forward order (at most one per attention width); add_embedding.linear_1
   int cond_nkv = 0;
+  CondSrc din_src;                     // conv_in's output gradient and weight, the operands of the input gradient (K = its output width); recorded by its plan_bwd
   size_t dehs_off = NONE, dpool_off = NONE, cond_slab_off = NONE;
   // direct adapter gradients (lora_grad.hip, Engine::lora): scratch of the widest targeted op, shared and stream-ordered (every launch
   // is on the side stream, or all on the caller's); nothing is reserved -- no offset of the plan moves -- without adapters
@@ -197,6 +198,10 @@ struct Engine {
   const ResidualReq* res_bwd = nullptr;
   bool res_gated = false;
   int num_skips() const { return 3 * cfg.layers_per_block + 3; }
+  // input gradient (input_dgrad.hip), consulted by the ConvOp that reads the plan's x_in (conv_in): the caller's fp32 [B, in_channels, H, W]
+  // buffer of the micro-step whose backward runs (sdxl_batch_din), set by the C ABI beside res_bwd; null = none; din_gated as cond_gated
+  float* din = nullptr;
+  bool din_gated = false;
   // Gradient selection (SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad, OFF after sdxl_create): one flag per state-dict tensor, 1 = the backward
   // produces its gradient.  A native parameter is frozen when EVERY tensor that maps into it is (fused q | k | v, the grouped K | V and
   // time-embedding projections: a tensor is a row range of the native weight), and an op skips its weight-gradient work -- the launch with

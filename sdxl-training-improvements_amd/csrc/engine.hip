@@ -436,6 +436,7 @@ struct ConvOp : Op {
   }
   void plan_bwd(Plan& p) override {
     dy_off = y->goff;
+    if (x == p.x_in) { p.din_src.dy_off = dy_off; p.din_src.w = w; p.din_src.K = Cout; p.din_src.lda = Cout; p.din_src.ldb = 9L * Cin; }      // (sdxl_debug_input_dgrad_operands)
     if (resid) {
       resid_alias = p.grad_alias(resid, y) ? 1 : 0;
       if (!resid_alias) dres = p.grad_dst(resid);
@@ -516,6 +517,10 @@ struct ConvOp : Op {
       if (KNOB(7) > 0) g.cfg = KNOB(7);     // experiment: configuration of the conv dgrads
       CHK(launch_gemm(g, st));
     }
+    // conv_in (its x is the plan's input, which has no gradient inside the plan): the input gradient, when this micro-step asked for it,
+    // in fp32 NCHW straight into the caller's buffer (write-once: no ordering beyond the stream's)
+    if (x == p.x_in && p.eng->din)
+      CHK(launch_input_dgrad(dy, p.eng->Wp(w), p.eng->din, p.eng->din_gated ? p.F(p.loss_off) + 7 : nullptr, Bn, H, W, p.eng->cfg.in_channels, Cout, st));
     return 0;
   }
 };

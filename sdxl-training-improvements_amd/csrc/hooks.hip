@@ -147,6 +147,20 @@ int sdxl_op_concat_residual_grad(const void* g, int Ca, int Cb, float* dra, floa
   return launch_residual_grad((const bf16*)g, Ca, Cb, dra, drb, gate_dev, B, HW, (hipStream_t)st);
 }
 
+// ---- input gradient (input_dgrad.hip) on caller buffers: the launch of conv_in's backward with a sdxl_batch_din request ----
+int sdxl_op_input_dgrad(const void* dy, const void* w, float* dx, const float* gate_dev, int B, int H, int W, int in_channels, int Cout, void* st) {
+  return launch_input_dgrad((const bf16*)dy, (const bf16*)w, dx, gate_dev, B, H, W, in_channels, Cout, (hipStream_t)st);
+}
+int sdxl_debug_input_dgrad_operands(sdxl_handle* h, size_t* dy_ws_byte_off, size_t* w_elem_off, int* Cout) {
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(dy_ws_byte_off && w_elem_off && Cout, "null output");
+  const Plan::CondSrc& s = h->e.cur->din_src;
+  ARG_CHECK(s.dy_off != NONE, "input dgrad operands: the plan has no backward for conv_in");
+  *dy_ws_byte_off = s.dy_off; *w_elem_off = s.w.off; *Cout = s.K;
+  return 0;
+}
+
 int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, size_t* a_ws_byte_off, long* lda, size_t* w_elem_off, long* ldb,
                              int* K) {
   H_CHECK(h);

@@ -361,6 +361,11 @@ int launch_split_add(const bf16* g, bf16* ga, int Ca, const bf16* add_a, bf16* g
 int launch_concat_residual(const bf16* a, int Ca, const bf16* b, int Cb, const void* ra, const void* rb, int rdtype, bf16* o, int B, int HW,
                            hipStream_t st);
 int launch_residual_grad(const bf16* g, int Ca, int Cb, float* da, float* db, const float* gate, int B, int HW, hipStream_t st);
+// input_dgrad.hip: the input gradient of conv_in (sdxl_batch_din), dx [B][in_channels][H][W] fp32 NCHW =
+// sum over taps and o of dy [B * H * W][Cout] (pixel y + 1 - ky, x + 1 - kx) . w [Cout][9][Cs] (Cs = input_cs(in_channels), zero pad channels),
+// fp32 sums in a fixed order (no atomics); exact zeros, dy not read, when *gate == 0 (gate may be null).  Cout % 32 == 0, in_channels 1 .. 16,
+// any B, H, W >= 1; dy, w, dx 16-byte aligned.  Not a GEMM route: a kernel and a launcher of its own.
+int launch_input_dgrad(const bf16* dy, const bf16* w, float* dx, const float* gate, int B, int H, int W, int in_channels, int Cout, hipStream_t st);
 int launch_upsample2x(const bf16* x, bf16* y, int B, int H, int W, int C, hipStream_t st);
 // GemmP::up2 companions: the [Cout][16][Cin] stencil weights of a [Cout][9][Cin] kernel; planar phase-major <-> high-resolution layout
 int launch_upconv_fold_weights(const bf16* w, bf16* weff, int Cout, int Cin, hipStream_t st);
@@ -428,7 +433,7 @@ struct LossP {
   float* mnorm;           // masked_mean: [B] scratch, M_b left by loss_finalize_kernel for loss_bwd_kernel
 };
 // ---- extra UNet input channels (in_channels > 4): what the COND instantiations of loss_prepare_kernel take; LossP itself, and with it
-// every kernel of the 4-channel UNet, stays as it is.  Read by the preparation only (conv_in has no input gradient). ----
+// every kernel of the 4-channel UNet, stays as it is.  Read by the preparation only (its gradient: input_dgrad.hip). ----
 struct LossCondP : LossP {
   const float* cond;      // [B][ncond][HW] fp32 NCHW: channels 4 .. 4 + ncond - 1 of the UNet input, bf16(cond) round to nearest even
   int ncond;              // in_channels - 4, 1 .. 12; unet_in is [B*HW][Cs] with Cs = input_cs(4 + ncond), the channels behind zero

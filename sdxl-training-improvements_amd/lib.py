@@ -119,6 +119,15 @@ class ResidualBatch(InputCondBatch):
     _fields_ = [("residuals", C.POINTER(Residuals))]
 
 
+BATCH_DIN = 0x80000    # SDXL_BATCH_DIN, or-ed into Batch.ctx_len: the struct passed is an InputGradBatch
+
+
+class InputGradBatch(ResidualBatch):
+    """sdxl_batch_din: ResidualBatch + the optional fp32 output [B, in_channels, H, W] of the gradient with respect to the UNet input, read
+    only when ctx_len carries BATCH_DIN (which also says that every field of CondGradBatch, InputCondBatch and ResidualBatch is there)"""
+    _fields_ = [("d_input", C.c_void_p)]
+
+
 DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
 DTYPE_LORA_LAYOUTS = 4  # SDXL_DTYPE_LORA_LAYOUTS: the same two calls and struct, targets in the arena's packed layouts accepted (lora.py, kinds="all")
 
@@ -228,6 +237,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_cond_dgrad": [_i, _P(_vp), _P(_l), _P(_vp), _P(_l), _P(_i), _vp, _l, _i, _i, _vp],
     "sdxl_op_concat_residual": [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
     "sdxl_op_concat_residual_grad": [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "sdxl_op_input_dgrad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "sdxl_debug_input_dgrad_operands": [_vp, _P(_sz), _P(_sz), _P(_i)],
     "sdxl_op_lora_merge": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_merge_layout": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],

@@ -61,17 +61,26 @@ INPUT_CONDITIONINGS = ("none", "inpaint", "concat")
 CONDITIONING_GRADS = ("auto", "off")
 
 
+_INPUT_COND = object()      # marks the input_cond tensor behind _NativeLoss.apply's residuals: (..., *residuals, _INPUT_COND, input_cond)
+
+
 class _NativeLoss(torch.autograd.Function):
     """0-d loss whose backward runs the HIP backward with the incoming scale (so `(loss / N).backward()` works).
     prompt_embeds / pooled: the conditioning tensors the UNet read (after conditioning dropout) when one of them requires grad, else
     None.  Their gradients come back from the device (NativeUNet.read_cond_grads) in each input's device and dtype, so the caller's
     autograd graph -- text encoders, an embedding table -- continues from here.
     residuals: the additional skip residuals a `control` module produced (down ..., mid; None where nothing requires grad): their
-    gradients come back the same way (NativeUNet.read_residual_grads), so the control module trains through the loss."""
+    gradients come back the same way (NativeUNet.read_residual_grads), so the control module trains through the loss.
+    An input_cond that requires grad follows the residuals behind the marker _INPUT_COND: it gets channels 4.. of the input gradient
+    (NativeUNet.read_input_grad), so an encoder in front of the UNet input trains through the loss."""
 
     @staticmethod
     def forward(ctx, anchor, trainer, value, prompt_embeds=None, pooled=None, *residuals):
         ctx.trainer = trainer
+        ctx.icond = None
+        if len(residuals) >= 2 and residuals[-2] is _INPUT_COND:
+            t, residuals = residuals[-1], residuals[:-2]
+            ctx.icond = (t.shape, t.dtype, t.device)
         ctx.cond = [None if t is None else (t.shape, t.dtype, t.device) for t in (prompt_embeds, pooled)]
         ctx.res = [None if t is None else (t.shape, t.dtype, t.device) for t in residuals]
         return anchor.new_tensor(value)
@@ -100,7 +109,15 @@ class _NativeLoss(torch.autograd.Function):
                     shape, dtype, device = meta
                     g = dev[i] if world == 1.0 else dev[i] * world
                     res[i] = g.reshape(shape).to(device=device, dtype=dtype)
-        return (None, None, None, grads[0], grads[1], *res)
+        if ctx.icond is None:
+            return (None, None, None, grads[0], grads[1], *res)
+        d_ic = None
+        if ctx.needs_input_grad[-1]:      # channels 4.. of d_input; the same world-size factor as the conditioning gradients, for the same reason
+            world = float(ctx.trainer.sync.world)
+            shape, dtype, device = ctx.icond
+            g = ctx.trainer.net.read_input_grad()[:, 4:]
+            d_ic = (g if world == 1.0 else g * world).reshape(shape).to(device=device, dtype=dtype)
+        return (None, None, None, grads[0], grads[1], *res, None, d_ic)
 
 
 class NativeSDXLTrainer:
@@ -240,32 +257,40 @@ class NativeSDXLTrainer:
         if self.input_conditioning == "none" and self.input_cond_dropout_prob > 0.0:
             raise ValueError("training.input_cond_dropout_prob: needs training.input_conditioning 'inpaint' or 'concat'")
 
-    def _input_cond(self, batch, B: int, H: int, W: int) -> torch.Tensor:
-        """the extra input channels [B, in_channels - 4, H, W] fp32 of a batch, a new tensor (ValueError names a missing key or a wrong shape)"""
+    def _input_cond(self, batch, B: int, H: int, W: int, detach: bool = True) -> torch.Tensor:
+        """the extra input channels [B, in_channels - 4, H, W] fp32 of a batch, a new tensor (ValueError names a missing key or a wrong shape);
+        detach=False keeps the autograd graph of the batch's tensors (_input_cond_ext, when one of them requires grad)"""
         def get(key, shapes):
             if key not in batch or batch[key] is None:
                 raise ValueError(f"training.input_conditioning {self.input_conditioning!r}: the batch has no {key!r}")
             t = torch.as_tensor(batch[key])
             if tuple(t.shape) not in shapes:
                 raise ValueError(f"batch[{key!r}]: expected shape {' or '.join(str(s) for s in shapes)}, got {tuple(t.shape)}")
-            return t.detach().to(torch.float32)
+            return (t.detach() if detach else t).to(torch.float32)
         if self.input_conditioning == "inpaint":        # diffusers' order: latents | mask | masked-image latents
             m = get("inpaint_mask", ((B, 1, H, W), (B, H, W))).reshape(B, 1, H, W)
             ml = get("masked_latents", ((B, 4, H, W),))
             return torch.cat([m, ml.to(m.device)], dim=1)
         return get("cond_latents", ((B, self.in_channels - 4, H, W),)).clone()
 
-    def _input_cond_ext(self, batch, lat, generator, augment: bool, ext: Dict[str, Any]) -> None:
+    def _input_cond_ext(self, batch, lat, generator, augment: bool, ext: Dict[str, Any], grads: bool = False) -> None:
         """forward_loss's input_cond, when the key is on; with augment (a training step) the per-sample dropout, drawn after every
-        other draw of the step and only when its key is on"""
+        other draw of the step and only when its key is on.  grads (compute_loss under autograd): when the assembled tensor requires
+        grad -- an encoder produced the batch's cond_latents / masked_latents -- it is kept for _NativeLoss and the input gradient is
+        requested; the net gets the detached values"""
+        self._din_input = None
         if self.input_conditioning == "none":
             return
         B, _c, H, W = lat.shape
-        ic = self._input_cond(batch, B, H, W)
+        track = grads and any(torch.is_tensor(batch.get(k)) and batch[k].requires_grad for k in ("cond_latents", "inpaint_mask", "masked_latents"))
+        ic = self._input_cond(batch, B, H, W, detach=not track)
         if augment and self.input_cond_dropout_prob > 0.0:
             drop = torch.rand(B, generator=generator) < self.input_cond_dropout_prob
             ic[drop.to(ic.device)] = 0
-        ext["input_cond"] = ic
+        if track and ic.requires_grad:
+            self._din_input = ic
+            ext["input_grad"] = True
+        ext["input_cond"] = ic.detach() if track else ic
 
     def _check_sampler_keys(self) -> None:
         """the validation / sampler keys, checked when the trainer is built (ValueError names the key)"""
@@ -503,7 +528,8 @@ class NativeSDXLTrainer:
         """draw what was not given, build the optional loss arguments, enqueue forward_loss; returns the timesteps used.
         augment: apply the training-only recipes (noise offset, input perturbation, conditioning dropout; _augment).
         cond_grads: compute_loss found a conditioning tensor that requires grad (_cond_request)
-        control_grads: compute_loss under autograd: `control` runs with a graph and its residuals get their gradients (_control_ext)"""
+        control_grads: compute_loss under autograd: `control` runs with a graph and its residuals get their gradients (_control_ext);
+        an input_cond that requires grad gets its gradient (_input_cond_ext)"""
         B = lat.shape[0]
         cm = self.config.model
         tag = batch.get("tag_weights")
@@ -516,7 +542,7 @@ class NativeSDXLTrainer:
             if augment:
                 batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
                 ext.update(aug)
-            self._input_cond_ext(batch, lat, generator, augment, ext)
+            self._input_cond_ext(batch, lat, generator, augment, ext, control_grads)
             if cond_grads:
                 batch = dict(batch)
                 self._cond_request(batch, ext)
@@ -538,7 +564,7 @@ class NativeSDXLTrainer:
         if augment:
             batch, noise, aug = self._augment(batch, noise, generator, cond_grads)
             ext.update(aug)
-        self._input_cond_ext(batch, lat, generator, augment, ext)
+        self._input_cond_ext(batch, lat, generator, augment, ext, control_grads)
         if cond_grads:
             batch = dict(batch)
             self._cond_request(batch, ext)
@@ -567,6 +593,7 @@ class NativeSDXLTrainer:
                 any(torch.is_tensor(batch[k]) and batch[k].requires_grad for k in ("prompt_embeds", "pooled_prompt_embeds")))
         self._cond_inputs = (None, None)
         self._res_inputs = ()
+        self._din_input = None
         ts = self._forward(batch, lat, noise, timesteps, generator, augment=True, cond_grads=cond, control_grads=torch.is_grad_enabled())
         o = self.net.read_loss()                                        # the single host sync of the step
         numel = lat.numel()
@@ -580,7 +607,8 @@ class NativeSDXLTrainer:
             metrics = {"loss": o[0], "x0_norm": math.sqrt(o[5]), "x1_norm": math.sqrt(o[6]),
                        "time_mean": float(ts.mean()), "time_std": float(ts.std()) if B > 1 else float("nan"),
                        "velocity_norm": math.sqrt(o[3]), "batch_size": B, "lr": lr}
-        loss = _NativeLoss.apply(self._anchor, self, o[0], *self._cond_inputs, *self._res_inputs)
+        icond = () if self._din_input is None else (_INPUT_COND, self._din_input)      # (only when it requires grad: the call is otherwise today's)
+        loss = _NativeLoss.apply(self._anchor, self, o[0], *self._cond_inputs, *self._res_inputs, *icond)
         out = {"loss": loss, "metrics": metrics}
         if bool(getattr(self.config.training, "log_per_sample_loss", False)):
             out["per_sample_loss"] = self.net.read_per_sample_loss()    # (after read_loss's sync: the copy only)

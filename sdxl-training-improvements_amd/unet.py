@@ -94,6 +94,52 @@ def widen_conv_in(state_dict, in_channels: int) -> dict:
     return out
 
 
+class _UNetFunction(torch.autograd.Function):
+    """NativeUNet.differentiable: unet_forward / unet_backward as one autograd node.  `net` needs unet_forward, unet_backward,
+    read_input_grad, read_cond_grads, read_residual_grads, device and the forward-generation counter _fwd_gen."""
+
+    @staticmethod
+    def forward(ctx, net, timestep, time_ids, sample, prompt_embeds, pooled, *res):
+        rg = lambda t: torch.is_tensor(t) and t.requires_grad
+        dev = net.device
+        kw = {}
+        cond = [k for k, t in (("prompt", prompt_embeds), ("pooled", pooled)) if rg(t)]
+        if cond:
+            kw["cond_grads"] = tuple(cond)
+        if res:
+            given = [t for t in res if t is not None]
+            dt = torch.bfloat16 if given and all(t.dtype == torch.bfloat16 for t in given) else torch.float32
+            conv = lambda t: None if t is None else t.detach().to(dev, dt).contiguous()
+            kw["residuals"] = ([conv(t) for t in res[:-1]], conv(res[-1]))
+            want = [("mid" if i == len(res) - 1 else i) for i, t in enumerate(res) if rg(t)]
+            if want:
+                kw["residual_grads"] = want
+        if rg(sample):
+            kw["input_grad"] = True
+        pred = net.unet_forward(sample.detach(), timestep, prompt_embeds.detach(), pooled.detach(), time_ids, **kw)
+        ctx.net, ctx.gen = net, getattr(net, "_fwd_gen", 0)
+        ctx.meta = [None if not torch.is_tensor(t) else (t.shape, t.dtype, t.device) for t in (sample, prompt_embeds, pooled) + tuple(res)]
+        return pred
+
+    @staticmethod
+    def backward(ctx, dpred):
+        net = ctx.net
+        if getattr(net, "_fwd_gen", 0) != ctx.gen:
+            raise lib.SdxlError("differentiable: backward of a stale forward -- the engine keeps the activations of one forward, and another "
+                                "forward of this net (forward_loss, unet_forward, differentiable or a sampler step) has run since this one")
+        net.unet_backward(dpred, first_micro=bool(getattr(net, "first_micro", True)))
+        d_prompt, d_pooled = net.read_cond_grads()
+        d_down, d_mid = net.read_residual_grads()
+        n_res = len(ctx.meta) - 3
+        dev = [net.read_input_grad(), d_prompt, d_pooled] + (list(d_down or [None] * (n_res - 1)) + [d_mid] if n_res else [])
+        out = [None] * len(ctx.meta)
+        for i, meta in enumerate(ctx.meta):
+            if meta is not None and ctx.needs_input_grad[3 + i] and dev[i] is not None:
+                shape, dtype, device = meta
+                out[i] = dev[i].reshape(shape).to(device=device, dtype=dtype)
+        return (None, None, None, *out)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -156,6 +202,8 @@ class NativeUNet:
         self._keep = []          # tensors whose device pointers the library still references
         self._trainable = None   # set_trainable's flag per state-dict tensor (None: no selection, every tensor trainable)
         self._lora_sel = False   # ... and whether it handed adapters to the library
+        self.first_micro = True  # differentiable(): its backward overwrites the gradient arena (True) or accumulates into it (False)
+        self._fwd_gen = 0        # counts the forwards: the engine keeps the activations of the last one only (differentiable())
         self.param_table = self._read_param_table()
 
     # ------------------------------------------------------------------ parameters
@@ -411,6 +459,32 @@ class NativeUNet:
         x.residuals = C.pointer(r)
         return x
 
+    def _input_grad_batch(self, b, input_grad, shape):
+        """b as a lib.InputGradBatch carrying the output buffer of the gradient with respect to the UNet input (flagged), or b itself
+        when input_grad is false: without the request every call is the one made before it existed.  The buffer [B, in_channels, H, W]
+        fp32 is owned here and kept until the next forward; read_input_grad() hands it out."""
+        self._d_input = None
+        self._fwd_gen = getattr(self, "_fwd_gen", 0) + 1      # (every forward replaces the activations the engine keeps: _UNetFunction)
+        if not input_grad:
+            return b
+        B, H, W = shape
+        self._d_input = torch.empty(B, int(self.cfg.in_channels), H, W, dtype=torch.float32, device=self.device)
+        x = lib.InputGradBatch(*[getattr(b, f[0]) for f in lib.Batch._fields_])
+        for f in ("sampler", "d_prompt_embeds", "d_pooled", "input_cond", "cond_channels", "residuals"):
+            if hasattr(b, f):
+                setattr(x, f, getattr(b, f))
+        x.ctx_len |= lib.BATCH_DIN
+        x.d_input = self._d_input.data_ptr()
+        return x
+
+    def read_input_grad(self):
+        """the gradient with respect to the UNet input, [B, in_channels, H, W] fp32 on the device, of the last forward_loss / unet_forward
+        that asked for it (input_grad=True) and whose backward has been enqueued; stream-ordered (no synchronisation); None when nothing
+        was asked.  Channels 0..3 belong to the latent input x_t as the UNet read it, channels 4.. to input_cond.  The gradient of
+        grad_scale x loss, as the parameter gradients of that micro-step (unet_backward: of <dpred, pred>); the chain rule through the
+        loss preparation (x_t from latents and noise) is the caller's ("Input gradients")."""
+        return getattr(self, "_d_input", None)
+
     def read_residual_grads(self):
         """([d_down[i] | None per skip], d_mid | None) of the last call that asked for them (residual_grads) and whose backward has
         been enqueued: fp32 NCHW, on the device, stream-ordered (no synchronisation); (None, None) when nothing was asked.  The
@@ -427,8 +501,10 @@ class NativeUNet:
                      tag_weights=None, prediction_type="v_prediction", min_snr_gamma: Optional[float] = 5.0,
                      use_ztsnr=True, sample_weights=None, huber_c=None, loss_type: str = "l2",
                      per_sample_loss: bool = False, loss_mask=None, noise_in=None, mask_norm: str = "mean",
-                     cond_grads=None, input_cond=None, residuals=None, residual_grads=None) -> None:
+                     cond_grads=None, input_cond=None, residuals=None, residual_grads=None, input_grad: bool = False) -> None:
         """loss preparation + UNet forward + loss; results stay on the device until read_loss().
+        input_grad: the backward of this micro-step also produces the gradient with respect to the UNet input (every channel: x_t and
+        input_cond), read with read_input_grad().
         residuals: (down, mid), diffusers' down_block_additional_residuals / mid_block_additional_residual (a ControlNet's outputs,
         already scaled): added to the skips where the up path reads them and to the mid block's output (_residual_batch has the
         shapes and dtypes).  residual_grads: True, None or a collection of skip indices / "mid": the backward of this micro-step also
@@ -476,6 +552,7 @@ class NativeUNet:
         self._cond_request(cond_grads, B, b.ctx_len)
         b = self._input_cond_batch(self._cond_batch(b), input_cond, latents.shape, "forward_loss")
         b = self._residual_batch(b, residuals, residual_grads, (B, latents.shape[2], latents.shape[3]), "forward_loss")
+        b = self._input_grad_batch(b, input_grad, (B, latents.shape[2], latents.shape[3]))
         lib.check(self.L.sdxl_forward_loss(self.h, C.byref(lc), C.byref(b), _stream()), "sdxl_forward_loss")
 
     def backward(self, grad_scale: float = 1.0, first_micro: bool = True, on_segment=None, segment_stream: bool = False) -> None:
@@ -537,9 +614,10 @@ class NativeUNet:
         return self._ps_loss.cpu()
 
     # UNet only (sample NCHW fp32/bf16 in, NCHW fp32 out) -- for parity tests and validation sampling
-    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids, cond_grads=None, residuals=None, residual_grads=None) -> torch.Tensor:
+    def unet_forward(self, sample, timestep, prompt_embeds, pooled, time_ids, cond_grads=None, residuals=None, residual_grads=None,
+                     input_grad: bool = False) -> torch.Tensor:
         """cond_grads as in forward_loss: the following unet_backward also produces d prompt_embeds / d pooled of <dpred, pred>;
-        residuals / residual_grads as in forward_loss (the gradients: of <dpred, pred>)"""
+        residuals / residual_grads as in forward_loss (the gradients: of <dpred, pred>); input_grad: also d sample (read_input_grad())"""
         B, Cc, H, W = sample.shape
         d = self.device
         dummy = torch.zeros(B, 4, H, W, device=d)
@@ -547,6 +625,7 @@ class NativeUNet:
         b = lib.SamplerBatch(*[getattr(tb, f[0]) for f in lib.Batch._fields_])      # sdxl_batch in full, sampler = NULL
         self._cond_request(cond_grads, B, tb.ctx_len)
         b = self._residual_batch(self._cond_batch(b), residuals, residual_grads, (B, H, W), "unet_forward")
+        b = self._input_grad_batch(b, input_grad, (B, H, W))
         cin = int(self.cfg.in_channels)      # the sample carries every input channel, packed into Cs columns
         if Cc != cin:
             raise ValueError(f"unet_forward: sample has {Cc} channels, the UNet has in_channels = {cin}")
@@ -580,6 +659,7 @@ class NativeUNet:
         b.sampler = C.cast(C.pointer(step), C.POINTER(lib.SamplerStep))      # (a SamplerStepExt goes through the same pointer)
         b = self._input_cond_batch(b, input_cond, x.shape, what, rows=PB, convert=False)      # [PB, in_channels - 4, H, W]: the uncond half has rows of its own
         b = self._residual_batch(b, residuals, None, (PB, H, W), what)      # [PB, C_i, h_i, w_i]: rows b + B feed the unconditional half
+        self._d_input, self._fwd_gen = None, getattr(self, "_fwd_gen", 0) + 1      # (a sampler step replaces the kept activations too)
         lib.check(self.L.sdxl_unet_forward(self.h, None, C.byref(b), None, _stream()), what)
 
     def sample_init(self, x, prompt_embeds, pooled, time_ids, timestep, *, cfg: bool, a_in: float = 1.0, clamp: float = 0.0,
@@ -617,6 +697,18 @@ class NativeUNet:
         d8[:, :4] = dpred_nchw.to(self.device).permute(0, 2, 3, 1).reshape(B * H * W, 4).to(torch.bfloat16)
         lib.check(self.L.sdxl_unet_backward(self.h, _ptr(d8), int(first_micro), _stream()), "sdxl_unet_backward")
         torch.cuda.current_stream().synchronize()
+
+    # ------------------------------------------------------------------ the UNet as a differentiable torch function
+    def differentiable(self, sample, timestep, prompt_embeds, pooled, time_ids, residuals=None) -> torch.Tensor:
+        """pred [B,4,H,W] fp32 = the UNet, as a torch.autograd.Function differentiable in all of its tensor inputs: sample
+        [B,in_channels,H,W], prompt_embeds, pooled and every residual of residuals = (down, mid) (as in forward_loss).  The backward
+        runs unet_backward(dpred) and hands back the gradient of each of those that requires grad, in the input's own device and
+        dtype; the parameter gradients go to the gradient arena, overwriting it when self.first_micro (an attribute, default True) else
+        accumulating.  The engine keeps the activations of ONE forward: a backward after any other forward of this net raises
+        SdxlError (retain_graph replays are refused the same way once another forward has run)."""
+        down, mid = (None, None) if residuals is None else residuals
+        res = () if residuals is None else tuple(down if down is not None else [None] * (3 * int(self.cfg.layers_per_block) + 3)) + (mid,)
+        return _UNetFunction.apply(self, timestep, time_ids, sample, prompt_embeds, pooled, *res)
 
     def grad_norm(self) -> float:
         out = torch.zeros(1, dtype=torch.float32, device=self.device)
