@@ -1341,7 +1341,8 @@ static int gemm_route_cfg128(const GemmP& p) {
   if ((cfg == 5 || cfg == 6) && !fast64) cfg = cfg == 5 ? 13 : 1;
   if ((cfg == 3 || cfg == 13 || cfg == 23 || cfg == 43) && p.N % 160 != 0) cfg = 1;
   if (cfg == 23 && FORM == GEMM_TN) cfg = 13;
-  if (p.geglu == 1 && cfg == 2) cfg = 1;                      // the BK = 32 configuration has no room for the GEGLU staging tile
+  if (p.geglu && cfg == 2) cfg = 1;                           // the BK = 32 configuration has no room for the GEGLU staging tile (32 KiB of ring against
+                                                              // 33 KiB: forward AND backward epilogue stage through it; on the backward it lost the tile's last rows)
   for (int k : {2, 3, 23, 13, 5, 6, SDXL_DIAG_BUILD ? 43 : 1}) if (cfg == k) return cfg;
   return 1;      // (whatever else was forced)
 }

@@ -1,0 +1,778 @@
+"""Per-element parity for the NON-LINEAR kernels (GroupNorm / LayerNorm forward and backward, SiLU, the GEGLU epilogues, the softmax's LSE and
+Delta): data designs on which the result is known exactly, float64 references, and for every element a bound DERIVED from the kernel's formula.
+tests/test_gpu_ops_nonlinear.py runs them on the device; tests/test_host_nonlinear.py shows on the CPU that they see what
+tests/test_gpu_ops.py's one number per tensor lets through.  No GPU needed here: everything is CPU torch (float64).
+
+The check.  A bf16 output `got` with float64 reference `ref` passes when, for EVERY element,
+        bf16_rn(ref - delta) <= got <= bf16_rn(ref + delta)
+delta >= 0: the bound on the error of the fp32 value that the kernel rounds; the final rounding gets no slack of its own; a NaN fails.
+An fp32 output passes when |got - ref| <= delta + 2^-24 |ref|.
+
+delta is accumulated operation by operation, as a running first-order error bound next to the float64 value:
+    U = 2^-24   each fp32 + - x fma and the correctly rounded division (relative to the operation's result),
+    H = 2^-22   each hardware v_exp_f32 / v_rcp_f32 / v_rsq_f32 / v_log_f32 (twice the documented 1 ulp),
+    a sum of N terms in ANY order: (N - 1) U sum|terms|   (used at the small shapes only; the long reductions get exact data),
+    TINY = 2^-118   where an intermediate leaves the fp32 normal range: e^-x overflows for x < -88.7, where the true result, at most
+                    |x| e^x <= 2^7 2^-128, is returned as 0, and a subnormal quotient (< 2^-126) may be flushed before it is multiplied by
+                    |x| <= 2^7; two such terms.
+The absolute error of the erf approximation in gelu_cdf_pdf (csrc/common.h) cannot be derived: it is MEASURED on the CPU by emulating the
+formula in float32 over every finite bf16 gate (gelu_cdf_emulated, test_host_nonlinear.py pins the figure) and doubled, because the hardware's
+exp2 and rcp are 1-ulp and fma contraction moves roundings."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from _exact import BF, bf16_rn, gen, ints, rnd, same_bits      # noqa: F401  (re-exported for the two test files)
+
+U = 2.0 ** -24
+H = 2.0 ** -22
+TINY = 2.0 ** -118
+F64 = torch.float64
+
+
+# ------------------------------------------------------------------------------------------------ the check
+def bf16_rn64(x):
+    """ONE round-to-nearest-even conversion float64 -> bfloat16.  (float64 -> float32 -> bfloat16 rounds twice: where the float32 is a bf16
+    tie that the float64 was not, it is moved one float32 step back towards the float64 first.)"""
+    x = x.double()
+    f = x.float()
+    tie = (f.contiguous().view(torch.int32) & 0xFFFF) == 0x8000
+    inexact = f.double() != x
+    toward = torch.where(x > f.double(), torch.full_like(f, math.inf), torch.full_like(f, -math.inf))
+    f = torch.where(tie & inexact & torch.isfinite(f), torch.nextafter(f, toward), f)
+    return f.to(BF)
+
+
+def _ratio_bf16(got_bf16, ref, delta, inside):
+    """err / allowed per element, for printing: err is the least error of the fp32 value that explains the bf16 result, the distance from ref
+    to the set of reals that round to `got` (0 where ref itself rounds to it), allowed is delta.  The verdict is the interval's, not this."""
+    g = got_bf16.float()
+    a = g.abs().contiguous().view(torch.int32)
+    up = (a + 0x10000).view(torch.float32).double()                                    # the next bf16 away from zero (inf above the largest)
+    sub = 2.0 ** -133
+    dn = torch.where(a > 0, (a - 0x10000).clamp_min(0).view(torch.float32).double(), torch.full_like(up, -sub))
+    mag = g.abs().double()
+    r = torch.where(g.double() < 0, -ref, ref)
+    err = torch.maximum(torch.maximum((mag + dn) / 2 - r, r - (mag + up) / 2), torch.zeros_like(r))
+    q = torch.where(err == 0, torch.zeros_like(err), err / delta.clamp_min(1e-300))
+    q = torch.where(torch.isfinite(g.double()), q, torch.where(inside, torch.zeros_like(q), torch.full_like(q, math.inf)))
+    return torch.nan_to_num(q, nan=math.inf, posinf=math.inf)
+
+
+def check_interval(tag, got, ref64, delta):
+    """bf16 output: every element inside [bf16_rn(ref - delta), bf16_rn(ref + delta)], none left out, a NaN fails; prints max err / allowed"""
+    got = got.detach().cpu()
+    assert got.dtype == BF, (tag, got.dtype)
+    ref64, delta = ref64.double(), torch.as_tensor(delta, dtype=F64).expand_as(ref64)
+    assert got.shape == ref64.shape, (tag, tuple(got.shape), tuple(ref64.shape))
+    assert bool((delta >= 0).all()) and not bool(torch.isnan(ref64).any()), f"{tag}: the expectation itself is broken"
+    g = got.double()
+    lo, hi = bf16_rn64(ref64 - delta).double(), bf16_rn64(ref64 + delta).double()
+    nan = torch.isnan(g)
+    bad = nan | (g < lo) | (g > hi)
+    ratio = float(_ratio_bf16(got, ref64, delta, ~bad).max()) if got.numel() else 0.0
+    print(f"[nonlinear] {tag}: max err / allowed {ratio:.4g} ({int(bad.sum())} of {got.numel()} outside)")
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        raise AssertionError(f"{tag}: {int(bad.sum())} of {got.numel()} elements outside their interval ({int(nan.sum())} NaN); first at flat index {i}: "
+                             f"got {float(g.flatten()[i])!r}, allowed [{float(lo.flatten()[i])!r}, {float(hi.flatten()[i])!r}], "
+                             f"reference {float(ref64.flatten()[i])!r}")
+    return ratio
+
+
+def check_f32(tag, got, ref64, delta):
+    """fp32 output: |got - ref| <= delta + 2^-24 |ref| for every element"""
+    got = got.detach().cpu()
+    assert got.dtype == torch.float32, (tag, got.dtype)
+    ref64, delta = ref64.double(), torch.as_tensor(delta, dtype=F64).expand_as(ref64)
+    assert got.shape == ref64.shape, (tag, tuple(got.shape), tuple(ref64.shape))
+    g = got.double()
+    allowed = delta + U * ref64.abs()
+    err = (g - ref64).abs()
+    bad = torch.isnan(g) | ~(err <= allowed)
+    r = torch.where(err == 0, torch.zeros_like(err), err / allowed.clamp_min(1e-300))
+    ratio = float(torch.nan_to_num(r, nan=math.inf, posinf=math.inf).max()) if got.numel() else 0.0
+    print(f"[nonlinear] {tag}: max err / allowed {ratio:.4g} ({int(bad.sum())} of {got.numel()} outside)")
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        raise AssertionError(f"{tag}: {int(bad.sum())} of {got.numel()} elements exceed their bound; first at flat index {i}: got {float(g.flatten()[i])!r}, "
+                             f"reference {float(ref64.flatten()[i])!r}, allowed {float(allowed.flatten()[i])!r}")
+    return ratio
+
+
+def check_bits(tag, got, want):
+    """bit equality with a value that is known exactly"""
+    got, want = got.detach().cpu(), want.detach().cpu()
+    ok = same_bits(got, want)
+    n = 0 if ok else int((got.double() != want.double()).sum())
+    print(f"[nonlinear] {tag}: {'bit-equal' if ok else f'{n} of {got.numel()} elements differ'}")
+    assert ok, f"{tag}: {n} of {got.numel()} elements differ from the exact value"
+
+
+def ulp32(x64):
+    """the spacing of float32 at |x| (normal range)"""
+    return 2.0 ** (torch.floor(torch.log2(x64.abs())) - 23)
+
+
+def check_ulps(tag, got, ref64, ulps):
+    got = got.detach().cpu().double()
+    r = (got - ref64).abs() / ulp32(ref64)
+    ratio = float(torch.nan_to_num(r, nan=math.inf).max())
+    print(f"[nonlinear] {tag}: max {ratio:.3f} fp32 ulp (allowed {ulps})")
+    assert ratio <= ulps, f"{tag}: {ratio:.3f} ulp > {ulps}"
+    return ratio
+
+
+# ------------------------------------------------------------------------------------------------ SiLU (csrc/common.h: silu_f, silu_grad_f)
+def silu64(n):
+    return n * torch.sigmoid(n)
+
+
+def silu_delta(n, dn):
+    """silu_f(n) = n / (1 + __expf(-n)) with n known to +-dn.  __expf is v_exp_f32 of n x log2(e): the product rounds and the constant is
+    rounded, 2 U relative on an argument of size |n| / ln 2, which the exponential turns into 2 |n| U relative; the instruction adds H.  Only
+    the share e / (1 + e) of that reaches 1 + e; the sum and the division add U each.  sup |silu'| = 1.0998 < 1.1."""
+    erel = H + 2 * n.abs() * U
+    return 1.1 * dn + silu64(n).abs() * (erel * torch.sigmoid(-n) + 2 * U) + TINY
+
+
+def silu_grad64(t):
+    s = torch.sigmoid(t)
+    return s * (1 + t * (1 - s))
+
+
+def silu_grad_delta(t, dt):
+    """silu_grad_f(t): s = 1 / (1 + e), w = 1 - s, p = t w, r = 1 + p, out = s r, each operation U of its result, e as in silu_delta.
+    ds / de = -s^2, so e's relative error reaches s as s (1 - s) erel.  Where e < 2^-25 the sum 1 + e rounds to 1 and 1 / 1 is exact: the
+    error of s is the omitted e / (1 + e) < e itself, not 2 U.  sup |silu''| = 1/2."""
+    e = torch.exp(-t)
+    s = torch.sigmoid(t)
+    erel = H + 2 * t.abs() * U
+    ds = s * (1 - s) * erel + torch.where(e < 2.0 ** -25, e, 2 * U * s)
+    w = 1 - s
+    dw = ds + U * w
+    p = torch.nan_to_num(t * w, nan=0.0)          # (t = +-huge with w = 0)
+    dp = torch.nan_to_num(t.abs() * dw, nan=0.0) + U * p.abs()
+    r = 1 + p
+    dr = dp + U * r.abs()
+    return r.abs() * ds + s * dr + U * silu_grad64(t).abs() + 0.5 * dt + TINY
+
+
+# ------------------------------------------------------------------------------------------------ data designs
+K_DYADIC = [k / 4 for k in range(-32, 33)]      # multiples of 1/4 in [-8, 8]: K +- s (s <= 2) is a multiple of 1/4 below 16: 6 bits, bf16-exact
+S_TWO_POINT = (0.5, 1.0, 2.0)
+
+
+def two_point(rows, n, seed, s=None):
+    """`rows` independent sets of n values K + s r: r in {-1, +1} balanced EXACTLY (n even) and shuffled, K a multiple of 1/4 in [-8, 8] and
+    s in {1/2, 1, 2} drawn per set (or `s` for all).  Returns (x [rows][n], K [rows], s [rows]), float32, every value bf16-exact."""
+    assert n % 2 == 0
+    g = gen(seed)
+    K = torch.tensor(K_DYADIC)[torch.randint(0, len(K_DYADIC), (rows,), generator=g)]
+    sv = torch.tensor(S_TWO_POINT)[torch.randint(0, 3, (rows,), generator=g)] if s is None else torch.full((rows,), float(s))
+    r = torch.cat([torch.ones(rows, n // 2), -torch.ones(rows, n // 2)], 1)
+    perm = torch.rand(rows, n, generator=g).argsort(1)
+    x = K[:, None] + sv[:, None] * r.gather(1, perm)
+    assert torch.equal(x.to(BF).float(), x)
+    return x, K, sv
+
+
+def graded(rows, n, seed):
+    """`rows` sets of n values offset + scale randn, offset uniform in [-8, 8] and scale = 2^uniform[-2, 2] drawn per set: no two sets share
+    statistics.  bf16-rounded float32."""
+    g = gen(seed)
+    off = torch.rand(rows, generator=g) * 16 - 8
+    sc = 2.0 ** (torch.rand(rows, generator=g) * 4 - 2)
+    return (off[:, None] + sc[:, None] * torch.randn(rows, n, generator=g)).to(BF).float()
+
+
+def edge_tiny(n, seed):
+    """+-2^-9: variance 2^-18 = 3.8e-6 < eps = 1e-5"""
+    sign = torch.randint(0, 2, (n,), generator=gen(seed)).float() * 2 - 1
+    return sign * 2.0 ** -9
+
+
+def to_groups(x, G):
+    """[B][HW][C] -> [B][G][HW][cpg] (a group's elements, rows first)"""
+    B, HW, C = x.shape
+    return x.view(B, HW, G, C // G).permute(0, 2, 1, 3)
+
+
+def from_groups(xg):
+    B, G, HW, cpg = xg.shape
+    return xg.permute(0, 2, 1, 3).reshape(B, HW, G * cpg).contiguous()
+
+
+def gn_two_point(B, HW, C, G, seed, s=None):
+    n = HW * (C // G)
+    x, K, sv = two_point(B * G, n, seed, s)
+    return from_groups(x.view(B, G, HW, C // G)), K.view(B, G), sv.view(B, G)
+
+
+CONST_VALUE = 3.0
+
+
+def gn_graded(B, HW, C, G, seed, edges=True):
+    """graded randn per (sample, group); sample 0's group 0 is the +-2^-9 group and its group 1 a constant one"""
+    n = HW * (C // G)
+    x = graded(B * G, n, seed).view(B, G, n).clone()
+    if edges:
+        x[0, 0] = edge_tiny(n, seed + 1)
+        x[0, 1] = CONST_VALUE
+    return from_groups(x.view(B, G, HW, C // G))
+
+
+def ln_graded(M, C, seed, edges=True):
+    x = graded(M, C, seed).clone()
+    if edges and M >= 3:
+        x[0] = edge_tiny(C, seed + 1)
+        x[1] = CONST_VALUE
+    return x
+
+
+def affine(C, seed):
+    """(gamma, beta) as tests/test_gpu_ops.py draws them: gamma = 1 + 0.1 randn, beta = randn, bf16-rounded"""
+    return (torch.randn(C, generator=gen(seed)) * 0.1 + 1.0).to(BF).float(), rnd(C, seed=seed + 1)
+
+
+# ------------------------------------------------------------------------------------------------ GroupNorm forward (csrc/norm.hip)
+def _gsum(t):
+    return t.sum((2, 3))
+
+
+def gn_stats_ref(x, G, eps, exact_sums=False, unbiased=False, eps_outside=False, skip_row=None):
+    """float64 (mean, rstd) [B][G] and their derived bounds, following gn_stats_kernel / gn_finalize_kernel:
+        d = x - K0 (K0: the group's first element; the difference rounds: U |d|),
+        a = sum d, q = sum d d: N = HW cpg terms in some order, (N - 1) U sum|terms| + the terms' own roundings (exact_sums: the data design
+        makes every partial sum exact, N U drops out),
+        m1 = a / n, m2 = q / n (U each), var = max(m2 - m1 m1, 0) (2 operations), mean = K0 + m1 (U),
+        rstd = rsqrtf(var + eps): the sum U, the instruction H, and d rstd / d v = -rstd / (2 v).
+    The keyword mutants are for tests/test_host_nonlinear.py."""
+    xg = to_groups(x.double(), G)
+    B, _, HW, cpg = xg.shape
+    N = HW * cpg
+    K0 = xg[:, :, :1, :1]
+    d = xg - K0
+    if skip_row is not None:      # mutant: one row left out of the sums (n unchanged)
+        d = d.clone()
+        d[:, :, skip_row] = 0
+    D1, D2 = _gsum(d.abs()), _gsum(d * d)
+    m1, m2 = _gsum(d) / N, _gsum(d * d) / N
+    var = (m2 - m1 * m1).clamp_min(0)
+    if unbiased:
+        var = var * N / (N - 1)
+    mean = K0[:, :, 0, 0] + m1
+    rstd = 1 / (var.sqrt() + eps) if eps_outside else (var + eps).rsqrt()
+    if exact_sums:      # the design's claim, checked: d, d d and every partial sum are multiples of one power of two below 2^24 of it; the quotients exact
+        f32 = lambda t: bool((t.float().double() == t).all())
+        assert skip_row is not None or unbiased or (f32(d) and f32(d * d) and f32(m1) and f32(m2) and f32(m1 * m1) and f32(var) and f32(mean)
+                                                    and float(D2.max()) < 2.0 ** 24 * float((d * d)[d != 0].min()))
+        dmean, dvar = torch.zeros_like(mean), torch.zeros_like(var)
+    else:
+        da = (N + 1) * U * D1
+        dq = (N + 3) * U * D2
+        dm1 = da / N + U * m1.abs()
+        dm2 = dq / N + U * m2
+        dvar = dm2 + 2 * m1.abs() * dm1 + U * m1 * m1 + U * var
+        dmean = dm1 + U * mean.abs()
+    v = var + eps
+    dv = dvar + U * v
+    drstd = rstd * dv / (2 * (v - dv).clamp_min(1e-300)) + H * rstd
+    return dict(mean=mean, rstd=rstd, dmean=dmean, drstd=drstd)
+
+
+def _per_channel(t, C):
+    """[B][G] -> [B][1][C]"""
+    return t.repeat_interleave(C // t.shape[1], 1)[:, None, :]
+
+
+def gn_fwd_ref(x, gamma, beta, G, eps, silu, exact_sums=False, **mutant):
+    """float64 y [B][HW][C], its bound, and the statistics, following gn_apply_kernel:
+        a = rstd gamma (U), s = beta - mean a (2 operations), n = x a + s (2), y = silu_f(n) | n."""
+    st = gn_stats_ref(x, G, eps, exact_sums, **mutant)
+    C = x.shape[2]
+    mean, rstd, dmean, drstd = (_per_channel(st[k], C) for k in ("mean", "rstd", "dmean", "drstd"))
+    return gn_apply_ref(x, gamma, beta, mean, rstd, dmean, drstd, silu) | st
+
+
+def gn_apply_ref(x, gamma, beta, mean, rstd, dmean, drstd, silu):
+    x, ga, be = x.double(), gamma.double()[None, None, :], beta.double()[None, None, :]
+    a = rstd * ga
+    da = ga.abs() * drstd + U * a.abs()
+    s = be - mean * a
+    n = x * a + s
+    # the SAME a multiplies x and mean: its error reaches n = (x - mean) a + beta as |x - mean| da, not |x| da + |mean| da; the four operations
+    # (mean a, beta - ., x a, . + s) round independently, each at its own size
+    dn = (x - mean).abs() * da + a.abs() * dmean + U * ((mean * a).abs() + s.abs() + (x * a).abs() + n.abs())
+    if not silu:
+        return dict(y=n, dy=dn)
+    return dict(y=silu64(n), dy=silu_delta(n, dn))
+
+
+def stats_f32(st):
+    """[B][G][2] float32 (mean, rstd) as the forward stores them: what the backward tests pass in"""
+    return torch.stack([st["mean"], st["rstd"]], -1).float().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ GroupNorm backward
+def gn_bwd_ref(x, dy, gamma, beta, stats, G, silu, addend=None, exact_sums=False, drop_addend=False):
+    """float64 (dx, dgamma, dbeta) and their bounds from the PASSED-IN fp32 stats [B][G][2], following gn_bwd_reduce_kernel, gn_bwd_group_kernel
+    and gn_bwd_apply_kernel:
+        xh = (x - mean) rstd (2 operations), dn = dy silu_grad_f(xh gamma + beta) (the argument: 2 operations on top of xh's error),
+        A[b][c] = sum_rows dn, Bs[b][c] = sum_rows dn xh   (HW terms each, any order), dbeta = sum_b A, dgamma = sum_b Bs,
+        S1 = sum_c gamma A / n, S2 = sum_c gamma Bs / n   (cpg terms, the product and the division U each),
+        c1 = rstd gamma, c3 = -rstd rstd S2, c2 = -rstd S1 - mean c3,
+        dx = c1 dn' + c3 x + c2 (+ addend), dn' = dy silu_grad_f(x a + s) with a = rstd gamma, s = beta - mean a as in the forward."""
+    B, HW, C = x.shape
+    cpg = C // G
+    x, dy, ga, be = x.double(), dy.double(), gamma.double()[None, None, :], beta.double()[None, None, :]
+    mean, rstd = _per_channel(stats[..., 0].double(), C), _per_channel(stats[..., 1].double(), C)
+    xm = x - mean
+    xh = xm * rstd
+    dxh = (0.0 if exact_sums else 2 * U) * xh.abs()
+    if silu:
+        t = xh * ga + be
+        dt = ga.abs() * dxh + U * (xh * ga).abs() + U * t.abs()
+        sg = silu_grad64(t)
+        dn = dy * sg
+        ddn = dy.abs() * silu_grad_delta(t, dt) + U * dn.abs()
+    else:
+        dn, ddn = dy, torch.zeros_like(dy)
+    ns = 0.0 if exact_sums else float(HW)
+    p = dn * xh
+    dp = dn.abs() * dxh + xh.abs() * ddn + (0.0 if exact_sums else U) * p.abs()
+    A, Bs = dn.sum(1), p.sum(1)                                        # [B][C]
+    dA = ddn.sum(1) + ns * U * dn.abs().sum(1)
+    dBs = dp.sum(1) + ns * U * p.abs().sum(1)
+    nb = 0.0 if exact_sums else float(B - 1)
+    dbeta, dgamma = A.sum(0), Bs.sum(0)
+    ddbeta = dA.sum(0) + nb * U * A.abs().sum(0)
+    ddgamma = dBs.sum(0) + nb * U * Bs.abs().sum(0)
+    n = float(HW * cpg)
+    g1 = ga[0]                                                          # [1][C]
+    grp = lambda v: v.view(B, G, cpg).sum(2)                            # [B][C] -> [B][G]
+    wa, wb = g1 * A, g1 * Bs
+    S1, S2 = grp(wa) / n, grp(wb) / n
+    dS1 = (grp(g1.abs() * dA + U * wa.abs()) + (cpg - 1) * U * grp(wa.abs())) / n + 2 * U * S1.abs()
+    dS2 = (grp(g1.abs() * dBs + U * wb.abs()) + (cpg - 1) * U * grp(wb.abs())) / n + 2 * U * S2.abs()
+    S1, S2, dS1, dS2 = (_per_channel(v, C) for v in (S1, S2, dS1, dS2))
+    c1 = rstd * ga
+    dc1 = U * c1.abs()
+    c3 = -rstd * rstd * S2
+    dc3 = rstd * rstd * dS2 + 2 * U * c3.abs()
+    c2 = -rstd * S1 - mean * c3
+    dc2 = rstd * dS1 + U * (rstd * S1).abs() + U * (mean * c3).abs() + U * c2.abs()      # without c3's own error: it enters dx below, once
+    if silu:      # the apply kernel rebuilds the activation's argument as x a + s
+        a = c1
+        s = be - mean * a
+        t2 = x * a + s
+        dt2 = (x - mean).abs() * dc1 + U * ((x * a).abs() + (mean * a).abs() + s.abs() + t2.abs())      # (the same a on both sides, as in the forward)
+        dn2 = dy * silu_grad64(t2)
+        ddn2 = dy.abs() * silu_grad_delta(t2, dt2) + U * dn2.abs()
+    else:
+        dn2, ddn2 = dy, torch.zeros_like(dy)
+    u1, u2 = c1 * dn2, c3 * x
+    g = u1 + u2 + c2
+    # c3's error reaches c3 x + c2 = c3 (x - mean) - rstd S1 as |x - mean| dc3 (the same c3 on both sides)
+    dg = c1.abs() * ddn2 + dn2.abs() * dc1 + U * u1.abs() + (x - mean).abs() * dc3 + U * u2.abs() + U * (u1 + u2).abs() + dc2 + U * g.abs()
+    if addend is not None:
+        if not drop_addend:
+            g = g + addend.double()
+        dg = dg + U * g.abs()
+    return dict(dx=g, ddx=dg, dgamma=dgamma, ddgamma=ddgamma, dbeta=dbeta, ddbeta=ddbeta)
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm (csrc/norm.hip)
+def ln_fwd_ref(x, gamma, beta, eps, exact_sums=False, unbiased=False, eps_outside=False):
+    """float64 y [M][C], (mean, rstd) [M] and the bounds, following ln_fwd_kernel (two passes over the row in registers):
+        mean = (sum x) (1 / C): C terms, the constant rounded (U unless C is a power of two) and the product (U),
+        d = x - mean (U + mean's error), sq = sum d d, rstd = rsqrtf(sq (1 / C) + eps) (the product and constant 2 U, the sum U, H),
+        y = d rstd gamma + beta: three operations.
+    exact_sums: the FIRST pass's partial sums are exact (two-point data)."""
+    x = x.double()
+    M, C = x.shape
+    pow2 = C & (C - 1) == 0
+    ku = 1.0 if pow2 else 2.0      # x (1 / C): exact scaling | a rounded constant and a rounded product
+    mean = x.mean(1, keepdim=True)
+    dmean = (0.0 if exact_sums else (C - 1) * U) * x.abs().mean(1, keepdim=True) + (0.0 if exact_sums and pow2 else ku * U) * mean.abs()
+    d = x - mean
+    dd = dmean + U * d.abs()
+    if exact_sums and pow2:
+        dd = torch.zeros_like(d)
+    sq = d * d
+    dsq = 2 * d.abs() * dd + U * sq
+    var = sq.mean(1, keepdim=True)
+    dvar = dsq.mean(1, keepdim=True) + (C - 1) * U * var + ku * U * var
+    if exact_sums and pow2 and bool((sq.float().double() == sq).all()):
+        dvar = torch.zeros_like(var)
+    if unbiased:
+        var = var * C / (C - 1)
+    v = var + eps
+    dv = dvar + U * v
+    rstd = 1 / (var.sqrt() + eps) if eps_outside else v.rsqrt()
+    drstd = rstd * dv / (2 * (v - dv).clamp_min(1e-300)) + H * rstd
+    ga, be = gamma.double()[None, :], beta.double()[None, :]
+    p = d * rstd
+    dp = d.abs() * drstd + rstd * dd + U * p.abs()
+    q = p * ga
+    dq = ga.abs() * dp + U * q.abs()
+    y = q + be
+    return dict(y=y, dy=dq + U * y.abs(), mean=mean[:, 0], rstd=rstd[:, 0], dmean=dmean[:, 0] + 0 * mean[:, 0], drstd=drstd[:, 0])
+
+
+def ln_bwd_ref(x, dy, gamma, stats, addend=None, exact_sums=False, drop_addend=False):
+    """float64 (dx, dgamma, dbeta) and bounds from the PASSED-IN fp32 stats [M][2], following ln_bwd_dx_kernel / ln_bwd_lean_kernel:
+        h = (x - mean) rstd (2 operations), t = dy gamma (bf16 x bf16: exact in fp32),
+        s1 = (sum t) (1 / C), s2 = (sum t h) (1 / C): C terms; the constant and the product 2 U,
+        dx = rstd (t - s1 - h s2) (+ addend): four operations (+ one),
+        dgamma = sum_rows dy h, dbeta = sum_rows dy: M terms in any order (block partials, the wave tree, the fixed-order reduce)."""
+    x, dy, ga = x.double(), dy.double(), gamma.double()[None, :]
+    M, C = x.shape
+    mean, rstd = stats[:, :1].double(), stats[:, 1:2].double()
+    h = (x - mean) * rstd
+    dh = (0.0 if exact_sums else 2 * U) * h.abs()
+    t = dy * ga
+    th = t * h
+    dth = t.abs() * dh + U * th.abs()
+    s1 = t.mean(1, keepdim=True)
+    ds1 = (C - 1) * U * t.abs().mean(1, keepdim=True) + 2 * U * s1.abs()
+    s2 = th.mean(1, keepdim=True)
+    ds2 = dth.mean(1, keepdim=True) + (C - 1) * U * th.abs().mean(1, keepdim=True) + 2 * U * s2.abs()
+    hs = h * s2
+    dhs = h.abs() * ds2 + s2.abs() * dh + U * hs.abs()
+    inner = t - s1 - hs
+    dinner = ds1 + U * (t - s1).abs() + dhs + U * inner.abs()
+    g = rstd * inner
+    dg = rstd * dinner + U * g.abs()
+    if addend is not None:
+        if not drop_addend:
+            g = g + addend.double()
+        dg = dg + U * g.abs()
+    pg = dy * h
+    ms = 0.0 if exact_sums else float(M - 1)
+    dgamma, dbeta = pg.sum(0), dy.sum(0)
+    ddgamma = (dy.abs() * dh + (0.0 if exact_sums else U) * pg.abs()).sum(0) + ms * U * pg.abs().sum(0)
+    ddbeta = ms * U * dy.abs().sum(0)
+    return dict(dx=g, ddx=dg, dgamma=dgamma, ddgamma=ddgamma, dbeta=dbeta, ddbeta=ddbeta)
+
+
+# ------------------------------------------------------------------------------------------------ the activation sweeps
+def bf16_sweep(limit, extra=()):
+    """every finite bf16 value with |v| <= limit (both zeros and the subnormals included), plus `extra`, as float32"""
+    bits = torch.arange(0, 0x7F80, dtype=torch.int32)
+    pos = (bits << 16).view(torch.float32)
+    pos = pos[pos <= limit]
+    v = torch.cat([pos, -pos, torch.tensor(extra, dtype=torch.float32).to(BF).float()])
+    return v
+
+
+SILU_EXTREMES = (1e4, -1e4, 3e38, -3e38)
+
+
+# ------------------------------------------------------------------------------------------------ GELU (csrc/common.h: gelu_cdf_pdf)
+def gelu_cdf_emulated(t32):
+    """gelu_cdf_pdf's cdf in numpy float32, operation by operation (an fma: the float64 product and sum, rounded once)"""
+    f = np.float32
+    x = np.asarray(t32, dtype=f)
+    fma = lambda a, b, c: (a.astype(np.float64) * np.float64(b) + np.float64(c)).astype(f) if not isinstance(b, np.ndarray) \
+        else (a.astype(np.float64) * b.astype(np.float64) + np.float64(c)).astype(f)
+    with np.errstate(over="ignore", under="ignore"):
+        e = np.exp2(((x * x).astype(f) * f(-0.72134752044448170)).astype(f)).astype(f)
+        k = (f(1) / fma(np.abs(x), f(0.23164189), f(1))).astype(f)
+        q = fma(k, f(1.061405429), f(-1.453152027))
+        q = fma(k, q, f(1.421413741))
+        q = fma(k, q, f(-0.284496736))
+        q = fma(k, q, f(0.254829592))
+        z = ((q * k).astype(f) * e).astype(f)
+        h = (f(0.5) - (f(0.5) * z).astype(f)).astype(f)
+        cdf = (f(0.5) + np.copysign(h, x)).astype(f)
+        pdf = (f(0.39894228040143268) * e).astype(f)
+    return cdf, pdf
+
+
+def phi_cdf64(t):
+    return 0.5 * torch.special.erfc(-t.double() / math.sqrt(2.0))
+
+
+def phi_pdf64(t):
+    return torch.exp(-0.5 * t.double() ** 2) / math.sqrt(2 * math.pi)
+
+
+def measure_cdf_error():
+    """max |emulated cdf - Phi| over EVERY finite bf16 gate"""
+    t = bf16_sweep(math.inf)
+    cdf, _ = gelu_cdf_emulated(t.numpy())
+    return float((torch.from_numpy(cdf).double() - phi_cdf64(t)).abs().max())
+
+
+CDF_ERR_MEASURED = 2.3226e-7      # what measure_cdf_error() gives (tests/test_host_nonlinear.py asserts that it still does); the source states 1.5e-7 for erf
+DELTA_CDF = 2 * CDF_ERR_MEASURED      # the absolute bound on the kernels' cdf: hardware exp2 / rcp (1 ulp each) and fma contraction move roundings
+
+
+# ------------------------------------------------------------------------------------------------ GEGLU: the non-linear half of the epilogues
+# (csrc/gemm.hip, gemm256.hip, gemm_cr256.hip, gemm_sk.hip: four copies of the same two formulas)
+GEGLU_EXTREMES = (32.0, -32.0, 64.0, -64.0, 1e4, -1e4)
+GEGLU_VALUES = (-1.5, 2.0 ** -20, 1.9921875, 1.0)      # a negative value, a tiny one, a full mantissa (255 / 128), and one that leaves the gate's GELU alone
+
+
+def geglu_gates():
+    """every finite bf16 gate with |t| <= 16, plus +-32, +-64 and +-1e4"""
+    return bf16_sweep(16.0, GEGLU_EXTREMES)
+
+
+def pdf_delta(t):
+    """pdf = 0.3989 exp2(t t c): the argument carries two products and a rounded constant, 3 U relative on t^2 / (2 ln 2), which the
+    exponential turns into 1.5 t^2 U relative; the instruction H, the constant and the last product 2 U"""
+    return phi_pdf64(t) * (H + 1.5 * t * t * U + 2 * U)
+
+
+def geglu_fwd_ref(value, gate):
+    """g = bf16(value x gelu_f(gate)), gelu_f = gate x cdf: two products (2 U) on top of the measured cdf bound scaled by |value gate|"""
+    v, t = value.double(), gate.double()
+    ref = v * t * phi_cdf64(t)
+    return ref, (v * t).abs() * DELTA_CDF + 2 * U * ref.abs() + TINY
+
+
+def geglu_bwd_ref(dG, value, gate):
+    """d value = bf16(dG gate cdf), d gate = bf16(dG value fma(gate, pdf, cdf)): ABSOLUTE bounds (the derivative crosses zero near -0.75)"""
+    d, v, t = dG.double(), value.double(), gate.double()
+    cdf, pdf = phi_cdf64(t), phi_pdf64(t)
+    ra = d * t * cdf
+    da = (d * t).abs() * DELTA_CDF + 2 * U * ra.abs() + TINY
+    gp = cdf + t * pdf
+    rt = d * v * gp
+    dt = (d * v).abs() * (DELTA_CDF + t.abs() * pdf_delta(t) + U * gp.abs()) + 2 * U * rt.abs() + TINY
+    return ra, da, rt, dt
+
+
+def geglu_pack_rows(t, C4, G):
+    """[2 C4, ...] source order (value rows | gate rows) -> the library's packed order (groups of G interleaved)"""
+    a, g = t[:C4], t[C4:]
+    shp = t.shape[1:]
+    return torch.stack([a.reshape(C4 // G, G, *shp), g.reshape(C4 // G, G, *shp)], 1).reshape(2 * C4, *shp).contiguous()
+
+
+def geglu_unpack_cols(u, C4, G):
+    """[M, 2 C4] packed columns -> source order (value | gate)"""
+    M = u.shape[0]
+    v = u.reshape(M, C4 // G, 2, G)
+    return torch.cat([v[:, :, 0].reshape(M, C4), v[:, :, 1].reshape(M, C4)], 1)
+
+
+def geglu_pack_cols(value, gate, G):
+    M, C4 = value.shape
+    return torch.stack([value.reshape(M, C4 // G, G), gate.reshape(M, C4 // G, G)], 2).reshape(M, 2 * C4).contiguous()
+
+
+GEGLU_FWD_C4, GEGLU_K = 5120, 64      # 5120 = 80 groups of 64 = 64 groups of 80
+GEGLU_PASSES = 4                      # each pass pairs every gate with another of the four values
+
+
+def geglu_fwd_launches(rows_options):
+    """(M, value bias [C4], gate bias [C4]) per launch: the gates spread over ceil(n / C4) launches a pass; pass p rotates the values by p and
+    takes M = rows_options[p % len]"""
+    gates = geglu_gates()
+    vals = torch.tensor(GEGLU_VALUES)
+    out = []
+    for p in range(GEGLU_PASSES):
+        for c0 in range(0, gates.numel(), GEGLU_FWD_C4):
+            t = torch.zeros(GEGLU_FWD_C4)
+            part = gates[c0:c0 + GEGLU_FWD_C4]
+            t[:part.numel()] = part
+            v = vals[(torch.arange(GEGLU_FWD_C4) + c0 + p) % 4]
+            out.append((rows_options[p % len(rows_options)], v, t))
+    return out
+
+
+GEGLU_BWD_M = 256
+
+
+def geglu_bwd_operands(G):
+    """u carries the sweep directly: M = 256 rows x C4 = 4 G channels hold every gate (cyclically, a second appearance with another value);
+    dy, w2 integers with K = 64: dG = dy w2 is an exact small integer (|dG| <= 256: bf16-exact, as the epilogue's bf16 cast needs)"""
+    M, C4 = GEGLU_BWD_M, 4 * G
+    gates = geglu_gates()
+    slot = torch.arange(M * C4)
+    perm = torch.randperm(M * C4, generator=gen(31))
+    gate = gates[slot % gates.numel()][perm].view(M, C4)
+    value = torch.tensor(GEGLU_VALUES)[(slot + slot // gates.numel()) % 4][perm].view(M, C4)
+    dy, w2 = ints(M, GEGLU_K, seed=32, nonzero=True), ints(GEGLU_K, C4, seed=33, nonzero=True)
+    dG = dy.double() @ w2.double()
+    assert float(dG.abs().max()) <= 256 and M * C4 >= gates.numel()
+    return dict(value=value, gate=gate, dy=dy, w2=w2, dG=dG)
+
+
+# name, gemm mode word (sdxl_set_gemm_mode: 1 the policy, 2 the 256 x 256 kernel where it applies, 4 c: configuration / co-resident mode c forced),
+# packing group, the M of each pass | M, and what the case needs: "" the product library, "diag" the diagnostics build, "sk" that build with
+# stream-K switched on (sdxl_set_sk_mode(2, 0)).  The 256 x 256 kernel and stream-K take whole 256-row tiles only: M = 256 there.
+GEGLU_FWD_ROUTES = [("policy", 1, 64, (128, 100), ""), ("policy", 1, 80, (128, 100), ""), ("256x256", 2, 64, (256,), ""),
+                    ("cfg 5", 4 * 5, 80, (128, 100), ""), ("cfg 6", 4 * 6, 64, (128, 100), ""), ("cfg 13", 4 * 13, 80, (128, 100), ""),
+                    ("cfg 23", 4 * 23, 80, (128, 100), ""), ("stream-K", 1, 64, (256,), "sk")]
+GEGLU_BWD_ROUTES = [("policy", 1, 64, ""), ("policy", 1, 80, ""), ("256x256", 2, 64, ""), ("cr256 31", 4 * 31, 80, ""),
+                    ("cr256 32", 4 * 32, 64, ""), ("cr256 35", 4 * 35, 80, ""), ("cr256 36", 4 * 36, 64, ""), ("forced cfg 2", 4 * 2, 64, ""),
+                    ("cfg 3", 4 * 3, 80, ""), ("cfg 5", 4 * 5, 80, ""), ("cfg 6", 4 * 6, 64, ""), ("cfg 13", 4 * 13, 80, ""),
+                    ("cfg 23", 4 * 23, 80, ""), ("cr256 33", 4 * 33, 80, "diag"), ("cr256 34", 4 * 34, 64, "diag"),
+                    ("stream-K", 1, 64, "sk")]
+# "forced cfg 2": the BK = 32 configuration of the 128-row kernel has 32 KiB of LDS ring, the GEGLU epilogues stage 33 KiB through it.  The route
+# function sent only the FORWARD back to configuration 1; on the backward (forced here; the policy takes configuration 2 for NN problems of 700
+# tiles or more whose N is no multiple of 160, which the model's GEGLU widths are), the staging tile's last rows fell outside the allocation and
+# 917 of 65 536 d value results came back as -0 (found by test_geglu_backward_gate_sweep[forced_cfg_2-g64], then still named cfg_2-g64).  Both
+# directions are rerouted now: the case stays, runs configuration 1, and tests/test_host_nonlinear.py holds the route to that.
+# routes that the route function names in either build but that only the diagnostics build is run with (tests/test_gpu_ops.py's cr256 fixture)
+GEGLU_DIAG_ONLY = {("bwd", "cr256", 33), ("bwd", "cr256", 34)}
+# NOT covered: configuration 43 of the 128-row kernel (diagnostics build only: a four-wave form that was measured once and never selected; no test
+# of the suite launches it in any form, and a gate sweep is not the place to launch it first).  It shares the epilogue source with 1 / 3 / 13 / 23.
+GEGLU_NOT_COVERED = {("fwd", "128-row", 43), ("bwd", "128-row", 43)}
+
+
+def geglu_route_scan(lib, L):
+    """every (direction, kernel, cfg) that sdxl_debug_gemm_route names for a GEGLU problem of the GPU file's sizes under ANY gemm mode word:
+    the policy, the 256 x 256 mode and every forced configuration 1 .. 63 (a word the library refuses is skipped), both packing groups"""
+    seen = set()
+    for mode in [1, 2] + [4 * c for c in range(1, 64)]:
+        for G in (64, 80):
+            for fwd, Ms in ((True, (128, 100, 256)), (False, (GEGLU_BWD_M,))):
+                for M in Ms:
+                    try:
+                        r = geglu_route(lib, L, mode, fwd, M, G)
+                    except Exception:      # not a mode word of this build
+                        lib.check(L.sdxl_set_gemm_mode(1))
+                        continue
+                    seen.add(("fwd" if fwd else "bwd", r["kernel"], r["cfg"]))
+    return seen
+
+
+def geglu_route(lib, L, mode, fwd, M, G, sk=False):
+    """the library's own answer for a GEGLU launch of the GPU file"""
+    from _exact import route_of
+    if sk:
+        lib.check(L.sdxl_set_sk_mode(2, 0))
+    try:
+        if fwd:
+            return route_of(lib, L, mode, form=0, M=M, N=2 * GEGLU_FWD_C4, K=GEGLU_K, geglu=1, geglu_group=G)
+        return route_of(lib, L, mode, form=1, M=M, N=4 * G, K=GEGLU_K, geglu=2, geglu_group=G)
+    finally:
+        if sk:
+            lib.check(L.sdxl_set_sk_mode(0, 0))
+
+
+# ------------------------------------------------------------------------------------------------ attention: the softmax away from uniform
+# (csrc/attention.hip, attention_bwd_pl.hip; head_dim 64, softmax scale 1/8)
+LOG2E_F32 = float(torch.tensor(1.4426950408889634, dtype=torch.float32))
+ATTN_C = float(torch.tensor(0.125, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32))      # SCALE * LOG2E in fp32
+LN2 = math.log(2.0)
+ATTN_SHAPES = [(1, 1, 128, 64, False),       # cross: dQ kernel + unsplit dK / dV kernel
+               (2, 2, 200, 77, False),       # cross: the split-query dK / dV kernel and its reduce (2 query splits)
+               (1, 2, 264, 257, False),      # Nk >= 256, ragged both ways; 2 query splits
+               (2, 4, 988, 988, True),       # self: the fused backward grid, the (batch, head) seam
+               (1, 1, 2048, 2048, True),     # self: 32 key tiles only, so 5 query splits: the split-query kernels at 2048 rows
+               (1, 4, 2048, 2048, True)]     # self: 128 key tiles, no split: the pipelined backward under the product policy
+
+
+def attn_bwd_route(B, heads, Nq, Nk):
+    """which backward sdxl_op_attention_bwd launches with the knobs at their defaults, restated from attn_pick_qsplit and launch_attn_bwd /
+    launch_attn_bwd_fused (csrc/attention.hip): (name, query splits)"""
+    blocks = -(-Nk // 64) * B * heads
+    qt = -(-Nq // 64)
+    s = max(160 // blocks, 1)
+    if s > qt // 2:
+        s = qt // 2 if qt // 2 > 0 else 1
+    s = min(s, 16)
+    if s <= 1 and Nk >= 256:
+        return ("pipelined" if Nq >= 2048 and Nk >= 2048 else "fused"), 1
+    return ("dq + split dkv + reduce" if s > 1 else "dq + dkv"), s
+
+
+def scale8_ref(x):
+    """scale8 (csrc/attn_tiles.h): bf16_rn(fp32(x) * fp32(SCALE * LOG2E)) -- the ONE rounding the kernels make by design, restated: the forward
+    and the dQ bodies round q this way, the dK / dV bodies round k"""
+    return (x.float() * torch.tensor(ATTN_C, dtype=torch.float32)).to(BF).double()
+
+
+def attn_operands(B, heads, Nq, Nk, seed=70):
+    """q = 2 randn (peaked rows), k, v, dO randn; bf16-rounded float32 [B][N][heads 64]"""
+    Cc = heads * 64
+    return dict(q=rnd(B, Nq, Cc, seed=seed, scale=2.0), k=rnd(B, Nk, Cc, seed=seed + 1), v=rnd(B, Nk, Cc, seed=seed + 2), dO=rnd(B, Nq, Cc, seed=seed + 3))
+
+
+def _heads(t, heads):
+    B, N, Cc = t.shape
+    return t.double().view(B, N, heads, 64).permute(0, 2, 1, 3).reshape(B * heads, N, 64)
+
+
+def _unheads(t, B, heads):
+    return t.view(B, heads, -1, 64).permute(0, 2, 1, 3).reshape(B, -1, heads * 64).contiguous()
+
+
+def _exp_rel(absdot, start):
+    """relative error of P = v_exp_f32(acc): the accumulator starts at -start and takes 64 exact products in fp32 (65 terms in any order, in
+    log2 units: x ln 2 in the exponential), the instruction H"""
+    return H + LN2 * 65 * U * (absdot + start.abs())
+
+
+def attn_fwd_ref(o, heads):
+    """lse [B heads][Nq] (natural units) with its bound 2^-22 (|m| + |log l|) + (Nk + 64) 2^-24 (m x 1 / log2 e and logf(l): H each of their
+    size; l a sum of Nk positive terms: (Nk - 1) U relative, U absolute on its log each; 64 U for the fp32 score sum), and O [B][Nq][C] with
+        delta_O = sum_j p_j |v_j| (2^-8 + relP_j) / l     P enters the matrix pipe as bf16 (pack8); relP: _exp_rel + the shift's rounding,
+                + sum_j p_j |v_j| / l x (Nk U + rel_l + 2 tiles U)      the fp32 sum of Nk products, l's own error, one rescale a tile at most,
+                + 3 U |O|                                             1 / l, the product, and slack for the last scaling.
+    The running reference of the kernel is within 8 log2 units of the row maximum (lazy rescaling), which |m| + 8 covers."""
+    B, Nq, _ = o["q"].shape
+    Nk = o["k"].shape[1]
+    q8, k, v = _heads(scale8_ref(o["q"]), heads), _heads(o["k"], heads), _heads(o["v"], heads)
+    s2 = q8 @ k.transpose(1, 2)
+    ab = q8.abs() @ k.abs().transpose(1, 2)
+    m2 = s2.max(2, keepdim=True).values
+    p = torch.exp2(s2 - m2)
+    l = p.sum(2, keepdim=True)
+    lse = ((m2 + torch.log2(l)) * LN2)[..., 0]
+    dlse = (H * ((m2 * LN2).abs() + torch.log(l).abs()) + (Nk + 64) * U)[..., 0]
+    relp = _exp_rel(ab, m2.abs() + 8) + LN2 * U * (s2.abs() + m2.abs() + 8)
+    pv = (p @ v.abs()) / l
+    rel_l = (p * relp).sum(2, keepdim=True) / l + Nk * U
+    O = (p @ v) / l
+    dO = ((p * (2.0 ** -8 + relp)) @ v.abs()) / l + pv * (Nk * U + rel_l + 2 * ((Nk + 63) // 64) * U) + 3 * U * O.abs()
+    return dict(lse=lse, dlse=dlse, o=_unheads(O, B, heads), do=_unheads(dO, B, heads))
+
+
+def attn_bwd_ref(o, heads, lse32, o16):
+    """Delta, dQ, dK, dV from the PASSED-IN lse (fp32) and O (bf16), with
+        Delta = sum_d dO O: 64 exact products, 64 U sum|dO O| (a sum of 64 terms in any order),
+        P  = exp2(q8 . k - lse2)  in the dQ bodies, P' = exp2(q . k8 - lse2) in the dK / dV bodies, lse2 = fp32(lse x LOG2E) (U |lse2|),
+        dPm = dO . v - Delta (65 terms + the kernel's own Delta error), dS = P dPm (U),
+        dV = P'^T dO:  sum_i P' |dO| (2^-8 + relP') + Nq U sum_i P' |dO|                  (P' enters the matrix pipe as bf16),
+        dQ = scale dS k, dK = scale dS'^T q:  scale [sum (2^-8 |dS| + delta_dS) |k or q| + N U sum |dS| |k or q|] + U |result|
+                                                                                          (dS enters the matrix pipe as bf16)."""
+    B, Nq, _ = o["q"].shape
+    Nk = o["k"].shape[1]
+    q, k, v, dO = (_heads(o[n], heads) for n in ("q", "k", "v", "dO"))
+    q8, k8 = _heads(scale8_ref(o["q"]), heads), _heads(scale8_ref(o["k"]), heads)
+    oh = _heads(o16.float(), heads)
+    delta = (dO * oh).sum(2)
+    ddelta = 64 * U * (dO * oh).abs().sum(2)
+    lse2 = (lse32.double() * LOG2E_F32)[..., None]
+    dl2 = U * lse2.abs()
+    dpm = dO @ v.transpose(1, 2) - delta[..., None]
+    ddpm = 65 * U * (dO.abs() @ v.abs().transpose(1, 2) + delta.abs()[..., None]) + (ddelta + U * delta.abs())[..., None]
+    out = {"delta": delta, "ddelta": ddelta}
+    for name, (sa, sb) in (("dq", (q8, k)), ("dkv", (q, k8))):
+        s2 = sa @ sb.transpose(1, 2)
+        P = torch.exp2(s2 - lse2)
+        relP = _exp_rel(sa.abs() @ sb.abs().transpose(1, 2), lse2) + LN2 * dl2
+        dS = P * dpm
+        ddS = dS.abs() * (relP + U) + P * ddpm
+        if name == "dq":
+            w = (2.0 ** -8 * dS.abs() + ddS) @ k.abs() + Nk * U * (dS.abs() @ k.abs())
+            g = 0.125 * (dS @ k)
+            out["dq"], out["ddq"] = _unheads(g, B, heads), _unheads(0.125 * w + U * g.abs(), B, heads)
+        else:
+            w = (2.0 ** -8 * dS.abs() + ddS).transpose(1, 2) @ q.abs() + Nq * U * (dS.abs().transpose(1, 2) @ q.abs())
+            g = 0.125 * (dS.transpose(1, 2) @ q)
+            out["dk"], out["ddk"] = _unheads(g, B, heads), _unheads(0.125 * w + U * g.abs(), B, heads)
+            gv = P.transpose(1, 2) @ dO
+            wv = (P * (2.0 ** -8 + relP)).transpose(1, 2) @ dO.abs() + Nq * U * (P.transpose(1, 2) @ dO.abs())
+            out["dv"], out["ddv"] = _unheads(gv, B, heads), _unheads(wv + U * gv.abs(), B, heads)
+    return out
