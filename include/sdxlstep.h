@@ -332,6 +332,26 @@ typedef struct {
  * convolution whose input channels are padded in the arena -- together the last two refuse exactly conv_in.  sdxl_grad_select.lora keeps
  * SDXL_DTYPE_LORA's rule.  The cached device table is keyed by the dtype too. */
 #define SDXL_DTYPE_LORA_LAYOUTS 4
+/* ---- LoHa (LyCORIS Hadamard product) by merge and project: dtype SDXL_DTYPE_LOHA of the same two calls, the same host struct ----
+ * For a targeted weight W [out][in] with the factors A1, A2 [rank][in], B1, B2 [out][rank] and s = scale:
+ *   dW = s (B1 A1) .* (B2 A2)    (.* elementwise: effective rank up to rank^2 at the storage of rank 2 rank)
+ * `adapters` holds per target A1 [rank][in], B1 [out][rank], A2 [rank][in], B2 [out][rank] in that order, bf16, each padded to 8 elements;
+ * `adapter_grads` is fp32 and laid out the same way; `base` is SDXL_DTYPE_LORA_LAYOUTS' packed W0 copies.  The targets are everything
+ * SDXL_DTYPE_LORA_LAYOUTS accepts, with its maps: the factors are indexed like the state-dict tensor flattened to [out][prod(rest)], and only
+ * the rows < out of a target are read or written (conv_out's 4 other native rows are not touched).
+ * merge (one launch): p1 <- p1 + B1[o][k] A1[k][i] for k = 0 .. rank - 1, every product and every sum rounded on its own in fp32 (no FMA);
+ * p2 likewise from B2, A2; h = p1 p2, t = s h, W = bf16_rn(W0 + t) (round to nearest even), and W = W0 where t == 0: scale 0, B1 = 0 or
+ * B2 = 0 give back W0 bit for bit.
+ * project (two launches, from G = dW in the bound fp32 gradient arena, with P1 = B1 A1 and P2 = B2 A2 recomputed in fp32 on the fly):
+ *   dB1[o][k] = s sum_i (G[o][i] P2[o][i]) A1[k][i]      dA1[k][i] = s sum_o B1[o][k] (G[o][i] P2[o][i])
+ *   dB2[o][k] = s sum_i (G[o][i] P1[o][i]) A2[k][i]      dA2[k][i] = s sum_o B2[o][k] (G[o][i] P1[o][i])
+ * one launch writes dB1 | dB2, the other dA1 | dA2; each reads G once.  No out x in scratch, no atomics, the outputs are OVERWRITTEN; the
+ * summation order is fixed by (out, in, rank, kind) alone, so results are bitwise reproducible and a target's bits do not depend on the
+ * other targets of the call.
+ * Bad arguments (1, before any launch, the message names the tensor or `rank`): everything SDXL_DTYPE_LORA_LAYOUTS refuses, and a rank
+ * outside 1 .. 64.  sdxl_grad_select.lora keeps SDXL_DTYPE_LORA's rule: adapter gradients written by the backward itself are LoRA's only.
+ * The cached device table is keyed by the dtype too. */
+#define SDXL_DTYPE_LOHA 5
 /* ---- gradient selection: dtype SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad (no entry point of its own) ----
  *   sdxl_export_grad(h, NULL, &sel, SDXL_DTYPE_GRAD_SELECT, stream)
  * tells the backward which state-dict tensors are trained.  `sel` is a HOST pointer, read during the call; `name` must be NULL; a NULL

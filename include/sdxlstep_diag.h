@@ -74,6 +74,15 @@ SDXL_API int sdxl_op_lora_merge_layout(const void* base, const void* A, const vo
                               int cg, int native_rows, void* stream);
 SDXL_API int sdxl_op_lora_project_layout(const float* dw, const void* A, const void* B, float* dA, float* dB, int out, int in, int rank,
                                 float scale, int kind, int cg, int native_rows, void* stream);
+/* the LoHa kernels of SDXL_DTYPE_LOHA (csrc/loha.hip) on caller buffers, a table of one target, no handle: base, w (bf16) and dw (fp32) are
+ * NATIVE [out][in]; A1, A2 [rank][in], B1, B2 [out][rank] bf16 and dA1, dA2, dB1, dB2 fp32 (overwritten) are indexed like the state-dict tensor.
+ * kind / group as the _layout hooks' kind / cg (0: plain rows, group unused; 1: a 3x3 convolution, group = cin and in == 9 cin; 2: GEGLU rows,
+ * group = G, (out / 2) % G == 0); there are no padded native rows.  Argument checks: rank 1 .. 64, in % 8 == 0, out >= 1, a finite scale,
+ * every pointer 16-byte aligned. */
+SDXL_API int sdxl_op_loha_merge(const void* base, const void* A1, const void* B1, const void* A2, const void* B2, void* w, int out, int in, int rank,
+                       float scale, int kind, int group, void* stream);
+SDXL_API int sdxl_op_loha_project(const float* dw, const void* A1, const void* B1, const void* A2, const void* B2, float* dA1, float* dB1, float* dA2,
+                         float* dB2, int out, int in, int rank, float scale, int kind, int group, void* stream);
 /* the direct adapter-gradient kernels of sdxl_grad_select.lora (csrc/lora_grad.hip) on caller buffers, a table of one target, no handle:
  * x [M][in] (row stride ldx), dy [M][out] (row stride ldy: a column slice of a wider tensor is dy + offset), A [rank][in], B [out][rank] bf16;
  * dA [rank][in], dB [out][rank] fp32 = (accumulate ? previous : 0) + scale * (dY B)^T X, scale * dY^T (X A^T).  Rows past M and columns outside

@@ -119,6 +119,10 @@ class TrainingConfig:                    # data/config.py:152-168
     # which tensors may carry an adapter (lora.LORA_TARGET_KINDS): "plain" = 2-D linears stored as plain rows (the default); "all" = also
     # ff.net.0.proj and the convolutions (3x3 and 1x1; LoCon), through SDXL_DTYPE_LORA_LAYOUTS.  Not conv_in; not with lora_backward "direct"
     lora_target_kinds: str = "plain"
+    # the adapter family (lora.LORA_ALGOS): "lora" = dW = s B A (the default); "loha" = LyCORIS' Hadamard product dW = s (B1 A1) .* (B2 A2),
+    # four factors per target through SDXL_DTYPE_LOHA (csrc/loha.hip), lora_rank 1 .. 64, lora_backward "project" or "project_frozen";
+    # lora_target_kinds keeps deciding which tensors the patterns may resolve to
+    lora_algo: str = "lora"
 
 
 @dataclass

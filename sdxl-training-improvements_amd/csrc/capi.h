@@ -19,10 +19,11 @@ struct StepState {  // what backward needs from the preceding forward
   ResidualReq res;             // the additional skip residuals this micro-step carried (sdxl_batch_res): the backward writes res.d_*
   float* d_input = nullptr;    // the input gradient this micro-step asked for (sdxl_batch_din): the caller's buffer, written by conv_in's backward
 };
-struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS call, keyed by (target list, rank, dtype)
+struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS / SDXL_DTYPE_LOHA call, keyed by (target list, rank, dtype)
   std::vector<int> params;
   int rank = 0, dtype = 0, mapped = 0;
   LoraTarget* dev = nullptr;
+  LohaTarget* dev_loha = nullptr;      // SDXL_DTYPE_LOHA's table (one of the two is held at a time)
   int tiles_m = 0, tiles_b = 0, tiles_a = 0;
 };
 struct sdxl_handle {
@@ -45,6 +46,11 @@ static int lora_check_shape(const char* who, int out, int in, int rank) {
   return 0;
 }
 static bool aligned16(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
+// ... and of every LoHa entry point (SDXL_DTYPE_LOHA, the sdxl_op_loha_* hooks): the effective rank is rank^2, so the cap is lower
+static int loha_check_rank(int rank) {
+  ARG_CHECK(rank >= 1 && rank <= LOHA_MAX_RANK, "loha: rank %d outside 1 .. %d", rank, LOHA_MAX_RANK);
+  return 0;
+}
 
 // a handle that can run a step: planned, bound, with its workspace
 static int ready(Engine& e) {

@@ -74,6 +74,7 @@ int sdxl_destroy(sdxl_handle* h) {
   if (h->e.side) (void)hipStreamDestroy(h->e.side);
   if (h->e.small_ranges_dev) (void)hipFree(h->e.small_ranges_dev);
   if (h->lora.dev) (void)hipFree(h->lora.dev);
+  if (h->lora.dev_loha) (void)hipFree(h->lora.dev_loha);
   if (h->e.lora.dev) (void)hipFree(h->e.lora.dev);
   delete h;
   return 0;
@@ -203,6 +204,7 @@ static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
     int mapped = 0;
     CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, dtype == SDXL_DTYPE_LORA_LAYOUTS, &mapped));
     if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
+    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
     HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = dtype; c.mapped = mapped;
@@ -216,8 +218,58 @@ static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
   return 0;
 }
 
+// ---- LoHa by merge and project (SDXL_DTYPE_LOHA): SDXL_DTYPE_LORA_LAYOUTS' checks and targets, the rank cap, four factors per target ----
+static int loha_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LohaP& q) {
+  ARG_CHECK(name == nullptr, "loha: `name` must be NULL with SDXL_DTYPE_LOHA (the targets are listed in sdxl_lora_op.param)");
+  ARG_CHECK(op != nullptr, "loha: empty target list");
+  CHK(loha_check_rank(op->rank));
+  CHK(lora_check_op(op, merge, !merge));
+  Engine& e = h->e;
+  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "loha: %s are not bound", merge ? "weights" : "grads");
+  LoraCache& c = h->lora;
+  std::vector<int> params(op->param, op->param + op->n);
+  if (!(c.dev_loha && c.rank == op->rank && c.dtype == SDXL_DTYPE_LOHA && c.params == params)) {
+    std::vector<LoraTarget> tab;
+    long tm = 0, tb = 0, ta = 0;
+    int mapped = 0;
+    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, true, &mapped));      // every check of the packed layouts; offsets and tiles follow
+    std::vector<LohaTarget> htab(tab.size());
+    long at = 0;
+    tm = tb = ta = 0;
+    for (size_t i = 0; i < tab.size(); ++i) {
+      LohaTarget& x = htab[i];
+      x.t = tab[i];
+      const long na = ((long)op->rank * x.t.in + 7) / 8 * 8, nb = ((long)x.t.out * op->rank + 7) / 8 * 8;
+      x.t.a_off = x.t.ga_off = at; at += na;      // A1, B1, A2, B2, each padded to 8 elements
+      x.t.b_off = x.t.gb_off = at; at += nb;
+      x.a2_off = x.ga2_off = at; at += na;
+      x.b2_off = x.gb2_off = at; at += nb;
+      x.t.tile_m = (int)tm; x.t.tile_b = (int)tb; x.t.tile_a = (int)ta;
+      tm += loha_tiles_m(x.t.out, x.t.in); tb += loha_tiles_b(x.t.out, x.t.in); ta += loha_tiles_a(x.t.out, x.t.in);
+      ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "loha: too many tiles");
+    }
+    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
+    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
+    HIP_CHECK_RET(hipMalloc((void**)&c.dev_loha, htab.size() * sizeof(LohaTarget)));
+    HIP_CHECK_RET(hipMemcpy(c.dev_loha, htab.data(), htab.size() * sizeof(LohaTarget), hipMemcpyHostToDevice));
+    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOHA; c.mapped = 1;
+    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
+  }
+  memset(&q, 0, sizeof(q));
+  q.table = c.dev_loha; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a;
+  q.w = e.weights; q.base = (const bf16*)op->base; q.a1 = q.b1 = q.a2 = q.b2 = (const bf16*)op->adapters;
+  q.dw = e.grads; q.ga1 = q.gb1 = q.ga2 = q.gb2 = op->adapter_grads;
+  return 0;
+}
+
 int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtype, void* st) {
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LOHA) {
+    LohaP q;
+    CHK(loha_prepare(h, name, (const sdxl_lora_op*)src, true, q));
+    return launch_loha_merge(q, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
     CHK(lora_prepare(h, name, (const sdxl_lora_op*)src, true, q, dtype));
@@ -325,6 +377,11 @@ static int grad_select(sdxl_handle* h, const char* name, const sdxl_grad_select*
 int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, void* st) {
   if (dtype == SDXL_DTYPE_GRAD_SELECT) return grad_select(h, name, (const sdxl_grad_select*)dst);
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LOHA) {
+    LohaP q;
+    CHK(loha_prepare(h, name, (const sdxl_lora_op*)dst, false, q));
+    return launch_loha_project(q, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
     CHK(lora_prepare(h, name, (const sdxl_lora_op*)dst, false, q, dtype));

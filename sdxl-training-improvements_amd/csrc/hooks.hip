@@ -89,6 +89,38 @@ int sdxl_op_lora_project(const float* dw, const void* A, const void* B, float* d
   return lora_project_hook(dw, A, B, dA, dB, out, in, rank, scale, nullptr, st);
 }
 
+// ---- LoHa on caller buffers (csrc/loha.hip): the descriptor of one target, every offset 0 ----
+static int loha_one(int out, int in, int rank, float scale, int kind, int group, LohaP& q) {
+  CHK(loha_check_rank(rank));
+  LoraP l;
+  CHK(lora_one_layout(out, in, rank, scale, kind, group, out, l));
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = scale;
+  q.one.t = l.one;
+  q.tiles_m = loha_tiles_m(out, in); q.tiles_b = loha_tiles_b(out, in); q.tiles_a = loha_tiles_a(out, in);
+  return 0;
+}
+int sdxl_op_loha_merge(const void* base, const void* A1, const void* B1, const void* A2, const void* B2, void* w, int out, int in, int rank,
+                       float scale, int kind, int group, void* st) {
+  ARG_CHECK(aligned16(base) && aligned16(A1) && aligned16(B1) && aligned16(A2) && aligned16(B2) && aligned16(w),
+            "loha_merge: every pointer must be 16-byte aligned and non-NULL");
+  LohaP q;
+  CHK(loha_one(out, in, rank, scale, kind, group, q));
+  q.w = (bf16*)w; q.base = (const bf16*)base;
+  q.a1 = (const bf16*)A1; q.b1 = (const bf16*)B1; q.a2 = (const bf16*)A2; q.b2 = (const bf16*)B2;
+  return launch_loha_merge(q, (hipStream_t)st);
+}
+int sdxl_op_loha_project(const float* dw, const void* A1, const void* B1, const void* A2, const void* B2, float* dA1, float* dB1, float* dA2,
+                         float* dB2, int out, int in, int rank, float scale, int kind, int group, void* st) {
+  ARG_CHECK(aligned16(dw) && aligned16(A1) && aligned16(B1) && aligned16(A2) && aligned16(B2) && aligned16(dA1) && aligned16(dB1) &&
+            aligned16(dA2) && aligned16(dB2), "loha_project: every pointer must be 16-byte aligned and non-NULL");
+  LohaP q;
+  CHK(loha_one(out, in, rank, scale, kind, group, q));
+  q.dw = dw; q.a1 = (const bf16*)A1; q.b1 = (const bf16*)B1; q.a2 = (const bf16*)A2; q.b2 = (const bf16*)B2;
+  q.ga1 = dA1; q.gb1 = dB1; q.ga2 = dA2; q.gb2 = dB2;
+  return launch_loha_project(q, (hipStream_t)st);
+}
+
 int sdxl_op_lora_grad(const void* x, long ldx, const void* dy, long ldy, const void* A, const void* B, float* dA, float* dB, int M, int out, int in,
                       int rank, float scale, int accumulate, void* st) {
   ARG_CHECK(x && dy && aligned16(A) && aligned16(B) && aligned16(dA) && aligned16(dB), "lora_grad: A, B, dA, dB must be 16-byte aligned, x and dy non-NULL");

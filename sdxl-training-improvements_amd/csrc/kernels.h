@@ -593,6 +593,36 @@ static inline int lora_tiles_a(int out, int in) { return cdiv(in, LORA_A_COLS); 
 int launch_lora_merge(const LoraP& p, hipStream_t st);
 int launch_lora_project(const LoraP& p, hipStream_t st);     // two launches: dB, dA
 
+// ---- LoHa by merge and project (loha.hip; SDXL_DTYPE_LOHA): dW = s (B1 A1) .* (B2 A2), table-driven like LoRA's, always kind-aware ----
+#define LOHA_MAX_RANK 64
+#define LOHA_M_ROWS 32    // merge tile
+#define LOHA_M_COLS 64
+#define LOHA_M_KC 32      // ranks staged per step
+#define LOHA_P_ROWS 32    // project: the G .* P tile both launches walk
+#define LOHA_P_COLS 32
+struct LohaTarget {       // LoraTarget (its a / b offsets: the first pair) and the second pair's offsets; t.nrows is not used: only the
+  LoraTarget t;           // rows < out of a target are read or written
+  long a2_off, b2_off;    // adapter arena: A2 [rank][in], B2 [out][rank]
+  long ga2_off, gb2_off;  // adapter-gradient arena: dA2, dB2
+};
+struct LohaP {
+  const LohaTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
+  LohaTarget one;
+  int n, rank;                  // rank 1 .. LOHA_MAX_RANK
+  float scale;
+  int tiles_m, tiles_b, tiles_a;
+  bf16* w;                      // merge: out
+  const bf16* base;             // merge
+  const bf16 *a1, *b1, *a2, *b2;      // what the a / b offsets count from: the adapter arena four times, or the hook's factors (offsets 0)
+  const float* dw;              // project
+  float *ga1, *gb1, *ga2, *gb2;       // project: out, overwritten
+};
+static inline int loha_tiles_m(int out, int in) { return cdiv(out, LOHA_M_ROWS) * cdiv(in, LOHA_M_COLS); }
+static inline int loha_tiles_b(int out, int in) { return cdiv(out, LOHA_P_ROWS); }
+static inline int loha_tiles_a(int out, int in) { return cdiv(in, LOHA_P_COLS); }
+int launch_loha_merge(const LohaP& p, hipStream_t st);
+int launch_loha_project(const LohaP& p, hipStream_t st);     // two launches: dB1 | dB2, dA1 | dA2
+
 // ---- direct LoRA adapter gradients (lora_grad.hip): dA, dB of every target of ONE linear op from its X and dY, no dW ----
 #define LORA_G_CHUNK 512      // rows of M per partial block (a multiple of 32): the split of M is fixed by M alone
 struct LoraGradTarget {

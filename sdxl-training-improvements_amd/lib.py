@@ -130,6 +130,7 @@ class InputGradBatch(ResidualBatch):
 
 DTYPE_LORA = 2        # SDXL_DTYPE_LORA of sdxl_load_weight (merge) / sdxl_export_grad (project): the pointer is a host LoraOp*, name NULL
 DTYPE_LORA_LAYOUTS = 4  # SDXL_DTYPE_LORA_LAYOUTS: the same two calls and struct, targets in the arena's packed layouts accepted (lora.py, kinds="all")
+DTYPE_LOHA = 5        # SDXL_DTYPE_LOHA: the same two calls and struct, four factors per target: dW = s (B1 A1) .* (B2 A2) (lora.py, algo="loha")
 
 
 class LoraOp(C.Structure):
@@ -243,6 +244,8 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_lora_project": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "sdxl_op_lora_merge_layout": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],
     "sdxl_op_lora_project_layout": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],
+    "sdxl_op_loha_merge": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
+    "sdxl_op_loha_project": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
     "sdxl_op_lora_grad": [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
 }

@@ -19,6 +19,13 @@ training.lora_backward chooses how much of the full model's backward runs for th
                     skips its weight / bias / norm-parameter gradient work; dW of the targets' ops is formed and projected as before;
   "direct"          every tensor is frozen and the targets' ops write dA = s (dY B)^T X, dB = s dY^T (X A^T) themselves
                     (csrc/lora_grad.hip): no dW anywhere, no projection pass.
+
+training.lora_algo (LORA_ALGOS) chooses the adapter family.  "loha" is LyCORIS' Hadamard product: four factors per target,
+  dW = s (B1 A1) .* (B2 A2),   A1, A2 [r, in], B1, B2 [out, r]   (LyCORIS: hada_w1_a = B1, hada_w1_b = A1, hada_w2_a = B2, hada_w2_b = A2)
+merged and projected the same way through dtype SDXL_DTYPE_LOHA (csrc/loha.hip): effective rank up to r^2 at the storage of rank 2 r, so
+the rank is capped at 64.  Its gradients are two projections of dW .* P with the other pair's product P recomputed on the fly; "direct" is
+LoRA's only.  Initialisation (this build's choice; LyCORIS was not at hand to compare with): B2 = 0, so dW = 0 and the first merged step
+has the plain trainer's bits; A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2) from lora_seed.
 """
 from __future__ import annotations
 
@@ -41,6 +48,16 @@ DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
 MAX_RANK = 128
 LORA_BACKWARDS = ("project", "project_frozen", "direct")
 LORA_TARGET_KINDS = ("plain", "all")
+LORA_ALGOS = ("lora", "loha")
+LOHA_MAX_RANK = 64
+EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors"}      # save_checkpoint's adapter file
+LOHA_FACTORS = (("A1", "hada_w1_b"), ("B1", "hada_w1_a"), ("A2", "hada_w2_b"), ("B2", "hada_w2_a"))      # arena order; the LyCORIS names
+
+
+def check_lora_algo(algo) -> str:
+    if algo not in LORA_ALGOS:
+        raise ValueError(f"training.lora_algo {algo!r}: expected one of {list(LORA_ALGOS)}")
+    return algo
 
 
 def check_lora_backward(mode) -> str:
@@ -139,15 +156,21 @@ def _prod(dims) -> int:
     return n
 
 
-def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int):
+def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int, algo: str = "lora"):
     """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements;
-    out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions"""
+    out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions.
+    algo "loha": {key: (A1 offset, B1 offset, A2 offset, B2 offset, out, in)}, the four factors in that order, each padded to 8"""
+    check_lora_algo(algo)
     lay, cur = {}, 0
     for k in targets:
         o, i = int(shapes[k][0]), _prod(shapes[k][1:])
-        a, cur = cur, cur + _pad8(rank * i)
-        b, cur = cur, cur + _pad8(o * rank)
-        lay[k] = (a, b, o, i)
+        offs = []
+        for _pair in range(2 if algo == "loha" else 1):
+            offs.append(cur)
+            cur += _pad8(rank * i)
+            offs.append(cur)
+            cur += _pad8(o * rank)
+        lay[k] = (*offs, o, i)
     return lay, cur
 
 
@@ -155,11 +178,14 @@ class LoRAAdapters:
     """The adapters of one net: bf16 arena `.weights`, fp32 `.grads` laid out like it, and the packed bf16 copy of the targets' W0."""
 
     def __init__(self, net, rank: int, alpha: Optional[float] = None, targets: Optional[Sequence[str]] = None, seed: int = 0,
-                 kinds: str = "plain"):
+                 kinds: str = "plain", algo: str = "lora"):
         self.kinds = check_target_kinds(kinds)
-        self.dtype = lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA
-        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
-            raise ValueError(f"lora_rank must be an integer in 1 .. {MAX_RANK} (got {rank!r})")
+        self.algo = check_lora_algo(algo)
+        # (loha: one dtype, the packed layouts' target rules in the library; `kinds` still says what the patterns may resolve to)
+        self.dtype = lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA
+        max_rank = LOHA_MAX_RANK if algo == "loha" else MAX_RANK
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
+            raise ValueError(f"lora_rank must be an integer in 1 .. {max_rank} (got {rank!r})" + (" with lora_algo 'loha'" if algo == "loha" else ""))
         self.net = net
         self.L = getattr(net, "L", None)
         self.rank = rank
@@ -172,17 +198,22 @@ class LoRAAdapters:
         self.shapes = {k: tuple(int(v) for v in shapes[k]) for k in self.targets}
         names = list(shapes)
         self.index = [names.index(k) for k in self.targets]
-        self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank)
+        self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank, algo)
         dev = net.weights.device
         self.weights = torch.zeros(self.param_elems, dtype=torch.bfloat16, device=dev)
         self.grads = torch.zeros(self.param_elems, dtype=torch.float32, device=dev)
         ranges = net.param_ranges()
         self.base = torch.cat([net.weights[ranges[k][0]: ranges[k][0] + ranges[k][1]] for k in self.targets])
         assert self.base.numel() == sum(ranges[k][1] for k in self.targets)      # (the targets' native ranges: out * in elements each)
-        g = torch.Generator().manual_seed(self.seed)          # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
+        g = torch.Generator().manual_seed(self.seed)
         for k in self.targets:
-            a, _b, _o, i = self.layout[k]
-            self.weights[a: a + rank * i] = (torch.randn(rank, i, generator=g) * (1.0 / rank)).to(torch.bfloat16).reshape(-1).to(dev)
+            o, i = self.layout[k][-2:]
+            if algo == "loha":      # this build's choice: B2 = 0 (dW = 0), A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2), drawn in the order A1, B1, A2
+                for name, shape, std in (("A1", (rank, i), 1.0), ("B1", (o, rank), 0.1), ("A2", (rank, i), 1.0)):
+                    self.factor(name, k).copy_((torch.randn(*shape, generator=g) * std).to(torch.bfloat16))
+            else:                   # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
+                a = self.layout[k][0]
+                self.weights[a: a + rank * i] = (torch.randn(rank, i, generator=g) * (1.0 / rank)).to(torch.bfloat16).reshape(-1).to(dev)
         self._param = (C.c_int * len(self.index))(*self.index)
 
     # ---- what a fused optimizer asks of its net
@@ -190,22 +221,55 @@ class LoRAAdapters:
         self.grads.zero_()
 
     def param_ranges(self) -> Dict[str, Tuple[int, int]]:
-        """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas"""
+        """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas;
+        algo "loha": "<module>.hada_w1_b" (A1), ".hada_w1_a" (B1), ".hada_w2_b" (A2), ".hada_w2_a" (B2), in arena order"""
         out = {}
-        for k, (a, b, o, i) in self.layout.items():
+        for k, lay in self.layout.items():
             mod = k[: -len(".weight")]
-            out[f"{mod}.lora_A.weight"] = (a, _pad8(self.rank * i))
-            out[f"{mod}.lora_B.weight"] = (b, _pad8(o * self.rank))
+            o, i = lay[-2:]
+            if self.algo == "loha":
+                for n, (_name, lyco) in enumerate(LOHA_FACTORS):
+                    out[f"{mod}.{lyco}"] = (lay[n], _pad8(self.rank * i if n % 2 == 0 else o * self.rank))
+                continue
+            out[f"{mod}.lora_A.weight"] = (lay[0], _pad8(self.rank * i))
+            out[f"{mod}.lora_B.weight"] = (lay[1], _pad8(o * self.rank))
         return out
 
     # ---- views
+    def _view(self, key: str, slot: int, grad: bool) -> torch.Tensor:
+        """slot-th block of the target (even: an A [rank, in], odd: a B [out, rank])"""
+        lay = self.layout[key]
+        o, i = lay[-2:]
+        rows, cols = (self.rank, i) if slot % 2 == 0 else (o, self.rank)
+        return (self.grads if grad else self.weights)[lay[slot]: lay[slot] + rows * cols].view(rows, cols)
+
+    def factor(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
+        """a LoHa factor "A1" | "B1" | "A2" | "B2" of a target (or its gradient), a view of the arena"""
+        if self.algo != "loha":
+            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r} (A and B)")
+        return self._view(key, [n for n, _l in LOHA_FACTORS].index(name), grad)
+
     def A(self, key: str, grad: bool = False) -> torch.Tensor:
-        a, _b, _o, i = self.layout[key]
-        return (self.grads if grad else self.weights)[a: a + self.rank * i].view(self.rank, i)
+        if self.algo == "loha":
+            raise ValueError("A: lora_algo 'loha' adapters have A1 and A2")
+        return self._view(key, 0, grad)
 
     def B(self, key: str, grad: bool = False) -> torch.Tensor:
-        _a, b, o, _i = self.layout[key]
-        return (self.grads if grad else self.weights)[b: b + o * self.rank].view(o, self.rank)
+        if self.algo == "loha":
+            raise ValueError("B: lora_algo 'loha' adapters have B1 and B2")
+        return self._view(key, 1, grad)
+
+    def A1(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor("A1", key, grad)
+
+    def B1(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor("B1", key, grad)
+
+    def A2(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor("A2", key, grad)
+
+    def B2(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor("B2", key, grad)
 
     # ---- the two device steps
     def _op(self, scale: float) -> lib.LoraOp:
@@ -241,7 +305,10 @@ class LoRAAdapters:
         self.net.set_trainable(names, lora=self._op(self.scale) if mode == "direct" else None)
 
     def check_direct(self) -> None:
-        """ValueError when a target is not one the direct adapter gradients (csrc/lora_grad.hip) take"""
+        """ValueError when a target is not one the direct adapter gradients (csrc/lora_grad.hip) take, or the adapters are not LoRA's"""
+        if self.algo != "lora":
+            raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
+                             f"{self.algo!r}'s (use 'project' or 'project_frozen')")
         bad = [k for k in self.targets if not is_plain_target(k, self.shapes[k])]
         if bad:
             raise ValueError(f"training.lora_backward 'direct': {bad[0]} {self.shapes[bad[0]]} is not a 2-D linear in plain row layout; the "
@@ -250,9 +317,11 @@ class LoRAAdapters:
     # ---- state
     def _meta(self) -> Dict[str, Any]:
         meta = {"rank": self.rank, "alpha": self.alpha, "seed": self.seed, "targets": list(self.targets),
-                "shapes": [[self.layout[k][2], self.layout[k][3]] for k in self.targets]}
+                "shapes": [list(self.layout[k][-2:]) for k in self.targets]}
         if self.kinds != "plain":      # (a plain state is what it has always been, byte for byte)
             meta["kinds"] = self.kinds
+        if self.algo != "lora":        # (and so is a LoRA state)
+            meta["algo"] = self.algo
         return meta
 
     def state_dict(self) -> Dict[str, Any]:
@@ -260,6 +329,8 @@ class LoRAAdapters:
 
     def check_state_dict(self, sd: Dict[str, Any]) -> None:
         mine = self._meta()
+        if sd.get("algo", "lora") != self.algo:
+            raise ValueError(f"lora state: lora_algo differs from this trainer's ({sd.get('algo', 'lora')!r} vs {self.algo!r})")
         if sd.get("kinds", "plain") != self.kinds:
             raise ValueError(f"lora state: kinds differs from this trainer's ({sd.get('kinds', 'plain')!r} vs {self.kinds!r})")
         for key in ("rank", "targets", "shapes"):
@@ -279,7 +350,18 @@ class LoRAAdapters:
     def export_tensors(self) -> Dict[str, torch.Tensor]:
         """{"unet.<module>.lora_A.weight", "unet.<module>.lora_B.weight"} in fp32 on the CPU, s folded into lora_B: a loader that
         assumes alpha = rank (scale 1) reproduces the delta s B A.  PEFT's shapes: [r, in] / [out, r] for a linear, [r, cin, kh, kw] /
-        [out, r, 1, 1] for a convolution (the down convolution has the layer's kernel, the up convolution is 1 x 1)."""
+        [out, r, 1, 1] for a convolution (the down convolution has the layer's kernel, the up convolution is 1 x 1).
+        algo "loha": the LyCORIS / kohya convention instead -- "lora_unet_<module path with '.' -> '_'>.hada_w1_a" [out, r] (B1), ".hada_w1_b"
+        [r, in kh kw] (A1), ".hada_w2_a" (B2), ".hada_w2_b" (A2) and ".alpha" (a scalar), fp32, s NOT folded in: a loader forms
+        (alpha / r) (w1_a w1_b) .* (w2_a w2_b) reshaped like the layer's weight."""
+        if self.algo == "loha":
+            out = {}
+            for k in self.targets:
+                pre = "lora_unet_" + k[: -len(".weight")].replace(".", "_")
+                for name, lyco in LOHA_FACTORS:
+                    out[f"{pre}.{lyco}"] = self.factor(name, k).float().cpu().contiguous()
+                out[f"{pre}.alpha"] = torch.tensor(self.alpha, dtype=torch.float32)
+            return out
         out = {}
         for k in self.targets:
             mod = k[: -len(".weight")]
@@ -331,8 +413,11 @@ class NativeLoRATrainer(NativeSDXLTrainer):
     def __init__(self, model, optimizer=None, train_dataloader=None, device=None, wandb_logger=None, config=None, **kwargs):
         tc = config.training if config is not None else None
         rank = getattr(tc, "lora_rank", 0)
-        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= MAX_RANK:
-            raise ValueError(f"training.lora_rank must be an integer in 1 .. {MAX_RANK} for the LoRA trainer (got {rank!r})")
+        self.lora_algo = check_lora_algo(getattr(tc, "lora_algo", "lora"))
+        max_rank = LOHA_MAX_RANK if self.lora_algo == "loha" else MAX_RANK
+        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
+            raise ValueError(f"training.lora_rank must be an integer in 1 .. {max_rank} for the LoRA trainer"
+                             + (" with training.lora_algo 'loha'" if self.lora_algo == "loha" else "") + f" (got {rank!r})")
         if bool(getattr(tc, "use_ema", False)):
             raise ValueError("training.use_ema: an EMA of adapters is not supported (training.lora_rank > 0)")
         if getattr(tc, "shard_optimizer", None):          # None = not given
@@ -341,6 +426,9 @@ class NativeLoRATrainer(NativeSDXLTrainer):
             logger.warning("NativeLoRATrainer builds its own fused optimizer on the adapter arena: the optimizer passed in is ignored")
         self.lora_backward = check_lora_backward(getattr(tc, "lora_backward", "project"))
         check_target_kinds(getattr(tc, "lora_target_kinds", "plain"))
+        if self.lora_algo != "lora" and self.lora_backward == "direct":
+            raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
+                             f"{self.lora_algo!r}'s (use 'project' or 'project_frozen')")
         super().__init__(model, None, train_dataloader, device, wandb_logger, config, **kwargs)
         self._projected = False
         if self.lora_backward != "project":
@@ -367,7 +455,7 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         if isinstance(targets, str):
             targets = [targets]
         self.lora = LoRAAdapters(self.net, int(tc.lora_rank), alpha, targets, int(getattr(tc, "lora_seed", 0)),
-                                 kinds=getattr(tc, "lora_target_kinds", "plain"))
+                                 kinds=getattr(tc, "lora_target_kinds", "plain"), algo=self.lora_algo)
         if self.lora_backward == "direct":      # (before any arena of the optimizer is built)
             self.lora.check_direct()
         opt = build_optimizer(self.lora, self.config.optimizer)
@@ -420,6 +508,7 @@ class NativeLoRATrainer(NativeSDXLTrainer):
 
     def save_checkpoint(self, epoch_or_path=0, is_final: bool = False) -> Optional[Path]:
         """`pytorch_lora_weights.safetensors` (fp32, keys unet.<module>.lora_A.weight / .lora_B.weight, s folded into lora_B),
+        with training.lora_algo "loha" `lycoris_loha.safetensors` instead (export_tensors has the keys),
         `lora_state.pt` (the bit-exact arena, settings and target list: load_lora_state), `optimizer.pt`, `config.json`; the merged
         UNet only with training.lora_save_merged.  Rank 0 writes; no collective."""
         if not D.is_main_process():
@@ -427,7 +516,7 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         from safetensors.torch import save_file
         d = checkpoint_dir(epoch_or_path, is_final)
         d.mkdir(parents=True, exist_ok=True)
-        save_file(self.lora.export_tensors(), str(d / "pytorch_lora_weights.safetensors"))
+        save_file(self.lora.export_tensors(), str(d / EXPORT_FILES[self.lora.algo]))
         torch.save(self.lora.state_dict(), str(d / "lora_state.pt"))
         with open(d / "config.json", "w") as f:
             json.dump(self.config.to_dict(), f, indent=2)
