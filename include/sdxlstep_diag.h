@@ -115,15 +115,34 @@ SDXL_API int sdxl_debug_input_dgrad_operands(sdxl_handle* h, size_t* dy_ws_byte_
 /* which kernel a GEMM launch takes (csrc/gemm.hip, gemm_route: the single implementation of DESIGN.md section 4's table), without launching it and
  * without a device.  The descriptor is what the problem's line in the launch log (SDXL_LAUNCH_LOG) carries, in the same order: emit_bf16 / delta /
  * bias_grad are presence flags (GemmP::Cb, delta_out, bias_grad); Hm .. sd the 3x3 gather's image sizes and strides (taps != 1).  The same checks and normalisation as
- * a launch are applied first (their errors are returned).  kernel: 0 the 128-row kernel (cfg 1, 2, 3, 13, 23, 5, 6), 1 the 256 x 256 kernel, 2 the
+ * a launch are applied first (their errors are returned).  rowvec, the struct's last field, is NOT in the launch log: a presence flag for a row vector in the
+ * epilogue (GemmP::rowvec; the pipelined kernel has none and refuses the problem).  kernel: 0 the 128-row kernel (cfg 1, 2, 3, 13, 23, 5, 6), 1 the 256 x 256 kernel, 2 the
  * co-resident 256-row kernel (cfg 31 .. 36), 3 the pipelined kernel (cfg 7, 8), 4 the long-reduction weight gradient, 5 the three-tap convolution
  * weight gradient, 6 stream-K (diagnostics build); fast: the 128-row kernel's FAST staging; post: 0 none, 1 fp32 split-K reduce, 2 split-K sum +
  * bf16 epilogue. */
 typedef struct sdxl_gemm_desc {
-  int form, taps, M, N, K, splitk, group, cfg, geglu, geglu_group, Hm, Wm, Hs, Ws, sm, sd, up2, emit_bf16, delta, bias_grad;
+  int form, taps, M, N, K, splitk, group, cfg, geglu, geglu_group, Hm, Wm, Hs, Ws, sm, sd, up2, emit_bf16, delta, bias_grad, rowvec;
 } sdxl_gemm_desc;
 typedef struct sdxl_gemm_route { int kernel, cfg, fast, post; } sdxl_gemm_route;
 SDXL_API int sdxl_debug_gemm_route(const sdxl_gemm_desc* problem, sdxl_gemm_route* out);
+
+/* the time-embedding path on caller buffers.  sdxl_op_gemm_rowvec: the NT form (form 0 only) with the row-vector epilogue of a resnet's first
+ * convolution, C [M][N] = bf16(A [M][K] . B [N][K]^T + bias [N] + rowvec [m / rows_per_batch][n] + resid [M][N]) in one rounding; rowvec points at the
+ * first used column of a [M / rows_per_batch][ldv] bf16 matrix (a column slice: ldv >= N).  cfg as sdxl_op_gemm_ld's, splitk > 1 as sdxl_op_gemm's.
+ * sdxl_op_conv3x3_fwd_rowvec: the same epilogue through the 3x3 convolution (stride 1, pad 1) as the plan builds it: its own split factor,
+ * rows_per_batch = H * W.  Both refuse, before any launch, a vector that is NULL or not 16-byte aligned, ldv % 8 != 0 or ldv < N,
+ * rows_per_batch < 1, M % rows_per_batch != 0. */
+SDXL_API int sdxl_op_gemm_rowvec(int form, const void* A, const void* B, void* C, int M, int N, int K, const void* bias, const void* resid,
+                        const void* rowvec, long ldv, int rows_per_batch, int splitk, int cfg, void* stream);
+SDXL_API int sdxl_op_conv3x3_fwd_rowvec(const void* x, const void* w, const void* bias, const void* rowvec, long ldv, void* y, int B, int H, int W,
+                               int Cin, int Cout, void* stream);
+/* the backward of that broadcast: out [b][n] (fp32, row stride ld_out) += sum over r < rows of x [b * rows + r][n] (bf16, row stride ldx), fp32 sums
+ * in a fixed order (no atomics between blocks: bitwise reproducible).  batches 1 .. 64, N % 8 == 0, ldx % 8 == 0; one batch with ld_out = 0 is the
+ * up-sampler's bias gradient. */
+SDXL_API int sdxl_op_colsum(const void* x, long ldx, float* out, long ld_out, int batches, int rows, int N, void* stream);
+/* the sinusoidal embedding: out [rows][ldo] bf16, columns [0, dim / 2) = cos, [dim / 2, dim) = sin of t [r] (fp32) * exp(-ln(10000) k / (dim / 2));
+ * dim even, ldo >= dim; columns past dim are not written. */
+SDXL_API int sdxl_op_sincos(const float* t, void* out, int rows, int dim, long ldo, void* stream);
 
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,

@@ -1644,6 +1644,9 @@ static int gemm_check(GemmP& p) {
   ARG_CHECK(p.taps == 1 || p.taps == 9, "gemm: taps=%d", p.taps);
   ARG_CHECK(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0 && ((uintptr_t)p.C & 15) == 0,
             "gemm: operands must be 16-byte aligned");
+  if (p.rowvec)      // the epilogues load the vector in 16-byte pieces and divide the row by rows_per_batch
+    ARG_CHECK(((uintptr_t)p.rowvec & 15) == 0 && p.ldv % 8 == 0 && p.rows_per_batch >= 1,
+              "gemm: the row vector must be 16-byte aligned, ldv=%ld a multiple of 8, rows_per_batch=%d at least 1", p.ldv, p.rows_per_batch);
   if (p.form == GEMM_TN) {
     ARG_CHECK(p.M % 8 == 0, "gemm TN: M=%d must be a multiple of 8", p.M);
     ARG_CHECK(p.out_f32, "gemm TN: only fp32 output is implemented");

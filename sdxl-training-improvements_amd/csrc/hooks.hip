@@ -446,6 +446,58 @@ int sdxl_op_gemm_ld(int form, const void* A, const void* B, void* C, int M, int 
   g.cfg = cfg;
   return launch_gemm(g, (hipStream_t)st);
 }
+// ---- the time-embedding path on caller buffers (include/sdxlstep_diag.h part 1) ----
+// what a hook refuses of a row vector before any launch: the kernels load it in 16-byte pieces and divide the row by rows_per_batch
+static int rowvec_check(const char* who, const void* rowvec, long ldv, int rows_per_batch, long M, int N) {
+  ARG_CHECK(aligned16(rowvec), "%s: the row vector must be 16-byte aligned and non-NULL", who);
+  ARG_CHECK(ldv % 8 == 0 && ldv >= N, "%s: ldv = %ld must be a multiple of 8 and at least N = %d", who, ldv, N);
+  ARG_CHECK(rows_per_batch >= 1 && M % rows_per_batch == 0, "%s: %ld rows are not whole samples of %d rows", who, M, rows_per_batch);
+  return 0;
+}
+// the NT problem of a resnet's first convolution as a dense launch: C = bf16(A . B^T + bias + rowvec[m / rows_per_batch] + resid), the vector a
+// column slice of a wider [M / rows_per_batch][ldv] matrix; cfg as sdxl_op_gemm_ld's, splitk > 1 as sdxl_op_gemm's
+int sdxl_op_gemm_rowvec(int form, const void* A, const void* B, void* C, int M, int N, int K, const void* bias, const void* resid, const void* rowvec,
+                        long ldv, int rows_per_batch, int splitk, int cfg, void* st) {
+  ARG_CHECK(form == GEMM_NT, "gemm_rowvec: NT only (form %d)", form);
+  ARG_CHECK(M > 0 && N > 0 && K > 0, "gemm_rowvec: empty problem M=%d N=%d K=%d", M, N, K);
+  CHK(rowvec_check("gemm_rowvec", rowvec, ldv, rows_per_batch, M, N));
+  GemmP g = linear_fwd_problem((const bf16*)A, K, (const bf16*)B, C, N, M, N, K, (const bf16*)bias, (const bf16*)resid, N);
+  g.rowvec = (const bf16*)rowvec; g.ldv = ldv; g.rows_per_batch = rows_per_batch;
+  g.cfg = cfg;
+  if (splitk > 1) {
+    g.splitk = splitk;
+    CHK(hook_floats(gemm_slab_floats(M, N, 1, splitk), &g.slab));
+  }
+  return launch_gemm(g, (hipStream_t)st);
+}
+// ... and as ConvOp::fwd builds it: stride 1, the plan's split factor, one vector per image
+int sdxl_op_conv3x3_fwd_rowvec(const void* x, const void* w, const void* bias, const void* rowvec, long ldv, void* y, int B, int H, int W, int Cin,
+                               int Cout, void* st) {
+  ARG_CHECK(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_fwd_rowvec: empty problem");
+  CHK(rowvec_check("conv3x3_fwd_rowvec", rowvec, ldv, H * W, (long)B * H * W, Cout));
+  GemmP g = conv3x3_fwd_problem(B, H, W, Cin, Cout, 1);
+  g.A = (const bf16*)x; g.B = (const bf16*)w; g.C = y;
+  g.bias = (const bf16*)bias;
+  g.rowvec = (const bf16*)rowvec; g.ldv = ldv; g.rows_per_batch = H * W;
+  g.splitk = conv3x3_fwd_splitk(B, H, W, Cin, Cout, 1);
+  if (g.splitk > 1) CHK(hook_floats(gemm_slab_floats(g.M, Cout, 1, g.splitk), &g.slab));
+  return launch_gemm(g, (hipStream_t)st);
+}
+// the backward of that broadcast (and, as one batch with ld_out = 0, the up-sampler's bias gradient): out[b][n] += sum over the rows of batch b
+int sdxl_op_colsum(const void* x, long ldx, float* out, long ld_out, int batches, int rows, int N, void* st) {
+  ARG_CHECK(batches >= 1 && batches <= LN_RED_MAX, "colsum: %d batches (1 .. %d)", batches, LN_RED_MAX);
+  ARG_CHECK(aligned16(x) && out && ((uintptr_t)out & 3) == 0, "colsum: x must be 16-byte aligned, out non-NULL");
+  ARG_CHECK(rows >= 1 && N >= 8 && N % 8 == 0 && ldx >= N && ldx % 8 == 0, "colsum: rows = %d, N = %d, ldx = %ld", rows, N, ldx);
+  ARG_CHECK(batches == 1 || ld_out >= N, "colsum: ld_out = %ld holds no row of %d sums", ld_out, N);
+  float* part;
+  CHK(hook_floats(colsum_part_floats(batches, rows, N), &part));
+  return launch_colsum_f32_batched((const bf16*)x, out, batches, rows, N, ldx, ld_out, part, (hipStream_t)st);
+}
+// the sinusoidal embedding: out [rows][ldo] bf16, columns [0, dim) = cos | sin of t[r] exp(-ln(1e4) k / (dim / 2))
+int sdxl_op_sincos(const float* t, void* out, int rows, int dim, long ldo, void* st) {
+  ARG_CHECK(t && out && rows >= 1 && dim >= 2 && ldo >= dim && (long)rows * dim < (1L << 31), "sincos: rows = %d, dim = %d, ldo = %ld", rows, dim, ldo);
+  return launch_sincos(t, (bf16*)out, rows, dim, ldo, (hipStream_t)st);
+}
 // test hook (include/sdxlstep_diag.h part 1): the NN dgrad with the Delta epilogue, as LinearOp::bwd launches it for a self-attention
 // layer's out-projection
 int sdxl_op_linear_dgrad_delta(const void* dy, const void* w, const void* o, const void* addend, void* d_o, float* delta, int B, int Nq,
@@ -482,6 +534,7 @@ int sdxl_debug_gemm_route(const sdxl_gemm_desc* d, sdxl_gemm_route* out) {
     for (int i = 0; i < d->group && i < GEMM_MAX_GROUP; ++i) { g.gA[i] = g.gB[i] = (const bf16*)word; g.gC[i] = word; g.gCb[i] = d->emit_bf16 ? (bf16*)word : nullptr; g.gbias_grad[i] = d->bias_grad ? word : nullptr; }
   } else if (d->emit_bf16) g.Cb = (bf16*)word;
   if (d->bias_grad) g.bias_grad = word;
+  if (d->rowvec) { g.rowvec = (const bf16*)word; g.ldv = 8; g.rows_per_batch = d->M; }      // (one sample: no route looks at the sample height)
   if (d->delta) { g.delta_out = word; g.delta_o = (const bf16*)word; g.delta_nq = d->M; g.delta_heads = d->N / 64; }
   GemmRoute r;
   if (int e = gemm_route_checked(g, &r)) return e;

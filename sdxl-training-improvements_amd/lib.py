@@ -247,9 +247,14 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_loha_merge": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
     "sdxl_op_loha_project": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
     "sdxl_op_lora_grad": [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
+    "sdxl_debug_gemm_route": [_P(_i), _P(_i)],      # sdxl_gemm_desc (GEMM_DESC_FIELDS + GEMM_DESC_HOOK_FIELDS ints) -> sdxl_gemm_route (GEMM_ROUTE_FIELDS ints)
+    "sdxl_op_gemm_rowvec": [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _l, _i, _i, _i, _vp],
+    "sdxl_op_conv3x3_fwd_rowvec": [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp],
+    "sdxl_op_colsum": [_vp, _l, _vp, _l, _i, _i, _i, _vp],
+    "sdxl_op_sincos": [_vp, _vp, _i, _i, _l, _vp],
 }
 GEMM_DESC_FIELDS = ("form", "taps", "M", "N", "K", "splitk", "group", "cfg", "geglu", "geglu_group", "Hm", "Wm", "Hs", "Ws", "sm", "sd", "up2", "emit_bf16", "delta", "bias_grad")
+GEMM_DESC_HOOK_FIELDS = ("rowvec",)      # the struct's tail that the launch log does not carry: a row vector in the epilogue (default 0)
 GEMM_ROUTE_FIELDS = ("kernel", "cfg", "fast", "post")
 GEMM_KERNELS = ("128-row", "256x256", "cr256", "pipelined", "wgrad256", "conv_wgrad3", "stream-K")
 GEMM_POSTS = ("none", "splitk_reduce", "splitk_epilogue")
@@ -258,11 +263,12 @@ GEMM_POSTS = ("none", "splitk_reduce", "splitk_epilogue")
 def gemm_route(**problem) -> dict:
     """what launch_gemm would run for a problem (sdxl_debug_gemm_route; no device needed): kernel and post by name, cfg, fast.  Unnamed fields: a plain
     unsplit linear problem."""
-    d = dict(dict.fromkeys(GEMM_DESC_FIELDS, 0), taps=1, splitk=1, group=1, sm=1, sd=1)
+    fields = GEMM_DESC_FIELDS + GEMM_DESC_HOOK_FIELDS
+    d = dict(dict.fromkeys(fields, 0), taps=1, splitk=1, group=1, sm=1, sd=1)
     assert set(problem) <= set(d), set(problem) - set(d)
     d.update(problem)
     out = (_i * len(GEMM_ROUTE_FIELDS))()
-    check(load().sdxl_debug_gemm_route((_i * len(GEMM_DESC_FIELDS))(*[int(d[k]) for k in GEMM_DESC_FIELDS]), out), "sdxl_debug_gemm_route")
+    check(load().sdxl_debug_gemm_route((_i * len(fields))(*[int(d[k]) for k in fields]), out), "sdxl_debug_gemm_route")
     r = dict(zip(GEMM_ROUTE_FIELDS, out))
     return dict(r, kernel=GEMM_KERNELS[r["kernel"]], post=GEMM_POSTS[r["post"]], fast=bool(r["fast"]))
 

@@ -157,8 +157,8 @@ def gemm_operands(form, M, N, K, integer, seed=0, nonzero=False):
 def gemm_ref64(form, ops, bias=True, resid=True):
     """(float64 result, the same product on absolute values + absolute addends) of one form"""
     d = {k: v.double() for k, v in ops.items()}
-    if form == 2:
-        return d["a"].T @ d["b"], d["a"].abs().T @ d["b"].abs()
+    if form == 2:      # (+ 0.0: the accumulator starts at +0, and (+0) + (-0) = +0 -- at K = 1 a lone product 0 x (-2) would otherwise leave the reference at -0)
+        return d["a"].T @ d["b"] + 0.0, d["a"].abs().T @ d["b"].abs()
     w = d["w"].T if form == 0 else d["w"]
     ref, ab = d["a"] @ w, d["a"].abs() @ w.abs()
     if bias:
@@ -197,6 +197,12 @@ PIPELINED_CFGS = [7, 8, 5, 6]
 PIPELINED = [(128, 160, 64), (128, 128, 256), (256, 320, 192)]
 STREAM_K_WORKERS = [1, 7, 37, 0]
 STREAM_K_PROBLEMS = [(0, 512, 768, 640), (1, 512, 768, 640), (2, 512, 256, 2048)]         # (form, M, N, K): tests/test_gpu_ops.py's stream-K launches
+# reductions shorter than one K block: the weight gradients of the embedding linears and of the grouped time-embedding projection reduce over the
+# BATCH (K = B in {1, 2, 4}); the last row is the grouped projection of the full-size model at batch 4, whose other two forms follow
+TN_SHORT = [(320, 128, 1, 0), (320, 128, 2, 0), (320, 128, 4, 0), (200, 72, 4, 0), (2240, 1280, 4, 0)]
+TN_SHORT_FORCED = (512, 256, 4, 0)        # under the 256 x 256 mode and the co-resident words: K % 64 / K % 32 turn both away, the 128-row kernel must run
+NT_GROUPED_PROJECTION = (4, 2240, 1280)
+NN_GROUPED_PROJECTION = (4, 1280, 2240)
 CONV_WGRAD3 = [(1, 256, 64, 64, 64)]       # (B, H, W, Cin, Cout): W = 64 is the smallest width of conv_wgrad3.hip, 256 rows the fewest that make 16 384 pixels
 CONV_WGRAD3_SPLITK = [0, 1, 5]
 # the rounding cases: every bf16-output GEMM case below runs with the even residual (forms 0 / 1; form 1 as accumulate = 1 onto it)
@@ -220,6 +226,11 @@ def gemm_cases():
     out += [_c("gemm256 tn", 2, 2, M, N, K, sk, bias_grad=1) for (M, N, K, sk) in G256_TN]
     out += [_c("cfg 23", 4 * 23, f, *s) for s in CFG23 for f in (0, 1)]
     out += [_c(f"pipelined cfg {c}", 4 * c, f, *s) for c in PIPELINED_CFGS for s in PIPELINED for f in (0, 1)]
+    out += [_c("tn wgrad short reduction", 1, 2, M, N, K, sk, bias_grad=1) for (M, N, K, sk) in TN_SHORT]
+    out += [_c("nt default grouped projection", 1, 0, *NT_GROUPED_PROJECTION), _c("nn default grouped projection", 1, 1, *NN_GROUPED_PROJECTION)]
+    M, N, K, sk = TN_SHORT_FORCED
+    out += [_c("tn short reduction forced 256x256", 2, 2, M, N, K, sk, bias_grad=1)]
+    out += [_c(f"tn short reduction forced cr256 mode {m}", 4 * m, 2, M, N, K, sk, bias_grad=1) for m in CR256_MODES]
     return out
 
 

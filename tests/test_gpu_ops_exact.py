@@ -159,7 +159,7 @@ def test_bf16_split_k_equals_the_unsplit_launch_on_integers(L):
         assert X.same_bits(outs[0].cpu(), outs[1].cpu()), (M, N, K, sk)
 
 
-_FORCED = _fam("cr256", "gemm256", "cfg 23", "pipelined")
+_FORCED = _fam("cr256", "gemm256", "cfg 23", "pipelined", "tn short reduction forced")
 
 
 @pytest.mark.parametrize("c", _FORCED, ids=_ids(_FORCED))
