@@ -575,7 +575,55 @@ typedef struct {
                                   separately rounded fp32 ops (t1 = e - p, t2 = omd * t1, e = e - t2), i.e. diffusers'
                                   EMAModel.step on the parameter the module holds (not p + shift / kahan_comp) */
   float ema_one_minus_decay;   /* omd: 1 - decay of this update, in [0, 1] (the caller's python double rounded to float32) */
+  /* ---- appended: algorithm 2, Prodigy (sdxl_adamw_default_config zeroes them; algorithms 0 and 1 do not read them) ---- */
+  double beta3, d0, d_coef, growth_rate;   /* beta3 in [0, 1); d0 > 0; d_coef > 0; growth_rate >= 1 (infinity = unbounded) */
+  double prodigy_bc;           /* this step's bias-correction factor sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)), computed by the
+                                  caller in double precision; 1 when bias correction is off.  Finite and > 0 */
+  int safeguard_warmup;        /* 1: s accumulates d/d0 * d * g instead of d/d0 * dlr * g */
+  const void* p0;              /* bf16 [n]: the parameters at construction, read only */
+  float* s;                    /* fp32 [n]: Prodigy's s */
+  float* prodigy_state;        /* device array of SDXL_PRODIGY_STATE_FLOATS floats (below) */
 } sdxl_adamw_config;
+/* ---- algorithm 2: Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner"): AdamW whose
+ * step size d is estimated from two sums over the whole arena and lives on the device, so a step costs no host read-back.
+ * Arguments of sdxl_adamw_bf16_step under algorithm 2: p bf16; shift = the bf16 compensation c (the true parameter is x = p + c);
+ * m, v = FP32 exp_avg, exp_avg_sq; grad, grad_dtype, grad_scale_dev as above; rand_inject NULL; n a multiple of 8 and the whole
+ * arena of the call (d is one number per call: there is no sub-range form).  Every pointer 16-byte aligned.  Read from the
+ * config: lr (the multiplier on d), beta1, beta2, eps, weight_decay, grad_round_bf16, ema, ema_one_minus_decay and the fields
+ * appended for algorithm 2; not read: elem_offset, step, seed, reference_ema, decay_this_iteration.  lr == 0 returns 0 without a
+ * launch and writes nothing.  Argument errors (a NULL or misaligned buffer, n % 8, rand_inject, beta3 outside [0, 1), d0 <= 0,
+ * d_coef <= 0, growth_rate < 1, prodigy_bc not finite and positive, lr < 0, weight_decay < 0) return 1 before anything touches
+ * the device.
+ *
+ * prodigy_state: [0] d  [1] d_max  [2] num  [3] Bs  [4] d_hat  [5] dlr  [6] A  [7] 0; a fresh state is d = d_max = d0, the rest 0.
+ * Floats 8 .. are the reduction scratch, written before they are read: workgroup b's partial sums at [8 + 2b], [8 + 2b + 1].
+ *
+ * The arithmetic, all fp32 with every operation rounded on its own (host doubles are rounded to float once: omb1 = float(1 - beta1)
+ * and so on), three launches:
+ *   scalars from d = state[0]:  dlr = (d*lr)*bc   cm = d*omb1   cv = (d*d)*omb2   r = d/d0   cs = r*(safeguard ? d : dlr)   cn = r*dlr
+ *   accumulate, per element:    gr = grad * scale (rounded to bf16 with grad_round_bf16)     x = float(p) + float(c)
+ *                               t = gr*(float(p0) - x)   m' = (b1*m) + (cm*gr)   v' = (b2*v) + ((cv*gr)*gr)   s' = (b3*s) + (cs*gr)
+ *                               a = |s'|;   writes m', v', s' and each workgroup's partial sums of t and a
+ *   finalize, one workgroup:    A = sum t   Bs = sum a   num' = (b3*num) + (cn*A)
+ *                               Bs > 0:  d_hat = (d_coef*num')/Bs   d1 = (d == d0) ? max(d, d_hat) : d   d_max' = max(d_max, d_hat)
+ *                                        d' = min(d_max', d1*growth)
+ *                               else:    d, d_max unchanged, d_hat = d
+ *   apply, per element:         de = d'*eps   x = float(p) + float(c)   weight_decay != 0: x = x - ((wd*dlr)*x)
+ *                               x = x - (dlr*(m'/(sqrt(v') + de)))   p' = bf16_rn(x)   c' = bf16_rn(x - float(p'))
+ *                               then the EMA of p' when one is attached
+ * One deliberate departure from the prodigyopt package: when Bs == 0 (every s' is zero, e.g. all-zero gradients) the package
+ * returns before the parameter update and does not count the step; here the apply pass runs (with m' = 0 it moves nothing but the
+ * decay) and the caller counts the step, so that no step needs a read-back.
+ *
+ * The sums are bitwise reproducible: no atomics, the kernel boundary is the only synchronisation.  Geometry: workgroups of 256
+ * threads, grid G(n) = min(ceil(n / 2048), SDXL_PRODIGY_MAX_GRID); thread j of workgroup b owns the 8-element vectors
+ * i = b*256 + j, i + 256*G, ... below n/8 and adds their t (and a) in that order, element 0 .. 7 of each, into one fp32 sum, so a
+ * thread adds at most T(n) = 8 * ceil(n / (2048 * G(n))) terms; the workgroup's 256 sums go through a fixed pairwise tree
+ * (x[j] += x[j + h], h = 128, 64, .. 1); the finalize adds the G partials in double precision in ascending workgroup index
+ * (thread j of its one workgroup takes the partials j*ceil(G/256) .., then the 256 sums are added in ascending j) and rounds
+ * A and Bs to float once.  The bits depend on n and this geometry alone. */
+#define SDXL_PRODIGY_MAX_GRID 4096                                   /* the largest grid of the optimizer launches: 256 CUs x 16 */
+#define SDXL_PRODIGY_STATE_FLOATS (8 + 2 * SDXL_PRODIGY_MAX_GRID)
 SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1, algorithm 0, no EMA */
 SDXL_API int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,

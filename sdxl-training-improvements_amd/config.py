@@ -42,6 +42,14 @@ class OptimizerConfig:                   # data/config.py:42-49
     schedule_free_arithmetic: str = "compensated"   # build-only key: "compensated" = the Kahan-compensated fp32 update the
                                          # reference's docstring describes, "reference" = its literal bf16 arithmetic bit for
                                          # bit; see optimizer.py::AdamWScheduleFreeKahanBF16
+    # build-only keys, read by optimizer_type "prodigy" (optimizer.py::ProdigyBF16; the prodigyopt package's arguments).  With it
+    # learning_rate is the multiplier on the estimated step size d: set it to 1.0 (a value below 1e-2 is warned about)
+    prodigy_d0: float = 1e-6             # the initial estimate of d
+    prodigy_d_coef: float = 1.0          # multiplies the estimate
+    prodigy_growth_rate: float = float("inf")   # d grows by at most this factor per step (inf = unbounded)
+    prodigy_beta3: Optional[float] = None       # the decay of the estimate's sums; None = sqrt(beta2)
+    prodigy_use_bias_correction: bool = False   # Adam's bias correction in the step size
+    prodigy_safeguard_warmup: bool = False      # leave lr out of the denominator's sum (for a schedule with a warm-up)
 
 
 @dataclass

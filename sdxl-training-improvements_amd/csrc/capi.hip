@@ -1019,15 +1019,44 @@ static int sf_kahan_step(void* p, const void* grad, int grad_dtype, void* m, voi
   q.decay = (float)(ss * wd);
   return launch_sfk(q, c->sf_reference, st);
 }
+// algorithm 2 of sdxl_adamw_bf16_step (Prodigy): every argument error is reported before anything touches the device, and every
+// message names the algorithm
+static int prodigy_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* comp, size_t n, const sdxl_adamw_config* c,
+                        const float* grad_scale_dev, const unsigned short* rand_inject, hipStream_t st) {
+  const char* who = "prodigy (algorithm 2)";
+  ARG_CHECK(rand_inject == nullptr, "%s: rand_inject must be NULL (the update has no random rounding)", who);
+  ARG_CHECK(c->beta3 >= 0.0 && c->beta3 < 1.0, "%s: beta3 %g must lie in [0, 1)", who, c->beta3);
+  ARG_CHECK(c->d0 > 0.0 && std::isfinite(c->d0), "%s: d0 %g must be finite and > 0", who, c->d0);
+  ARG_CHECK(c->d_coef > 0.0 && std::isfinite(c->d_coef), "%s: d_coef %g must be finite and > 0", who, c->d_coef);
+  ARG_CHECK(c->growth_rate >= 1.0, "%s: growth_rate %g must be >= 1", who, c->growth_rate);
+  ARG_CHECK(std::isfinite(c->prodigy_bc) && c->prodigy_bc > 0.0, "%s: prodigy_bc %g must be finite and > 0", who, c->prodigy_bc);
+  ARG_CHECK(c->lr >= 0.0 && std::isfinite(c->lr), "%s: lr %g must be finite and >= 0", who, c->lr);
+  ARG_CHECK(c->weight_decay >= 0.0 && std::isfinite(c->weight_decay), "%s: weight_decay %g must be finite and >= 0", who, c->weight_decay);
+  ProdigyP q;
+  memset(&q, 0, sizeof(q));
+  CHK(fill_optim(q, p, grad, grad_dtype, m, v, n, c, grad_scale_dev, true, who));
+  q.m32 = (float*)m; q.v32 = (float*)v; q.s = c->s;
+  q.c = (bf16*)comp; q.p0 = (const bf16*)c->p0; q.state = c->prodigy_state;
+  // host doubles rounded to float once
+  q.lr = (float)c->lr; q.bc = (float)c->prodigy_bc;
+  q.one_minus_beta1 = (float)(1.0 - c->beta1);
+  q.beta3 = (float)c->beta3; q.eps = (float)c->eps;
+  q.d0 = (float)c->d0; q.d_coef = (float)c->d_coef; q.growth = (float)c->growth_rate;
+  q.wd = (float)c->weight_decay;
+  q.safeguard = c->safeguard_warmup != 0;
+  return launch_prodigy(q, st);
+}
 int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,
                          void* st) {
   ARG_CHECK(c, "null config");
   ARG_CHECK(grad_dtype == 0 || grad_dtype == 1, "adamw: grad_dtype %d (0 = fp32, 1 = bf16)", grad_dtype);
-  ARG_CHECK(c->algorithm == 0 || c->algorithm == 1, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan)", c->algorithm);
+  ARG_CHECK(c->algorithm >= 0 && c->algorithm <= 2, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan, algorithm 2 = Prodigy)",
+            c->algorithm);
   ARG_CHECK(c->ema == nullptr || (c->ema_one_minus_decay >= 0.f && c->ema_one_minus_decay <= 1.f),
             "adamw: ema_one_minus_decay %g must lie in [0, 1]", (double)c->ema_one_minus_decay);
   if (c->algorithm == 1) return sf_kahan_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
+  if (c->algorithm == 2) return prodigy_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
   AdamWP q;
   memset(&q, 0, sizeof(q));
   CHK(fill_optim(q, p, grad, grad_dtype, m, v, n, c, grad_scale_dev, c->step >= 1.0, "adamw"));

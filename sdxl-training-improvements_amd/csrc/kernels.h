@@ -520,6 +520,19 @@ struct SfkP : OptimP {
   float decay;                 // compensated mode: step_size * weight_decay (float32)
 };
 int launch_sfk(const SfkP& q, int reference, hipStream_t st);
+// Prodigy (prodigy_accumulate_kernel, prodigy_finalize_kernel, prodigy_apply_kernel): fp32 moments, so OptimP's bf16 m / v carry the
+// addresses for check_arenas only and the kernels read m32 / v32; beta1, beta2, one_minus_beta2 are OptimP's, eps_bf16 is not read
+struct ProdigyP : OptimP {
+  float *m32, *v32, *s;        // exp_avg, exp_avg_sq, Prodigy's s
+  bf16* c;                     // compensation: the true parameter is p + c
+  const bf16* p0;              // the parameters at construction
+  float* state;                // [8] d, d_max, num, Bs, d_hat, dlr, A, 0, then [2 * grid] the workgroups' partial sums (t, a) by index
+  float lr, bc;                // float32 of the caller's doubles: the multiplier on d, this step's bias-correction factor
+  float one_minus_beta1, beta3, eps, d0, d_coef, growth;
+  float wd;                    // weight_decay (float32), 0 = none
+  int safeguard;
+};
+int launch_prodigy(const ProdigyP& q, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);
 
 

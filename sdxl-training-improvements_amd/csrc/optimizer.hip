@@ -13,7 +13,11 @@
 // contract(off)` keeps the compiler from fusing anything else.  Stochastic rounding: r in [0, 2^16) is added to the
 // fp32 bit pattern and the low half dropped; r comes from a counter-based generator (Philox-4x32-7 keyed by the
 // seed, counter = (element-pair index, step)) or, for the parity tests, from a caller-supplied table.
+//
+// Two more updates share its entry point and its core, each with its own head comment below: the schedule-free Kahan AdamW
+// (algorithm 1, one pass, 16 / 20 B per element) and Prodigy (algorithm 2, two passes around a chip-wide reduction, 50 B per element).
 #include "kernels.h"
+#include "../../include/sdxlstep.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -161,6 +165,7 @@ static int check_arenas(const OptimP& q, const bf16* third, bool need_third, siz
   return 0;
 }
 // 256 threads x 8 elements per workgroup, at most 16 workgroups per CU (256 CUs): the kernels grid-stride the rest
+static_assert(SDXL_PRODIGY_MAX_GRID == 256 * 16, "SDXL_PRODIGY_STATE_FLOATS is sized by the largest grid arena_grid returns");
 static dim3 arena_grid(size_t n) {
   size_t blocks = (n / 8 + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
@@ -262,6 +267,162 @@ int launch_sfk(const SfkP& q, int reference, hipStream_t st) {
     hipLaunchKernelGGL((sfk_kernel<decltype(ref)::value, decltype(kahan)::value, decltype(f32g)::value, decltype(ema)::value>),
                        arena_grid(q.n), dim3(256), 0, st, q);
   }, reference != 0, q.c != nullptr, q.grad_f32 != nullptr, q.ema != nullptr);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+// ---- Prodigy (Mishchenko & Defazio 2023; include/sdxlstep.h, algorithm 2, is the contract) -------------------------------------
+// AdamW whose step size d is estimated from two sums over the arena, A = sum g.(p0 - x) and Bs = sum |s|, so one update is two
+// grid-stride passes with a chip-wide reduction between them, in three launches; the kernel boundary is the only synchronisation
+// (no atomics, no in-launch ticket), and d lives in q.state on the device: a step costs no host read-back.
+//   accumulate: reads p, c, p0 (bf16), the fp32 gradient, m, v, s (fp32) = 22 B; writes m, v, s = 12 B; one partial pair per workgroup
+//   finalize:   one workgroup: the partials in ascending workgroup index, in double; the scalar recurrence of d
+//   apply:      reads p, c (bf16), m, v (fp32) = 12 B; writes p, c = 4 B (+8 B with the EMA)
+// Per element 50 B (48 B with bf16 gradients) -> 128 GB over the 2.567 B-parameter arena, >= 16 ms at 8 TB/s; the adapter arenas
+// it is mostly used on are a few MB.  fp32 throughout, each operation rounded on its own (fp contract(off) above).
+struct ProdigyScalars { float dlr, cm, cv, cs, cn; };
+__device__ __forceinline__ ProdigyScalars prodigy_scalars(const ProdigyP& q, float d) {
+  ProdigyScalars k;
+  k.dlr = (d * q.lr) * q.bc;
+  k.cm = d * q.one_minus_beta1;
+  k.cv = (d * d) * q.one_minus_beta2;
+  const float r = d / q.d0;
+  k.cs = r * (q.safeguard ? d : k.dlr);
+  k.cn = r * k.dlr;
+  return k;
+}
+__device__ __forceinline__ void load8(const float* x, float o[8]) {
+  const f32x4 a = __builtin_nontemporal_load((const f32x4*)x), b = __builtin_nontemporal_load((const f32x4*)(x + 4));
+  o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
+}
+__device__ __forceinline__ void store8(float* x, const float o[8]) {
+  const f32x4 a = {o[0], o[1], o[2], o[3]}, b = {o[4], o[5], o[6], o[7]};
+  __builtin_nontemporal_store(a, (f32x4*)x);
+  __builtin_nontemporal_store(b, (f32x4*)(x + 4));
+}
+
+template <bool F32G>
+__global__ __launch_bounds__(256) void prodigy_accumulate_kernel(const ProdigyP q) {
+  __shared__ float red_t[256], red_a[256];
+  const size_t nvec = q.n / 8;
+  const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
+  const ProdigyScalars k = prodigy_scalars(q, q.state[0]);
+  float sum_t = 0.f, sum_a = 0.f;       // this thread's vectors in grid-stride order, elements 0 .. 7 of each
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e0 = i * 8;
+    const bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0)),
+                 p0v = __builtin_nontemporal_load((const bf16x8*)(q.p0 + e0));
+    float g[8], m[8], v[8], s[8];
+    load_grad8<true>(q, F32G, e0, g);
+    load8(q.m32 + e0, m);
+    load8(q.v32 + e0, v);
+    load8(q.s + e0, s);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float gr = scaled_grad(q, g[e], gscale);
+      const float x = bf(pv[e]) + bf(cv[e]);
+      const float t = gr * (bf(p0v[e]) - x);
+      m[e] = (q.beta1 * m[e]) + (k.cm * gr);
+      v[e] = (q.beta2 * v[e]) + ((k.cv * gr) * gr);
+      s[e] = (q.beta3 * s[e]) + (k.cs * gr);
+      sum_t = sum_t + t;
+      sum_a = sum_a + __builtin_fabsf(s[e]);
+    }
+    store8(q.m32 + e0, m);
+    store8(q.v32 + e0, v);
+    store8(q.s + e0, s);
+  }
+  // the workgroup's fixed tree: x[j] += x[j + h], h = 128 .. 1
+  red_t[threadIdx.x] = sum_t;
+  red_a[threadIdx.x] = sum_a;
+  __syncthreads();
+#pragma unroll
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      red_t[threadIdx.x] = red_t[threadIdx.x] + red_t[threadIdx.x + h];
+      red_a[threadIdx.x] = red_a[threadIdx.x] + red_a[threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    q.state[8 + 2 * (size_t)blockIdx.x] = red_t[0];
+    q.state[8 + 2 * (size_t)blockIdx.x + 1] = red_a[0];
+  }
+}
+
+// one workgroup of 256 threads; grid = the accumulate launch's grid (<= SDXL_PRODIGY_MAX_GRID partial pairs)
+__global__ __launch_bounds__(256) void prodigy_finalize_kernel(const ProdigyP q, int grid) {
+  __shared__ double red_t[256], red_a[256];
+  const int per = (grid + 255) / 256;
+  double st = 0.0, sa = 0.0;
+  for (int b = (int)threadIdx.x * per; b < ((int)threadIdx.x + 1) * per && b < grid; ++b) {
+    st = st + (double)q.state[8 + 2 * b];
+    sa = sa + (double)q.state[8 + 2 * b + 1];
+  }
+  red_t[threadIdx.x] = st;
+  red_a[threadIdx.x] = sa;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double At = 0.0, Ba = 0.0;
+  for (int j = 0; j < 256; ++j) {
+    At = At + red_t[j];
+    Ba = Ba + red_a[j];
+  }
+  const float A = (float)At, Bs = (float)Ba;
+  const float d = q.state[0], d_max = q.state[1], num = q.state[2];
+  const ProdigyScalars k = prodigy_scalars(q, d);
+  const float num1 = (q.beta3 * num) + (k.cn * A);
+  float d_new = d, d_max_new = d_max, d_hat = d;
+  if (Bs > 0.f) {
+    d_hat = (q.d_coef * num1) / Bs;
+    const float d1 = d == q.d0 ? __builtin_fmaxf(d, d_hat) : d;
+    d_max_new = __builtin_fmaxf(d_max, d_hat);
+    d_new = __builtin_fminf(d_max_new, d1 * q.growth);
+  }
+  q.state[0] = d_new; q.state[1] = d_max_new; q.state[2] = num1; q.state[3] = Bs;
+  q.state[4] = d_hat; q.state[5] = k.dlr; q.state[6] = A; q.state[7] = 0.f;
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void prodigy_apply_kernel(const ProdigyP q) {
+  const size_t nvec = q.n / 8;
+  const float de = q.state[0] * q.eps, dlr = q.state[5];
+  const float decay = q.wd * dlr;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e0 = i * 8;
+    bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0));
+    float m[8], v[8];
+    load8(q.m32 + e0, m);
+    load8(q.v32 + e0, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float x = bf(pv[e]) + bf(cv[e]);
+      if (q.wd != 0.f) x = x - (decay * x);
+      x = x - (dlr * (m[e] / (__builtin_sqrtf(v[e]) + de)));
+      const bf16 pb = rn(x);
+      pv[e] = pb;
+      cv[e] = rn(x - bf(pb));
+    }
+    __builtin_nontemporal_store(pv, (bf16x8*)(q.p + e0));
+    __builtin_nontemporal_store(cv, (bf16x8*)(q.c + e0));
+    if constexpr (EMA) ema_update8(q.ema + e0, pv, q.ema_omd);
+  }
+}
+
+int launch_prodigy(const ProdigyP& q, hipStream_t st) {
+  const char* who = "prodigy (algorithm 2)";
+  if (int rc = check_arenas(q, q.c, true, 0, who, "%s: n=%zu must be a multiple of 8")) return rc;
+  ARG_CHECK(q.p0 && q.s && q.state, "%s: missing buffers (p0, s, prodigy_state)", who);
+  ARG_CHECK((((uintptr_t)q.p0 | (uintptr_t)q.s | (uintptr_t)q.state) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  if (q.n == 0 || q.lr == 0.f) return 0;      // a schedule that starts at 0: nothing is written
+  const dim3 grid = arena_grid(q.n);
+  with_flags([&](auto f32g) {
+    hipLaunchKernelGGL((prodigy_accumulate_kernel<decltype(f32g)::value>), grid, dim3(256), 0, st, q);
+  }, q.grad_f32 != nullptr);
+  hipLaunchKernelGGL(prodigy_finalize_kernel, dim3(1), dim3(256), 0, st, q, (int)grid.x);
+  with_flags([&](auto ema) {
+    hipLaunchKernelGGL((prodigy_apply_kernel<decltype(ema)::value>), grid, dim3(256), 0, st, q);
+  }, q.ema != nullptr);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -159,7 +159,15 @@ class AdamWConfig(C.Structure):
                 ("algorithm", C.c_int), ("kahan_sum", C.c_int), ("sf_reference", C.c_int),
                 ("weight_decay", C.c_double), ("sf_step_size", C.c_double),
                 # appended: fp32 EMA of the weights (ema.WeightEMA), NULL = none
-                ("ema", C.c_void_p), ("ema_one_minus_decay", C.c_float)]
+                ("ema", C.c_void_p), ("ema_one_minus_decay", C.c_float),
+                # appended: algorithm 2 = Prodigy (optimizer.ProdigyBF16)
+                ("beta3", C.c_double), ("d0", C.c_double), ("d_coef", C.c_double), ("growth_rate", C.c_double),
+                ("prodigy_bc", C.c_double), ("safeguard_warmup", C.c_int), ("p0", C.c_void_p), ("s", C.c_void_p),
+                ("prodigy_state", C.c_void_p)]
+
+
+PRODIGY_MAX_GRID = 4096                              # SDXL_PRODIGY_MAX_GRID: the largest grid of the optimizer launches
+PRODIGY_STATE_FLOATS = 8 + 2 * PRODIGY_MAX_GRID      # SDXL_PRODIGY_STATE_FLOATS
 
 
 _vp, _i, _f, _l, _sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t

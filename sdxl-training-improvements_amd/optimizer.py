@@ -3,8 +3,8 @@
 FusedArenaOptimizer is what the trainer knows: gradients taken from the arena, one fused launch per update (per piece under
 ZeRO-1), and the host surface step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups,
 step_count, state_dict / load_state_dict, state_arenas, attach_ema (an ema.WeightEMA updated inside the same launch, on the same
-pieces).  Its two algorithms, by optimizer_type (BY_TYPE): AdamWBF16 ("adamw_bf16", the default) and AdamWScheduleFreeKahanBF16
-("adamw_schedule_free_kahan", see its docstring).
+pieces).  Its three algorithms, by optimizer_type (BY_TYPE): AdamWBF16 ("adamw_bf16", the default), AdamWScheduleFreeKahanBF16
+("adamw_schedule_free_kahan") and ProdigyBF16 ("prodigy"); see the docstrings of the last two.
 
 AdamWBF16:
 
@@ -19,11 +19,15 @@ There is no PyTorch fallback: the step fails loudly without libsdxlstep.so.
 from __future__ import annotations
 
 import ctypes as C
+import logging
+import math
 from typing import Any, Dict, Optional
 
 import torch
 
 from . import lib
+
+logger = logging.getLogger(__name__)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -44,19 +48,24 @@ def _checked_ema(ema, weights: torch.Tensor):
 
 
 class FusedArenaOptimizer:
-    """What the algorithms share: bf16 state arenas laid out like the weight arena (exp_avg, exp_avg_sq, an optional third one)
+    """What the algorithms share: state arenas laid out like the weight arena (exp_avg, exp_avg_sq, an optional bf16 third one)
     and the skeleton of step().  A subclass names its third arena (THIRD: attribute and state key), the context string of its
-    launches (LAUNCH) and its own constructor keywords (CONFIG_KEYS), and has begin_step, finish_step and its state format."""
+    launches (LAUNCH) and its own constructor keywords (CONFIG_KEYS), and has begin_step, finish_step and its state format.
+    ZERO1: the update of a sub-range of the arena is the full update's (what ZeRO-1 needs); an algorithm whose step reduces over the
+    whole arena says False, takes no `pieces`, and the trainer exchanges its gradients by all-reduce."""
 
-    def __init__(self, net, group: Dict[str, Any], *, third: bool, grad_round_bf16: bool):
-        """group: param_groups[0], already checked (check_hyper and the subclass's own); third: allocate the third arena"""
+    ZERO1 = True
+
+    def __init__(self, net, group: Dict[str, Any], *, third: bool, grad_round_bf16: bool, moment_dtype=torch.bfloat16):
+        """group: param_groups[0], already checked (check_hyper and the subclass's own); third: allocate the third arena;
+        moment_dtype: of exp_avg and exp_avg_sq"""
         self.net = net
         self.L = getattr(net, "L", None)                      # the loaded libsdxlstep; step() refuses to run without it
         self.param_groups = [group]
         w = net.weights
         assert w.dtype == torch.bfloat16, "only bfloat16 is supported."          # adamw_bfloat16/__init__.py:98
-        self.exp_avg = torch.zeros_like(w)
-        self.exp_avg_sq = torch.zeros_like(w)
+        self.exp_avg = torch.zeros_like(w, dtype=moment_dtype)
+        self.exp_avg_sq = torch.zeros_like(w, dtype=moment_dtype)
         setattr(self, self.THIRD, torch.zeros_like(w) if third else None)
         self.grad_round_bf16 = bool(grad_round_bf16)
         self.step_count = 0
@@ -120,6 +129,8 @@ class FusedArenaOptimizer:
         g = self.net.grads if grads is None else grads
         if g.dtype not in (torch.float32, torch.bfloat16) or (pieces is None and g.numel() != w.numel()):
             raise ValueError("grads must be an fp32 or bf16 tensor in arena layout")
+        if pieces is not None and not self.ZERO1:
+            raise ValueError(f"{type(self).__name__}.step takes no pieces: its update reduces over the whole arena")
         cfg = lib.AdamWConfig()
         lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
         cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
@@ -133,7 +144,7 @@ class FusedArenaOptimizer:
         for off, cnt, goff in todo:
             cfg.elem_offset = off
             cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
-            at = lambda t, o=off: C.c_void_p(t.data_ptr() + 2 * o) if t is not None else None
+            at = lambda t, o=off: C.c_void_p(t.data_ptr() + t.element_size() * o) if t is not None else None
             lib.check(self.L.sdxl_adamw_bf16_step(at(w), C.c_void_p(g.data_ptr() + gsz * goff), 0 if g.dtype == torch.float32 else 1,
                                                   at(self.exp_avg), at(self.exp_avg_sq), at(getattr(self, self.THIRD)), cnt,
                                                   C.byref(cfg), _ptr(grad_scale), _ptr(rand), st), self.LAUNCH)
@@ -323,5 +334,118 @@ class AdamWScheduleFreeKahanBF16(FusedArenaOptimizer):
         self.last_lr = adjusted_lr
 
 
+class ProdigyBF16(FusedArenaOptimizer):
+    """Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner"; the prodigyopt package) on the
+    packed arenas: AdamW whose step size d is estimated during training, so `lr` is a multiplier on d and stays at 1.0.
+
+    State: fp32 exp_avg, exp_avg_sq and s, bf16 p0 (the weights at construction) and comp (the true parameter is p + comp), and the
+    device block prodigy_state (lib.PRODIGY_STATE_FLOATS floats: d, d_max, num, Bs, d_hat, dlr, A, 0, then the reduction scratch).
+    The arithmetic is include/sdxlstep.h's (algorithm 2), three launches per step (csrc/optimizer.hip: accumulate, finalize,
+    apply) and no host read-back: d stays on the device; d() reads it and is the only call that synchronises.  Host scalars are
+    python doubles: beta3 = sqrt(beta2) unless given; with use_bias_correction the factor of step k (0-based) is
+    sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)), else 1.  weight_decay is decoupled (x -= wd * dlr * x).
+
+    One d for the whole arena (no per-group d, no slice_p), and one deliberate departure from the package: when every s is zero
+    (all-zero gradients) the package skips the parameter update and does not count the step; here the step runs and is counted.
+    A step at lr == 0 (a schedule that starts there) launches nothing and is not counted, as in the package.
+    The sums run over the whole arena, so there is no ZeRO-1 form (ZERO1 = False): under data parallelism every rank runs the full
+    update on the all-reduced gradients.  There is no PyTorch fallback: the step fails loudly without libsdxlstep.so."""
+
+    algorithm = "prodigy"
+    ZERO1 = False
+    THIRD = "comp"
+    LAUNCH = "sdxl_adamw_bf16_step (Prodigy)"
+    LOW_LR = 1e-2
+    CONFIG_KEYS = {"d0": ("prodigy_d0", 1e-6), "d_coef": ("prodigy_d_coef", 1.0), "growth_rate": ("prodigy_growth_rate", math.inf),
+                   "beta3": ("prodigy_beta3", None), "use_bias_correction": ("prodigy_use_bias_correction", False),
+                   "safeguard_warmup": ("prodigy_safeguard_warmup", False)}
+    SETTINGS = ("d0", "d_coef", "growth_rate", "beta3", "use_bias_correction", "safeguard_warmup")
+
+    def __init__(self, net, *, lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0, d0=1e-6, d_coef=1.0,
+                 growth_rate=math.inf, use_bias_correction: bool = False, safeguard_warmup: bool = False, grad_round_bf16: bool = False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        self.check_hyper(betas, eps, weight_decay)
+        beta3 = math.sqrt(betas[1]) if beta3 is None else float(beta3)
+        if not 0.0 <= beta3 < 1.0:
+            raise ValueError(f"Invalid beta3 value: {beta3}")
+        if not (0.0 < d0 < math.inf):
+            raise ValueError(f"Invalid d0 value: {d0}")
+        if not (0.0 < d_coef < math.inf):
+            raise ValueError(f"Invalid d_coef value: {d_coef}")
+        if not 1.0 <= growth_rate:
+            raise ValueError(f"Invalid growth_rate value: {growth_rate}")
+        super().__init__(net, dict(lr=lr, betas=tuple(betas), beta3=beta3, eps=eps, weight_decay=weight_decay, d0=float(d0),
+                                   d_coef=float(d_coef), growth_rate=float(growth_rate), use_bias_correction=bool(use_bias_correction),
+                                   safeguard_warmup=bool(safeguard_warmup)),
+                         third=True, grad_round_bf16=grad_round_bf16, moment_dtype=torch.float32)
+        w = net.weights
+        self.s = torch.zeros_like(w, dtype=torch.float32)
+        self.p0 = w.detach().clone()
+        self.prodigy_state = torch.zeros(lib.PRODIGY_STATE_FLOATS, dtype=torch.float32, device=w.device)
+        self.prodigy_state[:2] = float(d0)
+
+    @classmethod
+    def from_config(cls, net, oc):
+        if float(oc.learning_rate) < cls.LOW_LR:
+            logger.warning("optimizer_type 'prodigy': optimizer.learning_rate %g multiplies the step size d that Prodigy estimates and is "
+                           "normally 1.0; a value below %g (the default 1e-6 is AdamW's) all but freezes training", float(oc.learning_rate), cls.LOW_LR)
+        return super().from_config(net, oc)
+
+    def d(self) -> float:
+        """the current step size estimate (reads the device state back: synchronises)"""
+        return float(self.prodigy_state[0])
+
+    def prodigy_bc(self) -> float:
+        """the bias-correction factor of the next step, in python doubles"""
+        grp = self.param_groups[0]
+        if not grp["use_bias_correction"]:
+            return 1.0
+        k, (beta1, beta2) = self.step_count, grp["betas"]
+        return math.sqrt(1 - beta2 ** (k + 1)) / (1 - beta1 ** (k + 1))
+
+    def state_arenas(self):
+        return (self.exp_avg, self.exp_avg_sq, self.comp, self.s)
+
+    def _tag(self) -> Dict[str, Any]:
+        grp = self.param_groups[0]
+        return {"algorithm": self.algorithm, **{k: grp[k] for k in self.SETTINGS}}
+
+    def state_dict(self) -> Dict[str, Any]:
+        st = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "comp": self.comp, "s": self.s,
+              "p0": self.p0, "prodigy_state": self.prodigy_state[:8].clone()}
+        return {**self._tag(), "state": st, "param_groups": self.param_groups}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        got = {k: sd.get(k) for k in self._tag()}
+        if got != self._tag():
+            raise ValueError(f"optimizer state tagged {got} cannot be loaded into an optimizer configured as {self._tag()}")
+        st = sd["state"]
+        self._load_arenas(st)
+        self.s.copy_(st["s"])
+        self.p0.copy_(st["p0"])
+        self.prodigy_state[:8].copy_(st["prodigy_state"])
+        self.param_groups = sd["param_groups"]
+
+    def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
+             zero_grad: bool = False, pieces=None) -> None:
+        """One update of every parameter: arguments as FusedArenaOptimizer._step, without pieces."""
+        self._step(grads, grad_scale, zero_grad, pieces)
+
+    def begin_step(self, cfg, grp):
+        cfg.algorithm = 2
+        cfg.weight_decay = float(grp["weight_decay"])
+        cfg.beta3, cfg.d0, cfg.d_coef, cfg.growth_rate = grp["beta3"], grp["d0"], grp["d_coef"], grp["growth_rate"]
+        cfg.prodigy_bc = self.prodigy_bc()
+        cfg.safeguard_warmup = int(grp["safeguard_warmup"])
+        cfg.p0, cfg.s, cfg.prodigy_state = self.p0.data_ptr(), self.s.data_ptr(), self.prodigy_state.data_ptr()
+        return float(grp["lr"]) != 0.0
+
+    def finish_step(self, launched, todo, st) -> None:
+        """counts the step after the launches (a step at lr == 0 launched nothing and is not counted)"""
+        if launched:
+            self.step_count += 1
+
+
 # optimizer_type (lower-cased, as the reference's OptimizerConfig.class_name does) -> the fused class built for it
-BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16}
+BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16, "prodigy": ProdigyBF16}

@@ -185,7 +185,11 @@ class NativeSDXLTrainer:
         """the gradient exchange of the full arena, with its exchange buffers"""
         # data parallel: ZeRO-1 (reduce-scatter, sharded fused AdamW, all-gather) with the fused optimizer, else all-reduce
         so = getattr(self.config.training, "shard_optimizer", None)          # None = not given: the default, sharded
-        want_sharded = (True if so is None else bool(so)) and isinstance(self.optimizer, FusedArenaOptimizer)
+        zero1 = isinstance(self.optimizer, FusedArenaOptimizer) and self.optimizer.ZERO1     # (False: its update reduces over the whole arena)
+        if so and isinstance(self.optimizer, FusedArenaOptimizer) and not zero1:
+            raise ValueError(f"training.shard_optimizer: ZeRO-1 is not built for {type(self.optimizer).__name__}; leave the key out "
+                             "(every rank then runs the full update on the all-reduced gradients)")
+        want_sharded = (True if so is None else bool(so)) and zero1
         seg_sizes = [n for _off, n in self.net.segment_ranges()] if hasattr(self.net, "segment_ranges") else None
         # force_exchange (build-only key / SDXL_FORCE_EXCHANGE=1): run the exchange through the backend even at world size 1
         force = bool(getattr(self.config.training, "force_exchange", False)) or os.environ.get("SDXL_FORCE_EXCHANGE", "0") == "1"
