@@ -144,6 +144,58 @@ SDXL_API int sdxl_op_colsum(const void* x, long ldx, float* out, long ld_out, in
  * dim even, ldo >= dim; columns past dim are not written. */
 SDXL_API int sdxl_op_sincos(const float* t, void* out, int rows, int dim, long ldo, void* stream);
 
+/* The plan map: what every op of the current plan reads and writes, so that a test can recompute each op of a finished step from the
+ * operands it actually had (tests/_insitu.py).  Pure host code: nothing is launched, nothing is reserved, no offset of the plan moves.
+ * The descriptor is a flat POD; SDXL_PLAN_NONE = (size_t)-1 marks an absent offset.  Offsets of activations, gradients, statistics and scratch
+ * are BYTE offsets into the workspace; w / b are ELEMENT offsets into the bf16 weight arena and the fp32 gradient arena alike.
+ * Tensor roles (t[r]; rows == 0: the op has no such role), by kind:
+ *   LINEAR     0 x, 1 y, 2 resid, 3 gact (the GEGLU first projection's activation output), 4 gu (the second projection: the pre-activation u)
+ *   CONV       0 x, 1 y, 2 resid, 3 rowvec (the time-embedding row vector [B][Cout], a column slice), 4 x_low (the nearest-2x input of up2)
+ *   GROUPNORM / LAYERNORM / SILU / UPSAMPLE   0 x, 1 y
+ *   ATTN       0 q, 1 o, 3 kv (self attention: q == kv == the fused q | k | v tensor, k at column C, v at 2 C; cross: k at 0, v at C of kv)
+ *   CONCAT     0 a, 1 o, 3 b
+ *   EMBED_IN   0 te_sin, 1 aug_in, 3 tid_emb
+ * Gradient destinations: dy_off the output gradient read; dx / dres / d3 the (out, addend) pairs of Plan::grad_dst for role 0 (LINEAR with gu:
+ * for gu), role 2 and role 3; an absent pair is NONE / NONE.  resid_alias: the residual's gradient IS dy (no launch).
+ * intact_after_step: bit r = the DATA of role r, bit 8 + r = its GRADIENT (for role 1: dy) holds after a finished step what the op read or wrote;
+ * a clear bit = never produced in this plan or overwritten by a later launch of the same step: an audit must skip that role. */
+#define SDXL_PLAN_NONE ((size_t)-1)
+#define SDXL_PLAN_ROLES 5
+enum { SDXL_OP_LINEAR = 0, SDXL_OP_CONV = 1, SDXL_OP_GROUPNORM = 2, SDXL_OP_LAYERNORM = 3, SDXL_OP_ATTN = 4, SDXL_OP_SILU = 5, SDXL_OP_CONCAT = 6,
+       SDXL_OP_UPSAMPLE = 7, SDXL_OP_EMBED_IN = 8 };
+typedef struct sdxl_plan_tensor {
+  size_t off, goff;            /* data / gradient (goff: NONE without one) */
+  long rows, cols, ld;         /* ld: row stride in elements (a column slice: the parent's width) */
+  int pad_rows, col0;          /* rows allocated behind `rows`; first column inside the parent */
+} sdxl_plan_tensor;
+typedef struct sdxl_plan_op_desc {
+  int kind, seg, hoist_fwd, resid_alias;
+  unsigned intact_after_step;
+  int K, N, splitk, wgroup, crcfg, crsplit, fsplit, dsplit, delta_on, ln_mode, ggroup;      /* LINEAR (splitk, fsplit, dsplit: CONV too) */
+  int B, H, W, Cin, Cout, stride, up2, up_fs, up_ds, up_ws, up_wg, three_tap, rows_per_batch, s2_dgrad;      /* CONV; B, H, W, Cin (= C): UPSAMPLE; B, H (= HW), Cin (= C): GROUPNORM */
+  int groups, silu;            /* GROUPNORM */
+  int heads, Nq, Nk, self_attn, qsplit, delta_fused, bwd_route;      /* ATTN; bwd_route: 0 dq + dkv, 1 dq + split dkv + reduce, 2 fused, 3 pipelined, -1 unknown (no workspace bound) */
+  int skip, first;             /* CONCAT */
+  int dims[4];                 /* EMBED_IN: ch0, addition_time_embed_dim, pooled_dim, 0 */
+  float eps;
+  long ldq, ldk, ldv, ldvec;   /* ATTN row strides; CONV: the row vector's */
+  size_t dy_off, dx_out, dx_addend, dres_out, dres_addend, d3_out, d3_addend, dy32_off;
+  size_t w_off, w_numel, b_off, b_numel;      /* weight | gamma, bias | beta */
+  size_t stats_off, lse_off, delta_off, rv32_off, planar_off, weff_off, dweff_off, s2_planar_off;
+  sdxl_plan_tensor t[SDXL_PLAN_ROLES];
+} sdxl_plan_op_desc;
+/* buffers that belong to no op */
+typedef struct sdxl_plan_tail {
+  int B, H, W, ctx;
+  sdxl_plan_tensor x_in, pred, ehs;
+  size_t tp32_off, tp32_bytes, t_off, tid_off, loss_off, workspace_bytes;
+} sdxl_plan_tail;
+SDXL_API int sdxl_debug_plan_num_ops(sdxl_handle* h, int* n);
+/* out_bytes: sizeof the caller's struct; a size that is not the library's is refused before anything else is looked at (a binding whose
+ * layout has drifted can never be written past) */
+SDXL_API int sdxl_debug_plan_op(sdxl_handle* h, int i, sdxl_plan_op_desc* out, size_t out_bytes);
+SDXL_API int sdxl_debug_plan_tail(sdxl_handle* h, sdxl_plan_tail* out, size_t out_bytes);
+
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,
  * W [K][N] bf16 (N = the LayerNorm width), x [M][N] the LayerNorm's input, stats [M][2] its (mean, rstd), gamma [N]; dx [M][N] = the

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sdxlstep.h"
+#include "../../include/sdxlstep_diag.h"
 #include "kernels.h"
 
 static const size_t NONE = (size_t)-1;
@@ -78,6 +79,9 @@ struct Op {
   virtual int fwd(Plan& p, hipStream_t st) = 0;
   virtual void plan_bwd(Plan& p) = 0;
   virtual int bwd(Plan& p, hipStream_t st, bool first_micro) = 0;
+  // the plan map (sdxl_debug_plan_op): what this op reads and writes, from the fields it already holds; launches nothing.  `d` arrives cleared
+  // (every offset NONE, every tensor role absent) with seg / hoist_fwd filled in.
+  virtual void describe(const Plan& p, sdxl_plan_op_desc* d) const = 0;
 };
 
 struct Plan {
@@ -281,6 +285,7 @@ T* Plan::add(A&&... a) {
   return o;
 }
 
+void plan_describe_tensor(sdxl_plan_tensor& t, const Act* a);      // the plan map's view of one activation (a == nullptr: absent)
 int engine_load_weight(Engine& e, const char* name, const void* src, int dtype, hipStream_t st);
 int engine_export(Engine& e, const char* name, void* dst, int dtype, bool grad, hipStream_t st);
 int probe_layout(void* out, hipStream_t st);

@@ -220,6 +220,20 @@ static WgradDst wgrad_dst(Plan& p, PRef w, PRef b, bool first) {
   return {e.Gp(w), b.off != NONE ? e.Gp(b) : nullptr, first ? 0 : 1, e.emit_base ? e.emit_base + w.off : nullptr, e.emit_scale};
 }
 
+// ---- the plan map (Op::describe): plain copies of what an op already holds ----
+void plan_describe_tensor(sdxl_plan_tensor& t, const Act* a) {      // (engine.h: the tail's tensors in hooks.hip take the same)
+  t.off = t.goff = SDXL_PLAN_NONE; t.rows = t.cols = t.ld = 0; t.pad_rows = t.col0 = 0;
+  if (!a) return;
+  t.off = a->off; t.goff = a->goff; t.rows = a->rows; t.cols = a->cols; t.ld = a->ld(); t.pad_rows = a->pad_rows; t.col0 = a->col0;
+}
+static void desc_tensor(sdxl_plan_op_desc* d, int role, const Act* a) { if (a) plan_describe_tensor(d->t[role], a); }
+static void desc_param(sdxl_plan_op_desc* d, PRef w, PRef b) {
+  d->w_off = w.off; d->w_numel = w.off == NONE ? 0 : w.numel;
+  d->b_off = b.off; d->b_numel = b.off == NONE ? 0 : b.numel;
+}
+enum { INTACT_DATA = 1, INTACT_GRAD = 1 << 8 };      // sdxl_plan_op_desc::intact_after_step: << role
+static void desc_lost(sdxl_plan_op_desc* d, unsigned bit, int role) { d->intact_after_step &= ~(bit << role); }
+
 static int kv_pad_rows(int B, int ctx) { return (int)((64 - ((long)B * ctx) % 64) % 64); }   // B * 77 prompt tokens -> multiple of 64
 
 struct AttnOp;
@@ -253,6 +267,15 @@ struct LinearOp : Op {
   Act* gact = nullptr;   // first projection: fused activation output [rows][N/2]
   Act* gu = nullptr;     // second projection: the first projection's pre-activation u [rows][2K]
   LinearOp(Act* x_, Act* y_, PRef w_, PRef b_, int K_, int N_, Act* resid_) : x(x_), y(y_), resid(resid_), w(w_), b(b_), K(K_), N(N_) {}
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_LINEAR;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y); desc_tensor(d, 2, resid); desc_tensor(d, 3, gact); desc_tensor(d, 4, gu);
+    desc_param(d, w, b);
+    d->K = K; d->N = N; d->splitk = splitk; d->wgroup = wgroup; d->crcfg = crcfg; d->crsplit = crsplit; d->fsplit = fsplit; d->dsplit = dsplit;
+    d->delta_on = delta_on ? 1 : 0; d->ln_mode = ln_mode; d->ggroup = ggroup; d->resid_alias = resid_alias;
+    d->dy_off = dy_off; d->dy32_off = dy32_off; d->dx_out = dx.out; d->dx_addend = dx.addend; d->dres_out = dres.out; d->dres_addend = dres.addend;
+    if (ln_mode == 1) desc_lost(d, INTACT_GRAD, 0);      // the fused LayerNorm backward does not store this op's input gradient
+  }
   int fwd(Plan& p, hipStream_t st) override {
     GemmP g = linear_fwd_problem(p.P(x), x->ld(), p.eng->Wp(w), p.P(y), y->ld(), (int)x->rows, N, K, b.off == NONE ? nullptr : p.eng->Wp(b),
                                  resid ? p.P(resid) : nullptr, resid ? resid->ld() : 0);
@@ -418,6 +441,27 @@ struct ConvOp : Op {
     Ho = (H - 1) / stride + 1;
     Wo = (W - 1) / stride + 1;
   }
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_CONV;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y); desc_tensor(d, 2, resid); desc_tensor(d, 3, rowvec); desc_tensor(d, 4, up2() ? x_low : nullptr);
+    desc_param(d, w, b);
+    d->B = Bn; d->H = H; d->W = W; d->Cin = Cin; d->Cout = Cout; d->stride = stride; d->splitk = splitk; d->fsplit = fsplit; d->dsplit = dsplit;
+    d->up2 = up2() ? 1 : 0; d->up_fs = up_fs; d->up_ds = up_ds; d->up_ws = up_ws; d->up_wg = up2() && up_wg && KNOB(2) != 128 ? 1 : 0;
+    d->resid_alias = resid_alias; d->dy_off = dy_off; d->dres_out = dres.out; d->dres_addend = dres.addend; d->d3_out = drv.out; d->d3_addend = drv.addend;
+    d->dx_out = up2() && up_dx ? up_dx->out : dx.out; d->dx_addend = up2() && up_dx ? up_dx->addend : dx.addend;      // (up2: the gradient of x_low)
+    if (rowvec) { d->ldvec = rowvec->ld(); d->rows_per_batch = Ho * Wo; d->rv32_off = rv32_off; }
+    d->s2_dgrad = x->need_grad && s2_planar_off != NONE && KNOB(2) != 256 ? 1 : 0;
+    d->planar_off = planar_off; d->weff_off = weff_off; d->dweff_off = dweff_off; d->s2_planar_off = s2_planar_off;
+    if (!d->up_wg) {      // the weight gradient's route: what launch_gemm decides for the problem bwd() builds
+      GemmP g = conv3x3_wgrad_problem(Bn, H, W, Cin, Cout, stride);
+      g.splitk = splitk;
+      d->three_tap = conv_wgrad3_applicable(g) && conv_wgrad3_policy(g.M, g.N, g.K, g.Wm, g.sm) ? 1 : 0;
+    }
+    if (up2()) {      // forward and dgrad work on x_low: the upsampled image has no gradient of its own, and is not produced when nothing reads it
+      desc_lost(d, INTACT_GRAD, 0);
+      if (d->up_wg) desc_lost(d, INTACT_DATA, 0);
+    }
+  }
   int fwd(Plan& p, hipStream_t st) override {
 #ifdef SDXL_DIAG
     if (s2x_off != NONE && KNOB(2) == 512)      // (knob 2 = 512, experiment: measured neutral in the step -- 114.0-114.4 on, 113.8-114.3 off -- the general strided gather stays)
@@ -540,6 +584,13 @@ struct GroupNormOp : Op {
     size_t need = groupnorm_ws_floats(Bn, C, G);
     if (need > p.gn_ws_floats) p.gn_ws_floats = need;  // one scratch, sized for the widest norm, allocated in build()
   }
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_GROUPNORM;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y);
+    desc_param(d, gm, bt);
+    d->B = Bn; d->H = HW; d->Cin = C; d->groups = G; d->silu = silu; d->eps = eps; d->stats_off = stats_off;
+    d->dy_off = dy_off; d->dx_out = dx.out; d->dx_addend = dx.addend;
+  }
   int fwd(Plan& p, hipStream_t st) override {
     if (KNOB(27) & 2) return 0;      // (knob 27: timing knock-outs, wrong results -- kernels.h)
     if (KNOB(27) & 128) return launch_silu_fwd(p.P(x), p.P(y), (long)Bn * HW * C, st);      // (timing only: ONE elementwise launch, live data downstream)
@@ -568,6 +619,14 @@ struct LayerNormOp : Op {
   int fused = 0;      // the consumer's dgrad epilogue produces dx (LinearOp::ln_mode); set by its plan_bwd, which runs first
   LayerNormOp(Plan& p, Act* x_, Act* y_, PRef g_, PRef b_, int C_, float eps_) : x(x_), y(y_), gm(g_), bt(b_), C(C_), eps(eps_) {
     stats_off = p.alloc(sizeof(float) * x->rows * 2);
+  }
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_LAYERNORM;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y);
+    desc_param(d, gm, bt);
+    d->Cin = C; d->eps = eps; d->stats_off = stats_off; d->ln_mode = fused;
+    d->dy_off = dy_off; d->dx_out = dx.out; d->dx_addend = dx.addend;
+    if (fused == 1) desc_lost(d, INTACT_GRAD, 1);      // the consumer's dgrad epilogue keeps dy in registers
   }
   int fwd(Plan& p, hipStream_t st) override {
     if (KNOB(27) & 4) return 0;
@@ -659,7 +718,7 @@ struct AttnOp : Op {
     if (self) { if (need > p.apart_floats) p.apart_floats = need; }
     else if (need > p.apart_side_floats) p.apart_side_floats = need;
   }
-  void fill(Plan& p, AttnP& a, bool grads) {
+  void fill(const Plan& p, AttnP& a, bool grads) const {
     memset(&a, 0, sizeof(a));
     a.B = Bn; a.H = heads; a.Nq = Nq; a.Nk = Nk;
     if (self) {
@@ -682,6 +741,28 @@ struct AttnOp : Op {
       } else {
         a.dQ = p.GP(dq.out); a.lddq = C;
         a.dK = p.GP(dkv.out); a.dV = a.dK + C; a.lddk = a.lddv = kv->ld();
+      }
+    }
+  }
+  void describe(const Plan& p, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_ATTN;
+    desc_tensor(d, 0, q); desc_tensor(d, 1, o); desc_tensor(d, 3, kv);
+    d->B = Bn; d->heads = heads; d->Nq = Nq; d->Nk = Nk; d->Cin = C; d->self_attn = self ? 1 : 0; d->qsplit = qsplit; d->delta_fused = delta_fused ? 1 : 0;
+    d->ldq = self ? 3L * C : C; d->ldk = d->ldv = self ? 3L * C : kv->ld();
+    d->lse_off = lse_off; d->delta_off = delta_off;
+    d->dy_off = do_off; d->dx_out = dq.out; d->dx_addend = dq.addend; d->d3_out = dkv.out; d->d3_addend = dkv.addend;
+    // the backward's route, restated from launch_attn_bwd / launch_attn_bwd_fused (attention.hip) and bwd() below
+    d->bwd_route = qsplit > 1 ? 1 : 0;
+    if (self && (KNOB(20) != 1 || delta_fused) && qsplit <= 1 && Nk >= 256 && o->ld() % 8 == 0) {
+      d->bwd_route = 2;
+      if (KNOB(35) != 1 && ((Nq >= 2048 && Nk >= 2048) || KNOB(35) == 2)) {
+        if (!p.eng->ws || do_off == NONE) d->bwd_route = -1;
+        else {
+          AttnP a;
+          fill(p, a, true);
+          a.qsplit = 1;
+          if (attn_bwd_pl_applicable(a)) d->bwd_route = 3;
+        }
       }
     }
   }
@@ -730,6 +811,11 @@ struct SiluOp : Op {
   size_t dy_off = NONE;
   Plan::GradDst dx;
   SiluOp(Act* x_, Act* y_) : x(x_), y(y_) {}
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_SILU;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y);
+    d->dy_off = dy_off; d->dx_out = dx.out; d->dx_addend = dx.addend;
+  }
   int fwd(Plan& p, hipStream_t st) override { return launch_silu_fwd(p.P(x), p.P(y), x->rows * x->cols, st); }
   void plan_bwd(Plan& p) override { dy_off = y->goff; dx = p.grad_dst(x); }
   int bwd(Plan& p, hipStream_t st, bool) override {
@@ -744,6 +830,12 @@ struct ConcatOp : Op {
   int skip;       // index of b among the saved skips, forward order (sdxl_residuals.down)
   bool first;     // the first concat of the up path: a is the mid block's output (sdxl_residuals.mid)
   ConcatOp(Act* a_, Act* b_, Act* o_, int skip_, bool first_) : a(a_), b(b_), o(o_), skip(skip_), first(first_) {}
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_CONCAT;
+    desc_tensor(d, 0, a); desc_tensor(d, 1, o); desc_tensor(d, 3, b);
+    d->skip = skip; d->first = first ? 1 : 0;
+    d->dy_off = do_off; d->dx_out = da.out; d->dx_addend = da.addend; d->d3_out = db.out; d->d3_addend = db.addend;
+  }
   int fwd(Plan& p, hipStream_t st) override {
     // an additional residual changes what the up path reads, never the saved skip: the down path and the backward keep the plain one
     if (const ResidualReq* r = p.eng->res_fwd) {
@@ -776,6 +868,16 @@ struct UpsampleOp : Op {
   Plan::GradDst dx;
   ConvOp* fused = nullptr;     // the convolution that consumes y works on x directly (ConvOp::up2): y is its weight gradient's operand only
   UpsampleOp(Act* x_, Act* y_, int B_, int H_, int W_, int C_) : x(x_), y(y_), Bn(B_), H(H_), W(W_), C(C_) {}
+  void describe(const Plan&, sdxl_plan_op_desc* d) const override {
+    d->kind = SDXL_OP_UPSAMPLE;
+    desc_tensor(d, 0, x); desc_tensor(d, 1, y);
+    d->B = Bn; d->H = H; d->W = W; d->Cin = C; d->up2 = fused && fused->up2() ? 1 : 0;
+    d->dy_off = dy_off; d->dx_out = dx.out; d->dx_addend = dx.addend;
+    if (d->up2) {      // the consuming convolution works on x: it writes dx, y gets no gradient, and y itself only where its weight gradient reads it
+      desc_lost(d, INTACT_GRAD, 1);
+      if (fused->up_wg && KNOB(2) != 128) desc_lost(d, INTACT_DATA, 1);
+    }
+  }
   int fwd(Plan& p, hipStream_t st) override {
     if (fused && fused->up2() && fused->up_wg && KNOB(2) != 128) return 0;      // nothing reads y
     if (fused && fused->up2() && !p.eng->use_graphs) {   // off the critical stream: nothing reads y before the backward's side-stream weight gradient
@@ -796,6 +898,12 @@ struct UpsampleOp : Op {
 // conditioning embeddings (inputs only: no gradient).  t -> sincos(320); time_ids -> sincos(256) x 6;
 // aug_in = [pooled | time-id embedding]
 struct EmbedInOp : Op {
+  void describe(const Plan& p, sdxl_plan_op_desc* d) const override {
+    const sdxl_unet_config& c = p.eng->cfg;
+    d->kind = SDXL_OP_EMBED_IN;
+    desc_tensor(d, 0, p.te_sin); desc_tensor(d, 1, p.aug_in); desc_tensor(d, 3, p.tid_emb);
+    d->B = p.B; d->dims[0] = c.block_out_channels[0]; d->dims[1] = c.addition_time_embed_dim; d->dims[2] = c.pooled_dim;
+  }
   int fwd(Plan& p, hipStream_t st) override {
     const sdxl_unet_config& c = p.eng->cfg;
     const int B = p.B, ch0 = c.block_out_channels[0], ad = c.addition_time_embed_dim;

@@ -206,6 +206,47 @@ int sdxl_debug_cond_operands(sdxl_handle* h, int which, int g, int* n_groups, si
   return 0;
 }
 
+// ---- the plan map: every op of the current plan described from its own fields (Op::describe); nothing is launched or reserved ----
+int sdxl_debug_plan_num_ops(sdxl_handle* h, int* n) {
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(n, "null output");
+  *n = (int)h->e.cur->ops.size();
+  return 0;
+}
+int sdxl_debug_plan_op(sdxl_handle* h, int i, sdxl_plan_op_desc* out, size_t out_bytes) {
+  ARG_CHECK(out_bytes == sizeof(sdxl_plan_op_desc), "plan op: the caller's descriptor has %zu bytes, the library's %zu", out_bytes, sizeof(sdxl_plan_op_desc));
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(out, "null output");
+  const Plan& p = *h->e.cur;
+  ARG_CHECK(i >= 0 && i < (int)p.ops.size(), "plan op %d out of range (the plan has %d)", i, (int)p.ops.size());
+  memset(out, 0, sizeof(*out));
+  size_t* const offs[] = {&out->dy_off, &out->dx_out, &out->dx_addend, &out->dres_out, &out->dres_addend, &out->d3_out, &out->d3_addend, &out->dy32_off,
+                          &out->w_off, &out->b_off, &out->stats_off, &out->lse_off, &out->delta_off, &out->rv32_off, &out->planar_off, &out->weff_off,
+                          &out->dweff_off, &out->s2_planar_off};
+  for (size_t* o : offs) *o = SDXL_PLAN_NONE;
+  for (int r = 0; r < SDXL_PLAN_ROLES; ++r) plan_describe_tensor(out->t[r], nullptr);
+  out->intact_after_step = ~0u;
+  const Op& op = *p.ops[i];
+  out->seg = op.seg; out->hoist_fwd = op.hoist_fwd ? 1 : 0;
+  op.describe(p, out);
+  return 0;
+}
+int sdxl_debug_plan_tail(sdxl_handle* h, sdxl_plan_tail* out, size_t out_bytes) {
+  ARG_CHECK(out_bytes == sizeof(sdxl_plan_tail), "plan tail: the caller's struct has %zu bytes, the library's %zu", out_bytes, sizeof(sdxl_plan_tail));
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(out, "null output");
+  const Plan& p = *h->e.cur;
+  memset(out, 0, sizeof(*out));
+  out->B = p.B; out->H = p.H; out->W = p.W; out->ctx = p.ctx;
+  plan_describe_tensor(out->x_in, p.x_in); plan_describe_tensor(out->pred, p.pred); plan_describe_tensor(out->ehs, p.ehs);
+  out->tp32_off = p.tp32_off; out->tp32_bytes = p.tp32_bytes; out->t_off = p.t_off; out->tid_off = p.tid_off; out->loss_off = p.loss_off;
+  out->workspace_bytes = p.ws_bytes;
+  return 0;
+}
+
 int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, float* const* dw, float* const* dbias, int Mo, int No,
                         int rows, int accumulate, void* st) {
   ARG_CHECK(n >= 1 && n <= GEMM_MAX_GROUP, "wgrad group of %d (1..%d)", n, GEMM_MAX_GROUP);

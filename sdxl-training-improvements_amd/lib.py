@@ -260,7 +260,73 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_op_conv3x3_fwd_rowvec": [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp],
     "sdxl_op_colsum": [_vp, _l, _vp, _l, _i, _i, _i, _vp],
     "sdxl_op_sincos": [_vp, _vp, _i, _i, _l, _vp],
+    "sdxl_debug_plan_num_ops": [_vp, _P(_i)],
+    "sdxl_debug_plan_op": [_vp, _i, _vp, _sz],       # sdxl_plan_op_desc* (PlanOpDesc), its size
+    "sdxl_debug_plan_tail": [_vp, _vp, _sz],         # sdxl_plan_tail* (PlanTail), its size
 }
+PLAN_NONE = (1 << 64) - 1      # SDXL_PLAN_NONE: an absent offset of the plan map
+PLAN_KINDS = ("linear", "conv", "groupnorm", "layernorm", "attn", "silu", "concat", "upsample", "embed_in")
+PLAN_ROLES = 5
+PLAN_ATTN_ROUTES = {0: "dq + dkv", 1: "dq + split dkv + reduce", 2: "fused", 3: "pipelined", -1: "unknown"}
+
+
+class PlanTensor(C.Structure):
+    """sdxl_plan_tensor: byte offsets of the data and the gradient in the workspace, rows, cols, row stride (elements), pad rows, first column"""
+    _fields_ = [("off", _sz), ("goff", _sz), ("rows", _l), ("cols", _l), ("ld", _l), ("pad_rows", _i), ("col0", _i)]
+
+
+class PlanOpDesc(C.Structure):
+    """sdxl_plan_op_desc (include/sdxlstep_diag.h has the roles per kind)"""
+    _fields_ = ([(k, _i) for k in ("kind", "seg", "hoist_fwd", "resid_alias")] + [("intact_after_step", C.c_uint)] +
+                [(k, _i) for k in ("K", "N", "splitk", "wgroup", "crcfg", "crsplit", "fsplit", "dsplit", "delta_on", "ln_mode", "ggroup",
+                                   "B", "H", "W", "Cin", "Cout", "stride", "up2", "up_fs", "up_ds", "up_ws", "up_wg", "three_tap", "rows_per_batch",
+                                   "s2_dgrad", "groups", "silu", "heads", "Nq", "Nk", "self_attn", "qsplit", "delta_fused", "bwd_route", "skip",
+                                   "first")] + [("dims", _i * 4), ("eps", _f)] + [(k, _l) for k in ("ldq", "ldk", "ldv", "ldvec")] +
+                [(k, _sz) for k in ("dy_off", "dx_out", "dx_addend", "dres_out", "dres_addend", "d3_out", "d3_addend", "dy32_off", "w_off", "w_numel",
+                                    "b_off", "b_numel", "stats_off", "lse_off", "delta_off", "rv32_off", "planar_off", "weff_off", "dweff_off",
+                                    "s2_planar_off")] + [("t", PlanTensor * PLAN_ROLES)])
+
+
+class PlanTail(C.Structure):
+    """sdxl_plan_tail: the buffers of the plan that belong to no op"""
+    _fields_ = ([(k, _i) for k in ("B", "H", "W", "ctx")] + [(k, PlanTensor) for k in ("x_in", "pred", "ehs")] +
+                [(k, _sz) for k in ("tp32_off", "tp32_bytes", "t_off", "tid_off", "loss_off", "workspace_bytes")])
+
+
+def _plain(st):
+    """a ctypes struct as a plain dict: absent offsets None, nested structs dicts, arrays lists"""
+    out = {}
+    for name, tp in st._fields_:
+        v = getattr(st, name)
+        if isinstance(v, C.Structure):
+            v = _plain(v)
+        elif isinstance(v, C.Array):
+            v = [_plain(e) if isinstance(e, C.Structure) else e for e in v]
+        elif tp is _sz and v == PLAN_NONE:
+            v = None
+        out[name] = v
+    return out
+
+
+def plan_map(handle):
+    """(ops, tail) of the handle's current plan: one plain dict per op in forward order (kind by name, "index" added; a tensor role the op
+    does not have is None) and the tail's dict.  Pure host code in the library: nothing is launched, the plan does not change."""
+    L = load()
+    n = _i()
+    check(L.sdxl_debug_plan_num_ops(handle, C.byref(n)), "sdxl_debug_plan_num_ops")
+    ops = []
+    for i in range(n.value):
+        d = PlanOpDesc()
+        check(L.sdxl_debug_plan_op(handle, i, C.byref(d), C.sizeof(d)), "sdxl_debug_plan_op")
+        o = _plain(d)
+        o["index"], o["kind"] = i, PLAN_KINDS[o["kind"]]
+        o["t"] = [None if t["rows"] == 0 else t for t in o["t"]]
+        ops.append(o)
+    t = PlanTail()
+    check(L.sdxl_debug_plan_tail(handle, C.byref(t), C.sizeof(t)), "sdxl_debug_plan_tail")
+    return ops, _plain(t)
+
+
 GEMM_DESC_FIELDS = ("form", "taps", "M", "N", "K", "splitk", "group", "cfg", "geglu", "geglu_group", "Hm", "Wm", "Hs", "Ws", "sm", "sd", "up2", "emit_bf16", "delta", "bias_grad")
 GEMM_DESC_HOOK_FIELDS = ("rowvec",)      # the struct's tail that the launch log does not carry: a row vector in the epilogue (default 0)
 GEMM_ROUTE_FIELDS = ("kernel", "cfg", "fast", "post")

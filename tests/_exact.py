@@ -324,3 +324,12 @@ def upsample2x_bwd_nhwc(g):
     """sum of each 2 x 2 block: the transpose of nearest-2x"""
     B, H2, W2, C = g.shape
     return g.view(B, H2 // 2, 2, W2 // 2, 2, C).sum((2, 4))
+
+
+def upsample2x_bwd_ref64(g_nhwc, addend_nhwc=None):
+    """(dx, its bound) of upsample2x_bwd_kernel (csrc/elementwise.hip): the fp32 sum of the four bf16 values of a 2 x 2 block (+ the addend): n
+    terms in a fixed order, (n - 1) 2^-24 sum|terms|; the one rounding to bf16 is the check's"""
+    ref, ab, n = upsample2x_bwd_nhwc(g_nhwc.double()), upsample2x_bwd_nhwc(g_nhwc.double().abs()), 4
+    if addend_nhwc is not None:
+        ref, ab, n = ref + addend_nhwc.double(), ab + addend_nhwc.double().abs(), 5
+    return ref, (n - 1) * 2.0 ** -24 * ab

@@ -161,6 +161,18 @@ def silu_grad_delta(t, dt):
     return r.abs() * ds + s * dr + U * silu_grad64(t).abs() + 0.5 * dt + TINY
 
 
+def silu_bwd_ref(x, dy, addend=None):
+    """(dx, its bound) of silu_bwd_kernel (csrc/elementwise.hip): g = dy silu_grad_f(x) (+ addend), x and dy bf16-exact: silu_grad_f's own error
+    times |dy|, U for the product, U for the addition"""
+    x, dy = x.double(), dy.double()
+    ref = dy * silu_grad64(x)
+    delta = dy.abs() * silu_grad_delta(x, torch.zeros_like(x)) + U * ref.abs()
+    if addend is not None:
+        ref = ref + addend.double()
+        delta = delta + U * ref.abs()
+    return ref, delta
+
+
 # ------------------------------------------------------------------------------------------------ data designs
 K_DYADIC = [k / 4 for k in range(-32, 33)]      # multiples of 1/4 in [-8, 8]: K +- s (s <= 2) is a multiple of 1/4 below 16: 6 bits, bf16-exact
 S_TWO_POINT = (0.5, 1.0, 2.0)
