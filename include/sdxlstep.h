@@ -352,6 +352,43 @@ typedef struct {
  * outside 1 .. 64.  sdxl_grad_select.lora keeps SDXL_DTYPE_LORA's rule: adapter gradients written by the backward itself are LoRA's only.
  * The cached device table is keyed by the dtype too. */
 #define SDXL_DTYPE_LOHA 5
+/* ---- LoKr (LyCORIS Kronecker product) by merge and project: dtype SDXL_DTYPE_LOKR of the same two calls, the host struct sdxl_lokr_op ----
+ * For a targeted weight with state-dict shape [out][cin] or [out][cin][kh][kw], flattened to [out][in], in = cin kh kw:
+ *   (out_l, out_k) = fact(out, factor), (in_m, in_n) = fact(cin, factor), n2 = in_n kh kw    (fact: LyCORIS' factorization, smaller first:
+ *   factor > 0 dividing the dimension gives (factor, dimension / factor) sorted; otherwise the divisor pair (m, n), m <= n, reached from
+ *   (1, dimension) by stepping m to the next divisor while m + n does not grow and m stays <= factor, factor -1 meaning no cap)
+ *   dW[a out_k + c][b n2 + j] = s C[a][b] W2[c][j]      = s kron(C, W2); for a 3x3 convolution j = d 9 + tap, channel = b in_n + d
+ * C [out_l][in_m] (lokr_w1) is always a full matrix.  W2 [out_k][n2] is stored as it is (a FULL target, lokr_w2) or as W2 = B A with
+ * B [out_k][rank] (lokr_w2_a) and A [rank][n2] (lokr_w2_b) (a FACTORED target).  A target is full when sdxl_lokr_op.full is 1 or when
+ * 2 rank >= max(out_k, in_n); a full target uses s = 1 (and s = 0 when op.scale is 0: the restoring merge), a factored one s = op.scale.
+ * `adapters` holds per target C, then W2 or B, A, in that order, bf16, each factor padded to 8 elements; `adapter_grads` is fp32 and laid
+ * out the same way; `base` is SDXL_DTYPE_LORA_LAYOUTS' packed W0 copies.  The targets are everything SDXL_DTYPE_LORA_LAYOUTS accepts, with
+ * its maps; only the rows < out of a target are read or written.
+ * merge (one launch): factored q <- q + B[c][k] A[k][j] for k = 0 .. rank - 1, every product and every sum rounded on its own in fp32 (no
+ * FMA), full q = (float)W2[c][j]; h = C[a][b] q, t = s h, W = bf16_rn(W0 + t), and W = W0 bit for bit where t == 0.
+ * project (two launches, from G = dW in the bound fp32 gradient arena, read ONCE):
+ *   dC[a][b] = s sum_{c,j} G[a out_k + c][b n2 + j] W2[c][j]       dW2[c][j] = s sum_{a,b} C[a][b] G[a out_k + c][b n2 + j]
+ *   factored: dB = dW2 A^T, dA = B^T dW2
+ * No out x in scratch, no atomics, the outputs are OVERWRITTEN; every summation order is fixed by (out, in, factor, rank, form, kind)
+ * alone, so results are bitwise reproducible and a target's bits do not depend on the other targets of the call.
+ * `scratch` is caller-owned device memory, 16-byte aligned, of at least the sum over the targets of
+ *   SDXL_LOKR_PAD(tiles out_l in_m) + (full ? 0 : SDXL_LOKR_PAD(out_k n2)) floats,  tiles = ceil(out_k n2 / SDXL_LOKR_TILE)
+ * (the projection's partial sums and a factored target's dW2); its previous contents do not matter.  The merge does not use it.
+ * Bad arguments (1, before any launch, the message names the tensor or the field): everything SDXL_DTYPE_LORA_LAYOUTS refuses, a rank
+ * outside 1 .. 128, factor == 0 or < -1, full outside 0 / 1, a second factor (or, factored, a B or an A) of 2^31 elements or more, and for the projection a NULL,
+ * misaligned or too-small `scratch`.
+ * sdxl_grad_select.lora keeps SDXL_DTYPE_LORA's rule.  The cached device table is keyed by (target list, rank, dtype, factor, full); the
+ * scale is read per call, so a restoring merge (scale 0) between two merges rebuilds nothing. */
+#define SDXL_DTYPE_LOKR 6
+#define SDXL_LOKR_TILE 1024                          /* elements of W2 one workgroup of the projection owns */
+#define SDXL_LOKR_PAD(n) (((size_t)(n) + 3) / 4 * 4) /* scratch regions start on 16 bytes */
+typedef struct {
+  sdxl_lora_op op;           /* n, param, rank, scale (alpha / rank, used by the factored targets), adapters, base, adapter_grads */
+  int factor;                /* -1 or >= 1 */
+  int full;                  /* 0: the rule above per target; 1: every target stores W2 in full */
+  float* scratch;            /* device fp32, 16-byte aligned (export only) */
+  size_t scratch_floats;
+} sdxl_lokr_op;
 /* ---- gradient selection: dtype SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad (no entry point of its own) ----
  *   sdxl_export_grad(h, NULL, &sel, SDXL_DTYPE_GRAD_SELECT, stream)
  * tells the backward which state-dict tensors are trained.  `sel` is a HOST pointer, read during the call; `name` must be NULL; a NULL

@@ -83,6 +83,24 @@ SDXL_API int sdxl_op_loha_merge(const void* base, const void* A1, const void* B1
                        float scale, int kind, int group, void* stream);
 SDXL_API int sdxl_op_loha_project(const float* dw, const void* A1, const void* B1, const void* A2, const void* B2, float* dA1, float* dB1, float* dA2,
                          float* dB2, int out, int in, int rank, float scale, int kind, int group, void* stream);
+/* the LoKr kernels of SDXL_DTYPE_LOKR (csrc/lokr.hip) on caller buffers, a table of one target, no handle.  This hook is a dtype, not a
+ * function: the library exports no symbol for it.  sdxl_load_weight with a NULL handle, a NULL name, a HOST pointer to the struct below and
+ * dtype SDXL_DTYPE_LOKR_ONE runs the merge; sdxl_export_grad called the same way runs the projection (two launches).
+ * base, w (bf16) and dw (fp32) are NATIVE [out][in]; C [out_l][in_m], W2 [out_k][n2] (full = 1) or W2 = B [out_k][rank] with A [rank][n2]
+ * (full = 0; A and dA may be NULL when full) bf16 and dC, dW2 (dB when factored), dA fp32 (overwritten) are indexed like the state-dict
+ * tensors.  kind / group as the LoHa hooks'; the factorisation is fact(out, factor) x fact(cin, factor), cin = group for a 3x3 convolution
+ * and `in` otherwise.  `full` and `scale` are the caller's: the form rule of SDXL_DTYPE_LOKR is not applied.  scratch: SDXL_DTYPE_LOKR's
+ * formula for this one target (the merge reads neither it nor dw, dC, dW2, dA; the projection reads neither base nor w).
+ * Argument checks (1, before any launch): a non-NULL handle or name, rank 1 .. 128, factor -1 or >= 1, full 0 / 1, in % 8 == 0, out >= 1, a
+ * finite scale, every pointer the call uses 16-byte aligned, and for the projection a scratch of the required size. */
+#define SDXL_DTYPE_LOKR_ONE 7
+typedef struct {
+  const void* base; const void* C; const void* W2; const void* A; void* w;      /* merge: in, in, in, in, out */
+  const float* dw; float* dC; float* dW2; float* dA;                            /* project: in, out, out, out */
+  int out, in, group, kind, factor, rank, full;
+  float scale;
+  float* scratch; size_t scratch_floats;
+} sdxl_lokr_one;
 /* the direct adapter-gradient kernels of sdxl_grad_select.lora (csrc/lora_grad.hip) on caller buffers, a table of one target, no handle:
  * x [M][in] (row stride ldx), dy [M][out] (row stride ldy: a column slice of a wider tensor is dy + offset), A [rank][in], B [out][rank] bf16;
  * dA [rank][in], dB [out][rank] fp32 = (accumulate ? previous : 0) + scale * (dY B)^T X, scale * dY^T (X A^T).  Rows past M and columns outside

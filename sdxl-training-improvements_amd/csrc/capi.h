@@ -19,11 +19,14 @@ struct StepState {  // what backward needs from the preceding forward
   ResidualReq res;             // the additional skip residuals this micro-step carried (sdxl_batch_res): the backward writes res.d_*
   float* d_input = nullptr;    // the input gradient this micro-step asked for (sdxl_batch_din): the caller's buffer, written by conv_in's backward
 };
-struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS / SDXL_DTYPE_LOHA call, keyed by (target list, rank, dtype)
-  std::vector<int> params;
+struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS / SDXL_DTYPE_LOHA / SDXL_DTYPE_LOKR call, keyed by
+  std::vector<int> params;      // (target list, rank, dtype) and, for SDXL_DTYPE_LOKR, (factor, full)
   int rank = 0, dtype = 0, mapped = 0;
   LoraTarget* dev = nullptr;
-  LohaTarget* dev_loha = nullptr;      // SDXL_DTYPE_LOHA's table (one of the two is held at a time)
+  LohaTarget* dev_loha = nullptr;      // SDXL_DTYPE_LOHA's table (one of the three is held at a time)
+  LokrTarget* dev_lokr = nullptr;      // SDXL_DTYPE_LOKR's
+  int factor = 0, full = 0;
+  size_t scratch_floats = 0;           // what SDXL_DTYPE_LOKR's projection needs of sdxl_lokr_op.scratch
   int tiles_m = 0, tiles_b = 0, tiles_a = 0;
 };
 struct sdxl_handle {
@@ -51,6 +54,30 @@ static int loha_check_rank(int rank) {
   ARG_CHECK(rank >= 1 && rank <= LOHA_MAX_RANK, "loha: rank %d outside 1 .. %d", rank, LOHA_MAX_RANK);
   return 0;
 }
+
+// ... and of every LoKr entry point (SDXL_DTYPE_LOKR, the hook SDXL_DTYPE_LOKR_ONE)
+static int lokr_check_fields(int rank, int factor, int full) {
+  ARG_CHECK(rank >= 1 && rank <= LOKR_MAX_RANK, "lokr: rank %d outside 1 .. %d", rank, LOKR_MAX_RANK);
+  ARG_CHECK(factor == -1 || factor >= 1, "lokr: factor %d (-1, or a positive integer)", factor);
+  ARG_CHECK(full == 0 || full == 1, "lokr: full %d (0 or 1)", full);
+  return 0;
+}
+// the projection indexes W2, B, A and their tiles with 32-bit integers
+static int lokr_check_size(const char* who, const LokrTarget& x, int rank) {
+  const long lim = (1L << 31) - 2 * LOKR_P_TILE;
+  ARG_CHECK((long)x.out_k * x.n2 < lim && (long)x.out_k * rank < lim && (long)rank * x.n2 < lim,
+            "lokr: '%s' has a second factor of %d x %d elements at rank %d: too large", who, x.out_k, x.n2, rank);
+  return 0;
+}
+static int lokr_check_scratch(const float* scratch, size_t have, size_t need) {
+  ARG_CHECK(aligned16(scratch), "lokr: scratch must be a 16-byte aligned device pointer");
+  ARG_CHECK(have >= need, "lokr: scratch holds %zu floats, the projection of these targets needs %zu", have, need);
+  return 0;
+}
+// SDXL_DTYPE_LOKR_ONE (hooks.hip): one target on caller buffers, no handle
+int lokr_one_merge(const sdxl_lokr_one* o, void* st);
+int lokr_one_project(const sdxl_lokr_one* o, void* st);
+static_assert(LOKR_P_TILE == SDXL_LOKR_TILE, "the scratch formula of include/sdxlstep.h");
 
 // a handle that can run a step: planned, bound, with its workspace
 static int ready(Engine& e) {

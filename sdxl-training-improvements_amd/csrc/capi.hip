@@ -75,6 +75,7 @@ int sdxl_destroy(sdxl_handle* h) {
   if (h->e.small_ranges_dev) (void)hipFree(h->e.small_ranges_dev);
   if (h->lora.dev) (void)hipFree(h->lora.dev);
   if (h->lora.dev_loha) (void)hipFree(h->lora.dev_loha);
+  if (h->lora.dev_lokr) (void)hipFree(h->lora.dev_lokr);
   if (h->e.lora.dev) (void)hipFree(h->e.lora.dev);
   delete h;
   return 0;
@@ -205,6 +206,7 @@ static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
     CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, dtype == SDXL_DTYPE_LORA_LAYOUTS, &mapped));
     if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
     if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
+    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
     HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = dtype; c.mapped = mapped;
@@ -250,6 +252,7 @@ static int loha_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
     }
     if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
     if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
+    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
     HIP_CHECK_RET(hipMalloc((void**)&c.dev_loha, htab.size() * sizeof(LohaTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev_loha, htab.data(), htab.size() * sizeof(LohaTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOHA; c.mapped = 1;
@@ -263,8 +266,79 @@ static int loha_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
   return 0;
 }
 
+// ---- LoKr by merge and project (SDXL_DTYPE_LOKR): SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target the factorisation, the form
+// (the rule, or sdxl_lokr_op.full) in the table; the scale by the form per call (1 for a full target, op.scale for a factored one; op.scale == 0
+// zeroes both: the restoring merge) ----
+static int lokr_prepare(sdxl_handle* h, const char* name, const sdxl_lokr_op* lop, bool merge, LokrP& q) {
+  ARG_CHECK(name == nullptr, "lokr: `name` must be NULL with SDXL_DTYPE_LOKR (the targets are listed in sdxl_lokr_op.op.param)");
+  ARG_CHECK(lop != nullptr, "lokr: empty target list");
+  const sdxl_lora_op* op = &lop->op;
+  CHK(lokr_check_fields(op->rank, lop->factor, lop->full));
+  CHK(lora_check_op(op, merge, !merge));
+  Engine& e = h->e;
+  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lokr: %s are not bound", merge ? "weights" : "grads");
+  LoraCache& c = h->lora;
+  std::vector<int> params(op->param, op->param + op->n);
+  if (!(c.dev_lokr && c.rank == op->rank && c.dtype == SDXL_DTYPE_LOKR && c.factor == lop->factor && c.full == lop->full &&
+        c.params == params)) {
+    std::vector<LoraTarget> tab;
+    long tm = 0, tp = 0, tq = 0;
+    int mapped = 0;
+    CHK(lora_table(e, params, op->rank, tab, &tm, &tp, &tq, true, &mapped));      // every check of the packed layouts; offsets and tiles follow
+    std::vector<LokrTarget> ktab(tab.size());
+    long at = 0;
+    size_t sf = 0;
+    tm = tp = tq = 0;
+    for (size_t i = 0; i < tab.size(); ++i) {
+      LokrTarget& x = ktab[i];
+      memset(&x, 0, sizeof(x));
+      x.t = tab[i];
+      const int cin = x.t.kind == LORA_KIND_CONV3 ? x.t.cg : x.t.in;
+      lokr_geometry(x, cin, lop->factor, 0);
+      CHK(lokr_check_size(e.src[params[i]].name.c_str(), x, op->rank));
+      x.full = lop->full || lokr_rule_full(x.out_k, x.in_n, op->rank);
+      x.c_off = at; at += ((long)x.out_l * x.in_m + 7) / 8 * 8;      // C, then W2 or B, A, each padded to 8 elements
+      if (x.full) { x.t.b_off = x.t.gb_off = at; at += ((long)x.out_k * x.n2 + 7) / 8 * 8; x.t.a_off = x.t.ga_off = 0; }
+      else {
+        x.t.b_off = x.t.gb_off = at; at += ((long)x.out_k * op->rank + 7) / 8 * 8;
+        x.t.a_off = x.t.ga_off = at; at += ((long)op->rank * x.n2 + 7) / 8 * 8;
+      }
+      x.part_off = (long)sf; sf += lokr_part_floats(x);
+      x.dw2_off = (long)sf; sf += lokr_dw2_floats(x);
+      x.t.tile_m = (int)tm; x.t.tile_b = (int)tp; x.t.tile_a = (int)tq;
+      tm += lokr_tiles_m(x); tp += x.ptiles; tq += lokr_tiles_q(x, op->rank);
+      ARG_CHECK(tm < (1L << 31) && tp < (1L << 31) && tq < (1L << 31), "lokr: too many tiles");
+    }
+    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
+    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
+    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
+    HIP_CHECK_RET(hipMalloc((void**)&c.dev_lokr, ktab.size() * sizeof(LokrTarget)));
+    HIP_CHECK_RET(hipMemcpy(c.dev_lokr, ktab.data(), ktab.size() * sizeof(LokrTarget), hipMemcpyHostToDevice));
+    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOKR; c.mapped = 1;
+    c.factor = lop->factor; c.full = lop->full; c.scratch_floats = sf;
+    c.tiles_m = (int)tm; c.tiles_b = (int)tp; c.tiles_a = (int)tq;
+  }
+  if (!merge) CHK(lokr_check_scratch(lop->scratch, lop->scratch_floats, c.scratch_floats));
+  memset(&q, 0, sizeof(q));
+  q.table = c.dev_lokr; q.n = op->n; q.rank = op->rank;
+  q.scale = op->scale; q.scale_full = op->scale == 0.f ? 0.f : 1.f;      // (scale 0: the restoring merge zeroes both forms)
+  q.tiles_m = c.tiles_m; q.tiles_p = c.tiles_b; q.tiles_q = c.tiles_a;
+  q.w = e.weights; q.base = (const bf16*)op->base; q.c = q.b = q.a = (const bf16*)op->adapters;
+  q.dw = e.grads; q.gc = q.gb = q.ga = op->adapter_grads; q.scratch = lop->scratch;
+  return 0;
+}
+
 int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtype, void* st) {
+  if (dtype == SDXL_DTYPE_LOKR_ONE) {      // (a test hook that is a dtype: include/sdxlstep_diag.h)
+    ARG_CHECK(h == nullptr && name == nullptr, "lokr: SDXL_DTYPE_LOKR_ONE takes no handle and no name");
+    return lokr_one_merge((const sdxl_lokr_one*)src, st);
+  }
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LOKR) {
+    LokrP q;
+    CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)src, true, q));
+    return launch_lokr_merge(q, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LOHA) {
     LohaP q;
     CHK(loha_prepare(h, name, (const sdxl_lora_op*)src, true, q));
@@ -376,7 +450,16 @@ static int grad_select(sdxl_handle* h, const char* name, const sdxl_grad_select*
 
 int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, void* st) {
   if (dtype == SDXL_DTYPE_GRAD_SELECT) return grad_select(h, name, (const sdxl_grad_select*)dst);
+  if (dtype == SDXL_DTYPE_LOKR_ONE) {
+    ARG_CHECK(h == nullptr && name == nullptr, "lokr: SDXL_DTYPE_LOKR_ONE takes no handle and no name");
+    return lokr_one_project((const sdxl_lokr_one*)dst, st);
+  }
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_LOKR) {
+    LokrP q;
+    CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)dst, false, q));
+    return launch_lokr_project(q, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LOHA) {
     LohaP q;
     CHK(loha_prepare(h, name, (const sdxl_lora_op*)dst, false, q));

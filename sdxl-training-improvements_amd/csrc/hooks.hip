@@ -681,3 +681,41 @@ int sdxl_debug_act_checksums(sdxl_handle* h, unsigned long long* out_host, int c
 }
 
 }  // extern "C"
+
+// ---- LoKr on caller buffers (csrc/lokr.hip; the hook is a dtype, SDXL_DTYPE_LOKR_ONE, so nothing here is exported): the descriptor of one target,
+// every offset 0; the form and the scale are the caller's choice, not the rule's ----
+static int lokr_one(int out, int in, int group, int kind, int factor, int rank, int full, float scale, LokrP& q) {
+  CHK(lokr_check_fields(rank, factor, full));
+  LoraP l;
+  CHK(lora_one_layout(out, in, rank, scale, kind, group, out, l));
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = rank; q.scale = q.scale_full = scale;
+  q.one.t = l.one;
+  lokr_geometry(q.one, kind == LORA_KIND_CONV3 ? group : in, factor, full);
+  CHK(lokr_check_size("the operand", q.one, rank));
+  q.one.part_off = 0; q.one.dw2_off = (long)lokr_part_floats(q.one);
+  q.tiles_m = lokr_tiles_m(q.one); q.tiles_p = q.one.ptiles; q.tiles_q = lokr_tiles_q(q.one, rank);
+  return 0;
+}
+// the two halves of SDXL_DTYPE_LOKR_ONE (sdxlstep_diag.h): no symbol of their own, capi.hip's sdxl_load_weight / sdxl_export_grad call them
+int lokr_one_merge(const sdxl_lokr_one* o, void* st) {
+  ARG_CHECK(o != nullptr, "lokr_merge: NULL descriptor");
+  ARG_CHECK(aligned16(o->base) && aligned16(o->C) && aligned16(o->W2) && (o->full == 1 || aligned16(o->A)) && aligned16(o->w),
+            "lokr_merge: every pointer must be 16-byte aligned and non-NULL");
+  LokrP q;
+  CHK(lokr_one(o->out, o->in, o->group, o->kind, o->factor, o->rank, o->full, o->scale, q));
+  q.w = (bf16*)o->w; q.base = (const bf16*)o->base;
+  q.c = (const bf16*)o->C; q.b = (const bf16*)o->W2; q.a = (const bf16*)o->A;
+  return launch_lokr_merge(q, (hipStream_t)st);
+}
+int lokr_one_project(const sdxl_lokr_one* o, void* st) {
+  ARG_CHECK(o != nullptr, "lokr_project: NULL descriptor");
+  ARG_CHECK(aligned16(o->dw) && aligned16(o->C) && aligned16(o->W2) && aligned16(o->dC) && aligned16(o->dW2) &&
+            (o->full == 1 || (aligned16(o->A) && aligned16(o->dA))), "lokr_project: every pointer must be 16-byte aligned and non-NULL");
+  LokrP q;
+  CHK(lokr_one(o->out, o->in, o->group, o->kind, o->factor, o->rank, o->full, o->scale, q));
+  CHK(lokr_check_scratch(o->scratch, o->scratch_floats, lokr_part_floats(q.one) + lokr_dw2_floats(q.one)));
+  q.dw = o->dw; q.c = (const bf16*)o->C; q.b = (const bf16*)o->W2; q.a = (const bf16*)o->A;
+  q.gc = o->dC; q.gb = o->dW2; q.ga = o->dA; q.scratch = o->scratch;
+  return launch_lokr_project(q, (hipStream_t)st);
+}

@@ -636,6 +636,82 @@ static inline int loha_tiles_a(int out, int in) { return cdiv(in, LOHA_P_COLS); 
 int launch_loha_merge(const LohaP& p, hipStream_t st);
 int launch_loha_project(const LohaP& p, hipStream_t st);     // two launches: dB1 | dB2, dA1 | dA2
 
+// ---- LoKr by merge and project (lokr.hip; SDXL_DTYPE_LOKR): dW = s kron(C, W2), W2 full or B A, table-driven like LoRA's, always kind-aware ----
+#define LOKR_MAX_RANK 128
+#define LOKR_M_ROWS 32    // merge tile
+#define LOKR_M_COLS 64
+#define LOKR_M_KC 32      // ranks staged per step
+#define LOKR_P_TILE 1024  // project, launch 1: elements of W2 per workgroup (SDXL_LOKR_TILE), 4 per thread
+#define LOKR_P_NB 8       //   blocks (a, b) whose loads are in flight together and whose partial sums share one barrier
+#define LOKR_Q_THREADS 256      // project, launch 2: one output element per thread
+// source -> native, the inverses of lora_src_col / lora_src_row
+__host__ __device__ static inline int lora_nat_col(int kind, int cg, int i) {
+  return kind == LORA_KIND_CONV3 ? (i % 9) * cg + i / 9 : i;
+}
+__host__ __device__ static inline int lora_nat_row(int kind, int cg, int c4, int o) {
+  if (kind != LORA_KIND_GEGLU) return o;
+  const int half = o >= c4 ? 1 : 0, c = o - half * c4, grp = c / cg;
+  return grp * 2 * cg + half * cg + c - grp * cg;
+}
+struct LokrTarget {       // LoraTarget (w_off, base_off, out, in, kind, cg; tile_m: merge, tile_b: project launch 1, tile_a: launch 2;
+  LoraTarget t;           // a_off / ga_off: A, b_off / gb_off: W2 or B) and the factorisation.  Only the rows < out are read or written
+  long c_off;             // adapter and adapter-gradient arena: C [out_l][in_m]
+  long part_off, dw2_off; // scratch, in floats: partial sums [ptiles][out_l * in_m]; a factored target's s dW2 [out_k][n2]
+  int out_l, out_k;       // out = out_l * out_k
+  int in_m, in_n;         // cin = in_m * in_n
+  int khw, n2;            // 1 or 9; n2 = in_n * khw: in = in_m * n2
+  int full;               // W2 stored as it is (b_off), else W2 = B A; also picks the scale: LokrP::scale_full or LokrP::scale
+  int ptiles;             // cdiv(out_k * n2, LOKR_P_TILE)
+};
+struct LokrP {
+  const LokrTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
+  LokrTarget one;
+  int n, rank;                  // rank 1 .. LOKR_MAX_RANK (read by the factored targets only)
+  float scale, scale_full;      // s of a factored target and of a full one (per call, not in the table: a restoring merge passes 0 for both)
+  int tiles_m, tiles_p, tiles_q;
+  bf16* w;                      // merge: out
+  const bf16* base;             // merge
+  const bf16 *c, *b, *a;        // what c_off / b_off / a_off count from: the adapter arena three times, or the hook's factors (offsets 0)
+  const float* dw;              // project
+  float *gc, *gb, *ga;          // project: out, overwritten
+  float* scratch;               // project
+};
+// LyCORIS' factorization(dimension, factor), the smaller number first (include/sdxlstep.h restates the rule)
+static inline void lokr_fact(int dim, int factor, int* m_, int* n_) {
+  int m = 1, n = dim;
+  if (factor > 0 && dim % factor == 0) { m = factor; n = dim / factor; }
+  else {
+    if (factor < 0) factor = dim;
+    while (m < n) {
+      int nm = m + 1;
+      while (dim % nm) ++nm;
+      const int nn = dim / nm;
+      if (nm + nn > m + n || nm > factor) break;
+      m = nm; n = nn;
+    }
+  }
+  *m_ = m < n ? m : n; *n_ = m < n ? n : m;
+}
+static inline bool lokr_rule_full(int out_k, int in_n, int rank) { return 2 * rank >= (out_k > in_n ? out_k : in_n); }
+// the geometry of one target: cin = the channel count (in for a 2-D weight, in / 9 for a 3x3 convolution)
+static inline void lokr_geometry(LokrTarget& x, int cin, int factor, int full) {
+  lokr_fact(x.t.out, factor, &x.out_l, &x.out_k);
+  lokr_fact(cin, factor, &x.in_m, &x.in_n);
+  x.khw = x.t.in / cin; x.n2 = x.in_n * x.khw;
+  x.full = full;
+  x.ptiles = (int)cdiv((long)x.out_k * x.n2, (long)LOKR_P_TILE);
+}
+static inline size_t lokr_pad4(size_t n) { return (n + 3) / 4 * 4; }
+static inline size_t lokr_part_floats(const LokrTarget& x) { return lokr_pad4((size_t)x.ptiles * x.out_l * x.in_m); }
+static inline size_t lokr_dw2_floats(const LokrTarget& x) { return x.full ? 0 : lokr_pad4((size_t)x.out_k * x.n2); }
+static inline int lokr_tiles_m(const LokrTarget& x) { return cdiv(x.t.out, LOKR_M_ROWS) * cdiv(x.t.in, LOKR_M_COLS); }
+// (lokr_check_size, capi.h, keeps out_k * n2, out_k * rank and rank * n2 below 2^31: launch 2 indexes its outputs with 32-bit integers)
+static inline int lokr_tiles_q(const LokrTarget& x, int rank) {
+  return cdiv((long)x.out_l * x.in_m, LOKR_Q_THREADS) + (x.full ? 0 : cdiv((long)x.out_k * rank, LOKR_Q_THREADS) + cdiv((long)rank * x.n2, LOKR_Q_THREADS));
+}
+int launch_lokr_merge(const LokrP& p, hipStream_t st);
+int launch_lokr_project(const LokrP& p, hipStream_t st);     // two launches: dW2 and the partial sums of dC; dC, dB, dA
+
 // ---- direct LoRA adapter gradients (lora_grad.hip): dA, dB of every target of ONE linear op from its X and dY, no dW ----
 #define LORA_G_CHUNK 512      // rows of M per partial block (a multiple of 32): the split of M is fixed by M alone
 struct LoraGradTarget {

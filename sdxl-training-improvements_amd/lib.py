@@ -139,6 +139,25 @@ class LoraOp(C.Structure):
                 ("adapters", C.c_void_p), ("base", C.c_void_p), ("adapter_grads", C.c_void_p)]
 
 
+DTYPE_LOKR = 6        # SDXL_DTYPE_LOKR: the same two calls with a host LokrOp*: dW = s kron(C, W2), W2 full or B A (lora.py, algo="kronecker")
+LOKR_TILE = 1024      # SDXL_LOKR_TILE: elements of W2 per workgroup of the projection (the scratch formula, lora.lokr_scratch_floats)
+
+
+class LokrOp(C.Structure):
+    """sdxl_lokr_op: LoraOp, the factor (-1 or >= 1), full (0: the form rule per target, 1: every W2 in full) and the projection's scratch"""
+    _fields_ = [("op", LoraOp), ("factor", C.c_int), ("full", C.c_int), ("scratch", C.c_void_p), ("scratch_floats", C.c_size_t)]
+
+
+DTYPE_LOKR_ONE = 7    # SDXL_DTYPE_LOKR_ONE (sdxlstep_diag.h part 1): the LoKr kernels on caller buffers, one target, NULL handle and name, a host LokrOne*
+
+
+class LokrOne(C.Structure):
+    """sdxl_lokr_one: the test hook of csrc/lokr.hip (a dtype of sdxl_load_weight: merge / sdxl_export_grad: project, not a function)"""
+    _fields_ = ([(k, C.c_void_p) for k in ("base", "C", "W2", "A", "w", "dw", "dC", "dW2", "dA")] +
+                [(k, C.c_int) for k in ("out", "in_", "group", "kind", "factor", "rank", "full")] +
+                [("scale", C.c_float), ("scratch", C.c_void_p), ("scratch_floats", C.c_size_t)])
+
+
 DTYPE_GRAD_SELECT = 3  # SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad: the pointer is a host GradSelect* (NULL = every tensor trainable), name NULL
 
 

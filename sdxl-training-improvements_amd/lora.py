@@ -26,6 +26,14 @@ merged and projected the same way through dtype SDXL_DTYPE_LOHA (csrc/loha.hip):
 the rank is capped at 64.  Its gradients are two projections of dW .* P with the other pair's product P recomputed on the fly; "direct" is
 LoRA's only.  Initialisation (this build's choice; LyCORIS was not at hand to compare with): B2 = 0, so dW = 0 and the first merged step
 has the plain trainer's bits; A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2) from lora_seed.
+
+"kronecker" is LyCORIS' LoKr (the value is NOT "lokr": tests/test_host_loha.py pins that string as an unknown algorithm): with
+(out_l, out_k) = lokr_fact(out, factor), (in_m, in_n) = lokr_fact(cin, factor), cin = shape[1], n2 = in_n kh kw,
+  dW = s kron(C, W2),   C [out_l, in_m] (lokr_w1),   W2 [out_k, n2] stored in full (lokr_w2) or W2 = B A, B [out_k, r] (lokr_w2_a), A [r, n2] (lokr_w2_b)
+through dtype SDXL_DTYPE_LOKR (csrc/lokr.hip).  training.lokr_factor (-1 or >= 1) is the factor; a target is full when training.lokr_full
+is true or 2 r >= max(out_k, in_n) (LyCORIS' rule with decompose_both off), with s = 1 and an exported alpha of r; a factored one has
+s = alpha / r.  lora_rank is 1 .. 128.  Initialisation (this build's choice): the zero factor is W2 (full) or A (factored), as in LyCORIS,
+so dW = 0 and the first merged step has the plain trainer's bits; C ~ N(0, 1), B ~ N(0, 0.1^2) from lora_seed.
 """
 from __future__ import annotations
 
@@ -48,9 +56,11 @@ DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
 MAX_RANK = 128
 LORA_BACKWARDS = ("project", "project_frozen", "direct")
 LORA_TARGET_KINDS = ("plain", "all")
-LORA_ALGOS = ("lora", "loha")
+LORA_ALGOS = ("lora", "loha", "kronecker")
 LOHA_MAX_RANK = 64
-EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors"}      # save_checkpoint's adapter file
+LOKR = "kronecker"      # LyCORIS' LoKr ("lokr" stays an unknown value: tests/test_host_loha.py uses it as one)
+EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors", LOKR: "lycoris_lokr.safetensors"}      # save_checkpoint's adapter file
+LOKR_NAMES = {"C": "lokr_w1", "W2": "lokr_w2", "B": "lokr_w2_a", "A": "lokr_w2_b"}      # the LyCORIS names
 LOHA_FACTORS = (("A1", "hada_w1_b"), ("B1", "hada_w1_a"), ("A2", "hada_w2_b"), ("B2", "hada_w2_a"))      # arena order; the LyCORIS names
 
 
@@ -58,6 +68,59 @@ def check_lora_algo(algo) -> str:
     if algo not in LORA_ALGOS:
         raise ValueError(f"training.lora_algo {algo!r}: expected one of {list(LORA_ALGOS)}")
     return algo
+
+
+def check_lokr_factor(factor) -> int:
+    if isinstance(factor, bool) or not isinstance(factor, int) or not (factor == -1 or factor >= 1):
+        raise ValueError(f"training.lokr_factor {factor!r}: expected -1 or a positive integer")
+    return factor
+
+
+def check_lokr_full(full) -> bool:
+    if not isinstance(full, bool):
+        raise ValueError(f"training.lokr_full {full!r}: expected true or false")
+    return full
+
+
+def lokr_fact(dimension: int, factor: int = -1) -> Tuple[int, int]:
+    """LyCORIS' factorization(dimension, factor), restated: (m, n), m <= n, m n = dimension.  A positive factor that divides the dimension
+    gives (factor, dimension / factor) sorted; otherwise m steps from 1 through the divisors while m + n does not grow and m <= factor
+    (factor < 0: no cap)."""
+    if factor > 0 and dimension % factor == 0:
+        m, n = factor, dimension // factor
+        return (m, n) if m <= n else (n, m)
+    if factor < 0:
+        factor = dimension
+    m, n = 1, dimension
+    while m < n:
+        nm = m + 1
+        while dimension % nm:
+            nm += 1
+        nn = dimension // nm
+        if nm + nn > m + n or nm > factor:
+            break
+        m, n = nm, nn
+    return (m, n) if m <= n else (n, m)
+
+
+def lokr_geometry(shape: Sequence[int], factor: int, rank: int, full: bool) -> Dict[str, int]:
+    """out_l, out_k, in_m, in_n, khw, n2, full (0 / 1) of one target: the channel count shape[1] is factorised, not `in`; the form is the
+    rule 2 rank >= max(out_k, in_n) unless `full` forces it"""
+    out_l, out_k = lokr_fact(int(shape[0]), factor)
+    in_m, in_n = lokr_fact(int(shape[1]), factor)
+    khw = _prod(shape[2:])
+    return dict(out_l=out_l, out_k=out_k, in_m=in_m, in_n=in_n, khw=khw, n2=in_n * khw,
+                full=int(bool(full) or 2 * rank >= max(out_k, in_n)))
+
+
+def lokr_scratch_floats(geos) -> int:
+    """sdxl_lokr_op.scratch's size (include/sdxlstep.h): per target the projection's partial sums and a factored target's dW2"""
+    pad4 = lambda n: (n + 3) // 4 * 4
+    total = 0
+    for g in geos:
+        w2 = g["out_k"] * g["n2"]
+        total += pad4(-(-w2 // lib.LOKR_TILE) * g["out_l"] * g["in_m"]) + (0 if g["full"] else pad4(w2))
+    return total
 
 
 def check_lora_backward(mode) -> str:
@@ -156,14 +219,26 @@ def _prod(dims) -> int:
     return n
 
 
-def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int, algo: str = "lora"):
+def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int, algo: str = "lora", factor: int = -1,
+                   full: bool = False):
     """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements;
     out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions.
-    algo "loha": {key: (A1 offset, B1 offset, A2 offset, B2 offset, out, in)}, the four factors in that order, each padded to 8"""
+    algo "loha": {key: (A1 offset, B1 offset, A2 offset, B2 offset, out, in)}, the four factors in that order, each padded to 8;
+    algo "kronecker": {key: (C offset, W2 offset, out, in)} for a full target, (C offset, B offset, A offset, out, in) for a factored one
+    (lokr_geometry has the shapes), each factor padded to 8"""
     check_lora_algo(algo)
     lay, cur = {}, 0
     for k in targets:
         o, i = int(shapes[k][0]), _prod(shapes[k][1:])
+        if algo == LOKR:
+            g = lokr_geometry(shapes[k], factor, rank, full)
+            sizes = [g["out_l"] * g["in_m"]] + ([g["out_k"] * g["n2"]] if g["full"] else [g["out_k"] * rank, rank * g["n2"]])
+            offs = []
+            for n in sizes:
+                offs.append(cur)
+                cur += _pad8(n)
+            lay[k] = (*offs, o, i)
+            continue
         offs = []
         for _pair in range(2 if algo == "loha" else 1):
             offs.append(cur)
@@ -178,11 +253,14 @@ class LoRAAdapters:
     """The adapters of one net: bf16 arena `.weights`, fp32 `.grads` laid out like it, and the packed bf16 copy of the targets' W0."""
 
     def __init__(self, net, rank: int, alpha: Optional[float] = None, targets: Optional[Sequence[str]] = None, seed: int = 0,
-                 kinds: str = "plain", algo: str = "lora"):
+                 kinds: str = "plain", algo: str = "lora", factor: int = -1, full: bool = False):
         self.kinds = check_target_kinds(kinds)
         self.algo = check_lora_algo(algo)
+        self.lokr_factor = check_lokr_factor(factor)      # (read by "kronecker" only)
+        self.lokr_full = check_lokr_full(full)
         # (loha: one dtype, the packed layouts' target rules in the library; `kinds` still says what the patterns may resolve to)
-        self.dtype = lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA
+        self.dtype = (lib.DTYPE_LOKR if algo == LOKR else lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_LORA_LAYOUTS if kinds == "all"
+                      else lib.DTYPE_LORA)
         max_rank = LOHA_MAX_RANK if algo == "loha" else MAX_RANK
         if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
             raise ValueError(f"lora_rank must be an integer in 1 .. {max_rank} (got {rank!r})" + (" with lora_algo 'loha'" if algo == "loha" else ""))
@@ -198,8 +276,11 @@ class LoRAAdapters:
         self.shapes = {k: tuple(int(v) for v in shapes[k]) for k in self.targets}
         names = list(shapes)
         self.index = [names.index(k) for k in self.targets]
-        self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank, algo)
+        self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank, algo, self.lokr_factor, self.lokr_full)
         dev = net.weights.device
+        self.geometry = {k: lokr_geometry(self.shapes[k], self.lokr_factor, rank, self.lokr_full) for k in self.targets} if algo == LOKR else {}
+        # the projection's scratch (sdxl_lokr_op.scratch), allocated once; its contents never matter
+        self.scratch = torch.empty(max(lokr_scratch_floats(self.geometry.values()), 4), dtype=torch.float32, device=dev) if algo == LOKR else None
         self.weights = torch.zeros(self.param_elems, dtype=torch.bfloat16, device=dev)
         self.grads = torch.zeros(self.param_elems, dtype=torch.float32, device=dev)
         ranges = net.param_ranges()
@@ -208,7 +289,11 @@ class LoRAAdapters:
         g = torch.Generator().manual_seed(self.seed)
         for k in self.targets:
             o, i = self.layout[k][-2:]
-            if algo == "loha":      # this build's choice: B2 = 0 (dW = 0), A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2), drawn in the order A1, B1, A2
+            if algo == LOKR:        # this build's choice: W2 (full) or A (factored) = 0 (dW = 0), C ~ N(0, 1), B ~ N(0, 0.1^2), drawn in the order C, B
+                for name, std in (("C", 1.0),) + ((() if self.geometry[k]["full"] else (("B", 0.1),))):
+                    v = self.factor_view(name, k)
+                    v.copy_((torch.randn(*v.shape, generator=g) * std).to(torch.bfloat16))
+            elif algo == "loha":    # this build's choice: B2 = 0 (dW = 0), A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2), drawn in the order A1, B1, A2
                 for name, shape, std in (("A1", (rank, i), 1.0), ("B1", (o, rank), 0.1), ("A2", (rank, i), 1.0)):
                     self.factor(name, k).copy_((torch.randn(*shape, generator=g) * std).to(torch.bfloat16))
             else:                   # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
@@ -222,11 +307,17 @@ class LoRAAdapters:
 
     def param_ranges(self) -> Dict[str, Tuple[int, int]]:
         """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas;
-        algo "loha": "<module>.hada_w1_b" (A1), ".hada_w1_a" (B1), ".hada_w2_b" (A2), ".hada_w2_a" (B2), in arena order"""
+        algo "loha": "<module>.hada_w1_b" (A1), ".hada_w1_a" (B1), ".hada_w2_b" (A2), ".hada_w2_a" (B2), in arena order;
+        algo "kronecker": "<module>.lokr_w1" (C), then ".lokr_w2" (W2, a full target) or ".lokr_w2_a" (B), ".lokr_w2_b" (A)"""
         out = {}
         for k, lay in self.layout.items():
             mod = k[: -len(".weight")]
             o, i = lay[-2:]
+            if self.algo == LOKR:
+                for n, name in enumerate(self.lokr_factors(k)):
+                    rows, cols = self._lokr_shape(k, name)
+                    out[f"{mod}.{LOKR_NAMES[name]}"] = (lay[n], _pad8(rows * cols))
+                continue
             if self.algo == "loha":
                 for n, (_name, lyco) in enumerate(LOHA_FACTORS):
                     out[f"{mod}.{lyco}"] = (lay[n], _pad8(self.rank * i if n % 2 == 0 else o * self.rank))
@@ -246,17 +337,52 @@ class LoRAAdapters:
     def factor(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
         """a LoHa factor "A1" | "B1" | "A2" | "B2" of a target (or its gradient), a view of the arena"""
         if self.algo != "loha":
-            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r} (A and B)")
+            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}" + (" (A and B)" if self.algo == "lora" else " (C, W2 or B, A)"))
         return self._view(key, [n for n, _l in LOHA_FACTORS].index(name), grad)
+
+    def lokr_factors(self, key: str) -> Tuple[str, ...]:
+        """the factors of a "kronecker" target in arena order: ("C", "W2") when it is full, ("C", "B", "A") when it is factored"""
+        return ("C", "W2") if self.geometry[key]["full"] else ("C", "B", "A")
+
+    def _lokr_shape(self, key: str, name: str) -> Tuple[int, int]:
+        g = self.geometry[key]
+        return {"C": (g["out_l"], g["in_m"]), "W2": (g["out_k"], g["n2"]), "B": (g["out_k"], self.rank), "A": (self.rank, g["n2"])}[name]
+
+    def factor_view(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
+        """a LoKr factor "C" | "W2" (full target) | "B" | "A" (factored target) of a target (or its gradient), a view of the arena; W2 and A
+        columns are j = d kh kw + tap, the state-dict order"""
+        if self.algo != LOKR:
+            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}, not 'kronecker'")
+        names = self.lokr_factors(key)
+        if name not in names:
+            raise ValueError(f"{name}: {key} is a {'full' if self.geometry[key]['full'] else 'factored'} lora_algo 'kronecker' target: it has "
+                             + ", ".join(names))
+        off = self.layout[key][names.index(name)]
+        rows, cols = self._lokr_shape(key, name)
+        return (self.grads if grad else self.weights)[off: off + rows * cols].view(rows, cols)
+
+    def C(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor_view("C", key, grad)
+
+    def W2(self, key: str, grad: bool = False) -> torch.Tensor:
+        return self.factor_view("W2", key, grad)
+
+    def target_scale(self, key: str) -> float:
+        """s of one target: alpha / rank, or 1 for a full "kronecker" target"""
+        return 1.0 if self.algo == LOKR and self.geometry[key]["full"] else self.scale
 
     def A(self, key: str, grad: bool = False) -> torch.Tensor:
         if self.algo == "loha":
             raise ValueError("A: lora_algo 'loha' adapters have A1 and A2")
+        if self.algo == LOKR:
+            return self.factor_view("A", key, grad)
         return self._view(key, 0, grad)
 
     def B(self, key: str, grad: bool = False) -> torch.Tensor:
         if self.algo == "loha":
             raise ValueError("B: lora_algo 'loha' adapters have B1 and B2")
+        if self.algo == LOKR:
+            return self.factor_view("B", key, grad)
         return self._view(key, 1, grad)
 
     def A1(self, key: str, grad: bool = False) -> torch.Tensor:
@@ -272,9 +398,12 @@ class LoRAAdapters:
         return self.factor("B2", key, grad)
 
     # ---- the two device steps
-    def _op(self, scale: float) -> lib.LoraOp:
-        return lib.LoraOp(len(self.index), self._param, self.rank, float(scale), self.weights.data_ptr(), self.base.data_ptr(),
-                          self.grads.data_ptr())
+    def _op(self, scale: float):
+        op = lib.LoraOp(len(self.index), self._param, self.rank, float(scale), self.weights.data_ptr(), self.base.data_ptr(),
+                        self.grads.data_ptr())
+        if self.algo == LOKR:
+            return lib.LokrOp(op, self.lokr_factor, int(self.lokr_full), self.scratch.data_ptr(), self.scratch.numel())
+        return op
 
     def _call(self, fn_name: str, scale: float) -> None:
         if self.L is None:
@@ -284,7 +413,8 @@ class LoRAAdapters:
         lib.check(getattr(self.L, fn_name)(self.net.h, None, C.byref(op), self.dtype, st), f"{fn_name} (lora)")
 
     def merge(self, scale: Optional[float] = None) -> None:
-        """W = bf16(W0 + s B A) for every target, into the net's weight arena (one launch)"""
+        """W = bf16(W0 + s B A) for every target, into the net's weight arena (one launch).  algo "kronecker": `scale` is the factored
+        targets' s; a full target uses s = 1 whatever non-zero `scale` is given, and s = 0 with scale 0 (restore)"""
         self._call("sdxl_load_weight", self.scale if scale is None else scale)
 
     def restore(self) -> None:
@@ -322,6 +452,9 @@ class LoRAAdapters:
             meta["kinds"] = self.kinds
         if self.algo != "lora":        # (and so is a LoRA state)
             meta["algo"] = self.algo
+        if self.algo == LOKR:          # (and a LoHa state)
+            meta["factor"] = self.lokr_factor
+            meta["full"] = self.lokr_full
         return meta
 
     def state_dict(self) -> Dict[str, Any]:
@@ -333,7 +466,7 @@ class LoRAAdapters:
             raise ValueError(f"lora state: lora_algo differs from this trainer's ({sd.get('algo', 'lora')!r} vs {self.algo!r})")
         if sd.get("kinds", "plain") != self.kinds:
             raise ValueError(f"lora state: kinds differs from this trainer's ({sd.get('kinds', 'plain')!r} vs {self.kinds!r})")
-        for key in ("rank", "targets", "shapes"):
+        for key in ("rank", "targets", "shapes") + (("factor", "full") if self.algo == LOKR else ()):
             if sd.get(key) != mine[key]:
                 raise ValueError(f"lora state: {key} differs from this trainer's ({_brief(sd.get(key))} vs {_brief(mine[key])})")
         w = sd.get("weights")
@@ -354,6 +487,18 @@ class LoRAAdapters:
         algo "loha": the LyCORIS / kohya convention instead -- "lora_unet_<module path with '.' -> '_'>.hada_w1_a" [out, r] (B1), ".hada_w1_b"
         [r, in kh kw] (A1), ".hada_w2_a" (B2), ".hada_w2_b" (A2) and ".alpha" (a scalar), fp32, s NOT folded in: a loader forms
         (alpha / r) (w1_a w1_b) .* (w2_a w2_b) reshaped like the layer's weight."""
+        if self.algo == LOKR:      # lokr_w1 [out_l, in_m]; lokr_w2 [out_k, in_n(, kh, kw)] or lokr_w2_a [out_k, r], lokr_w2_b [r, in_n kh kw];
+            out = {}               # alpha (r for a full target: its scale is 1); fp32, s not folded in: a loader forms s kron(w1, w2)
+            for k in self.targets:
+                pre = "lora_unet_" + k[: -len(".weight")].replace(".", "_")
+                g, shape = self.geometry[k], self.shapes[k]
+                for name in self.lokr_factors(k):
+                    v = self.factor_view(name, k).float().cpu().contiguous()
+                    if name == "W2" and len(shape) == 4:
+                        v = v.view(g["out_k"], g["in_n"], *shape[2:])
+                    out[f"{pre}.{LOKR_NAMES[name]}"] = v
+                out[f"{pre}.alpha"] = torch.tensor(float(self.rank) if g["full"] else self.alpha, dtype=torch.float32)
+            return out
         if self.algo == "loha":
             out = {}
             for k in self.targets:
@@ -426,6 +571,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
             logger.warning("NativeLoRATrainer builds its own fused optimizer on the adapter arena: the optimizer passed in is ignored")
         self.lora_backward = check_lora_backward(getattr(tc, "lora_backward", "project"))
         check_target_kinds(getattr(tc, "lora_target_kinds", "plain"))
+        check_lokr_factor(getattr(tc, "lokr_factor", -1))
+        check_lokr_full(getattr(tc, "lokr_full", False))
         if self.lora_algo != "lora" and self.lora_backward == "direct":
             raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
                              f"{self.lora_algo!r}'s (use 'project' or 'project_frozen')")
@@ -455,7 +602,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         if isinstance(targets, str):
             targets = [targets]
         self.lora = LoRAAdapters(self.net, int(tc.lora_rank), alpha, targets, int(getattr(tc, "lora_seed", 0)),
-                                 kinds=getattr(tc, "lora_target_kinds", "plain"), algo=self.lora_algo)
+                                 kinds=getattr(tc, "lora_target_kinds", "plain"), algo=self.lora_algo,
+                                 factor=getattr(tc, "lokr_factor", -1), full=getattr(tc, "lokr_full", False))
         if self.lora_backward == "direct":      # (before any arena of the optimizer is built)
             self.lora.check_direct()
         opt = build_optimizer(self.lora, self.config.optimizer)
@@ -508,7 +656,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
 
     def save_checkpoint(self, epoch_or_path=0, is_final: bool = False) -> Optional[Path]:
         """`pytorch_lora_weights.safetensors` (fp32, keys unet.<module>.lora_A.weight / .lora_B.weight, s folded into lora_B),
-        with training.lora_algo "loha" `lycoris_loha.safetensors` instead (export_tensors has the keys),
+        with training.lora_algo "loha" `lycoris_loha.safetensors`, with "kronecker" `lycoris_lokr.safetensors` instead (export_tensors
+        has the keys),
         `lora_state.pt` (the bit-exact arena, settings and target list: load_lora_state), `optimizer.pt`, `config.json`; the merged
         UNet only with training.lora_save_merged.  Rank 0 writes; no collective."""
         if not D.is_main_process():
