@@ -213,6 +213,17 @@ SDXL_API int sdxl_debug_plan_num_ops(sdxl_handle* h, int* n);
  * layout has drifted can never be written past) */
 SDXL_API int sdxl_debug_plan_op(sdxl_handle* h, int i, sdxl_plan_op_desc* out, size_t out_bytes);
 SDXL_API int sdxl_debug_plan_tail(sdxl_handle* h, sdxl_plan_tail* out, size_t out_bytes);
+/* The loss's buffers in the current plan (byte offsets into the workspace, named after the Plan fields of csrc/engine.h; NONE where the plan
+ * reserves none): the partial rows of loss_fwd_kernel, the [B] per-sample losses, the [B] masked_mean normaliser and the staged copies graph
+ * mode reads in place of the caller's arrays.  staged: 1 when the last sdxl_forward_loss handed the loss kernels the staged copies, 0 the
+ * caller's arrays, -1 before the first one.  part_floats: loss_part_floats(B, HW); ps_slots: loss_ps_slots(B, HW).  Pure host code. */
+typedef struct sdxl_plan_loss {
+  size_t loss_part_off, ps_loss_off, mask_norm_off;
+  size_t in_lat_off, in_noise_off, in_nin_off, in_sig_off, in_tag_off, in_sw_off, in_hc_off, in_mask_off, in_cond_off;
+  size_t part_floats;
+  int ps_slots, staged;
+} sdxl_plan_loss;
+SDXL_API int sdxl_debug_plan_loss(sdxl_handle* h, sdxl_plan_loss* out, size_t out_bytes);
 
 /* ---- part 2: experiment ABI (diagnostics build only) ---- */
 /* the linear dgrad whose epilogue runs the backward of the LayerNorm that produced its input (csrc/kernels.h, GemmP::ln_x): dY [M][K] bf16,

@@ -246,6 +246,22 @@ int sdxl_debug_plan_tail(sdxl_handle* h, sdxl_plan_tail* out, size_t out_bytes) 
   out->workspace_bytes = p.ws_bytes;
   return 0;
 }
+int sdxl_debug_plan_loss(sdxl_handle* h, sdxl_plan_loss* out, size_t out_bytes) {
+  ARG_CHECK(out_bytes == sizeof(sdxl_plan_loss), "plan loss: the caller's struct has %zu bytes, the library's %zu", out_bytes, sizeof(sdxl_plan_loss));
+  H_CHECK(h);
+  ARG_CHECK(h->e.cur, "no plan: call sdxl_plan first");
+  ARG_CHECK(out, "null output");
+  const Plan& p = *h->e.cur;
+  memset(out, 0, sizeof(*out));
+  out->loss_part_off = p.loss_part_off; out->ps_loss_off = p.ps_loss_off; out->mask_norm_off = p.mask_norm_off;
+  out->in_lat_off = p.in_lat_off; out->in_noise_off = p.in_noise_off; out->in_nin_off = p.in_nin_off; out->in_sig_off = p.in_sig_off;
+  out->in_tag_off = p.in_tag_off; out->in_sw_off = p.in_sw_off; out->in_hc_off = p.in_hc_off; out->in_mask_off = p.in_mask_off;
+  out->in_cond_off = p.in_cond_off;
+  out->part_floats = loss_part_floats(p.B, p.H * p.W); out->ps_slots = loss_ps_slots(p.B, p.H * p.W);
+  // the loss kernels of the last forward read what StepState::b holds: the staged latents of this plan, or the caller's pointer
+  out->staged = !h->step.valid ? -1 : (p.in_lat_off != NONE && h->step.b.latents == p.F(p.in_lat_off)) ? 1 : 0;
+  return 0;
+}
 
 int sdxl_op_wgrad_group(int n, const void* const* dy, const void* const* x, float* const* dw, float* const* dbias, int Mo, int No,
                         int rows, int accumulate, void* st) {

@@ -282,6 +282,7 @@ TEST_HOOK_SIGNATURES = {
     "sdxl_debug_plan_num_ops": [_vp, _P(_i)],
     "sdxl_debug_plan_op": [_vp, _i, _vp, _sz],       # sdxl_plan_op_desc* (PlanOpDesc), its size
     "sdxl_debug_plan_tail": [_vp, _vp, _sz],         # sdxl_plan_tail* (PlanTail), its size
+    "sdxl_debug_plan_loss": [_vp, _vp, _sz],         # sdxl_plan_loss* (PlanLoss), its size
 }
 PLAN_NONE = (1 << 64) - 1      # SDXL_PLAN_NONE: an absent offset of the plan map
 PLAN_KINDS = ("linear", "conv", "groupnorm", "layernorm", "attn", "silu", "concat", "upsample", "embed_in")
@@ -310,6 +311,13 @@ class PlanTail(C.Structure):
     """sdxl_plan_tail: the buffers of the plan that belong to no op"""
     _fields_ = ([(k, _i) for k in ("B", "H", "W", "ctx")] + [(k, PlanTensor) for k in ("x_in", "pred", "ehs")] +
                 [(k, _sz) for k in ("tp32_off", "tp32_bytes", "t_off", "tid_off", "loss_off", "workspace_bytes")])
+
+
+class PlanLoss(C.Structure):
+    """sdxl_plan_loss: the loss's buffers in the plan (named after the Plan fields) and whether the last forward_loss read the staged copies"""
+    _fields_ = ([(k, _sz) for k in ("loss_part_off", "ps_loss_off", "mask_norm_off", "in_lat_off", "in_noise_off", "in_nin_off", "in_sig_off",
+                                    "in_tag_off", "in_sw_off", "in_hc_off", "in_mask_off", "in_cond_off", "part_floats")] +
+                [(k, _i) for k in ("ps_slots", "staged")])
 
 
 def _plain(st):
@@ -344,6 +352,14 @@ def plan_map(handle):
     t = PlanTail()
     check(L.sdxl_debug_plan_tail(handle, C.byref(t), C.sizeof(t)), "sdxl_debug_plan_tail")
     return ops, _plain(t)
+
+
+def plan_loss(handle) -> dict:
+    """the loss's buffers in the handle's current plan (sdxl_debug_plan_loss): byte offsets into the workspace, None where the plan has none;
+    staged: 1 / 0 / -1 as the header says.  Pure host code in the library."""
+    t = PlanLoss()
+    check(load().sdxl_debug_plan_loss(handle, C.byref(t), C.sizeof(t)), "sdxl_debug_plan_loss")
+    return _plain(t)
 
 
 GEMM_DESC_FIELDS = ("form", "taps", "M", "N", "K", "splitk", "group", "cfg", "geglu", "geglu_group", "Hm", "Wm", "Hs", "Ws", "sm", "sd", "up2", "emit_bf16", "delta", "bias_grad")

@@ -25,7 +25,10 @@ delta by kind:
   GroupNorm / LayerNorm: _nonlinear.gn_*_ref / ln_*_ref; the backward is fed the stored statistics, the stored statistics are held to the forward's;
   GEGLU activation: geglu_fwd_ref on the stored u;  attention: attn_fwd_ref / attn_bwd_ref on the stored lse and O, Delta held to its bound in
       either form (its own pass, or the out-projection's dgrad epilogue);
-  SiLU: silu64 / silu_grad64 with their deltas (+ one product, + one addition with an addend);  nearest-2x backward: 4 (5) fp32 additions."""
+  SiLU: silu64 / silu_grad64 with their deltas (+ one product, + one addition with an addend);  nearest-2x backward: 4 (5) fp32 additions;
+  the loss seam (kind "loss", audit_seam): the UNet input bit for bit from the caller's arrays (from their staged copies in graph mode, each copy
+      bit-equal to the caller's array), the loss words, L_b, M_b and every lane of d pred from the prediction as it sits in the workspace, by
+      _loss_elem.reference's bounds."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -33,6 +36,7 @@ from collections import namedtuple
 import torch
 
 import _exact as X
+import _loss_elem as LE
 import _nonlinear as NL
 import _temb as TE
 
@@ -475,8 +479,89 @@ def audit_op(d, img, tail=None, ops=None):
     return AUDITS[d["kind"]](d, img)
 
 
+# ------------------------------------------------------------------------------------------------ the loss seam
+STAGED = (("in_lat_off", "lat"), ("in_noise_off", "noise"), ("in_nin_off", "noise_in"), ("in_sig_off", "sig"), ("in_tag_off", "tag"), ("in_sw_off", "sw"),
+          ("in_hc_off", "hc"), ("in_mask_off", "mask"), ("in_cond_off", "cond"))
+SEAM_ROLES = ("x_in_wired", "x_in", "dpred_wired", "dpred_pad", "dpred_zeros", "dpred", "loss_words", "gate")      # what every plan's seam must show
+SEAM_KIND = "loss"
+
+
+def audit_seam(ops, tail, img):
+    """The seam between the caller's batch and the audited UNet.  tail["loss"]: plan = lib.plan_loss's dict, caller = the arrays and options as the
+    caller handed them to forward_loss (lat, noise, sig and the optional noise_in, tag, sw, hc, mask, cond; method, prediction_type, min_snr, gamma,
+    ztsnr, loss_type, c, mask_norm, per_sample), grad_scale = the backward's.
+    Role x_in: conv_in reads tail.x_in, which is the bit-exact image of the caller's arrays; in graph mode every staged copy has the caller's bits
+    and the image is recomputed from the COPIES.  Role dpred: the last op writes tail.pred and reads its gradient at tail.pred.goff; the loss
+    words, L_b, M_b and d pred (pad lanes included) are recomputed from pred as it sits in the workspace; the gate word out[7] -- the one
+    cond_dgrad, input_dgrad and the residual gradients read at loss_off + 28 -- is the one checked here."""
+    s = tail["loss"]
+    pl, c = s["plan"], dict(s["caller"])
+    d = {"index": len(ops), "kind": SEAM_KIND}
+    B, H, W = tail["B"], tail["H"], tail["W"]
+    flag = lambda role, msg: Result(d["index"], SEAM_KIND, role, 0.0 if not msg else float("inf"), 0, not msg, msg)
+    out = []
+    xin, pred = tail["x_in"], tail["pred"]
+    convs = [o for o in ops if o["kind"] == "conv"]
+    first, last = convs[0], ops[-1]
+    same = lambda t, u: (t["off"], t["rows"], t["cols"], t["ld"]) == (u["off"], u["rows"], u["cols"], u["ld"])
+    out.append(flag("x_in_wired", "" if same(first["t"][0], xin) else f"the first convolution (op {first['index']}) reads {first['t'][0]}, not tail.x_in {xin}"))
+    wired = same(last["t"][1], pred) and pred["goff"] is not None and last["dy_off"] == pred["goff"]
+    out.append(flag("dpred_wired", "" if wired else f"the last op (op {last['index']}) writes {last['t'][1]} and reads dy at {last['dy_off']}; tail.pred is {pred}"))
+    # ---- the staged copies
+    if pl["staged"] == 1:
+        rs = []
+        for key, name in STAGED:
+            if c.get(name) is None:
+                continue
+            want = c[name].float().contiguous().flatten()
+            if pl[key] is None:
+                rs.append(flag("staged", f"the plan has no staging buffer {key} for the caller's {name}"))
+                continue
+            got = f32_at(img, pl[key], want.numel())
+            r = r_bits(d, "staged", got, want)
+            rs.append(r._replace(msg=f"{key}: {r.msg}" if r.msg else ""))
+            c[name] = got.clone().view(c[name].shape)          # ... and the audit recomputes from the copy
+        out.append(_merge(rs))
+    elif pl["staged"] != 0:
+        out.append(flag("staged", "no forward_loss has run on this plan"))
+    opts = dict(prediction_type=c.get("prediction_type", 1), min_snr=c.get("min_snr", True), gamma=c.get("gamma", 5.0), ztsnr=c.get("ztsnr", True))
+    zero = torch.zeros(B, 4, H, W)
+    cs0 = LE.case(c["method"], c["lat"], c["noise"], c["sig"], zero, noise_in=c.get("noise_in"), cond=c.get("cond"), **opts)
+    want = LE.prepare_rows(cs0)
+    got = data(img, xin)
+    out.append(r_bits(d, "x_in", got, want) if got.shape == want.shape else flag("x_in", f"tail.x_in is {tuple(got.shape)}, the caller's arrays make {tuple(want.shape)}"))
+    # ---- the loss words and d pred from pred as it sits in the workspace
+    rows = data(img, pred)
+    pn = rows[:, :4].float().view(B, H * W, 4).permute(0, 2, 1).reshape(B, 4, H, W)
+    cs = LE.case(c["method"], c["lat"], c["noise"], c["sig"], pn, loss_type=c.get("loss_type", "l2"), c=c.get("c", 0.0), hc=c.get("hc"), sw=c.get("sw"),
+                 tag=c.get("tag"), mask=c.get("mask"), mask_norm=c.get("mask_norm", "mean"), per_sample=c.get("per_sample", False),
+                 grad_scale=s.get("grad_scale", 1.0), **opts)
+    r = LE.reference(cs)
+    dp = grad(img, pred["goff"], pred) if pred["goff"] is not None else None
+    if dp is None:
+        return out + [flag("dpred", "tail.pred has no gradient")]
+    out.append(r_bits(d, "dpred_pad", dp[:, 4:], torch.zeros_like(dp[:, 4:])))
+    z8 = LE.rows8(r.zero.to(torch.uint8))[:, :4].bool()
+    out.append(r_bits(d, "dpred_zeros", dp[:, :4][z8], torch.zeros(int(z8.sum()), dtype=BF)))
+    out.append(r_interval(d, "dpred", dp[:, :4], LE.rows8(r.dpred)[:, :4], LE.rows8(r.ddpred)[:, :4]))
+    o8 = f32_at(img, tail["loss_off"], 8)
+    if r.guard:
+        out.append(r_bits(d, "loss_words", o8[0:1], torch.tensor([LE.LOSS_CAP])))
+        out.append(r_bits(d, "gate", o8[7:8], torch.zeros(1)))
+    else:
+        out.append(r_f32(d, "loss_words", o8[0:7], r.out[0:7], r.dout[0:7]))
+        out.append(r_f32(d, "gate", o8[7:8], r.out[7:8], r.dout[7:8]))
+    if cs.per_sample:
+        out.append(r_f32(d, "L_b", f32_at(img, pl["ps_loss_off"], B), r.Lb, r.dLb) if pl["ps_loss_off"] is not None else flag("L_b", "the plan has no per-sample buffer"))
+    if r.mm:
+        out.append(r_f32(d, "mnorm", f32_at(img, pl["mask_norm_off"], B), r.M, r.dM) if pl["mask_norm_off"] is not None else flag("mnorm", "the plan has no normaliser"))
+    return out
+
+
 def audit(ops, tail, img):
     out = chain_results(ops)
+    if "loss" in tail:      # (a tail without it: coverage reports the seam as missing)
+        out += audit_seam(ops, tail, img)
     ups = {d["t"][0]["off"]: d for d in ops if d["kind"] == "upsample" and d["up2"]}
     for d in ops:
         rs = audit_op(d, img, tail, ops)
@@ -629,6 +714,10 @@ def coverage(ops, results, param_ranges, kinds=None):
                 taken.append((d["index"], d["kind"], role))
             else:
                 problems.append(f"op {d['index']} ({d['kind']}): role {role} is neither audited nor a listed omission of a lost buffer")
+    seam = {r.role for r in results if r.kind == SEAM_KIND}
+    for role in SEAM_ROLES:      # the loss seam is part of every plan: without its roles the step is not covered
+        if role not in seam:
+            problems.append(f"the loss seam: role {role} is not audited")
     fwd_kinds, bwd_kinds = audited_kinds(ops, results)
     for k in (kinds if kinds is not None else {d["kind"] for d in ops}):
         if k not in fwd_kinds:

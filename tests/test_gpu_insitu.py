@@ -68,22 +68,31 @@ def grouped():
     net.close()
 
 
-def forward(net, cfg, B, H, W, method, seed):
+def forward(net, cfg, B, H, W, method, seed, **loss_kw):
+    """one forward_loss; x["loss"] keeps the caller's side of the loss seam (the arrays and options as handed over) for the audit.
+    loss_kw: forward_loss's optional loss arguments (sample_weights, tag_weights, huber_c, loss_type, per_sample_loss, loss_mask, mask_norm, noise_in,
+    input_cond)"""
     x = make_inputs(cfg, B, H, W, seed=seed)
     if method == "ddpm":
         ts = torch.tensor([700, 420, 133, 866][:B]) if B <= 4 else (torch.arange(B) * 61 + 17) % 1000
-        net.forward_loss("ddpm", x["lat"], x["noise"], R.karras_sigmas()[ts], ts.float(), x["ehs"], x["pooled"], x["tid"])
+        sig, tt = R.karras_sigmas()[ts], ts.float()
     else:
-        t = R.sample_logit_normal_from_z(x["z"])
-        assert B == 1 or len({float(v) for v in t}) == B, "the samples must differ in t"
-        net.forward_loss("flow_matching", x["lat"], x["noise"], t, t, x["ehs"], x["pooled"], x["tid"])
+        sig = tt = R.sample_logit_normal_from_z(x["z"])
+        assert B == 1 or len({float(v) for v in sig}) == B, "the samples must differ in t"
+    net.forward_loss(method, x["lat"], x["noise"], sig, tt, x["ehs"], x["pooled"], x["tid"], **loss_kw)
+    hc = loss_kw.get("huber_c")
+    x["loss"] = dict(method=method, lat=x["lat"], noise=x["noise"], sig=sig, noise_in=loss_kw.get("noise_in"), tag=loss_kw.get("tag_weights"),
+                     sw=loss_kw.get("sample_weights"), hc=hc if torch.is_tensor(hc) else None, c=hc if isinstance(hc, float) else 0.0,
+                     mask=loss_kw.get("loss_mask"), cond=loss_kw.get("input_cond"), loss_type=loss_kw.get("loss_type", "l2"),
+                     mask_norm=loss_kw.get("mask_norm", "mean"), per_sample=loss_kw.get("per_sample_loss", False))
     return x
 
 
-def snapshot(net, x, g0=None, accumulate=False):
+def snapshot(net, x, g0=None, accumulate=False, grad_scale=1.0):
     torch.cuda.synchronize()
     ops, tail = lib.plan_map(net.h)
     tail["pooled_in"] = x["pooled"]      # the caller's array: the audit holds aug_in's first half to its bf16 bits
+    tail["loss"] = dict(plan=lib.plan_loss(net.h), caller=x["loss"], grad_scale=grad_scale)      # the loss seam: _insitu.audit_seam
     img = IS.Image(net.workspace.cpu()[:tail["workspace_bytes"]], net.weights.cpu(), net.grads.cpu(), g0, accumulate)
     return ops, tail, img
 
@@ -194,8 +203,13 @@ def test_plan_map_refuses_bad_arguments(tiny):
     sz, tsz = C.sizeof(lib.PlanOpDesc), C.sizeof(lib.PlanTail)
     for i in (-1, n.value):
         assert L.sdxl_debug_plan_op(net.h, i, C.byref(d), sz) == 1 and b"out of range" in L.sdxl_last_error() and d.kind == -5
-    for rc in (L.sdxl_debug_plan_num_ops(net.h, None), L.sdxl_debug_plan_op(net.h, 0, None, sz), L.sdxl_debug_plan_tail(net.h, None, tsz)):
+    for rc in (L.sdxl_debug_plan_num_ops(net.h, None), L.sdxl_debug_plan_op(net.h, 0, None, sz), L.sdxl_debug_plan_tail(net.h, None, tsz),
+               L.sdxl_debug_plan_loss(net.h, None, C.sizeof(lib.PlanLoss))):
         assert rc == 1 and b"null output" in L.sdxl_last_error()
+    assert L.sdxl_debug_plan_loss(net.h, C.byref(lib.PlanLoss()), C.sizeof(lib.PlanLoss) + 8) == 1 and b"bytes" in L.sdxl_last_error()
+    pl = lib.plan_loss(net.h)
+    assert pl["loss_part_off"] is not None and pl["ps_loss_off"] is not None and pl["in_lat_off"] is not None and pl["in_cond_off"] is None
+    assert pl["ps_slots"] == 2 and pl["part_floats"] == (6 + 2 * 2) * 2
     # a struct of another size is refused before it is written to
     assert L.sdxl_debug_plan_op(net.h, 0, C.byref(d), sz - 8) == 1 and b"bytes" in L.sdxl_last_error() and d.kind == -5
     assert L.sdxl_debug_plan_tail(net.h, C.byref(lib.PlanTail()), tsz + 8) == 1 and b"bytes" in L.sdxl_last_error()
@@ -224,6 +238,95 @@ def test_second_micro_step_accumulates(tiny):
         print(f"[insitu] second micro-step {kind}: worst err / allowed {worst:.4g} over {n} parameter gradients, {elems} elements")
     bad = IS.failures(results)
     assert not bad, f"{len(bad)} accumulated gradients outside their bounds:\n" + "\n".join(bad[:20])
+
+
+# ------------------------------------------------------------------------------------------------ the loss seam in place
+def seam_kw(B, H, W, which, seed=0):
+    g = torch.Generator().manual_seed(900 + seed)
+    if which == "weights":      # sample_weights with a zero, tag_weights, per-sample losses, smooth_l1 with per-sample c
+        sw = torch.rand(B, generator=g) + 0.5
+        sw[1] = 0.0
+        return dict(sample_weights=sw, tag_weights=torch.rand(B, generator=g) + 0.5, per_sample_loss=True, loss_type="smooth_l1",
+                    huber_c=torch.rand(B, generator=g) * 0.5 + 0.1)
+    if which == "mask":         # a fractional mask under masked_mean and an input noise of its own
+        import _loss_elem as LE
+        return dict(loss_mask=LE.fractional_mask(B, H, W, seed=901 + seed, empty=None), mask_norm="masked_mean", per_sample_loss=True,
+                    noise_in=torch.randn(B, 4, H, W, generator=g))
+    raise KeyError(which)
+
+
+def seam_step(net, cfg, B, H, W, method, seed, first_micro=True, g0=None, **kw):
+    x = forward(net, cfg, B, H, W, method, seed, **kw)
+    if first_micro:
+        net.zero_grads()
+    net.backward(grad_scale=0.5, first_micro=first_micro)
+    return snapshot(net, x, g0=g0, accumulate=not first_micro, grad_scale=0.5)
+
+
+def seam_report(tag, ops, tail, img, staged, net):
+    results = IS.audit(ops, tail, img)
+    seam = [r for r in results if r.kind == IS.SEAM_KIND]
+    print(f"[insitu-seam] {tag}: staged {tail['loss']['plan']['staged']}; " + ", ".join(f"{r.role} {r.ratio:.3g}" for r in seam))
+    assert tail["loss"]["plan"]["staged"] == staged and {r.role for r in seam} >= set(IS.SEAM_ROLES) | ({"staged"} if staged else set())
+    report(tag, ops, results, net)
+    return results
+
+
+def test_loss_seam_with_weights_and_per_sample_huber(tiny):
+    cfg, net = tiny
+    B, H, W = 3, 12, 20
+    ops, tail, img = seam_step(net, cfg, B, H, W, "flow_matching", 21, **seam_kw(B, H, W, "weights"))
+    results = seam_report(f"seam {B}x{H}x{W} flow weights smooth_l1", ops, tail, img, 0, net)
+    assert any(r.role == "L_b" for r in results)
+
+
+def test_loss_seam_with_a_masked_mean_and_an_input_noise(tiny):
+    cfg, net = tiny
+    B, H, W = 2, 16, 16
+    ops, tail, img = seam_step(net, cfg, B, H, W, "ddpm", 22, **seam_kw(B, H, W, "mask"))
+    results = seam_report(f"seam {B}x{H}x{W} ddpm masked_mean noise_in", ops, tail, img, 0, net)
+    assert any(r.role == "mnorm" for r in results) and any(r.role == "L_b" for r in results)
+
+
+def test_loss_seam_with_input_cond_on_the_nine_channel_unet():
+    """the tiny UNet of test_gpu_input_cond.py with in_channels = 9 (Cs = 16).  The library takes latent sizes that are multiples of 4 only, so the
+    13 x 10 of the op tests cannot run through a UNet: 12 x 12 is the nearest size whose blocks straddle the samples (HW = 144)"""
+    cfg = dataclasses.replace(TINY, in_channels=9)
+    net = NU.NativeUNet(NU.make_config(in_channels=9, block_out_channels=cfg.block_out_channels, transformer_layers=cfg.transformer_layers_per_block,
+                                       layers_per_block=cfg.layers_per_block, cross_attention_dim=cfg.cross_attention_dim,
+                                       addition_time_embed_dim=cfg.addition_time_embed_dim, pooled_dim=cfg.pooled_dim))
+    try:
+        net.load_state_dict(U.synth_weights(cfg, seed=0))
+        B, H, W = 2, 12, 12
+        cond = torch.randn(B, 5, H, W, generator=torch.Generator().manual_seed(23))
+        ops, tail, img = seam_step(net, cfg, B, H, W, "ddpm", 23, input_cond=cond)
+        assert tail["x_in"]["cols"] == 16
+        seam_report(f"seam {B}x{H}x{W} ddpm input_cond 9 channels", ops, tail, img, 0, net)
+    finally:
+        net.close()
+
+
+def test_loss_seam_in_graph_mode_reads_the_staged_copies(tiny):
+    """the weights case again under hipGraph replay: the third call with one key is a replay; every call gets other arrays in other allocations,
+    and the audit of the third holds each staged copy to the caller's array and recomputes from the copies"""
+    cfg, net = tiny
+    B, H, W = 3, 12, 20
+    net.set_graph_mode(True)
+    try:
+        for i in range(3):
+            ops, tail, img = seam_step(net, cfg, B, H, W, "flow_matching", 24 + i, **seam_kw(B, H, W, "weights", seed=i))
+    finally:
+        net.set_graph_mode(False)
+    seam_report(f"seam {B}x{H}x{W} flow weights smooth_l1, graph replay", ops, tail, img, 1, net)
+
+
+def test_loss_seam_on_an_accumulating_micro_step(tiny):
+    cfg, net = tiny
+    B, H, W = 3, 12, 20
+    seam_step(net, cfg, B, H, W, "flow_matching", 27, **seam_kw(B, H, W, "weights", seed=3))
+    g0 = net.grads.cpu().clone()
+    ops, tail, img = seam_step(net, cfg, B, H, W, "flow_matching", 28, first_micro=False, g0=g0, **seam_kw(B, H, W, "weights", seed=4))
+    seam_report(f"seam {B}x{H}x{W} flow weights smooth_l1, first_micro = False", ops, tail, img, 0, net)
 
 
 DIAG_CASES = [

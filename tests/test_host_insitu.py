@@ -1,4 +1,4 @@
-"""The in-situ audit (tests/_insitu.py) on the CPU: a faithful image passes every check, and each of ten seeded single defects of the kind that
+"""The in-situ audit (tests/_insitu.py) on the CPU: a faithful image passes every check, and each of fourteen seeded single defects of the kind that
 tests/test_gpu_model.py's aggregate bars let through is caught by a named (op, role).  No GPU.
 
 The image: one resnet (GroupNorm + SiLU, 3x3 convolution with the time-embedding row vector, GroupNorm + SiLU, 3x3 convolution with the resnet's
@@ -20,6 +20,7 @@ import sdxl_amd  # noqa: F401
 from sdxl_amd import lib
 
 import _insitu as IS
+import _loss_elem as LE
 import _nonlinear as NL
 
 BF = torch.bfloat16
@@ -110,6 +111,25 @@ def strip(ops):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the loss seam's caller
+SEAM_GRAD_SCALE = 64.0      # d pred of order 1 at numel = 128, like the gradient the image used to be seeded with
+
+
+def seam_caller():
+    """the batch as a caller hands it to forward_loss: ddpm, an input noise of its own, a fractional mask under masked_mean, sample and tag weights,
+    per-sample Huber c, per-sample losses"""
+    g = torch.Generator().manual_seed(31)
+    lat, noise = torch.randn(B, 4, HH, WW, generator=g), torch.randn(B, 4, HH, WW, generator=g)
+    return dict(method="ddpm", lat=lat, noise=noise, noise_in=noise + 0.1 * torch.randn(B, 4, HH, WW, generator=g), sig=torch.tensor([0.8, 2.5]),
+                tag=torch.tensor([0.5, 1.25]), sw=torch.tensor([1.5, 0.75]), hc=torch.tensor([0.3, 0.6]), mask=LE.fractional_mask(B, HH, WW, seed=32, empty=None),
+                loss_type="huber", mask_norm="masked_mean", per_sample=True)
+
+
+def seam_case(c, pred):
+    return LE.case(c["method"], c["lat"], c["noise"], c["sig"], pred, noise_in=c.get("noise_in"), loss_type=c["loss_type"], hc=c["hc"], sw=c["sw"], tag=c["tag"],
+                   mask=c["mask"], mask_norm=c["mask_norm"], per_sample=True, grad_scale=SEAM_GRAD_SCALE)
+
+
 # ------------------------------------------------------------------------------------------------ the image
 class Mem:
     def __init__(self, nbytes, nparam):
@@ -142,12 +162,15 @@ def build(defect=None):
     D = lambda name: defect == name
     # ---- forward plan
     emb = dict(p.act(B, TEMB), need_grad=False)
+    x_in = dict(p.act(M, 8), need_grad=False)                     # the loss preparation's image: 4 channels + 4 zero lanes
     x0 = p.act(M, CH)
     ehs = dict(p.act(B * CTX, CROSS, KV_PAD), need_grad=False)
     tp_all = p.act(B, CH + 64)
     tp32_off = p.alloc(4 * B * (CH + 64))
     o_tp = p.op("linear", t=[emb, tp_all, None, None, None], K=TEMB, N=CH + 64, dy32_off=tp32_off)
     rowvec = p.view(tp_all, 64, CH)
+    feat = p.act(M, CH)                                           # conv_in: the plan's first convolution reads x_in (nothing here reads its output)
+    o_cin = p.op("conv", t=[x_in, feat, None, None, None], B=B, H=HH, W=WW, Cin=8, Cout=CH)
 
     def gn(x, silu):
         y = p.act(M, CH)
@@ -190,6 +213,11 @@ def build(defect=None):
     _, o_ff1 = lin(l3, 8 * CH, y=u, gact=gact)
     yout, o_ff2 = lin(gact, CH, resid=x2, gu=u)
     gact["need_grad"] = False                                     # (the activation gets no gradient buffer: the dgrad emits dU)
+    pred = p.act(M, 8)                                            # conv_out: the plan's last op writes the prediction, 4 channels + 4 zero lanes
+    o_cout = p.op("conv", t=[yout, pred, None, None, None], B=B, H=HH, W=WW, Cin=CH, Cout=8)
+    loss_off, ps_loss_off, mask_norm_off = p.alloc(32), p.alloc(4 * B), p.alloc(4 * B)
+    caller = seam_caller()
+    staged = {key: p.alloc(4 * caller[name].numel()) for key, name in IS.STAGED if caller.get(name) is not None}
     # parameters
     for d in p.ops:
         if d["kind"] == "linear":
@@ -197,28 +225,32 @@ def build(defect=None):
             if d is not o_qkv and d is not o_q and d is not o_kv:
                 d["b_off"], d["b_numel"] = p.param(d["N"])
         elif d["kind"] == "conv":
-            d["w_off"], d["w_numel"] = p.param(CH * 9 * CH)
-            d["b_off"], d["b_numel"] = p.param(CH)
+            d["w_off"], d["w_numel"] = p.param(d["Cout"] * 9 * d["Cin"])
+            d["b_off"], d["b_numel"] = p.param(d["Cout"])
         elif d["kind"] in ("groupnorm", "layernorm"):
             d["w_off"], d["w_numel"] = p.param(CH)
             d["b_off"], d["b_numel"] = p.param(CH)
-    # ---- reverse plan: the loss writes d(yout)
-    p.grad_dst(yout)
+    # ---- reverse plan: the loss writes d(pred)
+    p.grad_dst(pred)
     p.plan_bwd()
     mem = Mem(p.cursor + 256, p.pcursor)
     ranges = {}
     for d in p.ops:      # weights; the small vectors of the arena start at zero (sdxl_zero_grads)
         if d["w_off"] is not None:
             n, norm = d["w_numel"], d["kind"] in ("groupnorm", "layernorm")
-            fan = d["K"] if d["kind"] == "linear" else 9 * CH
+            fan = d["K"] if d["kind"] == "linear" else 9 * d["Cin"]
             mem.w[d["w_off"]: d["w_off"] + n] = (1 + 0.1 * rnd(n, seed=100 + d["index"]).float()).to(BF) if norm else rnd(n, seed=100 + d["index"], scale=fan ** -0.5)
-            ranges[f"op{d['index']}.weight"] = (d["w_off"], n)
+            if d["dy_off"] is not None:      # (conv_in's output has no reader here: no backward, no gradient to account for)
+                ranges[f"op{d['index']}.weight"] = (d["w_off"], n)
             if norm:
                 mem.g0[d["w_off"]: d["w_off"] + n] = 0
         if d["b_off"] is not None:
             mem.w[d["b_off"]: d["b_off"] + d["b_numel"]] = rnd(d["b_numel"], seed=200 + d["index"], scale=0.5)
             mem.g0[d["b_off"]: d["b_off"] + d["b_numel"]] = 0
-            ranges[f"op{d['index']}.bias"] = (d["b_off"], d["b_numel"])
+            if d["dy_off"] is not None:
+                ranges[f"op{d['index']}.bias"] = (d["b_off"], d["b_numel"])
+    mem.w[o_cout["w_off"]: o_cout["w_off"] + o_cout["w_numel"]].view(8, 9 * CH)[4:] = 0      # the pad channels of conv_out
+    mem.w[o_cout["b_off"] + 4: o_cout["b_off"] + 8] = 0
     mem.g = mem.g0.clone()
     W = lambda d: mem.w[d["w_off"]: d["w_off"] + d["w_numel"]].float()
     Bs = lambda d: mem.w[d["b_off"]: d["b_off"] + d["b_numel"]].float()
@@ -229,6 +261,17 @@ def build(defect=None):
     x0v[:, :, 0, :] = 1.0 + 2.0 ** -7 * torch.randint(0, 2, (B, HW, CH // G), generator=torch.Generator().manual_seed(3)).float()      # a low-variance group: two neighbouring bf16 values, var ~ 1.5e-5
     put(mem, x0["off"], x0, x0v.reshape(M, CH))
     put(mem, ehs["off"], ehs, rnd(B * CTX, CROSS, seed=4))
+    # the loss preparation, from the staged copies (graph mode): each copy holds the caller's array
+    copies = dict(caller)
+    for key, name in IS.STAGED:
+        if key in staged:
+            v = caller[name].float().clone()
+            if D("stale staged copy") and name == "noise_in":
+                v = v.roll(1, 0)                                   # the copy of the step before: the engine goes on from it, consistently
+            mem.f32(staged[key], v.numel()).copy_(v.flatten())
+            copies[name] = v
+    prep = dict(copies, noise_in=None) if D("x_in from noise") else copies
+    mem.bf(x_in["off"], M, 8, 8).copy_(LE.prepare_rows(seam_case(prep, torch.zeros(B, 4, HH, WW))))
 
     # ---- forward
     def f_lin(d):
@@ -261,17 +304,17 @@ def build(defect=None):
         put(mem, y["off"], y, F.layer_norm(xs, (CH,), W(d).double(), Bs(d).double(), d["eps"]).float())
 
     def nchw(v):
-        return v.view(B, HH, WW, CH).permute(0, 3, 1, 2)
+        return v.view(B, HH, WW, -1).permute(0, 3, 1, 2)
 
     def f_conv(d):
         x, y, resid, rv, _ = d["t"]
-        wn = W(d).view(CH, 3, 3, CH).permute(0, 3, 1, 2)
+        wn = W(d).view(d["Cout"], 3, 3, d["Cin"]).permute(0, 3, 1, 2)
         acc = F.conv2d(nchw(get(mem, x["off"], x).float()), wn, Bs(d), padding=1)
         if rv is not None:
             acc = acc + get(mem, rv["off"], rv).float()[:, :, None, None]
         if resid is not None:
             acc = acc + nchw(get(mem, resid["off"], resid).float())
-        put(mem, y["off"], y, acc.permute(0, 2, 3, 1).reshape(M, CH))
+        put(mem, y["off"], y, acc.permute(0, 2, 3, 1).reshape(M, d["Cout"]))
 
     def qkv_of(d, shift=0):
         qt, _, _, kt, _ = d["t"]
@@ -302,8 +345,17 @@ def build(defect=None):
         if d is o_kv:      # the rows behind the prompt's hold whatever was there before (finite: a shifted slice reads into them)
             mem.bf(kv_all["off"] + B * CTX * kv_all["ld"] * 2, KV_PAD, 4 * CH, kv_all["ld"]).copy_(rnd(KV_PAD, 4 * CH, seed=7))
 
-    # ---- backward
-    put(mem, yout["goff"], yout, rnd(M, CH, seed=5))
+    # ---- the loss on pred as it sits in the workspace, then the backward from its d pred
+    pn = lambda rows: rows[:, :4].float().view(B, HW, 4).permute(0, 2, 1).reshape(B, 4, HH, WW)
+    em = LE.emulate(seam_case(copies, pn(get(mem, pred["off"], pred))))
+    if D("stale d pred"):      # the gradient of the micro-step before: another prediction
+        em["dpred"] = LE.emulate(seam_case(copies, pn(get(mem, pred["off"], pred).roll(1, 0))))["dpred"]
+    if D("wrong gate word"):
+        em["out"][7] = 1.0
+    mem.f32(loss_off, 8).copy_(em["out"])
+    mem.f32(ps_loss_off, B).copy_(em["ps"])
+    mem.f32(mask_norm_off, B).copy_(em["mnorm"])
+    mem.bf(pred["goff"], M, 8, 8).copy_(em["dpred"])
     mem.f32(tp32_off, B * (CH + 64)).zero_()                              # (zeroed at the start of a backward)
     first = lambda d: mem.g0[d["w_off"]: d["w_off"] + d["w_numel"]].view(d["N"], d["K"]) if D("accumulate") and d is o_q else 0.0
 
@@ -367,16 +419,18 @@ def build(defect=None):
 
     def b_conv(d):
         x, y, resid, rv, _ = d["t"]
+        if d["dy_off"] is None:
+            return
         dy = get(mem, d["dy_off"], y)
         dres(d, dy)
         xs = nchw(get(mem, x["off"], x).float()).clone().requires_grad_(True)
-        wn = W(d).view(CH, 3, 3, CH).permute(0, 3, 1, 2).clone().requires_grad_(True)
+        wn = W(d).view(d["Cout"], 3, 3, d["Cin"]).permute(0, 3, 1, 2).clone().requires_grad_(True)
         F.conv2d(xs, wn, None, padding=1).backward(nchw(dy.float()))
-        mem.g[d["w_off"]: d["w_off"] + CH * 9 * CH] = wn.grad.permute(0, 2, 3, 1).reshape(-1)
-        mem.g[d["b_off"]: d["b_off"] + CH] += dy.float().sum(0)
+        mem.g[d["w_off"]: d["w_off"] + d["w_numel"]] = wn.grad.permute(0, 2, 3, 1).reshape(-1)
+        mem.g[d["b_off"]: d["b_off"] + d["Cout"]] += dy.float().sum(0)
         if rv is not None:
             mem.f32(d["rv32_off"], (B - 1) * rv["ld"] + CH).as_strided((B, CH), (rv["ld"], 1)).copy_(dy.float().view(B, HW, CH).sum(1))
-        dx = xs.grad.permute(0, 2, 3, 1).reshape(M, CH)
+        dx = xs.grad.permute(0, 2, 3, 1).reshape(M, d["Cin"])
         if d["dx_addend"] is not None:
             dx = dx + get(mem, d["dx_addend"], x).float()
         put(mem, d["dx_out"], x, dx)
@@ -414,9 +468,13 @@ def build(defect=None):
         e = ops[o_out1["index"]]
         e["resid_alias"], e["dres_out"], e["dres_addend"] = 1, None, None
     tail = dict(B=B, H=HH, W=WW, ctx=CTX, t_off=None, tid_off=None, tp32_off=tp32_off, tp32_bytes=4 * B * (CH + 64), workspace_bytes=p.cursor)
+    tdesc = lambda t: {k: t[k] for k in ("off", "goff", "rows", "cols", "ld", "pad_rows", "col0")}
+    plan_loss = dict(dict.fromkeys([k for k, _ in IS.STAGED]), loss_part_off=None, ps_loss_off=ps_loss_off, mask_norm_off=mask_norm_off, part_floats=0,
+                     ps_slots=LE.ps_slots(B, HW), staged=1, **staged)
+    tail.update(x_in=tdesc(x_in), pred=tdesc(pred), loss_off=loss_off, loss=dict(plan=plan_loss, caller=caller, grad_scale=SEAM_GRAD_SCALE))
     names = dict(tp=o_tp, sc=o_sc, gn1=o_gn1, c1=o_c1, gn2=o_gn2, c2=o_c2, ln1=o_ln1, qkv=o_qkv, sa=o_sa, out1=o_out1, ln2=o_ln2, q=o_q, kv=o_kv, ca=o_ca,
-                 out2=o_out2, ln3=o_ln3, ff1=o_ff1, ff2=o_ff2)
-    return ops, tail, mem.img(), ranges, {k: v["index"] for k, v in names.items()}
+                 out2=o_out2, ln3=o_ln3, ff1=o_ff1, ff2=o_ff2, cin=o_cin, cout=o_cout)
+    return ops, tail, mem.img(), ranges, dict({k: v["index"] for k, v in names.items()}, seam=len(ops))
 
 
 # defect -> (op, the roles that must catch it)
@@ -431,6 +489,10 @@ DEFECTS = {
     "double rounding": ("ln1", None),              # 8. a dgrad that rounded before it added its addend (any linear with an addend: found below)
     "delta head": ("sa", ["delta"]),               # 9. attention's Delta taken from another head
     "accumulate": ("q", ["dw"]),                   # 10. += onto a non-zero arena on the first micro-step
+    "stale staged copy": ("seam", ["staged"]),     # 11. graph mode replayed on the copy of the step before
+    "x_in from noise": ("seam", ["x_in"]),         # 12. the UNet input built from `noise` where `noise_in` was given
+    "stale d pred": ("seam", ["dpred"]),           # 13. d pred left from the previous micro-step
+    "wrong gate word": ("seam", ["gate"]),         # 14. out[7] is not the tag mean the gradients were scaled by
 }
 
 
@@ -488,6 +550,12 @@ def test_coverage_sees_a_deleted_op(faithful):
     # ... and a kind with no audited backward
     problems, _ = IS.coverage(ops, [r for r in IS.audit(ops, tail, img) if not (r.kind == "conv" and r.role != "y")], ranges)
     assert "kind conv: no audited backward output" in problems
+    # ... and a step whose loss seam was not audited: a problem, not an omission
+    problems, taken = IS.coverage(ops, [r for r in IS.audit(ops, tail, img) if r.kind != IS.SEAM_KIND], ranges)
+    assert problems == [f"the loss seam: role {r} is not audited" for r in IS.SEAM_ROLES] and not taken, problems
+    assert {"x_in", "dpred"} <= set(IS.SEAM_ROLES)
+    problems, _ = IS.coverage(ops, [r for r in IS.audit(ops, tail, img) if (r.kind, r.role) != (IS.SEAM_KIND, "dpred")], ranges)
+    assert problems == ["the loss seam: role dpred is not audited"], problems
 
 
 def test_omissions_are_only_of_lost_buffers(faithful):
@@ -497,16 +565,24 @@ def test_omissions_are_only_of_lost_buffers(faithful):
 
 
 def test_hooks_are_declared_and_refuse_bad_arguments():
-    for name in ("sdxl_debug_plan_num_ops", "sdxl_debug_plan_op", "sdxl_debug_plan_tail"):
+    for name in ("sdxl_debug_plan_num_ops", "sdxl_debug_plan_op", "sdxl_debug_plan_tail", "sdxl_debug_plan_loss"):
         assert name in lib.TEST_HOOK_SIGNATURES
     L = lib.load()
-    n, d, t = C.c_int(-7), lib.PlanOpDesc(), lib.PlanTail()
+    n, d, t, pl = C.c_int(-7), lib.PlanOpDesc(), lib.PlanTail(), lib.PlanLoss()
     for rc in (L.sdxl_debug_plan_num_ops(None, C.byref(n)), L.sdxl_debug_plan_op(None, 0, C.byref(d), C.sizeof(d)),
-               L.sdxl_debug_plan_tail(None, C.byref(t), C.sizeof(t))):
+               L.sdxl_debug_plan_tail(None, C.byref(t), C.sizeof(t)), L.sdxl_debug_plan_loss(None, C.byref(pl), C.sizeof(pl))):
         assert rc == 1 and b"null handle" in L.sdxl_last_error()      # (so the sizes of the Python mirrors ARE the library's: a wrong one is refused first)
     assert n.value == -7
     for rc in (L.sdxl_debug_plan_op(None, 0, C.byref(d), C.sizeof(d) - 4), L.sdxl_debug_plan_op(None, 0, C.byref(d), C.sizeof(d) + 8),
-               L.sdxl_debug_plan_tail(None, C.byref(t), C.sizeof(t) - 8), L.sdxl_debug_plan_tail(None, C.byref(t), 0)):
+               L.sdxl_debug_plan_tail(None, C.byref(t), C.sizeof(t) - 8), L.sdxl_debug_plan_tail(None, C.byref(t), 0),
+               L.sdxl_debug_plan_loss(None, C.byref(pl), C.sizeof(pl) - 8), L.sdxl_debug_plan_loss(None, C.byref(pl), C.sizeof(pl) + 8)):
         assert rc == 1 and b"bytes, the library's" in L.sdxl_last_error()
     assert len(lib.TEST_HOOK_SIGNATURES["sdxl_debug_plan_op"]) == 4 and len(lib.TEST_HOOK_SIGNATURES["sdxl_debug_plan_tail"]) == 3
+    assert len(lib.TEST_HOOK_SIGNATURES["sdxl_debug_plan_loss"]) == 3 and len(lib.TEST_HOOK_SIGNATURES) == 29
+    # the staging buffers are named after the Plan fields, the binding's struct after the header's
+    hdr = (lib.HERE.parent / "include" / "sdxlstep_diag.h").read_text().split("typedef struct sdxl_plan_loss {", 1)[1].split("}", 1)[0]
+    names = [f[0] for f in lib.PlanLoss._fields_]
+    assert names == [w.strip(" ;") for w in hdr.replace("size_t", ",").replace("int ", ",").replace(";", ",").replace("\n", ",").split(",") if w.strip(" ;")]
+    eng = (lib.HERE / "csrc" / "engine.h").read_text()
+    assert all(f"{k} = NONE" in eng for k, _ in IS.STAGED) and {k for k, _ in IS.STAGED} <= set(names)
     assert len(lib.PLAN_KINDS) == 9 and lib.PLAN_ROLES == 5 and lib.PLAN_NONE == 2 ** 64 - 1

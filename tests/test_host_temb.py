@@ -20,7 +20,7 @@ import _temb as T
 BF = torch.bfloat16
 ROOT = Path(__file__).resolve().parent.parent
 NEW_HOOKS = {"sdxl_op_gemm_rowvec": 15, "sdxl_op_conv3x3_fwd_rowvec": 12, "sdxl_op_colsum": 8, "sdxl_op_sincos": 6}
-N_TEST_HOOKS = 28      # (+ the three plan-map hooks: tests/test_host_insitu.py)
+N_TEST_HOOKS = 29      # (with the three plan-map hooks and the loss plan hook: tests/test_host_insitu.py)
 
 
 # ------------------------------------------------------------------------------------------------ the hooks
