@@ -389,6 +389,36 @@ typedef struct {
   float* scratch;            /* device fp32, 16-byte aligned (export only) */
   size_t scratch_floats;
 } sdxl_lokr_op;
+/* ---- DoRA (a trained magnitude per output row on the merged LoRA weight) by merge and project: dtype SDXL_DTYPE_DORA of the same two calls,
+ * the host struct sdxl_dora_op ----
+ * For a targeted weight [out][in] (the targets and maps of SDXL_DTYPE_LORA_LAYOUTS) with A [rank][in], B [out][rank], s = op.scale and a
+ * trained vector mu [out]:
+ *   acc = sum_k B[o][k] A[k][i]      LoRA's chain: every product and sum rounded on its own in fp32, no FMA
+ *   t = s acc;  v = (float)W0[o][i] + t
+ *   n_o  = sqrt(sum_i v^2)           the fp32 row norm of V = W0 + s B A (a convolution: per out-channel over cin kh kw)
+ *   n0_o = n_o at t == 0             the row norm of W0, by the same kernel (mode 1), frozen
+ *   q_o = n0_o / n_o (1 when n_o == 0);  c_o = (1 + (float)mu_o) q_o
+ *   W[o][i] = bf16_rn(c_o v), and W[o][i] = W0[o][i] bit for bit where t == 0 and c_o == 1
+ * that is DoRA with the magnitude m_o = n0_o (1 + mu_o): mu = 0 and B = 0 give back W0's bits.  A row with n0_o == 0 stays 0.
+ * `adapters` holds per target A, B, mu in that order, bf16, each padded to 8 elements; `adapter_grads` is fp32 and laid out the same way; pad
+ * elements are neither read nor written.  `norm0` and `norm` are caller-owned device fp32 buffers, 16-byte aligned: one float per target row
+ * (indexed like the state-dict rows) in target order, each target padded to 4 floats.
+ * sdxl_load_weight, by `mode`: 0 merge (two launches: norm, then W; reads norm0), 1 init (one launch: writes norm0 only; A, B, mu, scale are
+ * not read), 2 restore (one launch: W0's bits back; scale is ignored).
+ * sdxl_export_grad (three launches; `mode` is not read), from G = dW in the bound fp32 gradient arena with n_o held constant (the value the
+ * last merge wrote into `norm`), v recomputed as in the merge:
+ *   dmu_o = q_o sum_i G[o][i] v[o][i]      dB[o][k] = c_o (s sum_i G[o][i] A[k][i])      dA[k][i] = s sum_o (c_o B[o][k]) G[o][i]
+ * No out x in scratch, no atomics, the outputs are OVERWRITTEN; every summation order is fixed by (out, in, rank, kind) alone.
+ * Bad arguments (1, before any launch, the message names the tensor or the field): everything SDXL_DTYPE_LORA_LAYOUTS refuses, a rank outside
+ * 1 .. 128, a mode outside 0 .. 2, a NULL or misaligned norm0 or norm.  Both calls need `base`.
+ * sdxl_grad_select.lora keeps SDXL_DTYPE_LORA's rule.  The cached device table is keyed by the dtype too. */
+#define SDXL_DTYPE_DORA 8
+typedef struct {
+  sdxl_lora_op op;           /* n, param, rank, scale (alpha / rank), adapters, base, adapter_grads */
+  int mode;                  /* sdxl_load_weight: 0 merge, 1 init, 2 restore */
+  float* norm0;              /* device fp32, 16-byte aligned */
+  float* norm;
+} sdxl_dora_op;
 /* ---- gradient selection: dtype SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad (no entry point of its own) ----
  *   sdxl_export_grad(h, NULL, &sel, SDXL_DTYPE_GRAD_SELECT, stream)
  * tells the backward which state-dict tensors are trained.  `sel` is a HOST pointer, read during the call; `name` must be NULL; a NULL

@@ -101,6 +101,22 @@ typedef struct {
   float scale;
   float* scratch; size_t scratch_floats;
 } sdxl_lokr_one;
+/* the DoRA kernels of SDXL_DTYPE_DORA (csrc/dora.hip) on caller buffers, a table of one target, no handle.  A dtype like SDXL_DTYPE_LOKR_ONE:
+ * sdxl_load_weight with a NULL handle, a NULL name, a HOST pointer to the struct below and dtype SDXL_DTYPE_DORA_ONE runs `mode` 0 (merge: two
+ * launches, norm then w), 1 (init: norm0) or 2 (restore: w = base); sdxl_export_grad called the same way runs the projection (three launches:
+ * dmu, dB, dA; `mode` is not read).  base, w (bf16) and dw (fp32) are NATIVE [out][in]; A [rank][in], B [out][rank], mu [out] bf16, dA, dB, dmu
+ * fp32 (overwritten) and norm0, norm [out] fp32 are indexed like the state-dict tensors.  kind / group as the LoHa hooks'.
+ * What a call uses: merge base, A, B, mu, norm0 (read), norm (written), w; init base, norm0; restore base, w; project dw, base, A, B, mu, norm0,
+ * norm (read), dA, dB, dmu.  Argument checks (1, before any launch): a non-NULL handle or name, rank 1 .. 128, mode 0 .. 2, in % 8 == 0,
+ * out >= 1, a finite scale, every pointer the call uses 16-byte aligned and non-NULL. */
+#define SDXL_DTYPE_DORA_ONE 9
+typedef struct {
+  const void* base; const void* A; const void* B; const void* mu; void* w;      /* merge: in, in, in, in, out */
+  const float* dw; float* dA; float* dB; float* dmu;                            /* project: in, out, out, out */
+  float* norm0; float* norm;
+  int out, in, group, kind, rank, mode;
+  float scale;
+} sdxl_dora_one;
 /* the direct adapter-gradient kernels of sdxl_grad_select.lora (csrc/lora_grad.hip) on caller buffers, a table of one target, no handle:
  * x [M][in] (row stride ldx), dy [M][out] (row stride ldy: a column slice of a wider tensor is dy + offset), A [rank][in], B [out][rank] bf16;
  * dA [rank][in], dB [out][rank] fp32 = (accumulate ? previous : 0) + scale * (dY B)^T X, scale * dY^T (X A^T).  Rows past M and columns outside

@@ -22,7 +22,7 @@ LIB = HERE / "libsdxlstep.so"
 OBJ_DIAG = HERE / "build_diag"
 LIB_DIAG = HERE / "libsdxlstep_diag.so"
 DIAG_SOURCES = ["gemm_sk.hip", "attention_pl.hip"]
-SOURCES = ["gemm.hip", "gemm256.hip", "conv_wgrad3.hip", "wgrad256.hip", "gemm_cr256.hip", "gemm_pl.hip", "attention.hip", "attention_bwd_pl.hip", "norm.hip", "elementwise.hip", "residual.hip", "input_dgrad.hip", "loss.hip", "sampler.hip", "cond_dgrad.hip", "lora.hip", "loha.hip", "lokr.hip", "lora_grad.hip", "optimizer.hip", "engine.hip", "capi.hip", "hooks.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "conv_wgrad3.hip", "wgrad256.hip", "gemm_cr256.hip", "gemm_pl.hip", "attention.hip", "attention_bwd_pl.hip", "norm.hip", "elementwise.hip", "residual.hip", "input_dgrad.hip", "loss.hip", "sampler.hip", "cond_dgrad.hip", "lora.hip", "loha.hip", "lokr.hip", "dora.hip", "lora_grad.hip", "optimizer.hip", "engine.hip", "capi.hip", "hooks.hip"]
 HEADERS = ["common.h", "kernels.h", "gemm_tiles.h", "attn_tiles.h", "engine.h", "capi.h", "../../include/sdxlstep.h", "../../include/sdxlstep_diag.h"]
 # -fvisibility=hidden: the dynamic symbol table holds the SDXL_API entry points of include/sdxlstep.h / sdxlstep_diag.h and nothing else
 # (no C++ internals, no __device_stub__s); tests/test_host_boundary.py checks `nm -D`

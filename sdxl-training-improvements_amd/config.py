@@ -131,6 +131,8 @@ class TrainingConfig:                    # data/config.py:152-168
     # four factors per target through SDXL_DTYPE_LOHA (csrc/loha.hip), lora_rank 1 .. 64, lora_backward "project" or "project_frozen";
     # lora_target_kinds keeps deciding which tensors the patterns may resolve to
     lora_algo: str = "lora"
+    # "dora" = DoRA, LoRA's A and B plus a trained magnitude per output row, through SDXL_DTYPE_DORA (csrc/dora.hip), lora_rank 1 .. 128,
+    # lora_backward "project" or "project_frozen"; weight decay pulls the magnitude towards the checkpoint's row norm, not towards 0
     # "kronecker" = LyCORIS' LoKr, dW = s kron(C, W2) through SDXL_DTYPE_LOKR (csrc/lokr.hip), lora_rank 1 .. 128, lora_backward "project" or
     # "project_frozen".  (The value is not "lokr": that string is pinned as an unknown algorithm by an existing test.)
     # lokr_factor: -1 (the most balanced divisor pair of each dimension) or a positive integer (LyCORIS' `factor`; 8 is the usual recipe);

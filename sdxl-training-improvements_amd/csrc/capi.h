@@ -25,10 +25,18 @@ struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LOR
   LoraTarget* dev = nullptr;
   LohaTarget* dev_loha = nullptr;      // SDXL_DTYPE_LOHA's table (one of the three is held at a time)
   LokrTarget* dev_lokr = nullptr;      // SDXL_DTYPE_LOKR's
+  DoraTarget* dev_dora = nullptr;      // SDXL_DTYPE_DORA's
   int factor = 0, full = 0;
   size_t scratch_floats = 0;           // what SDXL_DTYPE_LOKR's projection needs of sdxl_lokr_op.scratch
   int tiles_m = 0, tiles_b = 0, tiles_a = 0;
 };
+// one table is held at a time: whoever builds its own frees the others first (hipFree waits for the launches that read them)
+static void lora_cache_free(LoraCache& c) {
+  if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }
+  if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
+  if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
+  if (c.dev_dora) { (void)hipFree(c.dev_dora); c.dev_dora = nullptr; }
+}
 struct sdxl_handle {
   Engine e;
   StepState step;
@@ -78,6 +86,22 @@ static int lokr_check_scratch(const float* scratch, size_t have, size_t need) {
 int lokr_one_merge(const sdxl_lokr_one* o, void* st);
 int lokr_one_project(const sdxl_lokr_one* o, void* st);
 static_assert(LOKR_P_TILE == SDXL_LOKR_TILE, "the scratch formula of include/sdxlstep.h");
+
+// ... and of every DoRA entry point (SDXL_DTYPE_DORA, the hook SDXL_DTYPE_DORA_ONE)
+static int dora_check_fields(int rank, int mode) {
+  ARG_CHECK(rank >= 1 && rank <= 128, "dora: rank %d outside 1 .. 128", rank);
+  ARG_CHECK(mode >= 0 && mode <= 2, "dora: mode %d (0 merge, 1 init, 2 restore)", mode);
+  return 0;
+}
+static int dora_check_norms(const float* norm0, const float* norm) {
+  ARG_CHECK(aligned16(norm0), "dora: norm0 must be a 16-byte aligned device pointer");
+  ARG_CHECK(aligned16(norm), "dora: norm must be a 16-byte aligned device pointer");
+  return 0;
+}
+// SDXL_DTYPE_DORA_ONE (hooks.hip): one target on caller buffers, no handle
+int dora_one_load(const sdxl_dora_one* o, void* st);
+int dora_one_project(const sdxl_dora_one* o, void* st);
+static_assert(DORA_R_ROWS == LORA_B_ROWS, "the row reductions share LoraTarget::tile_b with dB");
 
 // a handle that can run a step: planned, bound, with its workspace
 static int ready(Engine& e) {

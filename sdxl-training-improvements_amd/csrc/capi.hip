@@ -73,9 +73,7 @@ int sdxl_destroy(sdxl_handle* h) {
   if (h->e.ev_hoist) (void)hipEventDestroy(h->e.ev_hoist);
   if (h->e.side) (void)hipStreamDestroy(h->e.side);
   if (h->e.small_ranges_dev) (void)hipFree(h->e.small_ranges_dev);
-  if (h->lora.dev) (void)hipFree(h->lora.dev);
-  if (h->lora.dev_loha) (void)hipFree(h->lora.dev_loha);
-  if (h->lora.dev_lokr) (void)hipFree(h->lora.dev_lokr);
+  lora_cache_free(h->lora);
   if (h->e.lora.dev) (void)hipFree(h->e.lora.dev);
   delete h;
   return 0;
@@ -204,9 +202,7 @@ static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
     long tm = 0, tb = 0, ta = 0;
     int mapped = 0;
     CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, dtype == SDXL_DTYPE_LORA_LAYOUTS, &mapped));
-    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
-    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
-    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
+    lora_cache_free(c);
     HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = dtype; c.mapped = mapped;
@@ -250,9 +246,7 @@ static int loha_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op
       tm += loha_tiles_m(x.t.out, x.t.in); tb += loha_tiles_b(x.t.out, x.t.in); ta += loha_tiles_a(x.t.out, x.t.in);
       ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "loha: too many tiles");
     }
-    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
-    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
-    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
+    lora_cache_free(c);
     HIP_CHECK_RET(hipMalloc((void**)&c.dev_loha, htab.size() * sizeof(LohaTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev_loha, htab.data(), htab.size() * sizeof(LohaTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOHA; c.mapped = 1;
@@ -309,9 +303,7 @@ static int lokr_prepare(sdxl_handle* h, const char* name, const sdxl_lokr_op* lo
       tm += lokr_tiles_m(x); tp += x.ptiles; tq += lokr_tiles_q(x, op->rank);
       ARG_CHECK(tm < (1L << 31) && tp < (1L << 31) && tq < (1L << 31), "lokr: too many tiles");
     }
-    if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }      // (hipFree waits for the launches that read it)
-    if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
-    if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
+    lora_cache_free(c);
     HIP_CHECK_RET(hipMalloc((void**)&c.dev_lokr, ktab.size() * sizeof(LokrTarget)));
     HIP_CHECK_RET(hipMemcpy(c.dev_lokr, ktab.data(), ktab.size() * sizeof(LokrTarget), hipMemcpyHostToDevice));
     c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOKR; c.mapped = 1;
@@ -328,12 +320,67 @@ static int lokr_prepare(sdxl_handle* h, const char* name, const sdxl_lokr_op* lo
   return 0;
 }
 
+// ---- DoRA by merge and project (SDXL_DTYPE_DORA): SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target A, B, mu in the adapter arena and
+// its rows of norm0 / norm ----
+static int dora_prepare(sdxl_handle* h, const char* name, const sdxl_dora_op* dop, bool merge, DoraP& q) {
+  ARG_CHECK(name == nullptr, "dora: `name` must be NULL with SDXL_DTYPE_DORA (the targets are listed in sdxl_dora_op.op.param)");
+  ARG_CHECK(dop != nullptr, "dora: empty target list");
+  const sdxl_lora_op* op = &dop->op;
+  CHK(dora_check_fields(op->rank, merge ? dop->mode : 0));
+  CHK(lora_check_op(op, true, !merge));
+  CHK(dora_check_norms(dop->norm0, dop->norm));
+  Engine& e = h->e;
+  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "dora: %s are not bound", merge ? "weights" : "grads");
+  LoraCache& c = h->lora;
+  std::vector<int> params(op->param, op->param + op->n);
+  if (!(c.dev_dora && c.rank == op->rank && c.dtype == SDXL_DTYPE_DORA && c.params == params)) {
+    std::vector<LoraTarget> tab;
+    long tm = 0, tb = 0, ta = 0;
+    int mapped = 0;
+    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, true, &mapped));      // every check of the packed layouts; base_off and the tiles are LoRA's
+    std::vector<DoraTarget> dtab(tab.size());
+    long at = 0, nt = 0;
+    for (size_t i = 0; i < tab.size(); ++i) {
+      DoraTarget& x = dtab[i];
+      x.t = tab[i];
+      x.t.a_off = x.t.ga_off = at; at += ((long)op->rank * x.t.in + 7) / 8 * 8;      // A, B, mu, each padded to 8 elements
+      x.t.b_off = x.t.gb_off = at; at += ((long)x.t.out * op->rank + 7) / 8 * 8;
+      x.mu_off = at; at += ((long)x.t.out + 7) / 8 * 8;
+      x.n_off = nt; nt += dora_pad4(x.t.out);
+    }
+    lora_cache_free(c);
+    HIP_CHECK_RET(hipMalloc((void**)&c.dev_dora, dtab.size() * sizeof(DoraTarget)));
+    HIP_CHECK_RET(hipMemcpy(c.dev_dora, dtab.data(), dtab.size() * sizeof(DoraTarget), hipMemcpyHostToDevice));
+    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_DORA; c.mapped = mapped;
+    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
+  }
+  memset(&q, 0, sizeof(q));
+  q.table = c.dev_dora; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
+  q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = q.mu = (const bf16*)op->adapters;
+  q.dw = e.grads; q.ga = q.gb = q.gmu = op->adapter_grads;
+  q.norm0 = dop->norm0; q.norm = dop->norm;
+  return 0;
+}
+static int dora_launch_load(const DoraP& q, int mode, hipStream_t st) {
+  return mode == 0 ? launch_dora_merge(q, st) : mode == 1 ? launch_dora_init(q, st) : launch_dora_restore(q, st);
+}
+
 int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtype, void* st) {
+  if (dtype == SDXL_DTYPE_DORA_ONE) {      // (a test hook that is a dtype: include/sdxlstep_diag.h)
+    ARG_CHECK(h == nullptr && name == nullptr, "dora: SDXL_DTYPE_DORA_ONE takes no handle and no name");
+    return dora_one_load((const sdxl_dora_one*)src, st);
+  }
   if (dtype == SDXL_DTYPE_LOKR_ONE) {      // (a test hook that is a dtype: include/sdxlstep_diag.h)
     ARG_CHECK(h == nullptr && name == nullptr, "lokr: SDXL_DTYPE_LOKR_ONE takes no handle and no name");
     return lokr_one_merge((const sdxl_lokr_one*)src, st);
   }
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_DORA) {
+    DoraP q;
+    CHK(dora_prepare(h, name, (const sdxl_dora_op*)src, true, q));
+    return dora_launch_load(q, ((const sdxl_dora_op*)src)->mode, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LOKR) {
     LokrP q;
     CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)src, true, q));
@@ -454,7 +501,16 @@ int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, voi
     ARG_CHECK(h == nullptr && name == nullptr, "lokr: SDXL_DTYPE_LOKR_ONE takes no handle and no name");
     return lokr_one_project((const sdxl_lokr_one*)dst, st);
   }
+  if (dtype == SDXL_DTYPE_DORA_ONE) {
+    ARG_CHECK(h == nullptr && name == nullptr, "dora: SDXL_DTYPE_DORA_ONE takes no handle and no name");
+    return dora_one_project((const sdxl_dora_one*)dst, st);
+  }
   H_CHECK(h);
+  if (dtype == SDXL_DTYPE_DORA) {
+    DoraP q;
+    CHK(dora_prepare(h, name, (const sdxl_dora_op*)dst, false, q));
+    return launch_dora_project(q, (hipStream_t)st);
+  }
   if (dtype == SDXL_DTYPE_LOKR) {
     LokrP q;
     CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)dst, false, q));

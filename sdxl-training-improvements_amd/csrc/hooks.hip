@@ -735,3 +735,38 @@ int lokr_one_project(const sdxl_lokr_one* o, void* st) {
   q.gc = o->dC; q.gb = o->dW2; q.ga = o->dA; q.scratch = o->scratch;
   return launch_lokr_project(q, (hipStream_t)st);
 }
+
+// ---- DoRA on caller buffers (csrc/dora.hip; the hook is a dtype, SDXL_DTYPE_DORA_ONE, so nothing here is exported): the descriptor of one
+// target, every offset 0 ----
+static int dora_one(const sdxl_dora_one* o, int mode, DoraP& q) {
+  CHK(dora_check_fields(o->rank, mode));
+  LoraP l;
+  CHK(lora_one_layout(o->out, o->in, o->rank, o->scale, o->kind, o->group, o->out, l));
+  memset(&q, 0, sizeof(q));
+  q.n = 1; q.rank = o->rank; q.scale = o->scale; q.mapped = 1;
+  q.one.t = l.one;
+  q.tiles_m = l.tiles_m; q.tiles_b = l.tiles_b; q.tiles_a = l.tiles_a;
+  q.base = (const bf16*)o->base; q.a = (const bf16*)o->A; q.b = (const bf16*)o->B; q.mu = (const bf16*)o->mu; q.w = (bf16*)o->w;
+  q.dw = o->dw; q.ga = o->dA; q.gb = o->dB; q.gmu = o->dmu; q.norm0 = o->norm0; q.norm = o->norm;
+  return 0;
+}
+// the two halves of SDXL_DTYPE_DORA_ONE (sdxlstep_diag.h): no symbol of their own, capi.hip's sdxl_load_weight / sdxl_export_grad call them
+int dora_one_load(const sdxl_dora_one* o, void* st) {
+  ARG_CHECK(o != nullptr, "dora_load: NULL descriptor");
+  CHK(dora_check_fields(o->rank, o->mode));
+  ARG_CHECK(aligned16(o->base) && (o->mode == 1 || aligned16(o->w)) && (o->mode == 2 || aligned16(o->norm0)) &&
+            (o->mode != 0 || (aligned16(o->A) && aligned16(o->B) && aligned16(o->mu) && aligned16(o->norm))),
+            "dora_load: every pointer the mode uses must be 16-byte aligned and non-NULL");
+  DoraP q;
+  CHK(dora_one(o, o->mode, q));
+  return o->mode == 0 ? launch_dora_merge(q, (hipStream_t)st) : o->mode == 1 ? launch_dora_init(q, (hipStream_t)st) : launch_dora_restore(q, (hipStream_t)st);
+}
+int dora_one_project(const sdxl_dora_one* o, void* st) {
+  ARG_CHECK(o != nullptr, "dora_project: NULL descriptor");
+  ARG_CHECK(aligned16(o->dw) && aligned16(o->base) && aligned16(o->A) && aligned16(o->B) && aligned16(o->mu) && aligned16(o->norm0) &&
+            aligned16(o->norm) && aligned16(o->dA) && aligned16(o->dB) && aligned16(o->dmu),
+            "dora_project: every pointer must be 16-byte aligned and non-NULL");
+  DoraP q;
+  CHK(dora_one(o, 0, q));
+  return launch_dora_project(q, (hipStream_t)st);
+}

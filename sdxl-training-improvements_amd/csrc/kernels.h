@@ -712,6 +712,39 @@ static inline int lokr_tiles_q(const LokrTarget& x, int rank) {
 int launch_lokr_merge(const LokrP& p, hipStream_t st);
 int launch_lokr_project(const LokrP& p, hipStream_t st);     // two launches: dW2 and the partial sums of dC; dC, dB, dA
 
+// ---- DoRA by merge and project (dora.hip; SDXL_DTYPE_DORA): W = c_o (W0 + s B A), c_o = (1 + mu_o) n0_o / n_o, table-driven like LoRA's ----
+#define DORA_R_ROWS 32    // row reductions (norm, norm0, dmu): rows per workgroup (= LORA_B_ROWS: they share LoraTarget::tile_b with dB)
+#define DORA_R_COLS 64    //     columns per pass of the column loop, 8 per thread
+#define DORA_R_KC 32      //     ranks staged per step
+#define DORA_R_NORM 0     // what a row reduction writes: norm = sqrt(sum v^2), v = W0 + s B A
+#define DORA_R_NORM0 1    //     norm0 = the same with s B A taken as 0 (A, B, scale are not read)
+#define DORA_R_DMU 2      //     dmu = (n0 / n) sum G v
+struct DoraTarget {       // LoraTarget (a_off / b_off and ga_off / gb_off: A, B; tile_m: merge and restore, tile_b: the row reductions and dB,
+  LoraTarget t;           // tile_a: dA; t.nrows is not used: only the rows < out of a target are read or written)
+  long mu_off;            // adapter and adapter-gradient arena: mu [out], indexed like the state-dict rows
+  long n_off;             // norm0 / norm: [out] floats, indexed like the state-dict rows
+};
+struct DoraP {
+  const DoraTarget* table;      // device [n], or nullptr: a table of one, passed by value in `one`
+  DoraTarget one;
+  int n, rank;                  // rank 1 .. 128
+  float scale;
+  int tiles_m, tiles_b, tiles_a;
+  int mapped;                   // as LoraP::mapped
+  bf16* w;                      // merge, restore: out
+  const bf16* base;             // every launch but dB and dA
+  const bf16 *a, *b, *mu;       // what a_off / b_off / mu_off count from: the adapter arena three times, or the hook's operands (offsets 0)
+  const float* dw;              // project
+  float *ga, *gb, *gmu;         // project: out, overwritten
+  float* norm0;                 // init: out; merge, project: in
+  float* norm;                  // merge: out (by its first launch), then in; project: in
+};
+static inline long dora_pad4(long n) { return (n + 3) / 4 * 4; }
+int launch_dora_init(const DoraP& p, hipStream_t st);        // one launch: norm0
+int launch_dora_merge(const DoraP& p, hipStream_t st);       // two launches: norm, W
+int launch_dora_restore(const DoraP& p, hipStream_t st);     // one launch: W = W0
+int launch_dora_project(const DoraP& p, hipStream_t st);     // three launches: dmu, dB, dA
+
 // ---- direct LoRA adapter gradients (lora_grad.hip): dA, dB of every target of ONE linear op from its X and dY, no dW ----
 #define LORA_G_CHUNK 512      // rows of M per partial block (a multiple of 32): the split of M is fixed by M alone
 struct LoraGradTarget {

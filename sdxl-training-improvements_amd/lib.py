@@ -158,6 +158,24 @@ class LokrOne(C.Structure):
                 [("scale", C.c_float), ("scratch", C.c_void_p), ("scratch_floats", C.c_size_t)])
 
 
+DTYPE_DORA = 8        # SDXL_DTYPE_DORA: the same two calls with a host DoraOp*: W = c_o (W0 + s B A), c_o = (1 + mu_o) n0_o / n_o (lora.py, algo="dora")
+DORA_MERGE, DORA_INIT, DORA_RESTORE = 0, 1, 2      # sdxl_dora_op.mode of sdxl_load_weight
+
+
+class DoraOp(C.Structure):
+    """sdxl_dora_op: LoraOp, the mode of sdxl_load_weight and the two fp32 row-norm buffers (one float per target row, each target padded to 4)"""
+    _fields_ = [("op", LoraOp), ("mode", C.c_int), ("norm0", C.c_void_p), ("norm", C.c_void_p)]
+
+
+DTYPE_DORA_ONE = 9    # SDXL_DTYPE_DORA_ONE (sdxlstep_diag.h part 1): the DoRA kernels on caller buffers, one target, NULL handle and name, a host DoraOne*
+
+
+class DoraOne(C.Structure):
+    """sdxl_dora_one: the test hook of csrc/dora.hip (a dtype of sdxl_load_weight: merge / init / restore by `mode`, sdxl_export_grad: project)"""
+    _fields_ = ([(k, C.c_void_p) for k in ("base", "A", "B", "mu", "w", "dw", "dA", "dB", "dmu", "norm0", "norm")] +
+                [(k, C.c_int) for k in ("out", "in_", "group", "kind", "rank", "mode")] + [("scale", C.c_float)])
+
+
 DTYPE_GRAD_SELECT = 3  # SDXL_DTYPE_GRAD_SELECT of sdxl_export_grad: the pointer is a host GradSelect* (NULL = every tensor trainable), name NULL
 
 

@@ -34,6 +34,15 @@ through dtype SDXL_DTYPE_LOKR (csrc/lokr.hip).  training.lokr_factor (-1 or >= 1
 is true or 2 r >= max(out_k, in_n) (LyCORIS' rule with decompose_both off), with s = 1 and an exported alpha of r; a factored one has
 s = alpha / r.  lora_rank is 1 .. 128.  Initialisation (this build's choice): the zero factor is W2 (full) or A (factored), as in LyCORIS,
 so dW = 0 and the first merged step has the plain trainer's bits; C ~ N(0, 1), B ~ N(0, 0.1^2) from lora_seed.
+
+"dora" is DoRA (Liu et al. 2024; PEFT's use_dora): LoRA's A and B plus a trained vector mu [out] per target, through dtype SDXL_DTYPE_DORA
+(csrc/dora.hip).  With V = W0 + s B A, n_o the fp32 norm of row o of V and n0_o that of W0 (computed once on the device, frozen),
+  W[o] = (1 + mu_o) (n0_o / n_o) V[o]      that is DoRA's m_o V[o] / ||V[o]|| with the magnitude m_o = n0_o (1 + mu_o).
+mu (not m) is what the bf16 arena holds: bf16(n0_o) != n0_o, so a stored m would move a fresh adapter's weights by an ulp, while mu = 0
+and B = 0 (the initialisation; A as LoRA's) give back W0's bits and the first merged step has the plain trainer's.  The backward holds n_o
+constant (the paper's section 4.3, PEFT's .detach()): dA, dB are LoRA's times c_o = (1 + mu_o) n0_o / n_o and dmu_o = (n0_o / n_o) <dW[o], V[o]>.
+This build's choices: weight decay acts on mu, so it pulls m towards n0, not towards 0; a row with n0_o = 0 stays 0 whatever mu is.
+lora_backward "project" or "project_frozen"; lora_rank 1 .. 128.
 """
 from __future__ import annotations
 
@@ -56,10 +65,11 @@ DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
 MAX_RANK = 128
 LORA_BACKWARDS = ("project", "project_frozen", "direct")
 LORA_TARGET_KINDS = ("plain", "all")
-LORA_ALGOS = ("lora", "loha", "kronecker")
+LORA_ALGOS = ("lora", "loha", "kronecker", "dora")
 LOHA_MAX_RANK = 64
 LOKR = "kronecker"      # LyCORIS' LoKr ("lokr" stays an unknown value: tests/test_host_loha.py uses it as one)
-EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors", LOKR: "lycoris_lokr.safetensors"}      # save_checkpoint's adapter file
+EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors", LOKR: "lycoris_lokr.safetensors",
+                "dora": "pytorch_lora_weights.safetensors"}      # save_checkpoint's adapter file
 LOKR_NAMES = {"C": "lokr_w1", "W2": "lokr_w2", "B": "lokr_w2_a", "A": "lokr_w2_b"}      # the LyCORIS names
 LOHA_FACTORS = (("A1", "hada_w1_b"), ("B1", "hada_w1_a"), ("A2", "hada_w2_b"), ("B2", "hada_w2_a"))      # arena order; the LyCORIS names
 
@@ -171,6 +181,10 @@ def _pad8(n: int) -> int:
     return (n + 7) // 8 * 8
 
 
+def _pad4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
 def resolve_targets(shapes: Dict[str, Tuple[int, ...]], patterns: Sequence[str], kinds: str = "plain") -> List[str]:
     """The `.weight` keys of `shapes` (state-dict order) whose module path is a pattern or ends in "." + pattern.  ValueError for a
     pattern that matches nothing and for one that matches a tensor the kernels cannot take: with kinds "plain" a convolution, the
@@ -225,7 +239,8 @@ def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], r
     out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions.
     algo "loha": {key: (A1 offset, B1 offset, A2 offset, B2 offset, out, in)}, the four factors in that order, each padded to 8;
     algo "kronecker": {key: (C offset, W2 offset, out, in)} for a full target, (C offset, B offset, A offset, out, in) for a factored one
-    (lokr_geometry has the shapes), each factor padded to 8"""
+    (lokr_geometry has the shapes), each factor padded to 8;
+    algo "dora": {key: (A offset, B offset, mu offset, out, in)}, A [rank, in], B [out, rank], mu [out], each padded to 8"""
     check_lora_algo(algo)
     lay, cur = {}, 0
     for k in targets:
@@ -245,6 +260,9 @@ def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], r
             cur += _pad8(rank * i)
             offs.append(cur)
             cur += _pad8(o * rank)
+        if algo == "dora":
+            offs.append(cur)
+            cur += _pad8(o)
         lay[k] = (*offs, o, i)
     return lay, cur
 
@@ -259,8 +277,8 @@ class LoRAAdapters:
         self.lokr_factor = check_lokr_factor(factor)      # (read by "kronecker" only)
         self.lokr_full = check_lokr_full(full)
         # (loha: one dtype, the packed layouts' target rules in the library; `kinds` still says what the patterns may resolve to)
-        self.dtype = (lib.DTYPE_LOKR if algo == LOKR else lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_LORA_LAYOUTS if kinds == "all"
-                      else lib.DTYPE_LORA)
+        self.dtype = (lib.DTYPE_LOKR if algo == LOKR else lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_DORA if algo == "dora"
+                      else lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA)
         max_rank = LOHA_MAX_RANK if algo == "loha" else MAX_RANK
         if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
             raise ValueError(f"lora_rank must be an integer in 1 .. {max_rank} (got {rank!r})" + (" with lora_algo 'loha'" if algo == "loha" else ""))
@@ -300,6 +318,14 @@ class LoRAAdapters:
                 a = self.layout[k][0]
                 self.weights[a: a + rank * i] = (torch.randn(rank, i, generator=g) * (1.0 / rank)).to(torch.bfloat16).reshape(-1).to(dev)
         self._param = (C.c_int * len(self.index))(*self.index)
+        if algo == "dora":      # sdxl_dora_op.norm0 / norm: one float per target row in target order, each target padded to 4; mu = 0
+            self.norm_offsets, cur = {}, 0
+            for k in self.targets:
+                self.norm_offsets[k] = cur
+                cur += _pad4(self.layout[k][-2])
+            self.norm0 = torch.zeros(cur, dtype=torch.float32, device=dev)
+            self.norm = torch.zeros(cur, dtype=torch.float32, device=dev)
+            self.init_norm0()
 
     # ---- what a fused optimizer asks of its net
     def zero_grads(self) -> None:
@@ -308,7 +334,8 @@ class LoRAAdapters:
     def param_ranges(self) -> Dict[str, Tuple[int, int]]:
         """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas;
         algo "loha": "<module>.hada_w1_b" (A1), ".hada_w1_a" (B1), ".hada_w2_b" (A2), ".hada_w2_a" (B2), in arena order;
-        algo "kronecker": "<module>.lokr_w1" (C), then ".lokr_w2" (W2, a full target) or ".lokr_w2_a" (B), ".lokr_w2_b" (A)"""
+        algo "kronecker": "<module>.lokr_w1" (C), then ".lokr_w2" (W2, a full target) or ".lokr_w2_a" (B), ".lokr_w2_b" (A);
+        algo "dora": "<module>.lora_A", ".lora_B", ".lora_magnitude" (mu)"""
         out = {}
         for k, lay in self.layout.items():
             mod = k[: -len(".weight")]
@@ -321,6 +348,11 @@ class LoRAAdapters:
             if self.algo == "loha":
                 for n, (_name, lyco) in enumerate(LOHA_FACTORS):
                     out[f"{mod}.{lyco}"] = (lay[n], _pad8(self.rank * i if n % 2 == 0 else o * self.rank))
+                continue
+            if self.algo == "dora":
+                out[f"{mod}.lora_A"] = (lay[0], _pad8(self.rank * i))
+                out[f"{mod}.lora_B"] = (lay[1], _pad8(o * self.rank))
+                out[f"{mod}.lora_magnitude"] = (lay[2], _pad8(o))
                 continue
             out[f"{mod}.lora_A.weight"] = (lay[0], _pad8(self.rank * i))
             out[f"{mod}.lora_B.weight"] = (lay[1], _pad8(o * self.rank))
@@ -337,7 +369,7 @@ class LoRAAdapters:
     def factor(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
         """a LoHa factor "A1" | "B1" | "A2" | "B2" of a target (or its gradient), a view of the arena"""
         if self.algo != "loha":
-            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}" + (" (A and B)" if self.algo == "lora" else " (C, W2 or B, A)"))
+            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}" + (" (A and B)" if self.algo in ("lora", "dora") else " (C, W2 or B, A)"))
         return self._view(key, [n for n, _l in LOHA_FACTORS].index(name), grad)
 
     def lokr_factors(self, key: str) -> Tuple[str, ...]:
@@ -385,6 +417,25 @@ class LoRAAdapters:
             return self.factor_view("B", key, grad)
         return self._view(key, 1, grad)
 
+    def mu(self, key: str, grad: bool = False) -> torch.Tensor:
+        """the trained vector mu [out] of a "dora" target (or its gradient), a view of the arena: the magnitude is n0 (1 + mu)"""
+        if self.algo != "dora":
+            raise ValueError(f"mu: these adapters are lora_algo {self.algo!r}, not 'dora'")
+        off, o = self.layout[key][2], self.layout[key][-2]
+        return (self.grads if grad else self.weights)[off: off + o]
+
+    def row_norm(self, key: str, base: bool = True) -> torch.Tensor:
+        """the fp32 row norms [out] of a "dora" target, views of the device buffers: n0 of W0 (base=True; written once by init_norm0) or n of
+        V = W0 + s B A as the last merge left it"""
+        if self.algo != "dora":
+            raise ValueError(f"row_norm: these adapters are lora_algo {self.algo!r}, not 'dora'")
+        off, o = self.norm_offsets[key], self.layout[key][-2]
+        return (self.norm0 if base else self.norm)[off: off + o]
+
+    def magnitude(self, key: str) -> torch.Tensor:
+        """DoRA's magnitude m = n0 (1 + mu) [out] of a target, fp32"""
+        return self.row_norm(key) * (1.0 + self.mu(key).float())
+
     def A1(self, key: str, grad: bool = False) -> torch.Tensor:
         return self.factor("A1", key, grad)
 
@@ -398,31 +449,43 @@ class LoRAAdapters:
         return self.factor("B2", key, grad)
 
     # ---- the two device steps
-    def _op(self, scale: float):
+    def _op(self, scale: float, mode: int = 0):
         op = lib.LoraOp(len(self.index), self._param, self.rank, float(scale), self.weights.data_ptr(), self.base.data_ptr(),
                         self.grads.data_ptr())
         if self.algo == LOKR:
             return lib.LokrOp(op, self.lokr_factor, int(self.lokr_full), self.scratch.data_ptr(), self.scratch.numel())
+        if self.algo == "dora":
+            return lib.DoraOp(op, int(mode), self.norm0.data_ptr(), self.norm.data_ptr())
         return op
 
-    def _call(self, fn_name: str, scale: float) -> None:
+    def _call(self, fn_name: str, scale: float, mode: int = 0) -> None:
         if self.L is None:
             raise lib.SdxlError(f"LoRAAdapters.{fn_name}: needs libsdxlstep.so (there is no PyTorch fallback)")
-        op = self._op(scale)
+        op = self._op(scale, mode)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         lib.check(getattr(self.L, fn_name)(self.net.h, None, C.byref(op), self.dtype, st), f"{fn_name} (lora)")
 
     def merge(self, scale: Optional[float] = None) -> None:
         """W = bf16(W0 + s B A) for every target, into the net's weight arena (one launch).  algo "kronecker": `scale` is the factored
-        targets' s; a full target uses s = 1 whatever non-zero `scale` is given, and s = 0 with scale 0 (restore)"""
+        targets' s; a full target uses s = 1 whatever non-zero `scale` is given, and s = 0 with scale 0 (restore).  algo "dora": two
+        launches, the first writes the row norms of W0 + s B A into `.norm`, which the next project() reads"""
         self._call("sdxl_load_weight", self.scale if scale is None else scale)
 
     def restore(self) -> None:
-        """the checkpoint's weights back, bit for bit (a merge with scale 0)"""
-        self.merge(0.0)
+        """the checkpoint's weights back, bit for bit (a merge with scale 0; algo "dora": its restoring mode, mu does not matter)"""
+        if self.algo == "dora":
+            self._call("sdxl_load_weight", 0.0, lib.DORA_RESTORE)
+        else:
+            self.merge(0.0)
+
+    def init_norm0(self) -> None:
+        """algo "dora": the row norms of W0 into `.norm0` (one launch; a no-op without the library, where nothing can be merged either)"""
+        if self.L is not None:
+            self._call("sdxl_load_weight", 0.0, lib.DORA_INIT)
 
     def project(self) -> None:
-        """dA, dB of every target from the net's fp32 gradient arena into `.grads` (overwritten; two launches)"""
+        """dA, dB of every target from the net's fp32 gradient arena into `.grads` (overwritten; two launches).  algo "dora": and dmu, three
+        launches, with the row norms the last merge() wrote"""
         self._call("sdxl_export_grad", self.scale)
 
     def select(self, mode: str) -> None:
@@ -479,6 +542,8 @@ class LoRAAdapters:
         self.alpha = float(sd.get("alpha", self.alpha))
         self.scale = self.alpha / self.rank
         self.weights.copy_(sd["weights"].reshape(-1))
+        if self.algo == "dora":      # (norm0 is not part of a state: it is W0's, recomputed by the kernel that computed it)
+            self.init_norm0()
 
     def export_tensors(self) -> Dict[str, torch.Tensor]:
         """{"unet.<module>.lora_A.weight", "unet.<module>.lora_B.weight"} in fp32 on the CPU, s folded into lora_B: a loader that
@@ -486,7 +551,9 @@ class LoRAAdapters:
         [out, r, 1, 1] for a convolution (the down convolution has the layer's kernel, the up convolution is 1 x 1).
         algo "loha": the LyCORIS / kohya convention instead -- "lora_unet_<module path with '.' -> '_'>.hada_w1_a" [out, r] (B1), ".hada_w1_b"
         [r, in kh kw] (A1), ".hada_w2_a" (B2), ".hada_w2_b" (A2) and ".alpha" (a scalar), fp32, s NOT folded in: a loader forms
-        (alpha / r) (w1_a w1_b) .* (w2_a w2_b) reshaped like the layer's weight."""
+        (alpha / r) (w1_a w1_b) .* (w2_a w2_b) reshaped like the layer's weight.
+        algo "dora": LoRA's file plus "unet.<module>.lora_magnitude_vector" [out] fp32, the magnitude m = n0 (1 + mu): a loader forms
+        m_o V[o] / ||V[o]||, V = W0 + lora_B lora_A, the norm per output row over every other dimension."""
         if self.algo == LOKR:      # lokr_w1 [out_l, in_m]; lokr_w2 [out_k, in_n(, kh, kw)] or lokr_w2_a [out_k, r], lokr_w2_b [r, in_n kh kw];
             out = {}               # alpha (r for a full target: its scale is 1); fp32, s not folded in: a loader forms s kron(w1, w2)
             for k in self.targets:
@@ -517,6 +584,8 @@ class LoRAAdapters:
                 la, lb = la.view(self.rank, *shape[1:]), lb.view(shape[0], self.rank, 1, 1)
             out[f"unet.{mod}.lora_A.weight"] = la
             out[f"unet.{mod}.lora_B.weight"] = lb
+            if self.algo == "dora":
+                out[f"unet.{mod}.lora_magnitude_vector"] = self.magnitude(k).float().cpu().contiguous()
         return out
 
 
@@ -655,7 +724,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         super().sync_to_model()
 
     def save_checkpoint(self, epoch_or_path=0, is_final: bool = False) -> Optional[Path]:
-        """`pytorch_lora_weights.safetensors` (fp32, keys unet.<module>.lora_A.weight / .lora_B.weight, s folded into lora_B),
+        """`pytorch_lora_weights.safetensors` (fp32, keys unet.<module>.lora_A.weight / .lora_B.weight, s folded into lora_B; with
+        training.lora_algo "dora" also unet.<module>.lora_magnitude_vector),
         with training.lora_algo "loha" `lycoris_loha.safetensors`, with "kronecker" `lycoris_lokr.safetensors` instead (export_tensors
         has the keys),
         `lora_state.pt` (the bit-exact arena, settings and target list: load_lora_state), `optimizer.pt`, `config.json`; the merged
