@@ -612,6 +612,14 @@ SDXL_API int sdxl_op_loss(const sdxl_loss_config* lc, const sdxl_batch* b, void*
  * stochastic roundings in the reference's draw order (exp_avg, shift, p, shift) -- parity tests; NULL = Philox keyed
  * by (seed, step, element).  Weight decay is lazy in the reference (per tensor, paid when wd*lr accumulates past
  * 5e-3): decay_this_iteration applies to the whole launch; sdxl_adamw_decay pays it for one tensor's range. */
+/* one tensor of the Adafactor table (algorithm 3, below): a row-major matrix inside the arena */
+typedef struct sdxl_adafactor_tensor {
+  size_t elem_off;             /* arena element offset of its element (0, 0), a multiple of 8 */
+  int rows, cols;              /* cols is the arena row stride and a multiple of 8; the entry owns elem_off .. elem_off + rows*cols */
+  size_t numel;                /* the real elements, 1 .. rows*cols: the divisor of both RMS (pads hold g = 0, p = 0) */
+  int factored;                /* 1: row and column statistics R[rows], C[cols]; 0: one second moment per element, v[rows*cols] */
+  size_t state_off;            /* float offset into af_state, a multiple of 4: R then C (rows + cols floats), or v (rows*cols floats) */
+} sdxl_adafactor_tensor;
 typedef struct {
   double lr, beta1, beta2, eps; /* doubles: the reference derives 1-beta, -lr*sqrt(1-beta2^t) in python floats */
   double step;                 /* t >= 1 of this update (denominator correction sqrt(1 - beta2^t)) */
@@ -650,6 +658,19 @@ typedef struct {
   const void* p0;              /* bf16 [n]: the parameters at construction, read only */
   float* s;                    /* fp32 [n]: Prodigy's s */
   float* prodigy_state;        /* device array of SDXL_PRODIGY_STATE_FLOATS floats (below) */
+  /* ---- appended: algorithm 3, Adafactor (sdxl_adamw_default_config zeroes them; algorithms 0, 1 and 2 do not read them) ---- */
+  double clip_threshold;       /* > 0: the update of a tensor is divided by max(1, rms_u / clip_threshold) */
+  double eps1, eps2;           /* eps1 is added to the squared gradient, eps2 is the floor of rms_p under scale_parameter; both >= 0 */
+  double beta2t;               /* this step's decay of the second-moment statistics, 1 - k^decay_rate for step k >= 1, computed by
+                                  the caller in double precision; in [0, 1) (0 at k = 1) */
+  double rho;                  /* this step's step-size base, computed by the caller in double precision: lr, or with relative_step
+                                  min(warmup_init ? 1e-6 * k : 1e-2, 1 / sqrt(k)).  Finite */
+  int scale_parameter;         /* 1: rho is multiplied by max(eps2, rms_p) of each tensor */
+  int use_beta1;               /* 1: m carries the fp32 first moment and the update goes through it */
+  const struct sdxl_adafactor_tensor* tensors;   /* HOST array of n_tensors entries (below), read during the call */
+  int n_tensors;
+  float* af_state;             /* device, fp32: the factored statistics, addressed by each entry's state_off */
+  float* af_scratch;           /* device, fp32: adafactor_scratch_floats(table) floats (below), written before they are read */
 } sdxl_adamw_config;
 /* ---- algorithm 2: Prodigy (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner"): AdamW whose
  * step size d is estimated from two sums over the whole arena and lives on the device, so a step costs no host read-back.
@@ -691,6 +712,69 @@ typedef struct {
  * A and Bs to float once.  The bits depend on n and this geometry alone. */
 #define SDXL_PRODIGY_MAX_GRID 4096                                   /* the largest grid of the optimizer launches: 256 CUs x 16 */
 #define SDXL_PRODIGY_STATE_FLOATS (8 + 2 * SDXL_PRODIGY_MAX_GRID)
+/* ---- algorithm 3: Adafactor (Shazeer & Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost"; the arithmetic
+ * follows transformers.optimization.Adafactor.step): the second moment of a weight matrix is kept as one row and one column
+ * statistic, so the state is rows + cols floats per matrix instead of two arenas.  The update needs per-tensor sums (row and
+ * column sums of g^2, the RMS of the update for clipping, the RMS of the parameter), so the call takes a table of the tensors
+ * inside the arena and runs five launches whatever n_tensors is.
+ * Arguments of sdxl_adamw_bf16_step under algorithm 3: p bf16; shift = the bf16 compensation c (the true parameter is
+ * x = float(p) + float(c), as under algorithm 2); m = the FP32 first moment, or NULL when use_beta1 is 0; v must be NULL;
+ * rand_inject must be NULL; n a multiple of 8 and the whole arena.  Every pointer 16-byte aligned.  Read from the config: beta1
+ * (with use_beta1), weight_decay, grad_round_bf16, ema, ema_one_minus_decay and the fields appended for algorithm 3; not read: lr,
+ * beta2, eps, step, seed, elem_offset, reference_ema, decay_this_iteration.  Elements that belong to no table entry are neither
+ * read nor written: a frozen tensor is a tensor left out of the table.  n_tensors == 0 returns 0 without a launch.  The device
+ * copy of the table is cached inside the library, keyed by its contents.
+ * Argument errors return 1 before anything touches the device, and the message names the entry: entries that overlap or are not
+ * sorted by elem_off, a range past n, elem_off % 8, cols % 8, rows < 1, numel of 0 or above rows*cols, state_off % 4, factored
+ * other than 0 or 1; and a NULL or misaligned
+ * buffer (af_state, af_scratch, tensors included), clip_threshold <= 0, beta2t outside [0, 1), a non-finite rho, negative eps1,
+ * eps2 or weight_decay, a non-NULL v or rand_inject.
+ *
+ * Which tensors are factored is the caller's choice (optimizer.py::adafactor_layout): a 2-D weight as [out][in]; a 4-D
+ * convolution weight as [shape[0]][prod(rest)], in the arena the plain row-major matrix [cout][9*cin].  That is deliberately
+ * not the HF class's choice, which factors a 4-D tensor over its last two dimensions (kh, kw): factoring over a 3 x 3 pair
+ * saves nothing (6 floats for 9), while [cout][cin*kh*kw] is the convention of this project's LoRA targets and a permutation of
+ * the columns (tap-major in the arena) changes no statistic.  Row-permuted matrices (ff.net.0.proj) only permute R.
+ *
+ * The arithmetic, all fp32 with every operation rounded on its own (host doubles are rounded to float once: b2t = float(beta2t),
+ * omb2t = float(1 - beta2t), omb1 = float(1 - beta1) and so on); rsqrt(y) = 1 / sqrt(y), both correctly rounded; rows and cols
+ * enter the means as floats:
+ *   per element:      gr = grad * scale (rounded to bf16 with grad_round_bf16)   q = (gr*gr) + eps1   x = float(p) + float(c)
+ *   stats, factored:  R'_o = (b2t*R_o) + (omb2t*((sum_i q)/cols))      C'_i = (b2t*C_i) + (omb2t*((sum_o q)/rows))
+ *                     mean = (sum_o R'_o)/rows      u = (rsqrt(R'_o/mean) * rsqrt(C'_i)) * gr
+ *   unfactored:       v' = (b2t*v) + (omb2t*q)      u = rsqrt(v') * gr
+ *   per tensor:       rms_u = sqrt((sum u*u)/numel)   rms_p = sqrt((sum x*x)/numel)  (read only with scale_parameter, else 0)
+ *                     rho_t = scale_parameter ? rho*max(eps2, rms_p) : rho        eta_t = rho_t / max(1, rms_u/clip_threshold)
+ *   apply:            D = eta_t*u    use_beta1: m' = (b1*m) + (omb1*D), D = m'    weight_decay != 0: x = x - ((wd*rho_t)*x)
+ *                     x = x - D      p' = bf16_rn(x)      c' = bf16_rn(x - float(p'))      then the EMA of p' when one is attached
+ * A pad (g = 0, p = 0, c = 0) stays +0 bit for bit: u = 0 there, and it adds eps1 to its row's and column's sums as any element.
+ *
+ * Geometry.  A tensor is cut into tiles of SDXL_AF_ROWS x SDXL_AF_COLS elements, row blocks outer, column blocks inner:
+ * ncb = ceil(cols / SDXL_AF_COLS), nrb = ceil(rows / SDXL_AF_ROWS), tile (rb, cb) has the index rb*ncb + cb.  One workgroup of
+ * 256 threads takes one tile: thread j owns the 8-column vector j % 32 of the tile in the rows (j / 32) + 8*i, i = 0 .. 15.
+ * No atomics, no ticket or fence inside a launch: the kernel boundary is the only synchronisation, every sum has a fixed order that
+ * depends on the tensor's (rows, cols, factored) alone, so a tensor's bits do not depend on the other entries or on its place
+ * in the table, and repeated runs are bit-equal.
+ *   launch 1, stats:   a tile's row sums: each thread adds q of its 8 columns in ascending column order, then the 32 threads of
+ *                      the row combine by the butterfly s += s[lane ^ h], h = 16, 8, 4, 2, 1; its column sums: each thread adds
+ *                      its rows in ascending i per column, then the 8 threads of a column are added in ascending j / 32; its
+ *                      sum of x*x: per thread in (i, column) order, then the workgroup's tree x[j] += x[j + h], h = 128 .. 1.
+ *   launch 2, reduce:  one thread per row adds the row's ncb tile sums in ascending cb, one thread per column adds the column's
+ *                      nrb tile sums in ascending rb; R', C' are written; the R' of each chunk of 256 rows go through the
+ *                      workgroup's tree into one partial.
+ *   launch 3, usq:     mean = the chunk partials in ascending order / rows; u; v' is written; a tile's sum of u*u as for x*x.
+ *   launch 4, scalars: one workgroup per tensor adds the tensor's tile sums in double precision (thread j takes the tiles
+ *                      j*ceil(T/256) .. in ascending order, then the 256 sums are added in ascending j), rounds to float once,
+ *                      and writes rho_t, eta_t, rms_u, rms_p.
+ *   launch 5, apply:   u exactly as in launch 3, then the update.
+ * A thread adds at most 128 terms into one fp32 sum in launch 1 or 3, and max(ncb, nrb, ceil(rows/256)) in launch 2 or 3.
+ *
+ * af_scratch, adafactor_scratch_floats(table) floats in all: first 4 floats per entry in table order (rho_t, eta_t, rms_u,
+ * rms_p: what launch 4 writes and a caller may read back), then per entry in table order, with T = nrb*ncb:
+ *   T floats (the tiles' sums of x*x), T floats (of u*u), and for a factored entry ceil(rows/256) floats (the chunk partials of
+ *   R'), rows*ncb floats (row sums, [row][cb]) and nrb*cols floats (column sums, [rb][col]). */
+#define SDXL_AF_ROWS 128
+#define SDXL_AF_COLS 256
 SDXL_API int sdxl_adamw_default_config(sdxl_adamw_config* c);   /* lr 1e-4, betas (0.9, 0.999), eps 1e-8, reference_ema 1, algorithm 0, no EMA */
 SDXL_API int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,

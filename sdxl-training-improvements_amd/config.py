@@ -6,7 +6,7 @@ from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field, fields, is_dataclass
 from pathlib import Path
-from typing import List, Optional, Union
+from typing import List, Optional, Tuple, Union
 
 import yaml
 
@@ -50,6 +50,17 @@ class OptimizerConfig:                   # data/config.py:42-49
     prodigy_beta3: Optional[float] = None       # the decay of the estimate's sums; None = sqrt(beta2)
     prodigy_use_bias_correction: bool = False   # Adam's bias correction in the step size
     prodigy_safeguard_warmup: bool = False      # leave lr out of the denominator's sum (for a schedule with a warm-up)
+    # build-only keys, read by optimizer_type "adafactor" (optimizer.py::AdafactorBF16; the arguments and defaults of
+    # transformers.optimization.Adafactor).  The published SDXL full fine-tune recipe is scale_parameter: false, relative_step: false,
+    # learning_rate: 4.0e-7, weight_decay: 0.  beta1 and weight_decay above keep their own defaults: the first moment is
+    # adafactor_beta1 (None = no first moment, as in the class), the decay is weight_decay (set it to 0 for the class's default)
+    eps: Tuple[float, float] = (1e-30, 1e-3)    # (added to the squared gradient, floor of the parameter RMS under scale_parameter)
+    clip_threshold: float = 1.0          # the update of a tensor is divided by max(1, rms(update) / clip_threshold)
+    decay_rate: float = -0.8             # beta2 of step k is 1 - k^decay_rate
+    adafactor_beta1: Optional[float] = None     # the first moment's decay; None = none is kept
+    scale_parameter: bool = True         # multiply the step size by max(eps[1], rms(parameter)) per tensor
+    relative_step: bool = True           # the step size is min(1e-2, 1/sqrt(k)) and learning_rate must stay at its default
+    warmup_init: bool = False            # with relative_step: min(1e-6 * k, 1/sqrt(k))
 
 
 @dataclass

@@ -1,6 +1,7 @@
 // extern "C" surface of libsdxlstep (see include/sdxlstep.h for the contract of every entry point).
 #include "capi.h"
 #include <functional>
+#include <mutex>
 
 extern "C" {
 
@@ -1185,17 +1186,127 @@ static int prodigy_step(void* p, const void* grad, int grad_dtype, void* m, void
   q.safeguard = c->safeguard_warmup != 0;
   return launch_prodigy(q, st);
 }
+// algorithm 3 of sdxl_adamw_bf16_step (Adafactor).  The device copy of the table (the caller's entries plus their places in the work-item
+// prefix tables and in the scratch) is cached, keyed by the entries, the device and the two buffers the copy points into, as the
+// LoRA table is per handle; this call has no handle, so one table per process, under a lock
+struct AfCache {
+  std::vector<sdxl_adafactor_tensor> key;
+  int device = -1;
+  float *state = nullptr, *scratch = nullptr;
+  AfTensor* dev = nullptr;
+  int tiles = 0, chunks = 0;
+};
+static AfCache af_cache;
+static std::mutex af_mutex;
+static_assert(AF_ROWS == SDXL_AF_ROWS && AF_COLS == SDXL_AF_COLS, "the geometry and the scratch formula of include/sdxlstep.h");
+// the entries checked against n, then as the kernels read them; every message names the entry
+static int adafactor_table(const sdxl_adafactor_tensor* in, int nt, size_t n, float* state, float* scratch, const char* who,
+                           std::vector<AfTensor>& tab, long* tiles_, long* chunks_) {
+  tab.assign((size_t)nt, AfTensor());
+  size_t end = 0, sc = 4 * (size_t)nt;
+  long tiles = 0, chunks = 0;
+  for (int i = 0; i < nt; ++i) {
+    const sdxl_adafactor_tensor& e = in[i];
+    ARG_CHECK(e.rows >= 1 && e.cols >= 8 && e.cols % 8 == 0, "%s: entry %d is [%d][%d]: rows must be >= 1 and cols a positive multiple of 8", who, i,
+              e.rows, e.cols);
+    const size_t span = (size_t)e.rows * (size_t)e.cols;
+    ARG_CHECK(e.elem_off % 8 == 0, "%s: entry %d starts at element %zu, not a multiple of 8", who, i, e.elem_off);
+    ARG_CHECK(e.elem_off >= end, "%s: entry %d starts at element %zu, before the end %zu of entry %d: the entries must be sorted and must not overlap",
+              who, i, e.elem_off, end, i - 1);
+    ARG_CHECK(e.elem_off <= n && span <= n - e.elem_off, "%s: entry %d covers elements %zu .. %zu, past n = %zu", who, i, e.elem_off, e.elem_off + span, n);
+    ARG_CHECK(e.numel >= 1 && e.numel <= span, "%s: entry %d has numel %zu outside 1 .. rows*cols = %zu", who, i, e.numel, span);
+    ARG_CHECK(e.factored == 0 || e.factored == 1, "%s: entry %d has factored = %d (0 or 1)", who, i, e.factored);
+    ARG_CHECK(e.state_off % 4 == 0, "%s: entry %d has state_off %zu, not a multiple of 4 floats", who, i, e.state_off);
+    end = e.elem_off + span;
+    AfTensor& t = tab[(size_t)i];
+    t.elem_off = e.elem_off; t.numel = e.numel; t.rows = e.rows; t.cols = e.cols; t.factored = e.factored;
+    t.ncb = (e.cols + AF_COLS - 1) / AF_COLS; t.nrb = (e.rows + AF_ROWS - 1) / AF_ROWS;
+    t.nrc = e.factored ? (e.rows + 255) / 256 : 0; t.ncc = e.factored ? (e.cols + 255) / 256 : 0;
+    t.tile0 = (int)tiles; t.chunk0 = (int)chunks;
+    const size_t T = (size_t)t.nrb * t.ncb;
+    tiles += (long)T; chunks += t.nrc + t.ncc;
+    ARG_CHECK(tiles < (1L << 31) && chunks < (1L << 31), "%s: entry %d: too many tiles", who, i);
+    t.R = state + e.state_off; t.C = t.R + e.rows;
+    t.sx = scratch + sc; sc += T;
+    t.su = scratch + sc; sc += T;
+    if (e.factored) {
+      t.rch = scratch + sc; sc += (size_t)t.nrc;
+      t.rowp = scratch + sc; sc += (size_t)e.rows * t.ncb;
+      t.colp = scratch + sc; sc += (size_t)t.nrb * e.cols;
+    }
+  }
+  *tiles_ = tiles; *chunks_ = chunks;
+  return 0;
+}
+static int adafactor_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* comp, size_t n, const sdxl_adamw_config* c,
+                          const float* grad_scale_dev, const unsigned short* rand_inject, hipStream_t st) {
+  const char* who = "adafactor (algorithm 3)";
+  ARG_CHECK(v == nullptr, "%s: v must be NULL (the second moment is factored and lives in af_state: unlike algorithm 2 there is no arena-sized v)", who);
+  ARG_CHECK(rand_inject == nullptr, "%s: rand_inject must be NULL (the update has no random rounding)", who);
+  ARG_CHECK(c->clip_threshold > 0.0 && std::isfinite(c->clip_threshold), "%s: clip_threshold %g must be finite and > 0", who, c->clip_threshold);
+  ARG_CHECK(c->beta2t >= 0.0 && c->beta2t < 1.0, "%s: beta2t %g must lie in [0, 1)", who, c->beta2t);
+  ARG_CHECK(std::isfinite(c->rho), "%s: rho %g must be finite", who, c->rho);
+  ARG_CHECK(c->eps1 >= 0.0 && std::isfinite(c->eps1) && c->eps2 >= 0.0 && std::isfinite(c->eps2), "%s: eps1 %g and eps2 %g must be finite and >= 0", who,
+            c->eps1, c->eps2);
+  ARG_CHECK(c->weight_decay >= 0.0 && std::isfinite(c->weight_decay), "%s: weight_decay %g must be finite and >= 0", who, c->weight_decay);
+  ARG_CHECK(!c->use_beta1 || (c->beta1 >= 0.0 && c->beta1 < 1.0), "%s: beta1 %g must lie in [0, 1)", who, c->beta1);
+  ARG_CHECK((c->use_beta1 != 0) == (m != nullptr), "%s: m must be the fp32 first moment with use_beta1 and NULL without it (missing or unexpected buffer)", who);
+  ARG_CHECK(c->n_tensors >= 0 && (c->n_tensors == 0 || c->tensors != nullptr), "%s: missing buffers (tensors: %d entries)", who, c->n_tensors);
+  ARG_CHECK(c->af_state && c->af_scratch, "%s: missing buffers (af_state, af_scratch)", who);
+  ARG_CHECK((((uintptr_t)c->af_state | (uintptr_t)c->af_scratch) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  AdafactorP q;
+  memset(&q, 0, sizeof(q));
+  q.p = (bf16*)p; q.m = (bf16*)(m ? m : p); q.v = (bf16*)p; q.n = n;        // (m, v: addresses for the shared checks only)
+  if (grad_dtype == 0) q.grad_f32 = (const float*)grad; else q.grad_bf16 = (const bf16*)grad;
+  q.grad_round_bf16 = c->grad_round_bf16;
+  q.grad_scale = grad_scale_dev;
+  q.ema = c->ema; q.ema_omd = c->ema_one_minus_decay;
+  q.c = (bf16*)comp; q.m32 = (float*)m; q.scal = c->af_scratch;
+  // host doubles rounded to float once
+  q.beta1 = (float)c->beta1; q.omb1 = (float)(1.0 - c->beta1);
+  q.eps1 = (float)c->eps1; q.eps2 = (float)c->eps2; q.clip = (float)c->clip_threshold;
+  q.b2t = (float)c->beta2t; q.omb2t = (float)(1.0 - c->beta2t); q.rho = (float)c->rho; q.wd = (float)c->weight_decay;
+  q.scale_parameter = c->scale_parameter != 0;
+  q.n_tensors = c->n_tensors;
+  std::vector<AfTensor> tab;
+  long tiles = 0, chunks = 0;
+  CHK(adafactor_table(c->tensors, c->n_tensors, n, c->af_state, c->af_scratch, who, tab, &tiles, &chunks));
+  q.tiles = (int)tiles; q.chunks = (int)chunks;
+  {                                                                        // the buffer checks of the launch, with nothing to launch
+    AdafactorP none = q;
+    none.n_tensors = 0;
+    CHK(launch_adafactor(none, st));
+  }
+  if (q.n_tensors == 0 || n == 0) return 0;
+  std::lock_guard<std::mutex> lock(af_mutex);
+  int device = -1;
+  HIP_CHECK_RET(hipGetDevice(&device));
+  AfCache& k = af_cache;
+  const bool hit = k.dev && k.device == device && k.state == c->af_state && k.scratch == c->af_scratch && k.key.size() == (size_t)c->n_tensors &&
+                   memcmp(k.key.data(), c->tensors, sizeof(sdxl_adafactor_tensor) * (size_t)c->n_tensors) == 0;
+  if (!hit) {
+    if (k.dev) (void)hipFree(k.dev);
+    k.dev = nullptr;
+    HIP_CHECK_RET(hipMalloc((void**)&k.dev, tab.size() * sizeof(AfTensor)));
+    HIP_CHECK_RET(hipMemcpy(k.dev, tab.data(), tab.size() * sizeof(AfTensor), hipMemcpyHostToDevice));
+    k.key.assign(c->tensors, c->tensors + c->n_tensors);
+    k.device = device; k.state = c->af_state; k.scratch = c->af_scratch;
+  }
+  q.table = k.dev;
+  return launch_adafactor(q, st);
+}
 int sdxl_adamw_bf16_step(void* p, const void* grad, int grad_dtype, void* m, void* v, void* shift, size_t n,
                          const sdxl_adamw_config* c, const float* grad_scale_dev, const unsigned short* rand_inject,
                          void* st) {
   ARG_CHECK(c, "null config");
   ARG_CHECK(grad_dtype == 0 || grad_dtype == 1, "adamw: grad_dtype %d (0 = fp32, 1 = bf16)", grad_dtype);
-  ARG_CHECK(c->algorithm >= 0 && c->algorithm <= 2, "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan, algorithm 2 = Prodigy)",
-            c->algorithm);
+  ARG_CHECK(c->algorithm >= 0 && c->algorithm <= 3,
+            "adamw: algorithm %d (0 = AdamW_BF16, 1 = schedule-free Kahan, algorithm 2 = Prodigy, algorithm 3 = Adafactor)", c->algorithm);
   ARG_CHECK(c->ema == nullptr || (c->ema_one_minus_decay >= 0.f && c->ema_one_minus_decay <= 1.f),
             "adamw: ema_one_minus_decay %g must lie in [0, 1]", (double)c->ema_one_minus_decay);
   if (c->algorithm == 1) return sf_kahan_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
   if (c->algorithm == 2) return prodigy_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
+  if (c->algorithm == 3) return adafactor_step(p, grad, grad_dtype, m, v, shift, n, c, grad_scale_dev, rand_inject, (hipStream_t)st);
   AdamWP q;
   memset(&q, 0, sizeof(q));
   CHK(fill_optim(q, p, grad, grad_dtype, m, v, n, c, grad_scale_dev, c->step >= 1.0, "adamw"));

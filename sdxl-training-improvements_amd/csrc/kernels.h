@@ -533,6 +533,30 @@ struct ProdigyP : OptimP {
   int safeguard;
 };
 int launch_prodigy(const ProdigyP& q, hipStream_t st);
+// Adafactor (adafactor_*_kernel; include/sdxlstep.h, algorithm 3, is the contract).  One table entry per tensor, as the kernels read it:
+// the caller's entry plus its place in the two work-item prefix tables and in the scratch
+struct AfTensor {
+  size_t elem_off, numel;
+  float *R, *C;                // factored: the row and column statistics in af_state (C = R + rows); unfactored: R = v, C unused
+  float *sx, *su;              // [tiles] the tiles' sums of x*x and of u*u
+  float *rch, *rowp, *colp;    // factored: [ceil(rows/256)] chunk partials of R', [rows][ncb] row sums, [nrb][cols] column sums
+  int rows, cols, factored;
+  int ncb, nrb;                // column blocks of AF_COLS, row blocks of AF_ROWS
+  int tile0;                   // tiles of the entries before this one (launches 1, 3, 5)
+  int nrc, ncc, chunk0;        // chunks of 256 rows, of 256 columns, and the chunks of the entries before this one (launch 2)
+};
+constexpr int AF_ROWS = 128, AF_COLS = 256;
+// OptimP's bf16 m / v carry addresses for check_arenas only (v is p's: the algorithm has no arena-sized second moment)
+struct AdafactorP : OptimP {
+  const AfTensor* table;       // device
+  int n_tensors, tiles, chunks;
+  bf16* c;                     // compensation: the true parameter is p + c
+  float* m32;                  // first moment, or nullptr (use_beta1 == 0)
+  float* scal;                 // [n_tensors][4] rho_t, eta_t, rms_u, rms_p
+  float eps1, eps2, clip, b2t, omb2t, rho, omb1, wd;
+  int scale_parameter;
+};
+int launch_adafactor(const AdafactorP& q, hipStream_t st);
 int launch_adamw_decay(bf16* shift, const bf16* p, size_t n, float alpha_bf16, hipStream_t st);
 
 

@@ -16,6 +16,7 @@
 //
 // Two more updates share its entry point and its core, each with its own head comment below: the schedule-free Kahan AdamW
 // (algorithm 1, one pass, 16 / 20 B per element) and Prodigy (algorithm 2, two passes around a chip-wide reduction, 50 B per element).
+// Adafactor (algorithm 3) shares the entry point and the element-loop parts, but walks a table of tensors in tiles: five launches.
 #include "kernels.h"
 #include "../../include/sdxlstep.h"
 #include <type_traits>
@@ -423,6 +424,315 @@ int launch_prodigy(const ProdigyP& q, hipStream_t st) {
   with_flags([&](auto ema) {
     hipLaunchKernelGGL((prodigy_apply_kernel<decltype(ema)::value>), grid, dim3(256), 0, st, q);
   }, q.ema != nullptr);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+// ---- Adafactor (Shazeer & Stern 2018; include/sdxlstep.h, algorithm 3, is the contract) ------------------------------------------
+// The second moment of a matrix is a row and a column statistic, and the update is clipped by its own RMS per tensor, so the step
+// is per-tensor reductions around element passes.  One grid covers every tensor: a workgroup takes tiles of AF_ROWS x AF_COLS
+// elements from the prefix table (tensor, row block, column block); the kernel boundary is the only synchronisation.
+//   stats:   reads g (4 B; + p, c = 4 B with scale_parameter); a tile's row sums, column sums and sum of x^2 from one pass
+//   reduce:  the tile sums -> R', C' and the chunk partials of R' (a few bytes per row and column)
+//   usq:     reads g (4 B; unfactored: v read and written); a tile's sum of u^2
+//   scalars: one workgroup per tensor -> rho_t, eta_t
+//   apply:   reads g, p, c (8 B), writes p, c (4 B); + 8 B with beta1, + 8 B with the EMA
+// Per element 20 B (24 B with scale_parameter: g is read three times) against AdamW_BF16's 20 B; state rows + cols floats per matrix.
+__device__ __forceinline__ int af_find(const AfTensor* tab, int n, int item, int AfTensor::*first) {
+  int lo = 0, hi = n - 1;                  // the last entry whose first work item is <= item
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].*first <= item) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ float af_rsqrt(float y) { return 1.f / __builtin_sqrtf(y); }
+// the workgroup's fixed tree over one value per thread: x[j] += x[j + h], h = 128 .. 1; the sum is returned to thread 0
+__device__ __forceinline__ float af_block_sum(float* red, float x) {
+  __syncthreads();                         // red may still be read from the previous use
+  red[threadIdx.x] = x;
+  __syncthreads();
+#pragma unroll
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+// where a thread stands in a tile
+struct AfTile {
+  const AfTensor* t;
+  int rb, cb, lane, rl;                    // lane: its 8-column vector in the tile, rl: its first row in the tile
+  int col0;                                // its first column in the tensor
+  bool col_ok;
+};
+__device__ __forceinline__ AfTile af_tile(const AdafactorP& q, int tile) {
+  AfTile a;
+  a.t = q.table + af_find(q.table, q.n_tensors, tile, &AfTensor::tile0);
+  const int local = tile - a.t->tile0;
+  a.rb = local / a.t->ncb; a.cb = local - a.rb * a.t->ncb;
+  a.lane = threadIdx.x & 31; a.rl = threadIdx.x >> 5;
+  a.col0 = a.cb * AF_COLS + a.lane * 8;
+  a.col_ok = a.col0 < a.t->cols;
+  return a;
+}
+__device__ __forceinline__ float af_mean_row(const AfTensor& t) {
+  float s = 0.f;
+  for (int j = 0; j < t.nrc; ++j) s = s + t.rch[j];
+  return s / (float)t.rows;
+}
+// rf = rsqrt(R'_r / mean) of a tile's rows into LDS, once per row (thread j takes row j of the tile); every thread of the workgroup calls it
+__device__ __forceinline__ void af_row_factors(const AfTensor& t, int rb, float* rfs) {
+  __syncthreads();                         // rfs may still be read from the previous tile
+  if (t.factored && (int)threadIdx.x < AF_ROWS) {
+    const int r = rb * AF_ROWS + (int)threadIdx.x;
+    if (r < t.rows) rfs[threadIdx.x] = af_rsqrt(t.R[r] / af_mean_row(t));
+  }
+  __syncthreads();
+}
+
+template <bool F32G>
+__global__ __launch_bounds__(256) void adafactor_stats_kernel(const AdafactorP q) {
+  __shared__ float red[256];
+  __shared__ float colred[8][AF_COLS];
+  const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
+  for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x) {
+    const AfTile a = af_tile(q, tile);
+    const AfTensor& t = *a.t;
+    if (!t.factored && !q.scale_parameter) continue;       // (uniform over the workgroup) nothing to sum
+    float colacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float sx = 0.f;
+#pragma unroll 4
+    for (int i = 0; i < AF_ROWS / 8; ++i) {
+      const int r = a.rb * AF_ROWS + i * 8 + a.rl;
+      const bool ok = a.col_ok && r < t.rows;
+      float rs = 0.f;
+      if (ok) {
+        const size_t e0 = t.elem_off + (size_t)r * t.cols + a.col0;
+        if (t.factored) {
+          float g[8];
+          load_grad8<true>(q, F32G, e0, g);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float gr = scaled_grad(q, g[e], gscale);
+            const float qq = (gr * gr) + q.eps1;
+            rs = rs + qq;
+            colacc[e] = colacc[e] + qq;
+          }
+        }
+        if (q.scale_parameter) {
+          const bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float x = bf(pv[e]) + bf(cv[e]);
+            sx = sx + (x * x);
+          }
+        }
+      }
+      if (t.factored) {                                     // the row's 32 threads: every one of them ends with the same sum
+#pragma unroll
+        for (int h = 16; h >= 1; h >>= 1) rs = rs + __shfl_xor(rs, h);
+        if (a.lane == 0 && r < t.rows) t.rowp[(size_t)r * t.ncb + a.cb] = rs;
+      }
+    }
+    if (t.factored) {
+      __syncthreads();                                      // colred may still be read from the previous tile
+#pragma unroll
+      for (int e = 0; e < 8; ++e) colred[a.rl][a.lane * 8 + e] = colacc[e];
+      __syncthreads();
+      const int col = a.cb * AF_COLS + (int)threadIdx.x;
+      if (col < t.cols) {
+        float s = colred[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) s = s + colred[k][threadIdx.x];
+        t.colp[(size_t)a.rb * t.cols + col] = s;
+      }
+    }
+    if (q.scale_parameter) {
+      const float s = af_block_sum(red, sx);
+      if (threadIdx.x == 0) t.sx[tile - t.tile0] = s;
+    }
+  }
+}
+
+// work items: per factored tensor its chunks of 256 rows, then its chunks of 256 columns
+__global__ __launch_bounds__(256) void adafactor_reduce_kernel(const AdafactorP q) {
+  __shared__ float red[256];
+  for (int item = blockIdx.x; item < q.chunks; item += gridDim.x) {
+    const AfTensor& t = q.table[af_find(q.table, q.n_tensors, item, &AfTensor::chunk0)];
+    const int local = item - t.chunk0;
+    if (local < t.nrc) {
+      const int o = local * 256 + (int)threadIdx.x;
+      float r1 = 0.f;
+      if (o < t.rows) {
+        float s = 0.f;
+        for (int cb = 0; cb < t.ncb; ++cb) s = s + t.rowp[(size_t)o * t.ncb + cb];
+        r1 = (q.b2t * t.R[o]) + (q.omb2t * (s / (float)t.cols));
+        t.R[o] = r1;
+      }
+      const float part = af_block_sum(red, r1);
+      if (threadIdx.x == 0) t.rch[local] = part;
+    } else {
+      const int i = (local - t.nrc) * 256 + (int)threadIdx.x;
+      if (i < t.cols) {
+        float s = 0.f;
+        for (int rb = 0; rb < t.nrb; ++rb) s = s + t.colp[(size_t)rb * t.cols + i];
+        t.C[i] = (q.b2t * t.C[i]) + (q.omb2t * (s / (float)t.rows));
+      }
+    }
+  }
+}
+
+// u of a thread's 8 elements in row r (factored: rf = rsqrt(R'_r / mean), cf = rsqrt(C') of its columns; unfactored: from v, which
+// UPDATE_V also advances and writes back); the same expressions in usq and in apply, so both see the same bits
+template <bool F32G, bool UPDATE_V>
+__device__ __forceinline__ void af_update8(const AdafactorP& q, const AfTensor& t, size_t e0, size_t v0, float rf, const float cf[8], float gscale,
+                                           float u[8]) {
+  float g[8];
+  load_grad8<true>(q, F32G, e0, g);
+  if (t.factored) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) u[e] = (rf * cf[e]) * scaled_grad(q, g[e], gscale);
+  } else {
+    float v[8];
+    load8(t.R + v0, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float gr = scaled_grad(q, g[e], gscale);
+      if constexpr (UPDATE_V) v[e] = (q.b2t * v[e]) + (q.omb2t * ((gr * gr) + q.eps1));
+      u[e] = af_rsqrt(v[e]) * gr;
+    }
+    if constexpr (UPDATE_V) store8(t.R + v0, v);
+  }
+}
+
+template <bool F32G>
+__global__ __launch_bounds__(256) void adafactor_usq_kernel(const AdafactorP q) {
+  __shared__ float red[256], rfs[AF_ROWS];
+  const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
+  for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x) {
+    const AfTile a = af_tile(q, tile);
+    const AfTensor& t = *a.t;
+    float cf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (t.factored && a.col_ok) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cf[e] = af_rsqrt(t.C[a.col0 + e]);
+    }
+    af_row_factors(t, a.rb, rfs);
+    float su = 0.f;
+#pragma unroll 4
+    for (int i = 0; i < AF_ROWS / 8; ++i) {
+      const int r = a.rb * AF_ROWS + i * 8 + a.rl;
+      if (a.col_ok && r < t.rows) {
+        const size_t v0 = (size_t)r * t.cols + a.col0;
+        const float rf = t.factored ? rfs[i * 8 + a.rl] : 0.f;
+        float u[8];
+        af_update8<F32G, true>(q, t, t.elem_off + v0, v0, rf, cf, gscale, u);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) su = su + (u[e] * u[e]);
+      }
+    }
+    const float s = af_block_sum(red, su);
+    if (threadIdx.x == 0) t.su[tile - t.tile0] = s;
+  }
+}
+
+// one workgroup per tensor
+__global__ __launch_bounds__(256) void adafactor_scalars_kernel(const AdafactorP q) {
+  __shared__ double red_u[256], red_x[256];
+  for (int ti = blockIdx.x; ti < q.n_tensors; ti += gridDim.x) {
+    const AfTensor& t = q.table[ti];
+    const int T = t.nrb * t.ncb, per = (T + 255) / 256;
+    double su = 0.0, sx = 0.0;
+    for (int b = (int)threadIdx.x * per; b < ((int)threadIdx.x + 1) * per && b < T; ++b) {
+      su = su + (double)t.su[b];
+      if (q.scale_parameter) sx = sx + (double)t.sx[b];
+    }
+    __syncthreads();
+    red_u[threadIdx.x] = su;
+    red_x[threadIdx.x] = sx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double U = 0.0, X = 0.0;
+      for (int j = 0; j < 256; ++j) {
+        U = U + red_u[j];
+        X = X + red_x[j];
+      }
+      const float nf = (float)t.numel;
+      const float rms_u = __builtin_sqrtf((float)U / nf), rms_p = __builtin_sqrtf((float)X / nf);
+      const float rho_t = q.scale_parameter ? q.rho * __builtin_fmaxf(q.eps2, rms_p) : q.rho;
+      const float eta_t = rho_t / __builtin_fmaxf(1.f, rms_u / q.clip);
+      float* o = q.scal + 4 * (size_t)ti;
+      o[0] = rho_t; o[1] = eta_t; o[2] = rms_u; o[3] = rms_p;
+    }
+  }
+}
+
+template <bool F32G, bool EMA, bool BETA1>
+__global__ __launch_bounds__(256) void adafactor_apply_kernel(const AdafactorP q) {
+  __shared__ float rfs[AF_ROWS];
+  const float gscale = q.grad_scale ? *q.grad_scale : 1.f;
+  for (int tile = blockIdx.x; tile < q.tiles; tile += gridDim.x) {
+    const AfTile a = af_tile(q, tile);
+    const AfTensor& t = *a.t;
+    af_row_factors(t, a.rb, rfs);
+    if (!a.col_ok) continue;
+    const float* sc = q.scal + 4 * (size_t)(a.t - q.table);
+    const float rho_t = sc[0], eta_t = sc[1];
+    const float decay = q.wd * rho_t;
+    float cf[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (t.factored) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cf[e] = af_rsqrt(t.C[a.col0 + e]);
+    }
+#pragma unroll 2
+    for (int i = 0; i < AF_ROWS / 8; ++i) {
+      const int r = a.rb * AF_ROWS + i * 8 + a.rl;
+      if (r >= t.rows) break;
+      const size_t v0 = (size_t)r * t.cols + a.col0, e0 = t.elem_off + v0;
+      const float rf = t.factored ? rfs[i * 8 + a.rl] : 0.f;
+      float u[8], m[8];
+      af_update8<F32G, false>(q, t, e0, v0, rf, cf, gscale, u);
+      bf16x8 pv = __builtin_nontemporal_load((const bf16x8*)(q.p + e0)), cv = __builtin_nontemporal_load((const bf16x8*)(q.c + e0));
+      if constexpr (BETA1) load8(q.m32 + e0, m);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float d = eta_t * u[e];
+        if constexpr (BETA1) {
+          m[e] = (q.beta1 * m[e]) + (q.omb1 * d);
+          d = m[e];
+        }
+        float x = bf(pv[e]) + bf(cv[e]);
+        if (q.wd != 0.f) x = x - (decay * x);
+        x = x - d;
+        const bf16 pb = rn(x);
+        pv[e] = pb;
+        cv[e] = rn(x - bf(pb));
+      }
+      __builtin_nontemporal_store(pv, (bf16x8*)(q.p + e0));
+      __builtin_nontemporal_store(cv, (bf16x8*)(q.c + e0));
+      if constexpr (BETA1) store8(q.m32 + e0, m);
+      if constexpr (EMA) ema_update8(q.ema + e0, pv, q.ema_omd);
+    }
+  }
+}
+
+int launch_adafactor(const AdafactorP& q, hipStream_t st) {
+  const char* who = "adafactor (algorithm 3)";
+  if (int rc = check_arenas(q, q.c, true, 0, who, "%s: n=%zu must be a multiple of 8")) return rc;
+  ARG_CHECK((((uintptr_t)q.m32 | (uintptr_t)q.scal) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  if (q.n == 0 || q.n_tensors == 0) return 0;
+  // one workgroup per tile (per chunk, per tensor) up to arena_grid's cap, the rest by grid stride
+  const dim3 tiles = arena_grid((size_t)q.tiles * 2048), chunks = arena_grid((size_t)q.chunks * 2048), tensors = arena_grid((size_t)q.n_tensors * 2048);
+  with_flags([&](auto f32g) {
+    hipLaunchKernelGGL((adafactor_stats_kernel<decltype(f32g)::value>), tiles, dim3(256), 0, st, q);
+    if (q.chunks > 0) hipLaunchKernelGGL(adafactor_reduce_kernel, chunks, dim3(256), 0, st, q);
+    hipLaunchKernelGGL((adafactor_usq_kernel<decltype(f32g)::value>), tiles, dim3(256), 0, st, q);
+  }, q.grad_f32 != nullptr);
+  hipLaunchKernelGGL(adafactor_scalars_kernel, tensors, dim3(256), 0, st, q);
+  with_flags([&](auto f32g, auto ema, auto beta1) {
+    hipLaunchKernelGGL((adafactor_apply_kernel<decltype(f32g)::value, decltype(ema)::value, decltype(beta1)::value>), tiles, dim3(256), 0, st, q);
+  }, q.grad_f32 != nullptr, q.ema != nullptr, q.m32 != nullptr);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -188,6 +188,15 @@ LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}
 MASK_NORMS = {"mean": 0, "masked_mean": 1}
 
 
+class AdafactorTensor(C.Structure):
+    """sdxl_adafactor_tensor: one tensor of the Adafactor table, a row-major matrix inside the arena"""
+    _fields_ = [("elem_off", C.c_size_t), ("rows", C.c_int), ("cols", C.c_int), ("numel", C.c_size_t), ("factored", C.c_int),
+                ("state_off", C.c_size_t)]
+
+
+AF_ROWS, AF_COLS = 128, 256                          # SDXL_AF_ROWS, SDXL_AF_COLS: the tile of the Adafactor launches
+
+
 class AdamWConfig(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("step", C.c_double), ("decay_this_iteration", C.c_double), ("reference_ema", C.c_int),
@@ -200,7 +209,11 @@ class AdamWConfig(C.Structure):
                 # appended: algorithm 2 = Prodigy (optimizer.ProdigyBF16)
                 ("beta3", C.c_double), ("d0", C.c_double), ("d_coef", C.c_double), ("growth_rate", C.c_double),
                 ("prodigy_bc", C.c_double), ("safeguard_warmup", C.c_int), ("p0", C.c_void_p), ("s", C.c_void_p),
-                ("prodigy_state", C.c_void_p)]
+                ("prodigy_state", C.c_void_p),
+                # appended: algorithm 3 = Adafactor (optimizer.AdafactorBF16)
+                ("clip_threshold", C.c_double), ("eps1", C.c_double), ("eps2", C.c_double), ("beta2t", C.c_double), ("rho", C.c_double),
+                ("scale_parameter", C.c_int), ("use_beta1", C.c_int), ("tensors", C.c_void_p), ("n_tensors", C.c_int),
+                ("af_state", C.c_void_p), ("af_scratch", C.c_void_p)]
 
 
 PRODIGY_MAX_GRID = 4096                              # SDXL_PRODIGY_MAX_GRID: the largest grid of the optimizer launches

@@ -12,7 +12,7 @@ The objective comes from `training.native_objective` ("ddpm" | "flow_matching", 
 reference's config.  `model.unet` (the diffusers UNet loaded by models/sdxl.py:25-40) is imported into the native engine at
 construction and written back by `save_checkpoint` / `sync_to_model`.  The reference's AdamWBF16 instance (main.py:73-86)
 holds per-tensor PyTorch state and is replaced by the fused equivalent on the packed arena (same hyper-parameters, read from
-its `param_groups`).  The fused class follows `optimizer.optimizer_type` (trainer.build_optimizer); an optimizer handed in whose
+its `param_groups`).  The fused class follows `optimizer.optimizer_type` (trainer.build_optimizer: "adafactor" included); an optimizer handed in whose
 class is the reference's `AdamWScheduleFreeKahan` selects the fused schedule-free Kahan AdamW as well, with `warmup_steps` and
 `kahan_sum` also read from its `param_groups`.  The build-only keys of `training` (EMA, `loss_type` / `huber_c` / `huber_schedule`,
 `snr_weighting`, `tag_weights_per_sample`, `log_per_sample_loss`, `masked_loss`, `noise_offset`, `input_perturbation`,
@@ -52,7 +52,19 @@ class NativeMI355XTrainer(NativeSDXLTrainer):
         cfg.training.method = str(_get(config, "training.native_objective", "ddpm")).lower() if method == self.name else method
         native_opt = None
         groups = getattr(optimizer, "param_groups", None)
-        if groups is not None:                      # take the hyper-parameters of the optimizer main.py built
+        if groups is not None and type(optimizer).__name__ == "Adafactor":      # transformers.optimization.Adafactor: its own keys
+            g = next(iter(groups))
+            o = cfg.optimizer
+            o.optimizer_type = "adafactor"
+            o.relative_step = bool(g.get("relative_step", g.get("lr") is None))
+            if g.get("lr") is not None and not o.relative_step:
+                o.learning_rate = float(g["lr"])
+            o.eps = tuple(float(x) for x in g.get("eps", o.eps))
+            o.clip_threshold, o.decay_rate = float(g.get("clip_threshold", o.clip_threshold)), float(g.get("decay_rate", o.decay_rate))
+            o.adafactor_beta1 = None if g.get("beta1") is None else float(g["beta1"])
+            o.weight_decay = float(g.get("weight_decay", 0.0))
+            o.scale_parameter, o.warmup_init = bool(g.get("scale_parameter", True)), bool(g.get("warmup_init", False))
+        elif groups is not None:                    # take the hyper-parameters of the optimizer main.py built
             g = next(iter(groups))
             cfg.optimizer.learning_rate = float(g.get("lr", cfg.optimizer.learning_rate))
             b = g.get("betas", (cfg.optimizer.beta1, cfg.optimizer.beta2))

@@ -3,8 +3,8 @@
 FusedArenaOptimizer is what the trainer knows: gradients taken from the arena, one fused launch per update (per piece under
 ZeRO-1), and the host surface step(grads, grad_scale, zero_grad, pieces), zero_grad, register_step_post_hook, param_groups,
 step_count, state_dict / load_state_dict, state_arenas, attach_ema (an ema.WeightEMA updated inside the same launch, on the same
-pieces).  Its three algorithms, by optimizer_type (BY_TYPE): AdamWBF16 ("adamw_bf16", the default), AdamWScheduleFreeKahanBF16
-("adamw_schedule_free_kahan") and ProdigyBF16 ("prodigy"); see the docstrings of the last two.
+pieces).  Its four algorithms, by optimizer_type (BY_TYPE): AdamWBF16 ("adamw_bf16", the default), AdamWScheduleFreeKahanBF16
+("adamw_schedule_free_kahan"), ProdigyBF16 ("prodigy") and AdafactorBF16 ("adafactor"); see the docstrings of the last three.
 
 AdamWBF16:
 
@@ -21,7 +21,7 @@ from __future__ import annotations
 import ctypes as C
 import logging
 import math
-from typing import Any, Dict, Optional
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -56,16 +56,22 @@ class FusedArenaOptimizer:
 
     ZERO1 = True
 
-    def __init__(self, net, group: Dict[str, Any], *, third: bool, grad_round_bf16: bool, moment_dtype=torch.bfloat16):
+    def __init__(self, net, group: Dict[str, Any], *, third: bool, grad_round_bf16: bool, moment_dtype=torch.bfloat16, moments: bool = True):
         """group: param_groups[0], already checked (check_hyper and the subclass's own); third: allocate the third arena;
-        moment_dtype: of exp_avg and exp_avg_sq"""
+        moment_dtype: of exp_avg and exp_avg_sq; moments False: an algorithm without arena-sized moments -- exp_avg and exp_avg_sq are
+        then stride-0 views of one zero (they read as the zero moment of the arena's size and hold 4 bytes each), and the subclass
+        says what its launch gets in their place (moment_arenas)"""
         self.net = net
         self.L = getattr(net, "L", None)                      # the loaded libsdxlstep; step() refuses to run without it
         self.param_groups = [group]
         w = net.weights
         assert w.dtype == torch.bfloat16, "only bfloat16 is supported."          # adamw_bfloat16/__init__.py:98
-        self.exp_avg = torch.zeros_like(w, dtype=moment_dtype)
-        self.exp_avg_sq = torch.zeros_like(w, dtype=moment_dtype)
+        if moments:
+            self.exp_avg = torch.zeros_like(w, dtype=moment_dtype)
+            self.exp_avg_sq = torch.zeros_like(w, dtype=moment_dtype)
+        else:
+            self.exp_avg = torch.zeros(1, dtype=moment_dtype, device=w.device).expand(w.numel())
+            self.exp_avg_sq = torch.zeros(1, dtype=moment_dtype, device=w.device).expand(w.numel())
         setattr(self, self.THIRD, torch.zeros_like(w) if third else None)
         self.grad_round_bf16 = bool(grad_round_bf16)
         self.step_count = 0
@@ -108,6 +114,14 @@ class FusedArenaOptimizer:
         third = getattr(self, self.THIRD)
         return (self.exp_avg, self.exp_avg_sq) + ((third,) if third is not None else ())
 
+    def moment_arenas(self):
+        """the m and v arguments of the launch"""
+        return self.exp_avg, self.exp_avg_sq
+
+    def fill_hyper(self, cfg, grp) -> None:
+        """the fields of the config every launch gets from the group"""
+        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
+
     def _load_arenas(self, st: Dict[str, Any]) -> None:
         self.step_count = int(st["step"])
         for k, t in zip(("exp_avg", "exp_avg_sq", self.THIRD), self.state_arenas()):
@@ -133,7 +147,7 @@ class FusedArenaOptimizer:
             raise ValueError(f"{type(self).__name__}.step takes no pieces: its update reduces over the whole arena")
         cfg = lib.AdamWConfig()
         lib.check(self.L.sdxl_adamw_default_config(C.byref(cfg)))
-        cfg.lr, (cfg.beta1, cfg.beta2), cfg.eps = float(grp["lr"]), grp["betas"], float(grp["eps"])
+        self.fill_hyper(cfg, grp)
         cfg.grad_round_bf16 = int(self.grad_round_bf16)
         begun = self.begin_step(cfg, grp)                          # the algorithm's fields and what it books before the launches
         if self.ema is not None:
@@ -141,12 +155,13 @@ class FusedArenaOptimizer:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream) if w.is_cuda else None
         gsz = g.element_size()
         todo = [(0, w.numel(), 0)] if pieces is None else list(pieces)
+        m, v = self.moment_arenas()
         for off, cnt, goff in todo:
             cfg.elem_offset = off
             cfg.ema = self.ema.arena.data_ptr() + 4 * off if self.ema is not None else None
             at = lambda t, o=off: C.c_void_p(t.data_ptr() + t.element_size() * o) if t is not None else None
             lib.check(self.L.sdxl_adamw_bf16_step(at(w), C.c_void_p(g.data_ptr() + gsz * goff), 0 if g.dtype == torch.float32 else 1,
-                                                  at(self.exp_avg), at(self.exp_avg_sq), at(getattr(self, self.THIRD)), cnt,
+                                                  at(m), at(v), at(getattr(self, self.THIRD)), cnt,
                                                   C.byref(cfg), _ptr(grad_scale), _ptr(rand), st), self.LAUNCH)
         self.finish_step(begun, todo, st)                         # its remaining launches and bookkeeping
         if zero_grad:
@@ -447,5 +462,268 @@ class ProdigyBF16(FusedArenaOptimizer):
             self.step_count += 1
 
 
+# ---------------------------------------------------------------------------------------------- Adafactor
+class AfEntry(NamedTuple):
+    """one tensor of the Adafactor table (sdxl_adafactor_tensor without its state offset): a row-major [rows][cols] matrix at elem_off
+    of the arena, numel real elements, factored or not"""
+    name: str
+    elem_off: int
+    rows: int
+    cols: int
+    numel: int
+    factored: bool
+
+    def state_floats(self) -> int:
+        """R[rows] then C[cols] rounded up to 4 floats, or v[rows * cols]"""
+        return (self.rows + self.cols + 3) // 4 * 4 if self.factored else self.rows * self.cols
+
+
+def _pad8(n: int) -> int:
+    return (int(n) + 7) // 8 * 8
+
+
+def adafactor_layout(shapes: Dict[str, Sequence[int]], ranges: Dict[str, Tuple[int, int]]) -> List[AfEntry]:
+    """Which tensor of an arena Adafactor factors, as a pure function of the state-dict shapes and the arena ranges
+    {name: (element offset, element count)}; the entries sorted by offset.
+    A 2-D tensor is the matrix [out][in], a 4-D one [shape[0]][prod(rest)] (this project's LoRA convention; in the arena a convolution
+    is the plain row-major [cout][9 * cin], and a permutation of the columns changes no statistic; so ff.net.0.proj, whose rows are
+    permuted, is a plain matrix too).  It is factored when its range is exactly rows * cols elements and cols is a multiple of 8 (a row
+    is whole 16-byte vectors): conv_out is its 4 real rows.  Everything else runs unfactored with numel the real count: a tensor whose
+    range holds pads (conv_in: the input channels are padded to 8 inside its range), a matrix with short rows (a LoRA up factor of rank
+    4) and every 1-D tensor; its pads hold g = 0 and p = 0 and stay +0.
+    The HF class factors a 4-D tensor over its last two dimensions (kh, kw); factoring a 3 x 3 pair saves nothing, so that is
+    deliberately not followed.  ValueError when a range does not start on a multiple of 8 or two entries overlap."""
+    out = []
+    for name, shape in shapes.items():
+        off, n = (int(x) for x in ranges[name])
+        shape = tuple(int(x) for x in shape)
+        real = 1
+        for x in shape:
+            real *= x
+        if real < 1 or n < real:
+            raise ValueError(f"adafactor_layout: {name!r} has {real} elements in a range of {n}")
+        if off % 8:
+            raise ValueError(f"adafactor_layout: {name!r} starts at element {off}, not a multiple of 8")
+        rows = shape[0] if len(shape) in (2, 4) else 1
+        cols = real // rows
+        if len(shape) in (2, 4) and cols % 8 == 0 and n == real:
+            out.append(AfEntry(name, off, rows, cols, real, True))
+        elif len(shape) in (2, 4) and n % rows == 0 and (n // rows) % 8 == 0:
+            out.append(AfEntry(name, off, rows, n // rows, real, False))
+        else:
+            out.append(AfEntry(name, off, 1, _pad8(n), real, False))
+    out.sort(key=lambda e: e.elem_off)
+    for a, b in zip(out, out[1:]):
+        if a.elem_off + a.rows * a.cols > b.elem_off:
+            raise ValueError(f"adafactor_layout: {a.name!r} ([{a.rows}][{a.cols}] at {a.elem_off}) overlaps {b.name!r} at {b.elem_off}")
+    return out
+
+
+def adafactor_scratch_floats(entries: Sequence[AfEntry]) -> int:
+    """the floats of af_scratch for a table (include/sdxlstep.h, algorithm 3): 4 per entry, then per entry two floats per tile and, for a
+    factored one, the chunk partials of R', the row sums per column block and the column sums per row block"""
+    total = 4 * len(entries)
+    for e in entries:
+        ncb, nrb = -(-e.cols // lib.AF_COLS), -(-e.rows // lib.AF_ROWS)
+        total += 2 * nrb * ncb
+        if e.factored:
+            total += -(-e.rows // 256) + e.rows * ncb + nrb * e.cols
+    return total
+
+
+def adapter_shapes(adapters) -> Dict[str, Tuple[int, int]]:
+    """the factor matrices of a lora.LoRAAdapters arena under the keys of its param_ranges(): lora_A [rank][in], lora_B [out][rank].
+    ValueError for an algorithm whose arena this cannot describe."""
+    algo = getattr(adapters, "algo", "lora")
+    if algo != "lora":
+        raise ValueError(f"optimizer_type 'adafactor' is built for lora_algo 'lora' only: the adapter arena of lora_algo {algo!r} has factors "
+                         "its table does not describe (train it with adamw_bf16, adamw_schedule_free_kahan or prodigy)")
+    out = {}
+    for k, lay in adapters.layout.items():
+        mod = k[: -len(".weight")]
+        o, i = lay[-2:]
+        out[f"{mod}.lora_A.weight"] = (int(adapters.rank), int(i))
+        out[f"{mod}.lora_B.weight"] = (int(o), int(adapters.rank))
+    return out
+
+
+class AdafactorBF16(FusedArenaOptimizer):
+    """Adafactor (Shazeer & Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost") on the packed arenas, with the
+    arguments, defaults, checks and arithmetic of transformers.optimization.Adafactor: the second moment of a weight matrix is one row
+    and one column statistic, the update of each tensor is clipped by its own RMS, and with scale_parameter the step size follows the
+    RMS of the tensor.  The published SDXL full fine-tune recipe is scale_parameter=False, relative_step=False, lr=4e-7.
+
+    State: af_state (fp32: rows + cols floats per factored tensor, one per element of the others; adafactor_layout says which), the
+    bf16 compensation arena comp (the true parameter is p + comp), the fp32 exp_avg only with beta1, and the scratch of the
+    reductions.  No arena-sized second moment: about 2 B per element against AdamW_BF16's 6 B.  The arithmetic is
+    include/sdxlstep.h's (algorithm 3), five launches per step (csrc/optimizer.hip adafactor_*_kernel), no host read-back.  Host
+    scalars are python doubles, k the 1-based step: beta2t = 1 - k**decay_rate; rho = lr, or with relative_step
+    min(1e-6 * k if warmup_init else 1e-2, 1 / sqrt(k)).
+
+    relative_step=None (the constructor's default) means "exactly when no lr is given", the two combinations the HF class accepts;
+    an explicit relative_step=True with an lr, and warmup_init without relative_step, raise its errors.  One deliberate departure:
+    a convolution is factored as [cout][cin*kh*kw], not over (kh, kw) (adafactor_layout).
+    The table lists the tensors net.trainable() names (every tensor without a selection): a frozen tensor is not read or written.
+    The statistics span whole tensors, so there is no ZeRO-1 form (ZERO1 = False): under data parallelism every rank runs the full
+    update on the all-reduced gradients.  There is no PyTorch fallback: the step fails loudly without libsdxlstep.so."""
+
+    algorithm = "adafactor"
+    ZERO1 = False
+    THIRD = "comp"
+    LAUNCH = "sdxl_adamw_bf16_step (Adafactor)"
+    SETTINGS = ("eps", "clip_threshold", "decay_rate", "beta1", "scale_parameter", "relative_step", "warmup_init")
+
+    def __init__(self, net, *, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
+                 scale_parameter: bool = True, relative_step: Optional[bool] = None, warmup_init: bool = False,
+                 grad_round_bf16: bool = False):
+        relative_step = (lr is None) if relative_step is None else bool(relative_step)
+        if lr is not None and relative_step:
+            raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
+        if warmup_init and not relative_step:
+            raise ValueError("`warmup_init=True` requires `relative_step=True`")
+        if lr is None and not relative_step:
+            raise ValueError("relative_step=False needs a learning rate")
+        eps = tuple(float(x) for x in eps)
+        if len(eps) != 2 or not all(0.0 <= x < math.inf for x in eps):
+            raise ValueError(f"Invalid eps pair: {eps}")
+        if lr is not None and not 0.0 <= float(lr) < math.inf:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < float(clip_threshold) < math.inf:
+            raise ValueError(f"Invalid clip_threshold value: {clip_threshold}")
+        if not float(decay_rate) < 0.0:
+            raise ValueError(f"Invalid decay_rate value: {decay_rate} (beta2 of step k is 1 - k**decay_rate: it must be negative)")
+        if beta1 is not None and not 0.0 <= float(beta1) < 1.0:
+            raise ValueError(f"Invalid beta1 value: {beta1}")
+        if not 0.0 <= float(weight_decay) < math.inf:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(net, dict(lr=None if lr is None else float(lr), eps=eps, clip_threshold=float(clip_threshold),
+                                   decay_rate=float(decay_rate), beta1=None if beta1 is None else float(beta1),
+                                   weight_decay=float(weight_decay), scale_parameter=bool(scale_parameter),
+                                   relative_step=relative_step, warmup_init=bool(warmup_init)),
+                         third=True, grad_round_bf16=grad_round_bf16, moment_dtype=torch.float32, moments=False)
+        w = net.weights
+        if beta1 is not None:
+            self.exp_avg = torch.zeros_like(w, dtype=torch.float32)
+        if hasattr(net, "layout") and hasattr(net, "rank"):                  # a lora.LoRAAdapters arena
+            shapes, ranges = adapter_shapes(net), net.param_ranges()
+        elif hasattr(net, "param_shapes"):
+            shapes, ranges = net.param_shapes(), net.param_ranges()
+        else:                                                               # an arena without a tensor table: one unfactored tensor
+            shapes, ranges = {"arena": (w.numel(),)}, {"arena": (0, w.numel())}
+        self.entries = adafactor_layout(shapes, ranges)
+        self.state_offsets, cur = {}, 0
+        for e in self.entries:
+            self.state_offsets[e.name] = cur
+            cur += e.state_floats()
+        self.af_state = torch.zeros(max(cur, 4), dtype=torch.float32, device=w.device)
+        self.af_scratch = torch.empty(max(adafactor_scratch_floats(self.entries), 4), dtype=torch.float32, device=w.device)
+        self._tables: Dict[Any, Any] = {}
+
+    @classmethod
+    def from_config(cls, net, oc):
+        relative = bool(getattr(oc, "relative_step", True))
+        lr = float(oc.learning_rate)
+        if relative:
+            default = getattr(type(oc), "learning_rate", lr)      # (the section's own default: the key was not written)
+            if lr != default:           # a learning rate was written next to relative_step: the HF class's error
+                raise ValueError("Cannot combine manual `lr` and `relative_step=True` options (optimizer.learning_rate is set: "
+                                 "write relative_step: false, or leave learning_rate out)")
+        return cls(net, lr=None if relative else lr, eps=tuple(getattr(oc, "eps", (1e-30, 1e-3))),
+                   clip_threshold=getattr(oc, "clip_threshold", 1.0), decay_rate=getattr(oc, "decay_rate", -0.8),
+                   beta1=getattr(oc, "adafactor_beta1", None), weight_decay=oc.weight_decay,
+                   scale_parameter=getattr(oc, "scale_parameter", True), relative_step=relative,
+                   warmup_init=getattr(oc, "warmup_init", False))
+
+    # ---- the table
+    def table(self):
+        """(entries, ctypes array) of the trainable tensors, built once per selection"""
+        live = getattr(self.net, "trainable", None)
+        names = None if live is None else frozenset(live())
+        if names not in self._tables:
+            ents = [e for e in self.entries if names is None or e.name in names]
+            arr = (lib.AdafactorTensor * max(len(ents), 1))()
+            for a, e in zip(arr, ents):
+                a.elem_off, a.rows, a.cols, a.numel, a.factored, a.state_off = e.elem_off, e.rows, e.cols, e.numel, int(e.factored), \
+                    self.state_offsets[e.name]
+            self._tables = {names: (ents, arr)}
+        return self._tables[names]
+
+    def state_floats(self) -> int:
+        return sum(e.state_floats() for e in self.entries)
+
+    def schedule(self) -> Tuple[float, float]:
+        """(beta2t, rho) of the next step, in python doubles as the HF class computes them"""
+        grp = self.param_groups[0]
+        k = self.step_count + 1
+        beta2t = 1.0 - math.pow(k, grp["decay_rate"])
+        rho = grp["lr"]
+        if grp["relative_step"]:
+            rho = min(1e-6 * k if grp["warmup_init"] else 1e-2, 1.0 / math.sqrt(k))
+        return beta2t, float(rho)
+
+    # ---- state
+    def moment_arenas(self):
+        return (self.exp_avg if self.param_groups[0]["beta1"] is not None else None), None
+
+    def state_arenas(self):
+        return (self.comp,) + ((self.exp_avg,) if self.param_groups[0]["beta1"] is not None else ())
+
+    def _tag(self) -> Dict[str, Any]:
+        grp = self.param_groups[0]
+        return {"algorithm": self.algorithm, **{k: grp[k] for k in self.SETTINGS}}
+
+    def state_dict(self) -> Dict[str, Any]:
+        st = {"step": self.step_count, "af_state": self.af_state, "comp": self.comp}
+        if self.param_groups[0]["beta1"] is not None:
+            st["exp_avg"] = self.exp_avg
+        return {**self._tag(), "state": st, "param_groups": self.param_groups}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        got = {k: (tuple(sd[k]) if k == "eps" and sd.get(k) is not None else sd.get(k)) for k in self._tag()}
+        if got != self._tag():
+            raise ValueError(f"optimizer state tagged {got} cannot be loaded into an optimizer configured as {self._tag()}")
+        st = sd["state"]
+        if st["af_state"].numel() != self.af_state.numel():
+            raise ValueError(f"optimizer state holds {st['af_state'].numel()} Adafactor statistics, this arena's layout has {self.af_state.numel()}")
+        self.step_count = int(st["step"])
+        self.af_state.copy_(st["af_state"])
+        self.comp.copy_(st["comp"])
+        if self.param_groups[0]["beta1"] is not None:
+            self.exp_avg.copy_(st["exp_avg"])
+        self.param_groups = sd["param_groups"]
+
+    def step(self, grads: Optional[torch.Tensor] = None, grad_scale: Optional[torch.Tensor] = None,
+             zero_grad: bool = False, pieces=None) -> None:
+        """One update of every trainable tensor: arguments as FusedArenaOptimizer._step, without pieces."""
+        self._step(grads, grad_scale, zero_grad, pieces)
+
+    def fill_hyper(self, cfg, grp) -> None:
+        cfg.beta1 = grp["beta1"] if grp["beta1"] is not None else 0.0
+        cfg.use_beta1 = int(grp["beta1"] is not None)
+
+    def begin_step(self, cfg, grp):
+        ents, arr = self.table()
+        cfg.algorithm = 3
+        cfg.weight_decay = grp["weight_decay"]
+        cfg.eps1, cfg.eps2 = grp["eps"]
+        cfg.clip_threshold = grp["clip_threshold"]
+        cfg.beta2t, cfg.rho = self.schedule()
+        cfg.scale_parameter = int(grp["scale_parameter"])
+        cfg.tensors, cfg.n_tensors = C.addressof(arr), len(ents)
+        cfg.af_state, cfg.af_scratch = self.af_state.data_ptr(), self.af_scratch.data_ptr()
+        return None
+
+    def finish_step(self, _begun, todo, st) -> None:
+        """counts the step after the launches"""
+        self.step_count += 1
+
+    def tensor_scalars(self) -> Dict[str, Tuple[float, float, float, float]]:
+        """{name: (rho_t, eta_t, rms_u, rms_p)} of the last step, read back from the scratch (synchronises)"""
+        ents, _arr = self.table()
+        vals = self.af_scratch[: 4 * len(ents)].cpu().reshape(-1, 4).tolist()
+        return {e.name: tuple(v) for e, v in zip(ents, vals)}
+
+
 # optimizer_type (lower-cased, as the reference's OptimizerConfig.class_name does) -> the fused class built for it
-BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16, "prodigy": ProdigyBF16}
+BY_TYPE = {"adamw_bf16": AdamWBF16, "adamw_schedule_free_kahan": AdamWScheduleFreeKahanBF16, "prodigy": ProdigyBF16,
+           "adafactor": AdafactorBF16}
