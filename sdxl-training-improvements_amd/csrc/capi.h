@@ -19,23 +19,18 @@ struct StepState {  // what backward needs from the preceding forward
   ResidualReq res;             // the additional skip residuals this micro-step carried (sdxl_batch_res): the backward writes res.d_*
   float* d_input = nullptr;    // the input gradient this micro-step asked for (sdxl_batch_din): the caller's buffer, written by conv_in's backward
 };
-struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS / SDXL_DTYPE_LOHA / SDXL_DTYPE_LOKR call, keyed by
-  std::vector<int> params;      // (target list, rank, dtype) and, for SDXL_DTYPE_LOKR, (factor, full)
-  int rank = 0, dtype = 0, mapped = 0;
-  LoraTarget* dev = nullptr;
-  LohaTarget* dev_loha = nullptr;      // SDXL_DTYPE_LOHA's table (one of the three is held at a time)
-  LokrTarget* dev_lokr = nullptr;      // SDXL_DTYPE_LOKR's
-  DoraTarget* dev_dora = nullptr;      // SDXL_DTYPE_DORA's
+struct LoraCache {  // device table of the last SDXL_DTYPE_LORA / SDXL_DTYPE_LORA_LAYOUTS / SDXL_DTYPE_LOHA / SDXL_DTYPE_LOKR / SDXL_DTYPE_DORA call
+  void* dev = nullptr;          // LoraTarget, LohaTarget, LokrTarget or DoraTarget [params.size()]: `dtype` says which
+  int dtype = 0, rank = 0;      // the key: (dtype, rank, target list, factor, full); factor and full are 0 but for SDXL_DTYPE_LOKR
+  std::vector<int> params;
   int factor = 0, full = 0;
-  size_t scratch_floats = 0;           // what SDXL_DTYPE_LOKR's projection needs of sdxl_lokr_op.scratch
+  int mapped = 0;
+  size_t scratch_floats = 0;    // what SDXL_DTYPE_LOKR's projection needs of sdxl_lokr_op.scratch
   int tiles_m = 0, tiles_b = 0, tiles_a = 0;
 };
-// one table is held at a time: whoever builds its own frees the others first (hipFree waits for the launches that read them)
+// whoever builds a table frees the cached one first (hipFree waits for the launches that read it)
 static void lora_cache_free(LoraCache& c) {
   if (c.dev) { (void)hipFree(c.dev); c.dev = nullptr; }
-  if (c.dev_loha) { (void)hipFree(c.dev_loha); c.dev_loha = nullptr; }
-  if (c.dev_lokr) { (void)hipFree(c.dev_lokr); c.dev_lokr = nullptr; }
-  if (c.dev_dora) { (void)hipFree(c.dev_dora); c.dev_dora = nullptr; }
 }
 struct sdxl_handle {
   Engine e;

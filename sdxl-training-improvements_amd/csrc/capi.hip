@@ -142,14 +142,14 @@ static int lora_check_op(const sdxl_lora_op* op, bool need_base, bool need_grads
   if (need_grads) ARG_CHECK(aligned16(op->adapter_grads), "lora: adapter_grads must be a 16-byte aligned device pointer");
   return 0;
 }
-// the targets of `params` in order: every target checked, its place in the weight arena and in the adapter / W0 arenas, its first tiles
-// layouts (SDXL_DTYPE_LORA_LAYOUTS): also the tensors held in a packed layout, by their kind; *mapped_ = some target needs the kind-aware kernels
-static int lora_table(Engine& e, const std::vector<int>& params, int rank, std::vector<LoraTarget>& tab, long* tm_, long* tb_, long* ta_,
-                      bool layouts = false, int* mapped_ = nullptr) {
+// the targets of `params` in order, every one checked, with what every family's table shares of a target: its place in the weight arena and in
+// the packed W0 (w_off, base_off), out, in, kind, cg, nrows.  The adapter offsets and the first tiles are the family's placement step's (below).
+// layouts (every dtype but SDXL_DTYPE_LORA): also the tensors held in a packed layout, by their kind; *mapped_ = some target needs the kind-aware kernels
+static int lora_targets(Engine& e, const std::vector<int>& params, int rank, bool layouts, std::vector<LoraTarget>& tab, int* mapped_ = nullptr) {
   tab.assign(params.size(), LoraTarget());
   int mapped = 0;
   std::vector<char> seen(e.src.size(), 0);
-  long a = 0, b = 0, tm = 0, tb = 0, ta = 0;
+  long b = 0;
   for (size_t i = 0; i < params.size(); ++i) {
     const int pi = params[i];
     ARG_CHECK(pi >= 0 && pi < (int)e.src.size(), "lora: parameter index %d out of range", pi);
@@ -179,189 +179,191 @@ static int lora_table(Engine& e, const std::vector<int>& params, int rank, std::
     t.w_off = (long)(sp.native.off + sp.elem_off);
     ARG_CHECK(t.w_off % 8 == 0, "lora: '%s' does not start on a 16-byte boundary of the arena", sp.name.c_str());
     t.base_off = b; b += (long)out * in;
-    t.a_off = t.ga_off = a; a += ((long)rank * in + 7) / 8 * 8;
-    t.b_off = t.gb_off = a; a += ((long)out * rank + 7) / 8 * 8;
     t.out = out; t.in = in;
-    t.tile_m = (int)tm; t.tile_b = (int)tb; t.tile_a = (int)ta;
-    tm += lora_tiles_m(out, in); tb += lora_tiles_b(out, in); ta += lora_tiles_a(out, in);
-    ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "lora: too many tiles");
   }
-  *tm_ = tm; *tb_ = tb; *ta_ = ta;
   if (mapped_) *mapped_ = mapped;
   return 0;
 }
 
-static int lora_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LoraP& q, int dtype = SDXL_DTYPE_LORA) {
-  ARG_CHECK(name == nullptr, "lora: `name` must be NULL with SDXL_DTYPE_LORA (the targets are listed in sdxl_lora_op.param)");
-  CHK(lora_check_op(op, merge, !merge));
-  Engine& e = h->e;
-  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lora: %s are not bound", merge ? "weights" : "grads");
-  LoraCache& c = h->lora;
-  std::vector<int> params(op->param, op->param + op->n);
-  if (!(c.dev && c.rank == op->rank && c.dtype == dtype && c.params == params)) {
-    std::vector<LoraTarget> tab;
-    long tm = 0, tb = 0, ta = 0;
-    int mapped = 0;
-    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, dtype == SDXL_DTYPE_LORA_LAYOUTS, &mapped));
-    lora_cache_free(c);
-    HIP_CHECK_RET(hipMalloc((void**)&c.dev, tab.size() * sizeof(LoraTarget)));
-    HIP_CHECK_RET(hipMemcpy(c.dev, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice));
-    c.params = params; c.rank = op->rank; c.dtype = dtype; c.mapped = mapped;
-    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
-  }
-  memset(&q, 0, sizeof(q));
-  q.table = c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
-  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
-  q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = (const bf16*)op->adapters;
-  q.dw = e.grads; q.ga = q.gb = op->adapter_grads;
+// ---- the placement step: where a family puts one target's factors, scratch and workgroups, given the targets before it ----
+struct Placed {      // the running totals of a table
+  long at = 0;               // adapter (and adapter-gradient) arena, elements
+  long tiles[3] = {0, 0, 0}; // workgroups of the family's three launches (LoraTarget::tile_m, tile_b, tile_a)
+  size_t scratch = 0;        // sdxl_lokr_op.scratch, floats
+  long norm = 0;             // sdxl_dora_op.norm0 / norm, floats
+};
+// The walk over the adapter arena, the C twin of lora.py's adapter_layout: a target's factor sizes in arena order (lora.py's target_factors),
+// each padded to 8 elements; off[i] = where factor i starts.
+static void arena_place(Placed& pl, std::initializer_list<long> sizes, long* off) {
+  for (long n : sizes) { *off++ = pl.at; pl.at += (n + 7) / 8 * 8; }
+}
+// ... and over the launches: the target's first workgroup in each, from the number it takes of each
+static int tiles_place(Placed& pl, LoraTarget& t, long m, long b, long a, const char* who) {
+  t.tile_m = (int)pl.tiles[0]; t.tile_b = (int)pl.tiles[1]; t.tile_a = (int)pl.tiles[2];
+  pl.tiles[0] += m; pl.tiles[1] += b; pl.tiles[2] += a;
+  ARG_CHECK(pl.tiles[0] < (1L << 31) && pl.tiles[1] < (1L << 31) && pl.tiles[2] < (1L << 31), "%s: too many tiles", who);
   return 0;
 }
-
-// ---- LoHa by merge and project (SDXL_DTYPE_LOHA): SDXL_DTYPE_LORA_LAYOUTS' checks and targets, the rank cap, four factors per target ----
-static int loha_prepare(sdxl_handle* h, const char* name, const sdxl_lora_op* op, bool merge, LohaP& q) {
-  ARG_CHECK(name == nullptr, "loha: `name` must be NULL with SDXL_DTYPE_LOHA (the targets are listed in sdxl_lora_op.param)");
-  ARG_CHECK(op != nullptr, "loha: empty target list");
-  CHK(loha_check_rank(op->rank));
-  CHK(lora_check_op(op, merge, !merge));
-  Engine& e = h->e;
-  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "loha: %s are not bound", merge ? "weights" : "grads");
-  LoraCache& c = h->lora;
-  std::vector<int> params(op->param, op->param + op->n);
-  if (!(c.dev_loha && c.rank == op->rank && c.dtype == SDXL_DTYPE_LOHA && c.params == params)) {
-    std::vector<LoraTarget> tab;
-    long tm = 0, tb = 0, ta = 0;
-    int mapped = 0;
-    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, true, &mapped));      // every check of the packed layouts; offsets and tiles follow
-    std::vector<LohaTarget> htab(tab.size());
-    long at = 0;
-    tm = tb = ta = 0;
-    for (size_t i = 0; i < tab.size(); ++i) {
-      LohaTarget& x = htab[i];
-      x.t = tab[i];
-      const long na = ((long)op->rank * x.t.in + 7) / 8 * 8, nb = ((long)x.t.out * op->rank + 7) / 8 * 8;
-      x.t.a_off = x.t.ga_off = at; at += na;      // A1, B1, A2, B2, each padded to 8 elements
-      x.t.b_off = x.t.gb_off = at; at += nb;
-      x.a2_off = x.ga2_off = at; at += na;
-      x.b2_off = x.gb2_off = at; at += nb;
-      x.t.tile_m = (int)tm; x.t.tile_b = (int)tb; x.t.tile_a = (int)ta;
-      tm += loha_tiles_m(x.t.out, x.t.in); tb += loha_tiles_b(x.t.out, x.t.in); ta += loha_tiles_a(x.t.out, x.t.in);
-      ARG_CHECK(tm < (1L << 31) && tb < (1L << 31) && ta < (1L << 31), "loha: too many tiles");
-    }
-    lora_cache_free(c);
-    HIP_CHECK_RET(hipMalloc((void**)&c.dev_loha, htab.size() * sizeof(LohaTarget)));
-    HIP_CHECK_RET(hipMemcpy(c.dev_loha, htab.data(), htab.size() * sizeof(LohaTarget), hipMemcpyHostToDevice));
-    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOHA; c.mapped = 1;
-    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
-  }
-  memset(&q, 0, sizeof(q));
-  q.table = c.dev_loha; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
-  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a;
-  q.w = e.weights; q.base = (const bf16*)op->base; q.a1 = q.b1 = q.a2 = q.b2 = (const bf16*)op->adapters;
-  q.dw = e.grads; q.ga1 = q.gb1 = q.ga2 = q.gb2 = op->adapter_grads;
-  return 0;
+// LoRA: A [rank][in], B [out][rank]; also the direct backward's (grad_select) and, with mu behind them, DoRA's
+static int lora_place(Placed& pl, LoraTarget& t, int rank) {
+  long off[2];
+  arena_place(pl, {(long)rank * t.in, (long)t.out * rank}, off);
+  t.a_off = t.ga_off = off[0]; t.b_off = t.gb_off = off[1];
+  return tiles_place(pl, t, lora_tiles_m(t.out, t.in), lora_tiles_b(t.out, t.in), lora_tiles_a(t.out, t.in), "lora");
 }
 
-// ---- LoKr by merge and project (SDXL_DTYPE_LOKR): SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target the factorisation, the form
-// (the rule, or sdxl_lokr_op.full) in the table; the scale by the form per call (1 for a full target, op.scale for a factored one; op.scale == 0
-// zeroes both: the restoring merge) ----
-static int lokr_prepare(sdxl_handle* h, const char* name, const sdxl_lokr_op* lop, bool merge, LokrP& q) {
-  ARG_CHECK(name == nullptr, "lokr: `name` must be NULL with SDXL_DTYPE_LOKR (the targets are listed in sdxl_lokr_op.op.param)");
-  ARG_CHECK(lop != nullptr, "lokr: empty target list");
-  const sdxl_lora_op* op = &lop->op;
-  CHK(lokr_check_fields(op->rank, lop->factor, lop->full));
-  CHK(lora_check_op(op, merge, !merge));
-  Engine& e = h->e;
-  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "lokr: %s are not bound", merge ? "weights" : "grads");
-  LoraCache& c = h->lora;
-  std::vector<int> params(op->param, op->param + op->n);
-  if (!(c.dev_lokr && c.rank == op->rank && c.dtype == SDXL_DTYPE_LOKR && c.factor == lop->factor && c.full == lop->full &&
-        c.params == params)) {
-    std::vector<LoraTarget> tab;
-    long tm = 0, tp = 0, tq = 0;
-    int mapped = 0;
-    CHK(lora_table(e, params, op->rank, tab, &tm, &tp, &tq, true, &mapped));      // every check of the packed layouts; offsets and tiles follow
-    std::vector<LokrTarget> ktab(tab.size());
-    long at = 0;
-    size_t sf = 0;
-    tm = tp = tq = 0;
-    for (size_t i = 0; i < tab.size(); ++i) {
-      LokrTarget& x = ktab[i];
-      memset(&x, 0, sizeof(x));
-      x.t = tab[i];
-      const int cin = x.t.kind == LORA_KIND_CONV3 ? x.t.cg : x.t.in;
-      lokr_geometry(x, cin, lop->factor, 0);
-      CHK(lokr_check_size(e.src[params[i]].name.c_str(), x, op->rank));
-      x.full = lop->full || lokr_rule_full(x.out_k, x.in_n, op->rank);
-      x.c_off = at; at += ((long)x.out_l * x.in_m + 7) / 8 * 8;      // C, then W2 or B, A, each padded to 8 elements
-      if (x.full) { x.t.b_off = x.t.gb_off = at; at += ((long)x.out_k * x.n2 + 7) / 8 * 8; x.t.a_off = x.t.ga_off = 0; }
-      else {
-        x.t.b_off = x.t.gb_off = at; at += ((long)x.out_k * op->rank + 7) / 8 * 8;
-        x.t.a_off = x.t.ga_off = at; at += ((long)op->rank * x.n2 + 7) / 8 * 8;
-      }
-      x.part_off = (long)sf; sf += lokr_part_floats(x);
-      x.dw2_off = (long)sf; sf += lokr_dw2_floats(x);
-      x.t.tile_m = (int)tm; x.t.tile_b = (int)tp; x.t.tile_a = (int)tq;
-      tm += lokr_tiles_m(x); tp += x.ptiles; tq += lokr_tiles_q(x, op->rank);
-      ARG_CHECK(tm < (1L << 31) && tp < (1L << 31) && tq < (1L << 31), "lokr: too many tiles");
-    }
-    lora_cache_free(c);
-    HIP_CHECK_RET(hipMalloc((void**)&c.dev_lokr, ktab.size() * sizeof(LokrTarget)));
-    HIP_CHECK_RET(hipMemcpy(c.dev_lokr, ktab.data(), ktab.size() * sizeof(LokrTarget), hipMemcpyHostToDevice));
-    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_LOKR; c.mapped = 1;
-    c.factor = lop->factor; c.full = lop->full; c.scratch_floats = sf;
-    c.tiles_m = (int)tm; c.tiles_b = (int)tp; c.tiles_a = (int)tq;
+// ---- the four families of sdxl_load_weight / sdxl_export_grad: what adapter_prepare (below) asks of each ----
+//   who, dtype_name, list   the message prefix, the dtype and the struct field that lists the targets, as the messages name them
+//   check                   the op, field and pointer checks, in the family's own order
+//   lora, factor, full      the sdxl_lora_op inside the family's struct; the rest of the cache key
+//   place                   the placement step of one target
+//   fill                    the launch struct from the cached table and the call's pointers (and the checks that need the table)
+struct TargetsKey {      // the cache key of a family whose table follows from (dtype, rank, target list) alone
+  static int factor(const void*) { return 0; }
+  static int full(const void*) { return 0; }
+};
+struct LoraFamily : TargetsKey {      // SDXL_DTYPE_LORA, SDXL_DTYPE_LORA_LAYOUTS: the launches of csrc/lora.hip
+  typedef sdxl_lora_op Op; typedef LoraTarget Target; typedef LoraP P;
+  static constexpr const char *who = "lora", *dtype_name = "SDXL_DTYPE_LORA", *list = "sdxl_lora_op.param";
+  static int check(const Op* op, bool merge) { return lora_check_op(op, merge, !merge); }
+  static const sdxl_lora_op* lora(const Op* op) { return op; }
+  static int place(Placed& pl, Target& x, const LoraTarget& t, const char*, const Op* op) { x = t; return lora_place(pl, x, op->rank); }
+  static int fill(const Engine& e, const LoraCache& c, const Op* op, bool, P& q) {
+    q.table = (const Target*)c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+    q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
+    q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = (const bf16*)op->adapters;
+    q.dw = e.grads; q.ga = q.gb = op->adapter_grads;
+    return 0;
   }
-  if (!merge) CHK(lokr_check_scratch(lop->scratch, lop->scratch_floats, c.scratch_floats));
-  memset(&q, 0, sizeof(q));
-  q.table = c.dev_lokr; q.n = op->n; q.rank = op->rank;
-  q.scale = op->scale; q.scale_full = op->scale == 0.f ? 0.f : 1.f;      // (scale 0: the restoring merge zeroes both forms)
-  q.tiles_m = c.tiles_m; q.tiles_p = c.tiles_b; q.tiles_q = c.tiles_a;
-  q.w = e.weights; q.base = (const bf16*)op->base; q.c = q.b = q.a = (const bf16*)op->adapters;
-  q.dw = e.grads; q.gc = q.gb = q.ga = op->adapter_grads; q.scratch = lop->scratch;
-  return 0;
-}
+};
+struct LohaFamily : TargetsKey {      // SDXL_DTYPE_LOHA: SDXL_DTYPE_LORA_LAYOUTS' checks and targets, the rank cap, four factors per target
+  typedef sdxl_lora_op Op; typedef LohaTarget Target; typedef LohaP P;
+  static constexpr const char *who = "loha", *dtype_name = "SDXL_DTYPE_LOHA", *list = "sdxl_lora_op.param";
+  static int check(const Op* op, bool merge) {
+    ARG_CHECK(op != nullptr, "loha: empty target list");
+    CHK(loha_check_rank(op->rank));
+    return lora_check_op(op, merge, !merge);
+  }
+  static const sdxl_lora_op* lora(const Op* op) { return op; }
+  static int place(Placed& pl, Target& x, const LoraTarget& t, const char*, const Op* op) {
+    x.t = t;
+    const long na = (long)op->rank * t.in, nb = (long)t.out * op->rank;
+    long off[4];
+    arena_place(pl, {na, nb, na, nb}, off);      // A1, B1, A2, B2
+    x.t.a_off = x.t.ga_off = off[0]; x.t.b_off = x.t.gb_off = off[1];
+    x.a2_off = x.ga2_off = off[2]; x.b2_off = x.gb2_off = off[3];
+    return tiles_place(pl, x.t, loha_tiles_m(t.out, t.in), loha_tiles_b(t.out, t.in), loha_tiles_a(t.out, t.in), who);
+  }
+  static int fill(const Engine& e, const LoraCache& c, const Op* op, bool, P& q) {
+    q.table = (const Target*)c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+    q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a;
+    q.w = e.weights; q.base = (const bf16*)op->base; q.a1 = q.b1 = q.a2 = q.b2 = (const bf16*)op->adapters;
+    q.dw = e.grads; q.ga1 = q.gb1 = q.ga2 = q.gb2 = op->adapter_grads;
+    return 0;
+  }
+};
+// SDXL_DTYPE_LOKR: SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target the factorisation, the form (the rule, or sdxl_lokr_op.full) in the
+// table; the scale by the form per call (1 for a full target, op.scale for a factored one; op.scale == 0 zeroes both: the restoring merge)
+struct LokrFamily {
+  typedef sdxl_lokr_op Op; typedef LokrTarget Target; typedef LokrP P;
+  static constexpr const char *who = "lokr", *dtype_name = "SDXL_DTYPE_LOKR", *list = "sdxl_lokr_op.op.param";
+  static int check(const Op* lop, bool merge) {
+    ARG_CHECK(lop != nullptr, "lokr: empty target list");
+    CHK(lokr_check_fields(lop->op.rank, lop->factor, lop->full));
+    return lora_check_op(&lop->op, merge, !merge);
+  }
+  static const sdxl_lora_op* lora(const Op* lop) { return &lop->op; }
+  static int factor(const Op* lop) { return lop->factor; }
+  static int full(const Op* lop) { return lop->full; }
+  static int place(Placed& pl, Target& x, const LoraTarget& t, const char* name, const Op* lop) {
+    const int rank = lop->op.rank;
+    memset(&x, 0, sizeof(x));
+    x.t = t;
+    lokr_geometry(x, t.kind == LORA_KIND_CONV3 ? t.cg : t.in, lop->factor, 0);
+    CHK(lokr_check_size(name, x, rank));
+    x.full = lop->full || lokr_rule_full(x.out_k, x.in_n, rank);
+    long off[3];
+    if (x.full) {      // C, W2
+      arena_place(pl, {(long)x.out_l * x.in_m, (long)x.out_k * x.n2}, off);
+      x.t.a_off = x.t.ga_off = 0;
+    } else {           // C, B, A
+      arena_place(pl, {(long)x.out_l * x.in_m, (long)x.out_k * rank, (long)rank * x.n2}, off);
+      x.t.a_off = x.t.ga_off = off[2];
+    }
+    x.c_off = off[0]; x.t.b_off = x.t.gb_off = off[1];
+    x.part_off = (long)pl.scratch; pl.scratch += lokr_part_floats(x);
+    x.dw2_off = (long)pl.scratch; pl.scratch += lokr_dw2_floats(x);
+    return tiles_place(pl, x.t, lokr_tiles_m(x), x.ptiles, lokr_tiles_q(x, rank), who);
+  }
+  static int fill(const Engine& e, const LoraCache& c, const Op* lop, bool merge, P& q) {
+    const sdxl_lora_op* op = &lop->op;
+    if (!merge) CHK(lokr_check_scratch(lop->scratch, lop->scratch_floats, c.scratch_floats));
+    q.table = (const Target*)c.dev; q.n = op->n; q.rank = op->rank;
+    q.scale = op->scale; q.scale_full = op->scale == 0.f ? 0.f : 1.f;      // (scale 0: the restoring merge zeroes both forms)
+    q.tiles_m = c.tiles_m; q.tiles_p = c.tiles_b; q.tiles_q = c.tiles_a;
+    q.w = e.weights; q.base = (const bf16*)op->base; q.c = q.b = q.a = (const bf16*)op->adapters;
+    q.dw = e.grads; q.gc = q.gb = q.ga = op->adapter_grads; q.scratch = lop->scratch;
+    return 0;
+  }
+};
+// SDXL_DTYPE_DORA: SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target A, B, mu in the adapter arena, LoRA's tiles and its rows of norm0 / norm
+struct DoraFamily : TargetsKey {
+  typedef sdxl_dora_op Op; typedef DoraTarget Target; typedef DoraP P;
+  static constexpr const char *who = "dora", *dtype_name = "SDXL_DTYPE_DORA", *list = "sdxl_dora_op.op.param";
+  static int check(const Op* dop, bool merge) {
+    ARG_CHECK(dop != nullptr, "dora: empty target list");
+    CHK(dora_check_fields(dop->op.rank, merge ? dop->mode : 0));
+    CHK(lora_check_op(&dop->op, true, !merge));
+    return dora_check_norms(dop->norm0, dop->norm);
+  }
+  static const sdxl_lora_op* lora(const Op* dop) { return &dop->op; }
+  static int place(Placed& pl, Target& x, const LoraTarget& t, const char*, const Op* dop) {
+    x.t = t;
+    CHK(lora_place(pl, x.t, dop->op.rank));      // A, B
+    arena_place(pl, {(long)t.out}, &x.mu_off);   // mu
+    x.n_off = pl.norm; pl.norm += dora_pad4(t.out);
+    return 0;
+  }
+  static int fill(const Engine& e, const LoraCache& c, const Op* dop, bool, P& q) {
+    const sdxl_lora_op* op = &dop->op;
+    q.table = (const Target*)c.dev; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
+    q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
+    q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = q.mu = (const bf16*)op->adapters;
+    q.dw = e.grads; q.ga = q.gb = q.gmu = op->adapter_grads;
+    q.norm0 = dop->norm0; q.norm = dop->norm;
+    return 0;
+  }
+};
 
-// ---- DoRA by merge and project (SDXL_DTYPE_DORA): SDXL_DTYPE_LORA_LAYOUTS' checks and targets; per target A, B, mu in the adapter arena and
-// its rows of norm0 / norm ----
-static int dora_prepare(sdxl_handle* h, const char* name, const sdxl_dora_op* dop, bool merge, DoraP& q) {
-  ARG_CHECK(name == nullptr, "dora: `name` must be NULL with SDXL_DTYPE_DORA (the targets are listed in sdxl_dora_op.op.param)");
-  ARG_CHECK(dop != nullptr, "dora: empty target list");
-  const sdxl_lora_op* op = &dop->op;
-  CHK(dora_check_fields(op->rank, merge ? dop->mode : 0));
-  CHK(lora_check_op(op, true, !merge));
-  CHK(dora_check_norms(dop->norm0, dop->norm));
+// The launch struct of a merge (sdxl_load_weight) or a projection (sdxl_export_grad) of family F: the checks, then the device table of the
+// targets, built when the cached one (LoraCache) has another key.  The host table is complete before the cached one is freed -- a refused
+// call leaves the cache as it was -- and the free comes before the allocation: hipFree waits for the launches that still read the old table.
+extern "C++" template <class F>
+static int adapter_prepare(sdxl_handle* h, const char* name, const typename F::Op* fop, bool merge, int dtype, typename F::P& q) {
+  ARG_CHECK(name == nullptr, "%s: `name` must be NULL with %s (the targets are listed in %s)", F::who, F::dtype_name, F::list);
+  CHK(F::check(fop, merge));
+  const sdxl_lora_op* op = F::lora(fop);
   Engine& e = h->e;
-  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "dora: %s are not bound", merge ? "weights" : "grads");
+  ARG_CHECK(merge ? e.weights != nullptr : e.grads != nullptr, "%s: %s are not bound", F::who, merge ? "weights" : "grads");
   LoraCache& c = h->lora;
   std::vector<int> params(op->param, op->param + op->n);
-  if (!(c.dev_dora && c.rank == op->rank && c.dtype == SDXL_DTYPE_DORA && c.params == params)) {
+  const int factor = F::factor(fop), full = F::full(fop);
+  if (!(c.dev && c.dtype == dtype && c.rank == op->rank && c.factor == factor && c.full == full && c.params == params)) {
     std::vector<LoraTarget> tab;
-    long tm = 0, tb = 0, ta = 0;
     int mapped = 0;
-    CHK(lora_table(e, params, op->rank, tab, &tm, &tb, &ta, true, &mapped));      // every check of the packed layouts; base_off and the tiles are LoRA's
-    std::vector<DoraTarget> dtab(tab.size());
-    long at = 0, nt = 0;
-    for (size_t i = 0; i < tab.size(); ++i) {
-      DoraTarget& x = dtab[i];
-      x.t = tab[i];
-      x.t.a_off = x.t.ga_off = at; at += ((long)op->rank * x.t.in + 7) / 8 * 8;      // A, B, mu, each padded to 8 elements
-      x.t.b_off = x.t.gb_off = at; at += ((long)x.t.out * op->rank + 7) / 8 * 8;
-      x.mu_off = at; at += ((long)x.t.out + 7) / 8 * 8;
-      x.n_off = nt; nt += dora_pad4(x.t.out);
-    }
+    CHK(lora_targets(e, params, op->rank, dtype != SDXL_DTYPE_LORA, tab, &mapped));
+    std::vector<typename F::Target> ftab(tab.size());
+    Placed pl;
+    for (size_t i = 0; i < tab.size(); ++i) CHK(F::place(pl, ftab[i], tab[i], e.src[params[i]].name.c_str(), fop));
     lora_cache_free(c);
-    HIP_CHECK_RET(hipMalloc((void**)&c.dev_dora, dtab.size() * sizeof(DoraTarget)));
-    HIP_CHECK_RET(hipMemcpy(c.dev_dora, dtab.data(), dtab.size() * sizeof(DoraTarget), hipMemcpyHostToDevice));
-    c.params = params; c.rank = op->rank; c.dtype = SDXL_DTYPE_DORA; c.mapped = mapped;
-    c.tiles_m = (int)tm; c.tiles_b = (int)tb; c.tiles_a = (int)ta;
+    HIP_CHECK_RET(hipMalloc(&c.dev, ftab.size() * sizeof(ftab[0])));
+    HIP_CHECK_RET(hipMemcpy(c.dev, ftab.data(), ftab.size() * sizeof(ftab[0]), hipMemcpyHostToDevice));
+    c.params = params; c.rank = op->rank; c.dtype = dtype; c.factor = factor; c.full = full; c.mapped = mapped;
+    c.scratch_floats = pl.scratch;
+    c.tiles_m = (int)pl.tiles[0]; c.tiles_b = (int)pl.tiles[1]; c.tiles_a = (int)pl.tiles[2];
   }
   memset(&q, 0, sizeof(q));
-  q.table = c.dev_dora; q.n = op->n; q.rank = op->rank; q.scale = op->scale;
-  q.tiles_m = c.tiles_m; q.tiles_b = c.tiles_b; q.tiles_a = c.tiles_a; q.mapped = c.mapped;
-  q.w = e.weights; q.base = (const bf16*)op->base; q.a = q.b = q.mu = (const bf16*)op->adapters;
-  q.dw = e.grads; q.ga = q.gb = q.gmu = op->adapter_grads;
-  q.norm0 = dop->norm0; q.norm = dop->norm;
-  return 0;
+  return F::fill(e, c, fop, merge, q);
 }
 static int dora_launch_load(const DoraP& q, int mode, hipStream_t st) {
   return mode == 0 ? launch_dora_merge(q, st) : mode == 1 ? launch_dora_init(q, st) : launch_dora_restore(q, st);
@@ -379,22 +381,22 @@ int sdxl_load_weight(sdxl_handle* h, const char* name, const void* src, int dtyp
   H_CHECK(h);
   if (dtype == SDXL_DTYPE_DORA) {
     DoraP q;
-    CHK(dora_prepare(h, name, (const sdxl_dora_op*)src, true, q));
+    CHK(adapter_prepare<DoraFamily>(h, name, (const sdxl_dora_op*)src, true, dtype, q));
     return dora_launch_load(q, ((const sdxl_dora_op*)src)->mode, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LOKR) {
     LokrP q;
-    CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)src, true, q));
+    CHK(adapter_prepare<LokrFamily>(h, name, (const sdxl_lokr_op*)src, true, dtype, q));
     return launch_lokr_merge(q, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LOHA) {
     LohaP q;
-    CHK(loha_prepare(h, name, (const sdxl_lora_op*)src, true, q));
+    CHK(adapter_prepare<LohaFamily>(h, name, (const sdxl_lora_op*)src, true, dtype, q));
     return launch_loha_merge(q, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
-    CHK(lora_prepare(h, name, (const sdxl_lora_op*)src, true, q, dtype));
+    CHK(adapter_prepare<LoraFamily>(h, name, (const sdxl_lora_op*)src, true, dtype, q));
     return launch_lora_merge(q, (hipStream_t)st);
   }
   ARG_CHECK(name && src, "null argument");
@@ -431,8 +433,9 @@ static int grad_select(sdxl_handle* h, const char* name, const sdxl_grad_select*
     L.params.assign(op->param, op->param + op->n);
     L.rank = op->rank; L.scale = op->scale; L.adapters = (const bf16*)op->adapters; L.grads = op->adapter_grads;
     std::vector<LoraTarget> tab;
-    long tm = 0, tb = 0, ta = 0;
-    CHK(lora_table(e, L.params, op->rank, tab, &tm, &tb, &ta));
+    CHK(lora_targets(e, L.params, op->rank, false, tab));
+    Placed pl;
+    for (LoraTarget& t : tab) CHK(lora_place(pl, t, op->rank));
     for (size_t i = 0; i < tab.size(); ++i) {
       const SrcParam& sp = e.src[L.params[i]];
       ARG_CHECK(sp.elem_off % (size_t)tab[i].in == 0, "lora: '%s' does not start on a row of its native weight", sp.name.c_str());
@@ -509,22 +512,22 @@ int sdxl_export_grad(sdxl_handle* h, const char* name, void* dst, int dtype, voi
   H_CHECK(h);
   if (dtype == SDXL_DTYPE_DORA) {
     DoraP q;
-    CHK(dora_prepare(h, name, (const sdxl_dora_op*)dst, false, q));
+    CHK(adapter_prepare<DoraFamily>(h, name, (const sdxl_dora_op*)dst, false, dtype, q));
     return launch_dora_project(q, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LOKR) {
     LokrP q;
-    CHK(lokr_prepare(h, name, (const sdxl_lokr_op*)dst, false, q));
+    CHK(adapter_prepare<LokrFamily>(h, name, (const sdxl_lokr_op*)dst, false, dtype, q));
     return launch_lokr_project(q, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LOHA) {
     LohaP q;
-    CHK(loha_prepare(h, name, (const sdxl_lora_op*)dst, false, q));
+    CHK(adapter_prepare<LohaFamily>(h, name, (const sdxl_lora_op*)dst, false, dtype, q));
     return launch_loha_project(q, (hipStream_t)st);
   }
   if (dtype == SDXL_DTYPE_LORA || dtype == SDXL_DTYPE_LORA_LAYOUTS) {
     LoraP q;
-    CHK(lora_prepare(h, name, (const sdxl_lora_op*)dst, false, q, dtype));
+    CHK(adapter_prepare<LoraFamily>(h, name, (const sdxl_lora_op*)dst, false, dtype, q));
     return launch_lora_project(q, (hipStream_t)st);
   }
   ARG_CHECK(name && dst, "null argument");

@@ -11,17 +11,6 @@
 
 namespace {
 
-template <int LoraTarget::*FIRST>
-__device__ __forceinline__ DoraTarget dora_find(const DoraP& p, int tile) {
-  if (!p.table) return p.one;
-  int lo = 0, hi = p.n - 1;
-  while (lo < hi) {                        // the last target whose first tile is <= tile
-    const int mid = (lo + hi + 1) >> 1;
-    if (p.table[mid].t.*FIRST <= tile) lo = mid; else hi = mid - 1;
-  }
-  return p.table[lo];
-}
-
 // c_o of the state-dict row `srow`: one division, one sum, one product, each rounded on its own
 __device__ __forceinline__ float dora_q(const DoraP& p, const DoraTarget& x, int srow) {
   const float n0 = p.norm0[x.n_off + srow], n = p.norm[x.n_off + srow];
@@ -43,7 +32,7 @@ __global__ __launch_bounds__(256) void dora_rows_kernel(const DoraP p) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float As[DORA_R_KC][DORA_R_COLS];
   __shared__ float Bs[DORA_R_ROWS][DORA_R_KC + 1];
-  const DoraTarget x = dora_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
+  const DoraTarget x = adapter_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
   const LoraTarget& t = x.t;
   const int tid = threadIdx.x, rb = (int)blockIdx.x - t.tile_b;
   const int lr = tid >> 3, lc = (tid & 7) * 8;
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(256) void dora_merge_kernel(const DoraP p) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float As[LORA_M_KC][LORA_M_COLS];
   __shared__ float Bs[LORA_M_ROWS][LORA_M_KC + 1];
-  const DoraTarget x = dora_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
+  const DoraTarget x = adapter_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
   const LoraTarget& t = x.t;
   const int tid = threadIdx.x, local = (int)blockIdx.x - t.tile_m, ncb = (t.in + LORA_M_COLS - 1) / LORA_M_COLS;
   const int rb = local / ncb, cb = local - rb * ncb;
@@ -179,7 +168,7 @@ __global__ __launch_bounds__(256) void dora_merge_kernel(const DoraP p) {
 template <bool MAPPED>
 __global__ __launch_bounds__(256) void dora_db_kernel(const DoraP p) {
   __shared__ __attribute__((aligned(16))) float As[LORA_B_KC][LORA_B_COLS];
-  const DoraTarget x = dora_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
+  const DoraTarget x = adapter_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
   const LoraTarget& t = x.t;
   const int tid = threadIdx.x, j = tid & 15, rr = tid >> 4;
   const int r0 = ((int)blockIdx.x - t.tile_b) * LORA_B_ROWS + rr, r1 = r0 + 16;
@@ -261,7 +250,7 @@ __global__ __launch_bounds__(256) void dora_da_kernel(const DoraP p) {
   __shared__ __attribute__((aligned(16))) float Bs[LORA_A_ROWS][4 * KPT];
   __shared__ float Cs[LORA_A_ROWS];      // c_o and the state-dict row of the step's rows
   __shared__ int Rs[LORA_A_ROWS];
-  const DoraTarget x = dora_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
+  const DoraTarget x = adapter_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
   const LoraTarget& t = x.t;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int col0 = ((int)blockIdx.x - t.tile_a) * LORA_A_COLS;

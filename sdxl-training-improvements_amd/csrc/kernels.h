@@ -624,6 +624,20 @@ struct LoraP {
   const float* dw;              // project
   float *ga, *gb;               // project: out, overwritten; what ga_off / gb_off count from (the gradient arena twice, or dA and dB)
 };
+// the LoraTarget of a table row: the row itself, or the `t` a family's row (LohaTarget, LokrTarget, DoraTarget) wraps
+__device__ __forceinline__ const LoraTarget& lora_of(const LoraTarget& t) { return t; }
+template <class T> __device__ __forceinline__ const LoraTarget& lora_of(const T& x) { return x.t; }
+// a workgroup's row of a launch struct P (LoraP, LohaP, LokrP, DoraP): the last target whose first tile FIRST is <= tile
+template <int LoraTarget::*FIRST, class P>
+__device__ __forceinline__ auto adapter_find(const P& p, int tile) -> decltype(p.one) {
+  if (!p.table) return p.one;
+  int lo = 0, hi = p.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (lora_of(p.table[mid]).*FIRST <= tile) lo = mid; else hi = mid - 1;
+  }
+  return p.table[lo];
+}
 static inline int lora_tiles_m(int out, int in) { return cdiv(out, LORA_M_ROWS) * cdiv(in, LORA_M_COLS); }
 static inline int lora_tiles_b(int out, int in) { return cdiv(out, LORA_B_ROWS); }
 static inline int lora_tiles_a(int out, int in) { return cdiv(in, LORA_A_COLS); }

@@ -15,17 +15,6 @@
 
 namespace {
 
-template <int LoraTarget::*FIRST>
-__device__ __forceinline__ LohaTarget loha_find(const LohaP& p, int tile) {
-  if (!p.table) return p.one;
-  int lo = 0, hi = p.n - 1;
-  while (lo < hi) {                        // the last target whose first tile is <= tile
-    const int mid = (lo + hi + 1) >> 1;
-    if (p.table[mid].t.*FIRST <= tile) lo = mid; else hi = mid - 1;
-  }
-  return p.table[lo];
-}
-
 // ---- merge: 32 x 64 tile, thread = (row tid / 8, the 8 columns of one 16-byte vector) ----
 // p1 <- p1 + B1[o][k] * A1[k][i] and p2 <- p2 + B2[o][k] * A2[k][i] for k = 0 .. rank - 1, every product and sum rounded on its own;
 // h = p1 * p2; t = s * h; W = bf16_rn(W0 + t), and W = W0 where t == 0 (so s = 0, B1 = 0 or B2 = 0 give back W0's bits, a -0 included).
@@ -34,7 +23,7 @@ __global__ __launch_bounds__(256) void loha_merge_kernel(const LohaP p) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float As[2][LOHA_M_KC][LOHA_M_COLS];
   __shared__ float Bs[2][LOHA_M_ROWS][LOHA_M_KC + 1];
-  const LohaTarget h = loha_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
+  const LohaTarget h = adapter_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
   const LoraTarget& t = h.t;
   const int tid = threadIdx.x, local = (int)blockIdx.x - t.tile_m, ncb = (t.in + LOHA_M_COLS - 1) / LOHA_M_COLS;
   const int rb = local / ncb, cb = local - rb * ncb;
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(256) void loha_project_kernel(const LohaP p) {
   __shared__ __attribute__((aligned(16))) float As[2][R][XS];
   __shared__ float Bs[2][LOHA_P_ROWS][R + 1];
   __shared__ __attribute__((aligned(16))) float Xs[2][LOHA_P_ROWS][XS];
-  const LohaTarget h = DA ? loha_find<&LoraTarget::tile_a>(p, (int)blockIdx.x) : loha_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
+  const LohaTarget h = DA ? adapter_find<&LoraTarget::tile_a>(p, (int)blockIdx.x) : adapter_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
   const LoraTarget& t = h.t;
   const int tid = threadIdx.x;
   const int fixed0 = ((int)blockIdx.x - (DA ? t.tile_a : t.tile_b)) * 32;      // first native column (DA) or row of this workgroup

@@ -16,17 +16,6 @@
 
 namespace {
 
-template <int LoraTarget::*FIRST>
-__device__ __forceinline__ LokrTarget lokr_find(const LokrP& p, int tile) {
-  if (!p.table) return p.one;
-  int lo = 0, hi = p.n - 1;
-  while (lo < hi) {                        // the last target whose first tile is <= tile
-    const int mid = (lo + hi + 1) >> 1;
-    if (p.table[mid].t.*FIRST <= tile) lo = mid; else hi = mid - 1;
-  }
-  return p.table[lo];
-}
-
 // ---- merge: 32 x 64 tile, thread = (row tid / 8, the 8 columns of one 16-byte vector) ----
 // factored: q <- q + B[c][k] * A[k][j] for k = 0 .. rank - 1, every product and sum rounded on its own; full: q = (float)W2[c][j];
 // h = C[a][b] * q; t = s * h; W = bf16_rn(W0 + t), and W = W0 where t == 0 (so s = 0, C = 0, W2 = 0, A = 0 or B = 0 give back W0's bits, a -0
@@ -37,7 +26,7 @@ __global__ __launch_bounds__(256) void lokr_merge_kernel(const LokrP p) {
   __shared__ __attribute__((aligned(16))) float As[LOKR_M_KC][LOKR_M_COLS];
   __shared__ float Bs[LOKR_M_ROWS][LOKR_M_KC + 1];
   __shared__ int Ra[LOKR_M_ROWS], Rc[LOKR_M_ROWS], Cb[LOKR_M_COLS], Cj[LOKR_M_COLS];
-  const LokrTarget h = lokr_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
+  const LokrTarget h = adapter_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
   const LoraTarget& t = h.t;
   const int tid = threadIdx.x, local = (int)blockIdx.x - t.tile_m, ncb = (t.in + LOKR_M_COLS - 1) / LOKR_M_COLS;
   const int rb = local / ncb, cb = local - rb * ncb;
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(256) void lokr_merge_kernel(const LokrP p) {
 // Elements past the end of W2 (the last tile) hold W2 = 0 and load nothing.  One barrier per LOKR_P_NB blocks (the wave sums are double-buffered).
 __global__ __launch_bounds__(256) void lokr_project_w2_kernel(const LokrP p) {
   __shared__ float red[2][LOKR_P_NB][4];
-  const LokrTarget h = lokr_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
+  const LokrTarget h = adapter_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
   const LoraTarget& t = h.t;
   const int tid = threadIdx.x, tile = (int)blockIdx.x - t.tile_b;
   const int kind = t.kind, cg = t.cg, c4 = t.out >> 1, n2 = h.n2, in_n = h.in_n, rank = p.rank;
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(256) void lokr_project_w2_kernel(const LokrP p) {
 //   dC[a][b]  = s * (partial[0][ab] + partial[1][ab] + ...)                      every target
 //   dB[c][k]  = sum_j dW2s[c][j] A[k][j],   dA[k][j] = sum_c B[c][k] dW2s[c][j]     a factored target, dW2s = s dW2 from launch 1's scratch
 __global__ __launch_bounds__(LOKR_Q_THREADS) void lokr_project_out_kernel(const LokrP p) {
-  const LokrTarget h = lokr_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
+  const LokrTarget h = adapter_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
   const LoraTarget& t = h.t;
   const int nblk = h.out_l * h.in_m, n2 = h.n2, rank = p.rank;
   int local = (int)blockIdx.x - t.tile_a;

@@ -14,17 +14,6 @@
 
 namespace {
 
-template <int LoraTarget::*FIRST>
-__device__ __forceinline__ LoraTarget lora_find(const LoraP& p, int tile) {
-  if (!p.table) return p.one;
-  int lo = 0, hi = p.n - 1;
-  while (lo < hi) {                        // the last target whose first tile is <= tile
-    const int mid = (lo + hi + 1) >> 1;
-    if (p.table[mid].*FIRST <= tile) lo = mid; else hi = mid - 1;
-  }
-  return p.table[lo];
-}
-
 // ---- merge: 32 x 64 tile, thread = (row tid / 8, the 8 columns of one 16-byte vector) ----
 // acc <- acc + B[o][k] * A[k][i] for k = 0 .. rank - 1, every product and sum rounded on its own; t = s * acc; W = bf16_rn(W0 + t), and
 // W = W0 where t == 0 (so s = 0 or B = 0 give back W0's bits, a -0 included).  tests/_lora_ref.py restates it in torch, bit for bit.
@@ -35,7 +24,7 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(const LoraP p) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float As[LORA_M_KC][LORA_M_COLS];
   __shared__ float Bs[LORA_M_ROWS][LORA_M_KC + 1];
-  const LoraTarget t = lora_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
+  const LoraTarget t = adapter_find<&LoraTarget::tile_m>(p, (int)blockIdx.x);
   const int tid = threadIdx.x, local = (int)blockIdx.x - t.tile_m, ncb = (t.in + LORA_M_COLS - 1) / LORA_M_COLS;
   const int rb = local / ncb, cb = local - rb * ncb;
   const int lr = tid >> 3, lc = (tid & 7) * 8;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(const LoraP p) {
 template <bool MAPPED>
 __global__ __launch_bounds__(256) void lora_db_kernel(const LoraP p) {
   __shared__ __attribute__((aligned(16))) float As[LORA_B_KC][LORA_B_COLS];
-  const LoraTarget t = lora_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
+  const LoraTarget t = adapter_find<&LoraTarget::tile_b>(p, (int)blockIdx.x);
   const int tid = threadIdx.x, j = tid & 15, rr = tid >> 4;
   const int r0 = ((int)blockIdx.x - t.tile_b) * LORA_B_ROWS + rr, r1 = r0 + 16;
   const bf16* A = p.a + t.a_off;
@@ -166,7 +155,7 @@ template <int KPT, bool MAPPED>
 __global__ __launch_bounds__(256) void lora_da_kernel(const LoraP p) {
   __shared__ __attribute__((aligned(16))) float Ds[LORA_A_ROWS][LORA_A_COLS];
   __shared__ __attribute__((aligned(16))) float Bs[LORA_A_ROWS][4 * KPT];
-  const LoraTarget t = lora_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
+  const LoraTarget t = adapter_find<&LoraTarget::tile_a>(p, (int)blockIdx.x);
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int col0 = ((int)blockIdx.x - t.tile_a) * LORA_A_COLS;
   const bf16* B = p.b + t.b_off;

@@ -11,8 +11,9 @@ Both steps are one call into libsdxlstep (csrc/lora.hip through dtype SDXL_DTYPE
 training.lora_target_kinds (LORA_TARGET_KINDS) says which tensors may be targets: "plain" = 2-D linears stored as plain rows; "all" = every
 2-D or 4-D weight but conv_in -- also ff.net.0.proj and the convolutions, which the arena keeps in packed layouts -- through dtype
 SDXL_DTYPE_LORA_LAYOUTS.  There out = shape[0], in = prod(shape[1:]) and A, B are indexed like the state-dict tensor flattened to [out, in].
-LoRAAdapters owns the small arenas and looks to a fused optimizer like a net (weights, grads, L, zero_grads, param_ranges), so
-AdamWBF16 / AdamWScheduleFreeKahanBF16 update it unchanged.  NativeLoRATrainer is the trainer `training.lora_rank > 0` selects.
+LoRAAdapters owns the small arenas and looks to a fused optimizer like a net (weights, grads, L, zero_grads, param_ranges, param_shapes), so
+AdamWBF16 / AdamWScheduleFreeKahanBF16 update it unchanged.  target_factors says which factors a target of each family has, FAMILIES
+the rest that differs between the families; the layout, the ranges, the views, the initialisation and the export all follow from the two.  NativeLoRATrainer is the trainer `training.lora_rank > 0` selects.
 training.lora_backward chooses how much of the full model's backward runs for that (LORA_BACKWARDS):
   "project"         all of it, as above (the default);
   "project_frozen"  the engine's gradient selection (NativeUNet.set_trainable) keeps only the ops that hold a target: every other op
@@ -50,13 +51,13 @@ import ctypes as C
 import json
 import logging
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import distributed as D
 from . import lib
-from .optimizer import FusedArenaOptimizer
+from .optimizer import FusedArenaOptimizer, _pad8
 from .trainer import NativeSDXLTrainer, build_optimizer, checkpoint_dir
 
 logger = logging.getLogger(__name__)
@@ -68,16 +69,69 @@ LORA_TARGET_KINDS = ("plain", "all")
 LORA_ALGOS = ("lora", "loha", "kronecker", "dora")
 LOHA_MAX_RANK = 64
 LOKR = "kronecker"      # LyCORIS' LoKr ("lokr" stays an unknown value: tests/test_host_loha.py uses it as one)
-EXPORT_FILES = {"lora": "pytorch_lora_weights.safetensors", "loha": "lycoris_loha.safetensors", LOKR: "lycoris_lokr.safetensors",
-                "dora": "pytorch_lora_weights.safetensors"}      # save_checkpoint's adapter file
 LOKR_NAMES = {"C": "lokr_w1", "W2": "lokr_w2", "B": "lokr_w2_a", "A": "lokr_w2_b"}      # the LyCORIS names
 LOHA_FACTORS = (("A1", "hada_w1_b"), ("B1", "hada_w1_a"), ("A2", "hada_w2_b"), ("B2", "hada_w2_a"))      # arena order; the LyCORIS names
+
+
+class Family(NamedTuple):
+    """what differs between the adapter families besides their factors (target_factors)"""
+    dtype: Dict[str, int]                   # lib.DTYPE_* of sdxl_load_weight / sdxl_export_grad by lora_target_kinds (one dtype has the packed
+                                            # layouts' target rules in the library; `kinds` still says what the patterns may resolve to)
+    max_rank: int
+    init: Callable[[int], Tuple[Tuple[str, float], ...]]      # rank -> (factor, std) in draw order; the other factors are 0, so dW = 0
+    export: str                             # export_tensors' convention, "peft" or "lycoris"
+    file: str                               # save_checkpoint's adapter file
+    direct: bool = False                    # lora_backward "direct" writes this family's gradients
+    wrap: Callable = lambda ad, op, mode: op      # the struct the two device steps take, around the sdxl_lora_op
+    restore_mode: int = 0                   # the `mode` of the merge that restores W0
+    meta: Tuple[str, ...] = ()              # the settings (attributes lokr_<name>) a state carries besides LoRA's
+    setup: Optional[Callable] = None        # the family's buffers, once the arenas are there
+
+
+def _every_kind(dtype: int) -> Dict[str, int]:
+    return {kinds: dtype for kinds in LORA_TARGET_KINDS}
+
+
+FAMILIES = {
+    # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
+    "lora": Family({"plain": lib.DTYPE_LORA, "all": lib.DTYPE_LORA_LAYOUTS}, MAX_RANK, lambda r: (("A", 1.0 / r),), "peft",
+                   "pytorch_lora_weights.safetensors", direct=True),
+    "loha": Family(_every_kind(lib.DTYPE_LOHA), LOHA_MAX_RANK, lambda r: (("A1", 1.0), ("B1", 0.1), ("A2", 1.0)), "lycoris",
+                   "lycoris_loha.safetensors"),
+    LOKR: Family(_every_kind(lib.DTYPE_LOKR), MAX_RANK, lambda r: (("C", 1.0), ("B", 0.1)), "lycoris", "lycoris_lokr.safetensors",      # (B: a factored target's)
+                 wrap=lambda ad, op, mode: lib.LokrOp(op, ad.lokr_factor, int(ad.lokr_full), ad.scratch.data_ptr(), ad.scratch.numel()),
+                 meta=("factor", "full"), setup=lambda ad: ad._setup_lokr()),
+    "dora": Family(_every_kind(lib.DTYPE_DORA), MAX_RANK, lambda r: (("A", 1.0 / r),), "peft", "pytorch_lora_weights.safetensors",
+                   wrap=lambda ad, op, mode: lib.DoraOp(op, int(mode), ad.norm0.data_ptr(), ad.norm.data_ptr()),
+                   restore_mode=lib.DORA_RESTORE, setup=lambda ad: ad._setup_dora()),
+}
+assert tuple(FAMILIES) == LORA_ALGOS
+EXPORT_FILES = {algo: fam.file for algo, fam in FAMILIES.items()}
+
+
+class Factor(NamedTuple):
+    name: str                   # the accessor's: LoRAAdapters.view(name, key)
+    leaf: str                   # the param_ranges() key is "<module>." + leaf
+    shape: Tuple[int, ...]
 
 
 def check_lora_algo(algo) -> str:
     if algo not in LORA_ALGOS:
         raise ValueError(f"training.lora_algo {algo!r}: expected one of {list(LORA_ALGOS)}")
     return algo
+
+
+def check_rank(rank, algo: str = "lora") -> int:
+    cap = FAMILIES[check_lora_algo(algo)].max_rank
+    if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= cap:
+        raise ValueError(f"lora_rank must be an integer in 1 .. {cap} (got {rank!r})" + (f" with lora_algo {algo!r}" if cap != MAX_RANK else ""))
+    return rank
+
+
+def check_direct_algo(algo: str) -> None:
+    if not FAMILIES[algo].direct:
+        raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
+                         f"{algo!r}'s (use 'project' or 'project_frozen')")
 
 
 def check_lokr_factor(factor) -> int:
@@ -177,10 +231,6 @@ def trainable_for(mode: str, targets: Sequence[str], shapes: Dict[str, Tuple[int
     return [k for k in shapes if op_of(k, shapes[k]) in ops]
 
 
-def _pad8(n: int) -> int:
-    return (n + 7) // 8 * 8
-
-
 def _pad4(n: int) -> int:
     return (n + 3) // 4 * 4
 
@@ -233,37 +283,35 @@ def _prod(dims) -> int:
     return n
 
 
+def target_factors(algo: str, shape: Sequence[int], rank: int, factor: int = -1, full: bool = False) -> Tuple[Factor, ...]:
+    """The factors of one target in arena order, the one place that says which a family has, under what names and of what shape; out =
+    shape[0], in = prod(shape[1:]).  `factor`, `full`: training.lokr_factor / lokr_full, read by "kronecker" only."""
+    check_lora_algo(algo)
+    o, i = int(shape[0]), _prod(shape[1:])
+    if algo == "lora":
+        return (Factor("A", "lora_A.weight", (rank, i)), Factor("B", "lora_B.weight", (o, rank)))
+    if algo == "dora":
+        return (Factor("A", "lora_A", (rank, i)), Factor("B", "lora_B", (o, rank)), Factor("mu", "lora_magnitude", (o,)))
+    if algo == "loha":
+        return tuple(Factor(name, lyco, (rank, i) if name[0] == "A" else (o, rank)) for name, lyco in LOHA_FACTORS)
+    g = lokr_geometry(shape, factor, rank, full)
+    shapes = {"C": (g["out_l"], g["in_m"]), "W2": (g["out_k"], g["n2"]), "B": (g["out_k"], rank), "A": (rank, g["n2"])}
+    return tuple(Factor(name, LOKR_NAMES[name], shapes[name]) for name in (("C", "W2") if g["full"] else ("C", "B", "A")))
+
+
 def adapter_layout(shapes: Dict[str, Tuple[int, ...]], targets: Sequence[str], rank: int, algo: str = "lora", factor: int = -1,
                    full: bool = False):
-    """({key: (A offset, B offset, out, in)}, total elements): per target A [rank, in] then B [out, rank], each padded to 8 elements;
-    out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions.
-    algo "loha": {key: (A1 offset, B1 offset, A2 offset, B2 offset, out, in)}, the four factors in that order, each padded to 8;
-    algo "kronecker": {key: (C offset, W2 offset, out, in)} for a full target, (C offset, B offset, A offset, out, in) for a factored one
-    (lokr_geometry has the shapes), each factor padded to 8;
-    algo "dora": {key: (A offset, B offset, mu offset, out, in)}, A [rank, in], B [out, rank], mu [out], each padded to 8"""
+    """({key: (*offsets, out, in)}, total elements): per target the element offset of each of target_factors' factors, in that order, every
+    factor padded to 8 elements -- (A, B) for "lora", (A1, B1, A2, B2) for "loha", (C, W2) or (C, B, A) for "kronecker", (A, B, mu) for
+    "dora"; out = shape[0], in = prod(shape[1:]): the state-dict tensor flattened to two dimensions.  csrc/capi.hip's arena_place is its twin."""
     check_lora_algo(algo)
     lay, cur = {}, 0
     for k in targets:
-        o, i = int(shapes[k][0]), _prod(shapes[k][1:])
-        if algo == LOKR:
-            g = lokr_geometry(shapes[k], factor, rank, full)
-            sizes = [g["out_l"] * g["in_m"]] + ([g["out_k"] * g["n2"]] if g["full"] else [g["out_k"] * rank, rank * g["n2"]])
-            offs = []
-            for n in sizes:
-                offs.append(cur)
-                cur += _pad8(n)
-            lay[k] = (*offs, o, i)
-            continue
         offs = []
-        for _pair in range(2 if algo == "loha" else 1):
+        for f in target_factors(algo, shapes[k], rank, factor, full):
             offs.append(cur)
-            cur += _pad8(rank * i)
-            offs.append(cur)
-            cur += _pad8(o * rank)
-        if algo == "dora":
-            offs.append(cur)
-            cur += _pad8(o)
-        lay[k] = (*offs, o, i)
+            cur += _pad8(_prod(f.shape))
+        lay[k] = (*offs, int(shapes[k][0]), _prod(shapes[k][1:]))
     return lay, cur
 
 
@@ -276,15 +324,13 @@ class LoRAAdapters:
         self.algo = check_lora_algo(algo)
         self.lokr_factor = check_lokr_factor(factor)      # (read by "kronecker" only)
         self.lokr_full = check_lokr_full(full)
-        # (loha: one dtype, the packed layouts' target rules in the library; `kinds` still says what the patterns may resolve to)
-        self.dtype = (lib.DTYPE_LOKR if algo == LOKR else lib.DTYPE_LOHA if algo == "loha" else lib.DTYPE_DORA if algo == "dora"
-                      else lib.DTYPE_LORA_LAYOUTS if kinds == "all" else lib.DTYPE_LORA)
-        max_rank = LOHA_MAX_RANK if algo == "loha" else MAX_RANK
-        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
-            raise ValueError(f"lora_rank must be an integer in 1 .. {max_rank} (got {rank!r})" + (" with lora_algo 'loha'" if algo == "loha" else ""))
+        fam = FAMILIES[algo]
+        self.dtype = fam.dtype[kinds]
+        self.geometry, self.scratch = {}, None      # ("kronecker" has them: _setup_lokr)
+        self.norm0 = self.norm = None               # ("dora": _setup_dora)
         self.net = net
         self.L = getattr(net, "L", None)
-        self.rank = rank
+        self.rank = check_rank(rank, algo)
         self.alpha = float(rank if alpha is None else alpha)
         self.scale = self.alpha / rank
         self.seed = int(seed)
@@ -294,104 +340,87 @@ class LoRAAdapters:
         self.shapes = {k: tuple(int(v) for v in shapes[k]) for k in self.targets}
         names = list(shapes)
         self.index = [names.index(k) for k in self.targets]
+        self.factors = {k: target_factors(algo, self.shapes[k], rank, self.lokr_factor, self.lokr_full) for k in self.targets}
         self.layout, self.param_elems = adapter_layout(shapes, self.targets, rank, algo, self.lokr_factor, self.lokr_full)
         dev = net.weights.device
-        self.geometry = {k: lokr_geometry(self.shapes[k], self.lokr_factor, rank, self.lokr_full) for k in self.targets} if algo == LOKR else {}
-        # the projection's scratch (sdxl_lokr_op.scratch), allocated once; its contents never matter
-        self.scratch = torch.empty(max(lokr_scratch_floats(self.geometry.values()), 4), dtype=torch.float32, device=dev) if algo == LOKR else None
         self.weights = torch.zeros(self.param_elems, dtype=torch.bfloat16, device=dev)
         self.grads = torch.zeros(self.param_elems, dtype=torch.float32, device=dev)
         ranges = net.param_ranges()
         self.base = torch.cat([net.weights[ranges[k][0]: ranges[k][0] + ranges[k][1]] for k in self.targets])
         assert self.base.numel() == sum(ranges[k][1] for k in self.targets)      # (the targets' native ranges: out * in elements each)
         g = torch.Generator().manual_seed(self.seed)
-        for k in self.targets:
-            o, i = self.layout[k][-2:]
-            if algo == LOKR:        # this build's choice: W2 (full) or A (factored) = 0 (dW = 0), C ~ N(0, 1), B ~ N(0, 0.1^2), drawn in the order C, B
-                for name, std in (("C", 1.0),) + ((() if self.geometry[k]["full"] else (("B", 0.1),))):
-                    v = self.factor_view(name, k)
+        for k in self.targets:      # this build's choice for the LyCORIS families (the module docstring): one generator, the table's draw order
+            for name, std in fam.init(rank):
+                if any(f.name == name for f in self.factors[k]):
+                    v = self.view(name, k)
                     v.copy_((torch.randn(*v.shape, generator=g) * std).to(torch.bfloat16))
-            elif algo == "loha":    # this build's choice: B2 = 0 (dW = 0), A1, A2 ~ N(0, 1), B1 ~ N(0, 0.1^2), drawn in the order A1, B1, A2
-                for name, shape, std in (("A1", (rank, i), 1.0), ("B1", (o, rank), 0.1), ("A2", (rank, i), 1.0)):
-                    self.factor(name, k).copy_((torch.randn(*shape, generator=g) * std).to(torch.bfloat16))
-            else:                   # the reference's init: down ~ N(0, (1 / rank)^2), up = 0
-                a = self.layout[k][0]
-                self.weights[a: a + rank * i] = (torch.randn(rank, i, generator=g) * (1.0 / rank)).to(torch.bfloat16).reshape(-1).to(dev)
         self._param = (C.c_int * len(self.index))(*self.index)
-        if algo == "dora":      # sdxl_dora_op.norm0 / norm: one float per target row in target order, each target padded to 4; mu = 0
-            self.norm_offsets, cur = {}, 0
-            for k in self.targets:
-                self.norm_offsets[k] = cur
-                cur += _pad4(self.layout[k][-2])
-            self.norm0 = torch.zeros(cur, dtype=torch.float32, device=dev)
-            self.norm = torch.zeros(cur, dtype=torch.float32, device=dev)
-            self.init_norm0()
+        if fam.setup:
+            fam.setup(self)
+
+    def _setup_lokr(self) -> None:
+        self.geometry = {k: lokr_geometry(self.shapes[k], self.lokr_factor, self.rank, self.lokr_full) for k in self.targets}
+        # the projection's scratch (sdxl_lokr_op.scratch), allocated once; its contents never matter
+        self.scratch = torch.empty(max(lokr_scratch_floats(self.geometry.values()), 4), dtype=torch.float32, device=self.weights.device)
+
+    def _setup_dora(self) -> None:
+        """sdxl_dora_op.norm0 / norm: one float per target row in target order, each target padded to 4; mu = 0"""
+        self.norm_offsets, cur = {}, 0
+        for k in self.targets:
+            self.norm_offsets[k] = cur
+            cur += _pad4(self.layout[k][-2])
+        self.norm0 = torch.zeros(cur, dtype=torch.float32, device=self.weights.device)
+        self.norm = torch.zeros(cur, dtype=torch.float32, device=self.weights.device)
+        self.init_norm0()
 
     # ---- what a fused optimizer asks of its net
     def zero_grads(self) -> None:
         self.grads.zero_()
 
-    def param_ranges(self) -> Dict[str, Tuple[int, int]]:
-        """{"<module>.lora_A.weight" / "<module>.lora_B.weight": (element offset, padded element count)} inside the adapter arenas;
-        algo "loha": "<module>.hada_w1_b" (A1), ".hada_w1_a" (B1), ".hada_w2_b" (A2), ".hada_w2_a" (B2), in arena order;
-        algo "kronecker": "<module>.lokr_w1" (C), then ".lokr_w2" (W2, a full target) or ".lokr_w2_a" (B), ".lokr_w2_b" (A);
-        algo "dora": "<module>.lora_A", ".lora_B", ".lora_magnitude" (mu)"""
-        out = {}
+    def _params(self):
+        """(param_ranges() key, element offset, Factor) of every factor, in arena order"""
         for k, lay in self.layout.items():
-            mod = k[: -len(".weight")]
-            o, i = lay[-2:]
-            if self.algo == LOKR:
-                for n, name in enumerate(self.lokr_factors(k)):
-                    rows, cols = self._lokr_shape(k, name)
-                    out[f"{mod}.{LOKR_NAMES[name]}"] = (lay[n], _pad8(rows * cols))
-                continue
-            if self.algo == "loha":
-                for n, (_name, lyco) in enumerate(LOHA_FACTORS):
-                    out[f"{mod}.{lyco}"] = (lay[n], _pad8(self.rank * i if n % 2 == 0 else o * self.rank))
-                continue
-            if self.algo == "dora":
-                out[f"{mod}.lora_A"] = (lay[0], _pad8(self.rank * i))
-                out[f"{mod}.lora_B"] = (lay[1], _pad8(o * self.rank))
-                out[f"{mod}.lora_magnitude"] = (lay[2], _pad8(o))
-                continue
-            out[f"{mod}.lora_A.weight"] = (lay[0], _pad8(self.rank * i))
-            out[f"{mod}.lora_B.weight"] = (lay[1], _pad8(o * self.rank))
-        return out
+            for off, f in zip(lay, self.factors[k]):
+                yield f"{k[: -len('.weight')]}.{f.leaf}", off, f
+
+    def param_ranges(self) -> Dict[str, Tuple[int, int]]:
+        """{"<module>.<leaf>": (element offset, padded element count)} inside the adapter arenas, target_factors' leaves in arena order:
+        "lora_A.weight", "lora_B.weight"; algo "loha": "hada_w1_b" (A1), "hada_w1_a" (B1), "hada_w2_b" (A2), "hada_w2_a" (B2);
+        algo "kronecker": "lokr_w1" (C), then "lokr_w2" (W2, a full target) or "lokr_w2_a" (B), "lokr_w2_b" (A);
+        algo "dora": "lora_A", "lora_B", "lora_magnitude" (mu)"""
+        return {name: (off, _pad8(_prod(f.shape))) for name, off, f in self._params()}
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """the factors' shapes under the keys of param_ranges()"""
+        return {name: f.shape for name, _off, f in self._params()}
 
     # ---- views
-    def _view(self, key: str, slot: int, grad: bool) -> torch.Tensor:
-        """slot-th block of the target (even: an A [rank, in], odd: a B [out, rank])"""
-        lay = self.layout[key]
-        o, i = lay[-2:]
-        rows, cols = (self.rank, i) if slot % 2 == 0 else (o, self.rank)
-        return (self.grads if grad else self.weights)[lay[slot]: lay[slot] + rows * cols].view(rows, cols)
+    def view(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
+        """the factor `name` (target_factors) of a target, or its gradient: a view of the arena.  A "kronecker" target's W2 and A columns
+        are j = d kh kw + tap, the state-dict order"""
+        names = [f.name for f in self.factors[key]]
+        if name not in names:
+            form = ("full " if self.geometry[key]["full"] else "factored ") if self.geometry else ""
+            raise ValueError(f"{name}: {key} is a {form}lora_algo {self.algo!r} target: it has " + ", ".join(names))
+        n = names.index(name)
+        shape, off = self.factors[key][n].shape, self.layout[key][n]
+        return (self.grads if grad else self.weights)[off: off + _prod(shape)].view(*shape)
 
     def factor(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
-        """a LoHa factor "A1" | "B1" | "A2" | "B2" of a target (or its gradient), a view of the arena"""
+        """a LoHa factor "A1" | "B1" | "A2" | "B2" of a target (or its gradient)"""
         if self.algo != "loha":
-            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}" + (" (A and B)" if self.algo in ("lora", "dora") else " (C, W2 or B, A)"))
-        return self._view(key, [n for n, _l in LOHA_FACTORS].index(name), grad)
+            raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}" + (" (C, W2 or B, A)" if self.geometry else " (A and B)"))
+        return self.view(name, key, grad)
 
     def lokr_factors(self, key: str) -> Tuple[str, ...]:
         """the factors of a "kronecker" target in arena order: ("C", "W2") when it is full, ("C", "B", "A") when it is factored"""
-        return ("C", "W2") if self.geometry[key]["full"] else ("C", "B", "A")
-
-    def _lokr_shape(self, key: str, name: str) -> Tuple[int, int]:
-        g = self.geometry[key]
-        return {"C": (g["out_l"], g["in_m"]), "W2": (g["out_k"], g["n2"]), "B": (g["out_k"], self.rank), "A": (self.rank, g["n2"])}[name]
+        return tuple(f.name for f in self.factors[key])
 
     def factor_view(self, name: str, key: str, grad: bool = False) -> torch.Tensor:
-        """a LoKr factor "C" | "W2" (full target) | "B" | "A" (factored target) of a target (or its gradient), a view of the arena; W2 and A
-        columns are j = d kh kw + tap, the state-dict order"""
+        """a LoKr factor "C" | "W2" (full target) | "B" | "A" (factored target) of a target (or its gradient)"""
         if self.algo != LOKR:
             raise ValueError(f"{name}: these adapters are lora_algo {self.algo!r}, not 'kronecker'")
-        names = self.lokr_factors(key)
-        if name not in names:
-            raise ValueError(f"{name}: {key} is a {'full' if self.geometry[key]['full'] else 'factored'} lora_algo 'kronecker' target: it has "
-                             + ", ".join(names))
-        off = self.layout[key][names.index(name)]
-        rows, cols = self._lokr_shape(key, name)
-        return (self.grads if grad else self.weights)[off: off + rows * cols].view(rows, cols)
+        return self.view(name, key, grad)
 
     def C(self, key: str, grad: bool = False) -> torch.Tensor:
         return self.factor_view("C", key, grad)
@@ -401,28 +430,26 @@ class LoRAAdapters:
 
     def target_scale(self, key: str) -> float:
         """s of one target: alpha / rank, or 1 for a full "kronecker" target"""
-        return 1.0 if self.algo == LOKR and self.geometry[key]["full"] else self.scale
+        return 1.0 if self._full(key) else self.scale
+
+    def _full(self, key: str) -> bool:
+        return bool(self.geometry) and bool(self.geometry[key]["full"])
 
     def A(self, key: str, grad: bool = False) -> torch.Tensor:
         if self.algo == "loha":
             raise ValueError("A: lora_algo 'loha' adapters have A1 and A2")
-        if self.algo == LOKR:
-            return self.factor_view("A", key, grad)
-        return self._view(key, 0, grad)
+        return self.view("A", key, grad)
 
     def B(self, key: str, grad: bool = False) -> torch.Tensor:
         if self.algo == "loha":
             raise ValueError("B: lora_algo 'loha' adapters have B1 and B2")
-        if self.algo == LOKR:
-            return self.factor_view("B", key, grad)
-        return self._view(key, 1, grad)
+        return self.view("B", key, grad)
 
     def mu(self, key: str, grad: bool = False) -> torch.Tensor:
         """the trained vector mu [out] of a "dora" target (or its gradient), a view of the arena: the magnitude is n0 (1 + mu)"""
         if self.algo != "dora":
             raise ValueError(f"mu: these adapters are lora_algo {self.algo!r}, not 'dora'")
-        off, o = self.layout[key][2], self.layout[key][-2]
-        return (self.grads if grad else self.weights)[off: off + o]
+        return self.view("mu", key, grad)
 
     def row_norm(self, key: str, base: bool = True) -> torch.Tensor:
         """the fp32 row norms [out] of a "dora" target, views of the device buffers: n0 of W0 (base=True; written once by init_norm0) or n of
@@ -452,11 +479,7 @@ class LoRAAdapters:
     def _op(self, scale: float, mode: int = 0):
         op = lib.LoraOp(len(self.index), self._param, self.rank, float(scale), self.weights.data_ptr(), self.base.data_ptr(),
                         self.grads.data_ptr())
-        if self.algo == LOKR:
-            return lib.LokrOp(op, self.lokr_factor, int(self.lokr_full), self.scratch.data_ptr(), self.scratch.numel())
-        if self.algo == "dora":
-            return lib.DoraOp(op, int(mode), self.norm0.data_ptr(), self.norm.data_ptr())
-        return op
+        return FAMILIES[self.algo].wrap(self, op, mode)
 
     def _call(self, fn_name: str, scale: float, mode: int = 0) -> None:
         if self.L is None:
@@ -473,10 +496,7 @@ class LoRAAdapters:
 
     def restore(self) -> None:
         """the checkpoint's weights back, bit for bit (a merge with scale 0; algo "dora": its restoring mode, mu does not matter)"""
-        if self.algo == "dora":
-            self._call("sdxl_load_weight", 0.0, lib.DORA_RESTORE)
-        else:
-            self.merge(0.0)
+        self._call("sdxl_load_weight", 0.0, FAMILIES[self.algo].restore_mode)
 
     def init_norm0(self) -> None:
         """algo "dora": the row norms of W0 into `.norm0` (one launch; a no-op without the library, where nothing can be merged either)"""
@@ -499,9 +519,7 @@ class LoRAAdapters:
 
     def check_direct(self) -> None:
         """ValueError when a target is not one the direct adapter gradients (csrc/lora_grad.hip) take, or the adapters are not LoRA's"""
-        if self.algo != "lora":
-            raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
-                             f"{self.algo!r}'s (use 'project' or 'project_frozen')")
+        check_direct_algo(self.algo)
         bad = [k for k in self.targets if not is_plain_target(k, self.shapes[k])]
         if bad:
             raise ValueError(f"training.lora_backward 'direct': {bad[0]} {self.shapes[bad[0]]} is not a 2-D linear in plain row layout; the "
@@ -515,9 +533,8 @@ class LoRAAdapters:
             meta["kinds"] = self.kinds
         if self.algo != "lora":        # (and so is a LoRA state)
             meta["algo"] = self.algo
-        if self.algo == LOKR:          # (and a LoHa state)
-            meta["factor"] = self.lokr_factor
-            meta["full"] = self.lokr_full
+        for key in FAMILIES[self.algo].meta:      # (and a LoHa state)
+            meta[key] = getattr(self, "lokr_" + key)
         return meta
 
     def state_dict(self) -> Dict[str, Any]:
@@ -529,7 +546,7 @@ class LoRAAdapters:
             raise ValueError(f"lora state: lora_algo differs from this trainer's ({sd.get('algo', 'lora')!r} vs {self.algo!r})")
         if sd.get("kinds", "plain") != self.kinds:
             raise ValueError(f"lora state: kinds differs from this trainer's ({sd.get('kinds', 'plain')!r} vs {self.kinds!r})")
-        for key in ("rank", "targets", "shapes") + (("factor", "full") if self.algo == LOKR else ()):
+        for key in ("rank", "targets", "shapes") + FAMILIES[self.algo].meta:
             if sd.get(key) != mine[key]:
                 raise ValueError(f"lora state: {key} differs from this trainer's ({_brief(sd.get(key))} vs {_brief(mine[key])})")
         w = sd.get("weights")
@@ -542,7 +559,7 @@ class LoRAAdapters:
         self.alpha = float(sd.get("alpha", self.alpha))
         self.scale = self.alpha / self.rank
         self.weights.copy_(sd["weights"].reshape(-1))
-        if self.algo == "dora":      # (norm0 is not part of a state: it is W0's, recomputed by the kernel that computed it)
+        if self.norm0 is not None:      # (norm0 is not part of a state: it is W0's, recomputed by the kernel that computed it)
             self.init_norm0()
 
     def export_tensors(self) -> Dict[str, torch.Tensor]:
@@ -553,39 +570,32 @@ class LoRAAdapters:
         [r, in kh kw] (A1), ".hada_w2_a" (B2), ".hada_w2_b" (A2) and ".alpha" (a scalar), fp32, s NOT folded in: a loader forms
         (alpha / r) (w1_a w1_b) .* (w2_a w2_b) reshaped like the layer's weight.
         algo "dora": LoRA's file plus "unet.<module>.lora_magnitude_vector" [out] fp32, the magnitude m = n0 (1 + mu): a loader forms
-        m_o V[o] / ||V[o]||, V = W0 + lora_B lora_A, the norm per output row over every other dimension."""
-        if self.algo == LOKR:      # lokr_w1 [out_l, in_m]; lokr_w2 [out_k, in_n(, kh, kw)] or lokr_w2_a [out_k, r], lokr_w2_b [r, in_n kh kw];
-            out = {}               # alpha (r for a full target: its scale is 1); fp32, s not folded in: a loader forms s kron(w1, w2)
-            for k in self.targets:
-                pre = "lora_unet_" + k[: -len(".weight")].replace(".", "_")
-                g, shape = self.geometry[k], self.shapes[k]
-                for name in self.lokr_factors(k):
-                    v = self.factor_view(name, k).float().cpu().contiguous()
-                    if name == "W2" and len(shape) == 4:
-                        v = v.view(g["out_k"], g["in_n"], *shape[2:])
-                    out[f"{pre}.{LOKR_NAMES[name]}"] = v
-                out[f"{pre}.alpha"] = torch.tensor(float(self.rank) if g["full"] else self.alpha, dtype=torch.float32)
-            return out
-        if self.algo == "loha":
-            out = {}
-            for k in self.targets:
-                pre = "lora_unet_" + k[: -len(".weight")].replace(".", "_")
-                for name, lyco in LOHA_FACTORS:
-                    out[f"{pre}.{lyco}"] = self.factor(name, k).float().cpu().contiguous()
-                out[f"{pre}.alpha"] = torch.tensor(self.alpha, dtype=torch.float32)
-            return out
+        m_o V[o] / ||V[o]||, V = W0 + lora_B lora_A, the norm per output row over every other dimension.
+        algo "kronecker": LyCORIS' names under the same prefix -- lokr_w1 [out_l, in_m]; lokr_w2 [out_k, in_n(, kh, kw)] or lokr_w2_a [out_k, r], lokr_w2_b [r, in_n kh kw]; alpha (r for a full target:
+        its scale is 1); fp32, s not folded in: a loader forms s kron(w1, w2)."""
         out = {}
         for k in self.targets:
-            mod = k[: -len(".weight")]
-            shape = self.shapes[k]
-            la = self.A(k).float().cpu().contiguous()
-            lb = (self.B(k).float().cpu() * torch.tensor(self.scale, dtype=torch.float32)).contiguous()
-            if len(shape) == 4:
-                la, lb = la.view(self.rank, *shape[1:]), lb.view(shape[0], self.rank, 1, 1)
-            out[f"unet.{mod}.lora_A.weight"] = la
-            out[f"unet.{mod}.lora_B.weight"] = lb
-            if self.algo == "dora":
-                out[f"unet.{mod}.lora_magnitude_vector"] = self.magnitude(k).float().cpu().contiguous()
+            mod, shape = k[: -len(".weight")], self.shapes[k]
+            if FAMILIES[self.algo].export == "lycoris":
+                pre = "lora_unet_" + mod.replace(".", "_")
+                for f in self.factors[k]:
+                    v = self.view(f.name, k).float().cpu().contiguous()
+                    if f.name == "W2" and len(shape) == 4:
+                        v = v.view(f.shape[0], -1, *shape[2:])
+                    out[f"{pre}.{f.leaf}"] = v
+                out[f"{pre}.alpha"] = torch.tensor(float(self.rank) if self._full(k) else self.alpha, dtype=torch.float32)
+                continue
+            for f in self.factors[k]:
+                if f.name == "mu":
+                    out[f"unet.{mod}.lora_magnitude_vector"] = self.magnitude(k).float().cpu().contiguous()
+                    continue
+                v = self.view(f.name, k).float().cpu()
+                if f.name == "B":
+                    v = v * torch.tensor(self.scale, dtype=torch.float32)
+                v = v.contiguous()
+                if len(shape) == 4:
+                    v = v.view(self.rank, *shape[1:]) if f.name == "A" else v.view(shape[0], self.rank, 1, 1)
+                out[f"unet.{mod}.lora_{f.name}.weight"] = v
         return out
 
 
@@ -626,12 +636,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
 
     def __init__(self, model, optimizer=None, train_dataloader=None, device=None, wandb_logger=None, config=None, **kwargs):
         tc = config.training if config is not None else None
-        rank = getattr(tc, "lora_rank", 0)
         self.lora_algo = check_lora_algo(getattr(tc, "lora_algo", "lora"))
-        max_rank = LOHA_MAX_RANK if self.lora_algo == "loha" else MAX_RANK
-        if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= max_rank:
-            raise ValueError(f"training.lora_rank must be an integer in 1 .. {max_rank} for the LoRA trainer"
-                             + (" with training.lora_algo 'loha'" if self.lora_algo == "loha" else "") + f" (got {rank!r})")
+        check_rank(getattr(tc, "lora_rank", 0), self.lora_algo)
         if bool(getattr(tc, "use_ema", False)):
             raise ValueError("training.use_ema: an EMA of adapters is not supported (training.lora_rank > 0)")
         if getattr(tc, "shard_optimizer", None):          # None = not given
@@ -642,9 +648,8 @@ class NativeLoRATrainer(NativeSDXLTrainer):
         check_target_kinds(getattr(tc, "lora_target_kinds", "plain"))
         check_lokr_factor(getattr(tc, "lokr_factor", -1))
         check_lokr_full(getattr(tc, "lokr_full", False))
-        if self.lora_algo != "lora" and self.lora_backward == "direct":
-            raise ValueError(f"training.lora_backward 'direct': the backward writes LoRA's adapter gradients only, not training.lora_algo "
-                             f"{self.lora_algo!r}'s (use 'project' or 'project_frozen')")
+        if self.lora_backward == "direct":
+            check_direct_algo(self.lora_algo)
         super().__init__(model, None, train_dataloader, device, wandb_logger, config, **kwargs)
         self._projected = False
         if self.lora_backward != "project":

@@ -531,22 +531,6 @@ def adafactor_scratch_floats(entries: Sequence[AfEntry]) -> int:
     return total
 
 
-def adapter_shapes(adapters) -> Dict[str, Tuple[int, int]]:
-    """the factor matrices of a lora.LoRAAdapters arena under the keys of its param_ranges(): lora_A [rank][in], lora_B [out][rank].
-    ValueError for an algorithm whose arena this cannot describe."""
-    algo = getattr(adapters, "algo", "lora")
-    if algo != "lora":
-        raise ValueError(f"optimizer_type 'adafactor' is built for lora_algo 'lora' only: the adapter arena of lora_algo {algo!r} has factors "
-                         "its table does not describe (train it with adamw_bf16, adamw_schedule_free_kahan or prodigy)")
-    out = {}
-    for k, lay in adapters.layout.items():
-        mod = k[: -len(".weight")]
-        o, i = lay[-2:]
-        out[f"{mod}.lora_A.weight"] = (int(adapters.rank), int(i))
-        out[f"{mod}.lora_B.weight"] = (int(o), int(adapters.rank))
-    return out
-
-
 class AdafactorBF16(FusedArenaOptimizer):
     """Adafactor (Shazeer & Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost") on the packed arenas, with the
     arguments, defaults, checks and arithmetic of transformers.optimization.Adafactor: the second moment of a weight matrix is one row
@@ -604,9 +588,11 @@ class AdafactorBF16(FusedArenaOptimizer):
         w = net.weights
         if beta1 is not None:
             self.exp_avg = torch.zeros_like(w, dtype=torch.float32)
-        if hasattr(net, "layout") and hasattr(net, "rank"):                  # a lora.LoRAAdapters arena
-            shapes, ranges = adapter_shapes(net), net.param_ranges()
-        elif hasattr(net, "param_shapes"):
+        algo = getattr(net, "algo", "lora")                                  # (a lora.LoRAAdapters arena says its family)
+        if algo != "lora":
+            raise ValueError(f"optimizer_type 'adafactor' is built for lora_algo 'lora' only: the adapter arena of lora_algo {algo!r} has factors "
+                             "its table does not describe (train it with adamw_bf16, adamw_schedule_free_kahan or prodigy)")
+        if hasattr(net, "param_shapes"):
             shapes, ranges = net.param_shapes(), net.param_ranges()
         else:                                                               # an arena without a tensor table: one unfactored tensor
             shapes, ranges = {"arena": (w.numel(),)}, {"arena": (0, w.numel())}
